@@ -3,6 +3,8 @@
 all-reduce + clip_grad_norm_(1.0) + AdamW) of the VQA model.
 
   python bench.py --gpus 1 --steps K --warmup W                      # BASELINE configs[2]: B=512/GPU, 224x224, 20 tokens, bf16 MFMA
+  python bench.py ... --dump-outputs DIR                             # + the last timed step's loss, logits and a fixed sample of the
+                                                                     #   updated parameters as DIR/<name>.npy (compare two builds)
   python bench.py --config stress                                    # BASELINE configs[4]: B=256/GPU, 384x384 -> 144 image tokens,
                                                                      #   d=512, 8 text layers, 2000 answers, bf16
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
@@ -141,6 +143,32 @@ def dropin_loop(model, batch, steps, warmup):
     return images.shape[0] * steps / (time.perf_counter() - t0)
 
 
+def _seeded_rows(n, limit, seed):
+    """All of range(n), or a fixed seeded choice of `limit` of them in increasing order."""
+    if n <= limit:
+        return None
+    g = torch.Generator().manual_seed(seed)
+    return torch.randperm(n, generator=g)[:limit].sort().values
+
+
+def dump_outputs(dirname, step_out, flat):
+    """--dump-outputs: what the caller of HipTrainer.step holds after the last timed step -- the loss and the fp32 logits the step
+    returns, and the parameters it updated in place (the model's flat fp32 parameter buffer) -- as float32 DIR/<name>.npy, at most 48 MB:
+    logits whole up to 4M elements (else a seeded sample of rows), the parameters a seeded sample of at most 8M elements.  The samples
+    depend only on the shapes, so two builds run with the same arguments compare element for element."""
+    import numpy as np
+    loss, logits = step_out
+    B, N = logits.shape
+    rows = _seeded_rows(B, max(1, (4 << 20) // N), seed=1)
+    pos = _seeded_rows(flat.numel(), 8 << 20, seed=2)
+    arrays = {"loss": loss.detach().reshape(-1),
+              "logits": logits.detach() if rows is None else logits.detach()[rows.to(logits.device)],
+              "params": flat.detach().reshape(-1) if pos is None else flat.detach().reshape(-1)[pos.to(flat.device)]}
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), t.float().cpu().numpy())
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -155,7 +183,11 @@ def main(argv=None):
     ap.add_argument("--no-extras", action="store_true", help="skip the forward-only and drop-in-loop secondary measurements")
     ap.add_argument("--no-overlap", action="store_true", help="no RCCL/backward overlap")
     ap.add_argument("--serial", action="store_true", help="single-stream execution (no text-encoder / weight-gradient side streams)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, logits, a fixed sample of the updated parameters) as DIR/<name>.npy")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     # The contract is ONE JSON line on stdout.  RCCL prints a version banner to stdout when its communicator initialises (seen on
     # the MI355X box), so file descriptor 1 is pointed at stderr for the whole run and the line is written to the saved descriptor.
     sys.stdout.flush()
@@ -225,13 +257,16 @@ def _run(args, real_stdout):
     note("warm-up done")
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        trainer.step(*data)
+        last = trainer.step(*data)
     barrier()
     el = time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([el], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if args.dump_outputs and rank == 0:      # before the profiling steps below move the parameters on
+        dump_outputs(args.dump_outputs, last, model._flat)
+        note(f"outputs of the last timed step written to {args.dump_outputs}")
     loss = float(trainer.loss.item())
     trainer.check()                        # (one host sync, outside the timed region: raises if a step was rejected)
     ms = el / args.steps * 1e3

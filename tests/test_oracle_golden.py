@@ -9,11 +9,38 @@ import torch
 
 from oracle import vqa_oracle as O
 
-torch.set_num_threads(8)
+
+@pytest.fixture(autouse=True)
+def _golden_threads():
+    """8 intra-op threads, as make_golden.py ran: a CPU reduction splits its work by the thread count, and the float64 weight
+    checksums are compared exactly.  Set per test, since tests earlier in the same process may change it (test_gpu_model.py and
+    test_gpu_insitu.py set 16)."""
+    prev = torch.get_num_threads()
+    torch.set_num_threads(8)
+    yield
+    torch.set_num_threads(prev)
 
 
 def _checksum(sd):
     return np.array([[float(sd[k].double().sum()), float(sd[k].double().abs().sum())] for k in sorted(sd)])
+
+
+# The seeded generators reproduce the goldens bit for bit on AVX2 and AVX-512 CPUs, so those entries are compared exactly.  The
+# sinusoidal position table is exp / sin / cos evaluated by the CPU's vector math at init, and another processor than the one
+# that wrote the goldens has rounded some of its elements differently in the last place: its checksums are held to one float32
+# ulp per element.
+_VECTOR_MATH = ("text_encoder.positional_encoding.pe",)
+
+
+def _assert_weights_match(sd, golden):
+    got = _checksum(sd)
+    tol = np.zeros_like(got)
+    for i, k in enumerate(sorted(sd)):
+        if k in _VECTOR_MATH:
+            a = sd[k].abs()
+            tol[i] = float((torch.nextafter(a, torch.full_like(a, float("inf"))) - a).double().sum())
+    bad = np.abs(got - golden) > tol
+    assert not bad.any(), [(k, got[i].tolist(), golden[i].tolist()) for i, k in enumerate(sorted(sd)) if bad[i].any()]
 
 
 def _mask(lens, L=20):
@@ -33,7 +60,7 @@ def test_full_eval_matches_reference(golden_dir):
     g = np.load(os.path.join(golden_dir, "full_eval.npz"))
     cfg = O.full_config()
     sd = O.init_state_dict(cfg, 1, jitter=True)
-    np.testing.assert_allclose(_checksum(sd), g["weight_checksum"], rtol=0, atol=0)
+    _assert_weights_match(sd, g["weight_checksum"])
     images, ids, _, _ = O.synthetic_batch(4, seed=11)
     with torch.no_grad():
         logits, aux = O.vqa_forward(images, ids, _mask([20, 15, 7, 5]), sd, cfg, training=False)
@@ -67,7 +94,7 @@ def test_train_step_matches_reference(golden_dir, tag, cfgkw, seed, B, isz, L, v
     g = np.load(os.path.join(golden_dir, tag + ".npz"))
     cfg = O.full_config(**cfgkw)
     sd = O.init_state_dict(cfg, seed, jitter=True)
-    np.testing.assert_allclose(_checksum(sd), g["weight_checksum"], rtol=0, atol=0)
+    _assert_weights_match(sd, g["weight_checksum"])
     images, ids, mask, answers = O.synthetic_batch(B, seed=seed + 100, image_size=isz, seq_len=L, vocab=vocab,
                                                    num_answers=cfg["num_answers"])
     tr = O.OracleTrainer(sd, cfg)

@@ -1,7 +1,7 @@
 """Host-side timeline of the unchanged train.py loop on the drop-in model (measurement tool): where the HOST spends its time per step,
 in particular how long after a step's sync the first kernel of the next forward goes out (that stretch is idle GPU time)."""
 import importlib, os, sys, time, torch
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 pkg = importlib.import_module("visual-question-answering-vqa-system_amd")
 import bench
 M = pkg.load_dropin()
