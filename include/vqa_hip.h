@@ -265,6 +265,15 @@ int vqa_attention_bwd(int dtype, const void* dctx, int ldc, const void* q, const
 int vqa_attention_bwd_mfma(const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
                            const float* probs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv, int B, int H, int Lq, int Lk,
                            int hd, float p, unsigned long long seed, hipStream_t stream);
+/* attention backward with an upstream gradient on the saved softmax (graph-connected aux['cross_attention_weights']):
+ * dprobs [B][H][Lq][Lk] fp32 like probs; dP = keep_scale * (dctx V^T) + dprobs, dS = P * (dP - rowsum(P * dP)) / sqrt(hd), dV unchanged.
+ * Same arguments as vqa_attention_bwd / vqa_attention_bwd_mfma plus dprobs (never NULL); with dprobs == 0 the results are bit-equal. */
+int vqa_attention_bwd_dp(int dtype, const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
+                         const float* probs, const float* dprobs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv, int B, int H,
+                         int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t stream);
+int vqa_attention_bwd_mfma_dp(const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
+                              const float* probs, const float* dprobs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv, int B, int H,
+                              int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t stream);
 /* Device-side accuracy counters: counters[3] (u64) += {top-1 correct, top-5 correct, samples} for fp32 logits [B][N] and i64 targets.
  * Replaces the argmax/topk + .cpu() + .item() of VQAAccuracy.update (utils/metrics.py:55-94); ties resolve to the lowest index. */
 int vqa_accuracy_update(const float* logits, const long long* targets, unsigned long long* counters, int B, int N, hipStream_t stream);
@@ -281,6 +290,9 @@ int vqa_masked_pool_bwd(int dtype, const void* dpool, int ldo, int col0, const f
 int vqa_gate_fwd(int dtype, const void* z, const void* cat, void* fused, int B, int D, hipStream_t stream);
 int vqa_gate_bwd(int dtype, const void* dfused, const void* z, const void* cat, void* dz, void* dcat, int B, int D, hipStream_t stream);
 int vqa_add(int dtype, const void* a, const void* b, void* out, long long n, hipStream_t stream);
+/* gradient tap: acc (compute dtype) += g (fp32).  layout 0: acc[r*ld + c] += g[r*cols + c] (r < rows, c < cols, ld >= cols);
+ * layout 1 (NCHW -> NHWC): acc is [rows][cols] with rows = B*HW and ld = HW, g is [B][cols][HW] (aux['image_features']) */
+int vqa_grad_tap_add(int dtype, const float* g, void* acc, int rows, int cols, int ld, int layout, hipStream_t stream);
 /* gradient at the pre-activation of linear(+bias)(+ReLU)(+dropout); dbias += column sums */
 long long vqa_bias_act_bwd_ws(int dtype, int M, int N);
 int vqa_bias_act_bwd(int dtype, const void* dout, const void* outact, void* dz, float* dbias, int M, int N, float p,

@@ -91,6 +91,8 @@ SIGNATURES = {
     "vqa_attention_bwd": [I, P, I, P, P, P, I, I, I, P, P, P, P, I, I, I, I, I, I, I, I, F, ULL, P],
     "vqa_accuracy_update": [P, P, P, I, I, P],
     "vqa_attention_bwd_mfma": [P, I, P, P, P, I, I, I, P, P, P, P, I, I, I, I, I, I, I, I, F, ULL, P],
+    "vqa_attention_bwd_dp": [I, P, I, P, P, P, I, I, I, P, P, P, P, P, I, I, I, I, I, I, I, I, F, ULL, P],
+    "vqa_attention_bwd_mfma_dp": [P, I, P, P, P, I, I, I, P, P, P, P, P, I, I, I, I, I, I, I, I, F, ULL, P],
     "vqa_masked_pool_fwd": [I, P, P, P, I, I, I, I, I, P],
     "vqa_masked_pool_bwd": [I, P, I, I, P, P, P, I, I, I, P],
     "vqa_masked_pool_pair_fwd": [I, P, P, P, P, I, I, I, P],
@@ -98,6 +100,7 @@ SIGNATURES = {
     "vqa_gate_fwd": [I, P, P, P, I, I, P],
     "vqa_gate_bwd": [I, P, P, P, P, P, I, I, P],
     "vqa_add": [I, P, P, P, LL, P],
+    "vqa_grad_tap_add": [I, P, P, I, I, I, I, P],
     "vqa_bias_act_bwd_ws": [I, I, I],
     "vqa_bias_act_bwd": [I, P, P, P, P, I, I, F, ULL, P, I, P],
     "vqa_bias_act_bwd_fold_rows": [I, I, I],

@@ -448,11 +448,14 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ q, 
   }
 }
 
-template <typename T>
+// DPR: dprobs [B][H][Lq][Lk] (fp32, like probs) is an upstream gradient on the saved softmax, added to dP before the row sums
+// (vqa_attention_bwd_dp); read per (q, k) pair along the rows exactly like probs (lane = key: coalesced).
+template <typename T, bool DPR>
 __global__ __launch_bounds__(256) void attn_bwd_kernel(const T* __restrict__ dctx, int ldc, const T* __restrict__ q, const T* __restrict__ k,
                                                       const T* __restrict__ v, int ldq, int ldk, int ldv, const float* __restrict__ probs,
                                                       T* __restrict__ dq, T* __restrict__ dk, T* __restrict__ dv, int lddq, int lddk, int lddv,
-                                                      int H, int Lq, int Lk, int hd, float scale, float p, uint64_t seed) {
+                                                      int H, int Lq, int Lk, int hd, float scale, float p, uint64_t seed,
+                                                      const float* __restrict__ dprobs) {
   extern __shared__ float sm[];
   const int b = blockIdx.x / H, h = blockIdx.x - b * H, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ldh = hd + 1, ldp = Lk + 1;
   float* Qs = sm; float* Os = Qs + Lq * ldh; float* Ks = Os + Lq * ldh; float* Vs = Ks + Lk * ldh;
@@ -477,7 +480,8 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const T* __restrict__ dct
       if (p > 0.f) ks = drop_keep32(drop_key(seed), (uint32_t)(((size_t)(b * H + h) * Lq + r) * Lk + c), p) ? 1.f / (1.f - p) : 0.f;
       float dpd = 0.f;
       for (int d = 0; d < hd; ++d) dpd += Os[r * ldh + d] * Vs[c * ldh + d];
-      const float dp = dpd * ks;
+      float dp = dpd * ks;
+      if constexpr (DPR) dp += dprobs[((size_t)(b * H + h) * Lq + r) * Lk + c];
       Ps[r * ldp + c] = pr * ks;
       Ds[r * ldp + c] = dp;
       t += dp * pr;
@@ -594,6 +598,37 @@ template <typename T>
 __global__ void add_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ out, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = from_f<T>(to_f<T>(a[i]) + to_f<T>(b[i]));
+}
+
+// gradient taps (graph-connected aux outputs): an fp32 upstream gradient added into a compute-dtype gradient buffer.
+//   rows:  acc[r*ld + c] += g[r*cols + c]                                   (row-major, row stride ld: e.g. one half of dcat)
+//   nchw:  acc[(b*HW + s)*C + c] += g[(b*C + c)*HW + s], HW = ld, C = cols  (aux['image_features'] into the NHWC stage-4 gradient)
+// The NCHW form transposes through a 64-channel x 32-position LDS tile: reads run along positions, writes along channels.
+template <typename T>
+__global__ void grad_tap_rows_kernel(const float* __restrict__ g, T* __restrict__ acc, int cols, int ld, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const size_t r = i / cols, c = i - r * cols;
+  T* a = acc + r * ld + c;
+  *a = from_f<T>(to_f<T>(*a) + g[i]);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void grad_tap_nchw_kernel(const float* __restrict__ g, T* __restrict__ acc, int C, int HW) {
+  __shared__ float tile[64][33];
+  const int b = blockIdx.z, c0 = blockIdx.y * 64, s0 = blockIdx.x * 32, tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  for (int cc = ty; cc < 64; cc += 8) {
+    const int c = c0 + cc, sp = s0 + tx;
+    tile[cc][tx] = (c < C && sp < HW) ? g[((size_t)b * C + c) * HW + sp] : 0.f;
+  }
+  __syncthreads();
+  const int cl = threadIdx.x & 63, sl = threadIdx.x >> 6;
+  for (int ss = sl; ss < 32; ss += 4) {
+    const int sp = s0 + ss, c = c0 + cl;
+    if (sp < HW && c < C) {
+      T* a = acc + ((size_t)b * HW + sp) * C + c;
+      *a = from_f<T>(to_f<T>(*a) + tile[cl][ss]);
+    }
+  }
 }
 
 // dz = dout * [out>0] * dropout-keep-scale ; dbias[n] += column sums of dz
@@ -786,6 +821,20 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 #define DT(call_f, call_b) do { if (dtype) { call_b; } else { call_f; } } while (0)
 static inline unsigned g1(size_t n) { return (unsigned)((n + 255) / 256); }
 
+template <bool DPR>
+static int attention_bwd_valu(int dtype, const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
+                              const float* probs, const float* dprobs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv,
+                              int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t st) {
+  const size_t shm = ((size_t)(2 * Lq + 2 * Lk) * (hd + 1) + (size_t)2 * Lq * (Lk + 1)) * 4;
+  if (shm > 160 * 1024) return VQA_EARG;
+  const float scale = sqrtf((float)hd);
+  if (dtype) { if (shm > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<bf16_t, DPR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); }
+  else { if (shm > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<float, DPR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); }
+  DT(hipLaunchKernelGGL((attn_bwd_kernel<float, DPR>), dim3(B * H), dim3(256), shm, st, (const float*)dctx, ldc, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, probs, (float*)dq, (float*)dk, (float*)dv, lddq, lddk, lddv, H, Lq, Lk, hd, scale, p, seed, dprobs),
+     hipLaunchKernelGGL((attn_bwd_kernel<bf16_t, DPR>), dim3(B * H), dim3(256), shm, st, (const bf16_t*)dctx, ldc, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, probs, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, lddq, lddk, lddv, H, Lq, Lk, hd, scale, p, seed, dprobs));
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+
 extern "C" {
 
 int vqa_embed_fwd(int dtype, const long long* ids, const float* emb, const float* pe, void* out, int rows, int L, int D, int V,
@@ -899,14 +948,13 @@ int vqa_attention_fwd(int dtype, const void* q, const void* k, const void* v, in
 int vqa_attention_bwd(int dtype, const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
                       const float* probs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv,
                       int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t st) {
-  const size_t shm = ((size_t)(2 * Lq + 2 * Lk) * (hd + 1) + (size_t)2 * Lq * (Lk + 1)) * 4;
-  if (shm > 160 * 1024) return VQA_EARG;
-  const float scale = sqrtf((float)hd);
-  if (dtype) { if (shm > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); }
-  else { if (shm > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); }
-  DT(hipLaunchKernelGGL(attn_bwd_kernel<float>, dim3(B * H), dim3(256), shm, st, (const float*)dctx, ldc, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, probs, (float*)dq, (float*)dk, (float*)dv, lddq, lddk, lddv, H, Lq, Lk, hd, scale, p, seed),
-     hipLaunchKernelGGL(attn_bwd_kernel<bf16_t>, dim3(B * H), dim3(256), shm, st, (const bf16_t*)dctx, ldc, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, probs, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, lddq, lddk, lddv, H, Lq, Lk, hd, scale, p, seed));
-  VQA_LAUNCH_CHECK(); return VQA_OK;
+  return attention_bwd_valu<false>(dtype, dctx, ldc, q, k, v, ldq, ldk, ldv, probs, nullptr, dq, dk, dv, lddq, lddk, lddv, B, H, Lq, Lk, hd, p, seed, st);
+}
+int vqa_attention_bwd_dp(int dtype, const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
+                         const float* probs, const float* dprobs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv,
+                         int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t st) {
+  if (!dprobs) return VQA_EARG;
+  return attention_bwd_valu<true>(dtype, dctx, ldc, q, k, v, ldq, ldk, ldv, probs, dprobs, dq, dk, dv, lddq, lddk, lddv, B, H, Lq, Lk, hd, p, seed, st);
 }
 int vqa_masked_pool_fwd(int dtype, const void* x, const float* mask, void* out, int ldo, int col0, int B, int L, int D, hipStream_t st) {
   DT(hipLaunchKernelGGL(masked_pool_fwd_kernel<float>, dim3(B), dim3(256), 0, st, (const float*)x, mask, (float*)out, ldo, col0, L, D),
@@ -938,6 +986,26 @@ int vqa_gate_fwd(int dtype, const void* z, const void* cat, void* fused, int B, 
 int vqa_gate_bwd(int dtype, const void* dfused, const void* z, const void* cat, void* dz, void* dcat, int B, int D, hipStream_t st) {
   DT(hipLaunchKernelGGL(gate_bwd_kernel<float>, dim3(g1((size_t)B * D)), dim3(256), 0, st, (const float*)dfused, (const float*)z, (const float*)cat, (float*)dz, (float*)dcat, B, D),
      hipLaunchKernelGGL(gate_bwd_kernel<bf16_t>, dim3(g1((size_t)B * D)), dim3(256), 0, st, (const bf16_t*)dfused, (const bf16_t*)z, (const bf16_t*)cat, (bf16_t*)dz, (bf16_t*)dcat, B, D));
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+int vqa_grad_tap_add(int dtype, const float* g, void* acc, int rows, int cols, int ld, int layout, hipStream_t st) {
+  if (!g || !acc || rows < 0 || cols <= 0 || ld <= 0) return VQA_EARG;
+  if (rows == 0) return VQA_OK;
+  if (layout == 0) {
+    if (ld < cols) return VQA_EARG;
+    const size_t n = (size_t)rows * cols;
+    DT(hipLaunchKernelGGL(grad_tap_rows_kernel<float>, dim3(g1(n)), dim3(256), 0, st, g, (float*)acc, cols, ld, n),
+       hipLaunchKernelGGL(grad_tap_rows_kernel<bf16_t>, dim3(g1(n)), dim3(256), 0, st, g, (bf16_t*)acc, cols, ld, n));
+  } else if (layout == 1) {
+    if (rows % ld) return VQA_EARG;
+    const int B = rows / ld;
+    if (B > 65535) return VQA_EARG;
+    const dim3 grid((unsigned)((ld + 31) / 32), (unsigned)((cols + 63) / 64), (unsigned)B);
+    DT(hipLaunchKernelGGL(grad_tap_nchw_kernel<float>, grid, dim3(256), 0, st, g, (float*)acc, cols, ld),
+       hipLaunchKernelGGL(grad_tap_nchw_kernel<bf16_t>, grid, dim3(256), 0, st, g, (bf16_t*)acc, cols, ld));
+  } else {
+    return VQA_EARG;
+  }
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
 int vqa_add(int dtype, const void* a, const void* b, void* out, long long n, hipStream_t st) {
@@ -1192,6 +1260,8 @@ extern "C" int vqa_attention_fwd_mfma(const void* q, const void* k, const void* 
 // In both, the bf16-rounded accumulator registers are the A operand of the following MFMA (as in the forward kernel) and the
 // B operand (K, Q or dctx rows) is read transposed from a wave-private LDS tile in the matching permuted order.
 // probs is the softmax BEFORE dropout saved by the forward; the dropout mask is regenerated from (seed, index).
+// DPR (vqa_attention_bwd_mfma_dp): dprobs [B][H][Lq][Lk] fp32, an upstream gradient on that softmax, is staged in a wave-private LDS
+// tile by the same coalesced row copy as probs and added to dP in both orientations: dP = ks * (dctx V^T) + dprobs.
 // ---------------------------------------------------------------------------------------------
 template <int HD>
 __device__ __forceinline__ bf16x8 attn_ldsB(const bf16_t* tile, int row0, int c, int hh, int g2, int qd, int pp) {
@@ -1203,15 +1273,15 @@ __device__ __forceinline__ bf16x8 attn_ldsB(const bf16_t* tile, int row0, int c,
   return __builtin_bit_cast(bf16x8, tt);
 }
 
-template <int HD, int NKT, int WPB>
+template <int HD, int NKT, int WPB, bool DPR>
 __global__ __launch_bounds__(WPB * 64, 1) void attn_bwd_mfma_kernel(const bf16_t* __restrict__ dctx, int ldc, const bf16_t* __restrict__ q,
                                                             const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int ldq, int ldk, int ldv,
                                                             const float* __restrict__ probs, bf16_t* __restrict__ dq, bf16_t* __restrict__ dk,
                                                             bf16_t* __restrict__ dv, int lddq, int lddk, int lddv, int BH, int H, int Lq, int Lk,
-                                                            float p, uint64_t seed) {
+                                                            float p, uint64_t seed, const float* __restrict__ dprobs) {
   constexpr int KR = NKT * 32;
   constexpr int LDP = KR + 1;
-  constexpr int WAVE_BYTES = (KR + 32 + 32) * HD * 2 + 32 * LDP * 4 + 32 * 4;
+  constexpr int WAVE_BYTES = (KR + 32 + 32) * HD * 2 + 32 * LDP * 4 + 32 * 4 + (DPR ? 32 * LDP * 4 : 0);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int bh = blockIdx.x * WPB + wave;
@@ -1222,6 +1292,7 @@ __global__ __launch_bounds__(WPB * 64, 1) void attn_bwd_mfma_kernel(const bf16_t
   bf16_t* Os = Qs + 32 * HD;                               // [32][HD]  (dctx)
   float* Ps = reinterpret_cast<float*>(Os + 32 * HD);      // [32][LDP]
   float* Ts = Ps + 32 * LDP;                               // [32]
+  float* DPs = Ts + 32;                                    // [32][LDP]  (DPR only: dprobs)
   const int b = bh / H, h = bh - b * H;
   const int r = lane & 31, hh = lane >> 5;
   const int g2 = (lane >> 4) & 1, li = lane & 15, qd = li >> 2, pp = li & 3;
@@ -1246,6 +1317,8 @@ __global__ __launch_bounds__(WPB * 64, 1) void attn_bwd_mfma_kernel(const bf16_t
     *reinterpret_cast<u32x4*>(&Os[row * HD + cv * 8]) = o;
   }
   for (int i = lane; i < Lq * Lk; i += 64) { const int qi = i / Lk, kj = i - qi * Lk; Ps[qi * LDP + kj] = probs[(size_t)bh * Lq * Lk + i]; }
+  if constexpr (DPR)
+    for (int i = lane; i < Lq * Lk; i += 64) { const int qi = i / Lk, kj = i - qi * Lk; DPs[qi * LDP + kj] = dprobs[(size_t)bh * Lq * Lk + i]; }
 
   // ---- both orientations of dP = dctx V^T from the same global fragments
   f32x16 d1[NKT], d2[NKT];
@@ -1279,7 +1352,8 @@ __global__ __launch_bounds__(WPB * 64, 1) void attn_bwd_mfma_kernel(const bf16_t
       const float pr = ok ? Ps[r * LDP + key] : 0.f;
       float ks = 1.f;
       if (p > 0.f && ok) ks = drop_keep32(drop_key(seed), (uint32_t)(prow + key), p) ? keep : 0.f;
-      const float dp = ok ? d1[t][e] * ks : 0.f;
+      float dp = ok ? d1[t][e] * ks : 0.f;
+      if constexpr (DPR) dp += ok ? DPs[r * LDP + key] : 0.f;
       tq += dp * pr;
       d1[t][e] = dp;
     }
@@ -1331,7 +1405,8 @@ __global__ __launch_bounds__(WPB * 64, 1) void attn_bwd_mfma_kernel(const bf16_t
       const float pr = ok ? Ps[qi * LDP + key] : 0.f;
       float ks = 1.f;
       if (p > 0.f && ok) ks = drop_keep32(drop_key(seed), (uint32_t)(((size_t)bh * Lq + qi) * Lk + key), p) ? keep : 0.f;
-      const float dp = ok ? d2[t][e] * ks : 0.f;
+      float dp = ok ? d2[t][e] * ks : 0.f;
+      if constexpr (DPR) dp += ok ? DPs[qi * LDP + key] : 0.f;
       const float tt = ok ? Ts[qi] : 0.f;
       ds2[e] = pr * (dp - tt) * inv_scale;
       pd2[e] = pr * ks;
@@ -1365,21 +1440,33 @@ __global__ __launch_bounds__(WPB * 64, 1) void attn_bwd_mfma_kernel(const bf16_t
   }
 }
 
-extern "C" int vqa_attention_bwd_mfma(const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
-                                      const float* probs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv,
-                                      int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t st) {
-  if (!dctx || !q || !k || !v || !probs || !dq || !dk || !dv || Lq > 32 || Lk > 160 || (hd != 32 && hd != 64) ||
+template <bool DPR>
+static int attention_bwd_mfma(const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
+                              const float* probs, const float* dprobs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv,
+                              int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t st) {
+  if (!dctx || !q || !k || !v || !probs || !dq || !dk || !dv || (DPR && !dprobs) || Lq > 32 || Lk > 160 || (hd != 32 && hd != 64) ||
       (ldq % 8) || (ldk % 8) || (ldv % 8) || (ldc % 8)) return VQA_EARG;
   const int BH = B * H;
   auto go = [&](auto kern, int nkt, int wpb) {
-    const size_t shm = (size_t)wpb * ((nkt * 32 + 32 + 32) * hd * 2 + 32 * (nkt * 32 + 1) * 4 + 32 * 4);
+    const size_t shm = (size_t)wpb * ((nkt * 32 + 32 + 32) * hd * 2 + 32 * (nkt * 32 + 1) * 4 + 32 * 4 + (DPR ? 32 * (nkt * 32 + 1) * 4 : 0));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
     hipLaunchKernelGGL(kern, dim3((BH + wpb - 1) / wpb), dim3(wpb * 64), shm, st, (const bf16_t*)dctx, ldc, (const bf16_t*)q, (const bf16_t*)k,
-                       (const bf16_t*)v, ldq, ldk, ldv, probs, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, lddq, lddk, lddv, BH, H, Lq, Lk, p, seed);
+                       (const bf16_t*)v, ldq, ldk, ldv, probs, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, lddq, lddk, lddv, BH, H, Lq, Lk, p, seed, dprobs);
   };
-  if (Lk <= 64) { if (hd == 32) go(&attn_bwd_mfma_kernel<32, 2, 4>, 2, 4); else go(&attn_bwd_mfma_kernel<64, 2, 4>, 2, 4); }
-  else { if (hd == 32) go(&attn_bwd_mfma_kernel<32, 5, 2>, 5, 2); else go(&attn_bwd_mfma_kernel<64, 5, 2>, 5, 2); }
+  if (Lk <= 64) { if (hd == 32) go(&attn_bwd_mfma_kernel<32, 2, 4, DPR>, 2, 4); else go(&attn_bwd_mfma_kernel<64, 2, 4, DPR>, 2, 4); }
+  else { if (hd == 32) go(&attn_bwd_mfma_kernel<32, 5, 2, DPR>, 5, 2); else go(&attn_bwd_mfma_kernel<64, 5, 2, DPR>, 5, 2); }
   VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+
+extern "C" int vqa_attention_bwd_mfma(const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
+                                      const float* probs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv,
+                                      int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t st) {
+  return attention_bwd_mfma<false>(dctx, ldc, q, k, v, ldq, ldk, ldv, probs, nullptr, dq, dk, dv, lddq, lddk, lddv, B, H, Lq, Lk, hd, p, seed, st);
+}
+extern "C" int vqa_attention_bwd_mfma_dp(const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
+                                         const float* probs, const float* dprobs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv,
+                                         int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t st) {
+  return attention_bwd_mfma<true>(dctx, ldc, q, k, v, ldq, ldk, ldv, probs, dprobs, dq, dk, dv, lddq, lddk, lddv, B, H, Lq, Lk, hd, p, seed, st);
 }
 
 // ---------------------------------------------------------------------------------------------

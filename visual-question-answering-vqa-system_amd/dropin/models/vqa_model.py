@@ -94,6 +94,216 @@ def _backward(ctx, dlogits):
 torch.library.register_autograd("vqa_hip::vqa_forward", _backward, setup_context=_setup_ctx)
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# graph-connected aux outputs: forward(..., return_aux=True) under autograd is three chained ops, split where the engine's backward
+# reports its segments (engine.backward_head / _fusion / _encoders):
+#   vqa_aux_encoders(images, token_ids, mask, params, handle, training) -> image_features, text_features
+#   vqa_aux_fusion(image_features, text_features, handle, tape_id)       -> fused, image_projected, cross_attention_weights (stacked),
+#                                                                           attended_pooled, text_pooled
+#   vqa_aux_head(fused, handle, tape_id)                                  -> logits
+# The forward is still ONE engine pass (issued by the encoders op; the other two hand out what it computed), so values and launches
+# are those of vqa_forward.  Each op's backward runs its part of the engine backward; the parameter gradients of all three parts
+# accumulate into one flat buffer per forward and backward pass, which the encoders op (the last node of every backward that reaches
+# the parameters) returns.  A pass that ends before the encoders node (autograd.grad w.r.t. an aux tensor) drops that buffer with
+# it.  Gradients on the aux tensors enter where those tensors enter the backward; autograd itself sums the gradients of
+# image_features / text_features / fused with those of their consumers.
+# ----------------------------------------------------------------------------------------------------------------------
+def _aux_tape(model, tape_id, part):
+    tape = model._tapes.get(tape_id)
+    if tape is None or part not in tape:
+        raise RuntimeError(f"vqa_backward: the activations of forward #{tape_id} are gone -- either backward ran twice through it "
+                           f"(the reference needs retain_graph=True for that) or more than max_live_tapes = {model.max_live_tapes} "
+                           "training forwards were issued before its backward (raise VQAModel.max_live_tapes)")
+    return tape
+
+
+_AUX_SEGMENTS = ("answer_head", "fusion")     # segments of the head / fusion parts, reported in this order before the encoders' ones
+
+
+def _aux_grad_buffer(model, tape):
+    """The flat gradient buffer of the CURRENT backward pass through this forward (created by the first of its nodes that runs)."""
+    if tape.get("_G") is None:
+        tape["_G"] = torch.zeros_like(model._flat)
+        tape["_reported"] = set()
+
+        def end_of_pass():
+            # a pass that reached the encoders node has handed the buffer out already; otherwise what the head / fusion nodes put
+            # there belongs to a backward that did not ask for parameter gradients: dropped, never returned by a later pass
+            tape.pop("_G", None)
+            tape.pop("_reported", None)
+        torch.autograd.Variable._execution_engine.queue_callback(end_of_pass)
+    return tape["_G"]
+
+
+def _report_skipped_segments(model, tape, upto):
+    """Segments of the parts before `upto` that this pass did not run (a loss on aux alone skips the head; one on image_features
+    alone skips the fusion part too): their parameters' gradients are the buffer's zeros, and a reducer driven by on_segment still
+    sees every bucket, in the usual order."""
+    for name in _AUX_SEGMENTS[:upto]:
+        if name not in tape["_reported"]:
+            tape["_reported"].add(name)
+            if model._on_segment is not None:
+                ev = torch.cuda.Event(); ev.record(torch.cuda.current_stream())
+                model._on_segment(name, [ev])
+
+
+def _to_f32(model, t):
+    """Compute-dtype gradient -> fp32 (the dtype of the public aux tensors)."""
+    if t.dtype == torch.float32:
+        return t
+    out = torch.empty(t.shape, device=t.device, dtype=torch.float32)
+    model._pkg._lib.call("vqa_convert", 1, 0, t.data_ptr(), out.data_ptr(), t.numel())
+    return out
+
+
+def _from_f32(model, g):
+    """fp32 gradient of a public aux tensor -> compute dtype (a copy only where the dtypes differ)."""
+    g = g.contiguous()
+    if model.compute_dtype == torch.float32:
+        return g
+    out = torch.empty(g.shape, device=g.device, dtype=model.compute_dtype)
+    model._pkg._lib.call("vqa_convert", 0, 1, g.data_ptr(), out.data_ptr(), g.numel())
+    return out
+
+
+def _final_hw(h):
+    h = (h + 6 - 7) // 2 + 1            # stem conv 7x7 / 2
+    h = (h + 2 - 3) // 2 + 1            # max pool 3x3 / 2
+    for _ in range(3):                  # stages 2-4 open with a stride-2 block
+        h = (h + 2 - 3) // 2 + 1
+    return h
+
+
+@torch.library.custom_op("vqa_hip::vqa_aux_encoders", mutates_args=(), device_types="cuda")
+def _aux_encoders_op(images: torch.Tensor, token_ids: torch.Tensor, mask: Optional[torch.Tensor], flat_params: torch.Tensor,
+                     handle: int, training: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    model = _MODELS[handle]
+    logits, aux, tape = model._engine.forward(images, token_ids, mask, training, True, need_tape=True)
+    hw = (_final_hw(images.shape[2]), _final_hw(images.shape[3]))
+    if tuple(aux["image_features"].shape[1:]) != (512,) + hw:              # the fake below derives the same shape from the geometry
+        raise RuntimeError(f"image_features {tuple(aux['image_features'].shape)} disagrees with the stem / stage geometry {hw}")
+    tape["_aux"] = (logits, aux)
+    model._tape_seq += 1
+    model._tapes[model._tape_seq] = tape
+    while len(model._tapes) > model.max_live_tapes:
+        model._tapes.pop(next(iter(model._tapes)))
+    return aux["image_features"], aux["text_features"]
+
+
+@_aux_encoders_op.register_fake
+def _(images, token_ids, mask, flat_params, handle, training):
+    m = _MODELS[handle]
+    B, L = token_ids.shape
+    return (images.new_empty((images.shape[0], 512, _final_hw(images.shape[2]), _final_hw(images.shape[3]))),
+            images.new_empty((B, L, m.embed_dim)))
+
+
+def _aux_encoders_setup(ctx, inputs, output):
+    ctx.set_materialize_grads(False)
+    ctx.handle = inputs[4]
+    ctx.tape_id = _MODELS[inputs[4]]._tape_seq
+
+
+def _aux_encoders_bwd(ctx, dfeat, dtext):
+    model = _MODELS[ctx.handle]
+    tape = _aux_tape(model, ctx.tape_id, "stages")
+    G = _aux_grad_buffer(model, tape)
+    _report_skipped_segments(model, tape, 2)
+    eng = model._engine
+    if dfeat is not None:
+        B, C, H, W = dfeat.shape
+        g, dfeat = dfeat.contiguous(), torch.empty((B * H * W, C), device=dfeat.device, dtype=model.compute_dtype)
+        model._pkg._lib.call("vqa_nchw_to_nhwc", model._pkg._lib.dt(model.compute_dtype), g.data_ptr(), dfeat.data_ptr(), B, H * W, C)
+    if dtext is not None:
+        dtext = _from_f32(model, dtext).view(-1, dtext.shape[-1])
+    eng.backward_encoders(tape, dfeat, dtext, G, on_segment=model._on_segment)
+    model._tapes.pop(ctx.tape_id, None)
+    tape.pop("_G", None)
+    return None, None, None, G, None, None
+
+
+torch.library.register_autograd("vqa_hip::vqa_aux_encoders", _aux_encoders_bwd, setup_context=_aux_encoders_setup)
+
+
+@torch.library.custom_op("vqa_hip::vqa_aux_fusion", mutates_args=(), device_types="cuda")
+def _aux_fusion_op(image_features: torch.Tensor, text_features: torch.Tensor, handle: int,
+                   tape_id: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    model = _MODELS[handle]
+    tape = _aux_tape(model, tape_id, "pool")
+    _, aux = tape["_aux"]
+    att, txt = aux["attended_pooled"], aux["text_pooled"]
+    if att.untyped_storage().data_ptr() == txt.untyped_storage().data_ptr():
+        txt = txt.clone()                 # fp32: both are column halves of one buffer; the outputs of an op may not alias
+    caw = tape.get("caw")
+    if caw is None:                       # no cross-attention layer: an empty stack
+        B, ntok, _ = aux["image_projected"].shape
+        caw = att.new_empty((0, B, model.config["num_attention_heads"], aux["text_features"].shape[1], ntok))
+    return aux["fused"], aux["image_projected"], caw, att, txt
+
+
+@_aux_fusion_op.register_fake
+def _(image_features, text_features, handle, tape_id):
+    m = _MODELS[handle]
+    B, L, d = text_features.shape
+    ntok = image_features.shape[2] * image_features.shape[3]
+    heads, ncl = m.config["num_attention_heads"], m.config["num_cross_layers"]
+    e = image_features.new_empty
+    return e((B, d)), e((B, ntok, d)), e((ncl, B, heads, L, ntok)), e((B, d)), e((B, d))
+
+
+def _aux_fusion_setup(ctx, inputs, output):
+    ctx.set_materialize_grads(False)
+    ctx.handle, ctx.tape_id = inputs[2], inputs[3]
+    ctx.text_shape = tuple(inputs[1].shape)
+    ctx.feat_shape = tuple(inputs[0].shape)
+
+
+def _aux_fusion_bwd(ctx, dfused, dimg, dcaw, datt, dtxt):
+    model = _MODELS[ctx.handle]
+    tape = _aux_tape(model, ctx.tape_id, "pool")
+    G = _aux_grad_buffer(model, tape)
+    _report_skipped_segments(model, tape, 1)
+    taps = {"image_projected": dimg, "attended_pooled": datt, "text_pooled": dtxt,
+            "cross_attention_weights": None if dcaw is None else dcaw.unbind(0)}
+    dfeat, denc = model._engine.backward_fusion(tape, dfused, G, on_segment=model._on_segment, taps=taps)
+    tape["_reported"].add("fusion")
+    B, C, H, W = ctx.feat_shape
+    dfeat_nchw = torch.empty(ctx.feat_shape, device=dfeat.device, dtype=torch.float32)
+    model._pkg._lib.call("vqa_nhwc_to_nchw", model._pkg._lib.dt(dfeat), dfeat.data_ptr(), dfeat_nchw.data_ptr(), B, H * W, C)
+    return dfeat_nchw, _to_f32(model, denc).view(ctx.text_shape), None, None
+
+
+torch.library.register_autograd("vqa_hip::vqa_aux_fusion", _aux_fusion_bwd, setup_context=_aux_fusion_setup)
+
+
+@torch.library.custom_op("vqa_hip::vqa_aux_head", mutates_args=(), device_types="cuda")
+def _aux_head_op(fused: torch.Tensor, handle: int, tape_id: int) -> torch.Tensor:
+    tape = _aux_tape(_MODELS[handle], tape_id, "head")
+    logits, _ = tape.pop("_aux")
+    return logits
+
+
+@_aux_head_op.register_fake
+def _(fused, handle, tape_id):
+    return fused.new_empty((fused.shape[0], _MODELS[handle].num_answers), dtype=torch.float32)
+
+
+def _aux_head_setup(ctx, inputs, output):
+    ctx.handle, ctx.tape_id = inputs[1], inputs[2]
+
+
+def _aux_head_bwd(ctx, dlogits):
+    model = _MODELS[ctx.handle]
+    tape = _aux_tape(model, ctx.tape_id, "head")
+    G = _aux_grad_buffer(model, tape)
+    dfused = model._engine.backward_head(tape, dlogits, G, on_segment=model._on_segment)
+    tape["_reported"].add("answer_head")
+    return _to_f32(model, dfused), None, None
+
+
+torch.library.register_autograd("vqa_hip::vqa_aux_head", _aux_head_bwd, setup_context=_aux_head_setup)
+
+
 class _FlatParams(torch.autograd.Function):
     """The flat parameter buffer as a function of the 164 leaf Parameters that are views into it: forward aliases the buffer (no
     copy), backward hands each Parameter its slice of the flat gradient (views of ONE tensor, as `.grad` wants them for the flat
@@ -235,6 +445,8 @@ class VQAModel(nn.Module):
             # tapes are kept by id (gradient accumulation / loss1 + loss2: several forwards, then their backwards), oldest dropped
             # beyond max_live_tapes
             flat = _FlatParams.apply(self._flat, self._handle, *params)
+            if return_aux:                   # aux tensors on the autograd graph (three chained ops, see vqa_aux_encoders above)
+                return self._forward_aux_graph(images, token_ids, maskf, flat)
             logits = torch.ops.vqa_hip.vqa_forward(images, token_ids, maskf, flat, self._handle, self.training, return_aux)
             aux, self._last_aux = self._last_aux, None
         elif (self.graph_inference and not self.training and not return_aux and 0 < images.shape[0] <= self.graph_max_batch
@@ -246,6 +458,15 @@ class VQAModel(nn.Module):
         else:
             logits, aux, _ = eng.forward(images, token_ids, maskf, self.training, return_aux, need_tape=False)
         return (logits, aux) if return_aux else (logits, None)
+
+    def _forward_aux_graph(self, images, token_ids, maskf, flat):
+        feat, text = torch.ops.vqa_hip.vqa_aux_encoders(images, token_ids, maskf, flat, self._handle, self.training)
+        tape_id = self._tape_seq
+        fused, img, caw, att, txt = torch.ops.vqa_hip.vqa_aux_fusion(feat, text, self._handle, tape_id)
+        logits = torch.ops.vqa_hip.vqa_aux_head(fused, self._handle, tape_id)
+        aux = {"image_features": feat, "text_features": text, "text_pooled": txt, "fused": fused,
+               "cross_attention_weights": list(caw.unbind(0)), "image_projected": img, "attended_pooled": att}
+        return logits, aux
 
     def _forward_eager_eval(self, images, token_ids, maskf):
         logits, _, _ = self._ensure_engine().forward(images, token_ids, maskf, False, False, need_tape=False)

@@ -728,6 +728,8 @@ class HipEngine:
         tape["clayers"] = []
         probs_all = []
         ncl = cfg["num_cross_layers"]
+        # aux: every layer's probabilities are views of ONE [ncl][B][H][L][ntok] buffer (the drop-in hands it out as one graph output)
+        caw = torch.empty((ncl, Bt, heads, L, ntok), device=dev, dtype=torch.float32) if (want_aux and ncl) else None
         pre_kv = [None] * ncl
         if self.hoist_cross and use_side and ncl > 1:
             # every layer's K / V come from the SAME image tokens: layers >= 1 are projected on the (now idle) text stream while
@@ -748,7 +750,7 @@ class HipEngine:
                 main.wait_event(ev_kv)
             rec = self._attn_block_fwd(q, img, None, p + ".norm_query", p + ".norm_kv", p + ".cross_attention", None, Bt, L, ntok,
                                        heads, hd, pdrop, p + ".norm_ffn", p + ".ffn.0", p + ".ffn.3", self_attn=False,
-                                       pre_q=text.get("q0") if l == 0 else None, pre_kv=pkv)
+                                       pre_q=text.get("q0") if l == 0 else None, pre_kv=pkv, probs=None if caw is None else caw[l])
             tape["clayers"].append(rec)
             probs_all.append(rec["probs"])
             q = rec["out"]
@@ -776,6 +778,8 @@ class HipEngine:
         logits_f = logits.float() if (T != torch.float32 and not lowp_logits) else logits
 
         aux = None
+        if caw is not None:
+            tape["caw"] = caw
         if want_aux:
             feat_nchw = torch.empty((B, Cf, Hf, Wf), device=dev, dtype=torch.float32)
             call("vqa_nhwc_to_nchw", dt(T), ptr(feat), ptr(feat_nchw), B, Hf * Wf, Cf)
@@ -809,7 +813,7 @@ class HipEngine:
         return nkv, stkv, self._lin(nkv, wk), self._lin(nkv, wv), d, False
 
     def _attn_block_fwd(self, q_in, kv_in, _unused, norm_q, norm_kv, attn, kmask, B, Lq, Lk, heads, hd, p, norm_f, fc1, fc2, self_attn,
-                        pre_q=None, pre_kv=None):
+                        pre_q=None, pre_kv=None, probs=None):
         """pre-norm attention + FFN block (TransformerEncoderLayer.forward text_encoder.py:373-399 and
         MultiHeadCrossAttention.forward cross_attention.py:285-299).  pre_q / pre_kv: the results of _cross_q_path / _cross_kv_path when
         the caller issued them earlier (on another stream, already joined)."""
@@ -829,7 +833,8 @@ class HipEngine:
             nq, stq, Q = pre_q if pre_q is not None else self._cross_q_path(q_in, norm_q, attn)
             nkv, stkv, Kt, V, ldkv, fused = pre_kv if pre_kv is not None else self._cross_kv_path(kv_in, norm_kv, attn, d)
             ldq = d
-        probs = torch.empty((B, heads, Lq, Lk), device=Q.device, dtype=torch.float32)
+        if probs is None:
+            probs = torch.empty((B, heads, Lq, Lk), device=Q.device, dtype=torch.float32)
         ctx = torch.empty((B * Lq, d), device=Q.device, dtype=T)
         sa = self._seed()
         if T == torch.bfloat16 and Lq <= 32 and Lk <= 160 and hd in (32, 64):
@@ -849,8 +854,9 @@ class HipEngine:
                     x1=x1, nf=nf, stf=stf, h=h, s1=s1, s2=s2, out=out, p=p, norm_q=norm_q, norm_kv=norm_kv, attn=attn, norm_f=norm_f,
                     fc1=fc1, fc2=fc2, self_attn=self_attn, B=B, Lq=Lq, Lk=Lk, heads=heads, hd=hd)
 
-    def _attn_block_bwd(self, rec, dout, G, dkv_addend=None, kv_side=False, addend_event=None):
+    def _attn_block_bwd(self, rec, dout, G, dkv_addend=None, kv_side=False, addend_event=None, dprobs=None):
         """Returns (d q_in, d kv_in, event) ; for self-attention d kv_in is folded into d q_in.
+        dprobs: fp32 gradient on the saved softmax rec["probs"] (aux['cross_attention_weights']) -> the _dp attention backward.
         kv_side: the K / V projection's data gradient and norm_kv's backward (they only feed the image-token gradient, which the query
         chain of the remaining layers does not need) run on the text stream; `event` then marks d kv_in.  addend_event: the event of
         the dkv_addend handed in by such a layer."""
@@ -876,11 +882,13 @@ class HipEngine:
             dK, dV = dkv, dkv[:, d:]
         else:
             dQ = torch.empty((B * Lq, d), device=dev, dtype=T); dK = torch.empty((B * Lk, d), device=dev, dtype=T); dV = torch.empty((B * Lk, d), device=dev, dtype=T)
+        pr = (ptr(rec["probs"]),) if dprobs is None else (ptr(rec["probs"]), ptr(dprobs))
+        dp = "" if dprobs is None else "_dp"
         if T == torch.bfloat16 and Lq <= 32 and Lk <= 160 and hd in (32, 64):
-            call("vqa_attention_bwd_mfma", ptr(dctx), d, ptr(rec["Q"]), ptr(rec["K"]), ptr(rec["V"]), ldq, ldkv, ldkv, ptr(rec["probs"]),
+            call("vqa_attention_bwd_mfma" + dp, ptr(dctx), d, ptr(rec["Q"]), ptr(rec["K"]), ptr(rec["V"]), ldq, ldkv, ldkv, *pr,
                  ptr(dQ), ptr(dK), ptr(dV), ldq, ldkv, ldkv, B, heads, Lq, Lk, hd, float(p), rec["sa"])
         else:
-            call("vqa_attention_bwd", dt(T), ptr(dctx), d, ptr(rec["Q"]), ptr(rec["K"]), ptr(rec["V"]), ldq, ldkv, ldkv, ptr(rec["probs"]),
+            call("vqa_attention_bwd" + dp, dt(T), ptr(dctx), d, ptr(rec["Q"]), ptr(rec["K"]), ptr(rec["V"]), ldq, ldkv, ldkv, *pr,
                  ptr(dQ), ptr(dK), ptr(dV), ldq, ldkv, ldkv, B, heads, Lq, Lk, hd, float(p), rec["sa"])
         if rec["self_attn"]:
             if fused:
@@ -924,10 +932,65 @@ class HipEngine:
 
     # ------------------------------------------------------------------ backward
     def backward(self, tape: dict, dlogits: torch.Tensor, G: torch.Tensor, on_segment: Optional[Callable[[str], None]] = None):
-        """G: flat fp32 gradient buffer (same layout as the parameters), accumulated into (+=)."""
-        cfg, T = self.cfg, self.dtype
-        training = tape["training"]
-        B = tape["B"]
+        """G: flat fp32 gradient buffer (same layout as the parameters), accumulated into (+=).  The three parts below (head,
+        fusion, encoders) run back to back without joining their side streams in between."""
+        self._bwd_begin()
+        seg = self._seg_fn(on_segment)
+        dfused = self._head_bwd(tape, dlogits, G, seg)
+        dfeat, denc, dq, add_dq = self._fusion_bwd(tape, dfused, G, seg)
+        ev_tb = self._encoders_bwd(tape, dfeat, denc, dq, G, seg, add_dq=add_dq)
+        self._bwd_join(ev_tb)
+
+    # The same backward in three separately callable parts, split where it reports its segments (graph-connected aux outputs:
+    # dropin/models/vqa_model.py).  Each part joins its side streams, flushes its weight-gradient / fold queues, releases the tensors
+    # it kept for the side streams and drops its records from the tape (running a part twice raises).  `taps`: optional fp32
+    # gradients on the aux outputs, added where those tensors enter the backward (a tap that is None costs nothing).
+    def backward_head(self, tape: dict, dlogits: Optional[torch.Tensor], G: torch.Tensor, on_segment=None):
+        """dlogits -> dfused (compute dtype [B][d]); None when dlogits is None (the head is skipped, its gradients stay as they are)."""
+        self._bwd_begin()
+        dfused = self._head_bwd(self._tape_part(tape, "head"), dlogits, G, self._seg_fn(on_segment))
+        self._bwd_join()
+        tape.pop("head", None)
+        return dfused
+
+    def backward_fusion(self, tape: dict, dfused: Optional[torch.Tensor], G: torch.Tensor, on_segment=None, taps: Optional[dict] = None):
+        """dfused (compute dtype or fp32 [B][d], or None) -> (dfeat [B*Hf*Wf][Cf], denc [B*L][d]) in the compute dtype.
+        taps: fused / attended_pooled / text_pooled ([B][d]), image_projected ([B][ntok][d]), cross_attention_weights (per layer
+        [B][H][L][ntok] or None)."""
+        self._bwd_begin()
+        dfeat, denc, dq, add_dq = self._fusion_bwd(self._tape_part(tape, "pool"), dfused, G, self._seg_fn(on_segment), taps or {})
+        if add_dq:
+            call("vqa_add", dt(self.dtype), ptr(denc), ptr(dq), ptr(denc), denc.numel())
+        self._bwd_join()
+        for k in ("pool", "clayers", "proj", "caw"):
+            tape.pop(k, None)
+        return dfeat, denc
+
+    def backward_encoders(self, tape: dict, dfeat: Optional[torch.Tensor], denc: Optional[torch.Tensor], G: torch.Tensor, on_segment=None,
+                          taps: Optional[dict] = None):
+        """(dfeat, denc) -> parameter gradients of the text encoder, the CNN stages and the stem.
+        taps: image_features (fp32 NCHW [B][Cf][Hf][Wf]) -> dfeat, text_features (fp32 [B][L][d]) -> denc."""
+        self._bwd_begin()
+        ev_tb = self._encoders_bwd(self._tape_part(tape, "stages"), dfeat, denc, None, G, self._seg_fn(on_segment), taps or {}, add_dq=False)
+        self._bwd_join(ev_tb)
+        for k in ("stages", "stem", "tlayers", "final_norm", "embed", "feat"):
+            tape.pop(k, None)
+
+    @staticmethod
+    def _tape_part(tape, key):
+        if key not in tape:
+            raise RuntimeError(f"backward: the activations of this part ({key}) are gone -- its backward already ran "
+                               "(the reference needs retain_graph=True for that)")
+        return tape
+
+    def _tap(self, g, acc, rows, cols, ld, layout=0):
+        """acc (compute dtype) += g (fp32 upstream gradient of an aux output)."""
+        g = g.detach().to(device=acc.device, dtype=torch.float32).contiguous()
+        if g.numel() != rows * cols:
+            raise RuntimeError(f"aux gradient of {g.numel()} elements where {rows} x {cols} are expected")
+        call("vqa_grad_tap_add", dt(acc), ptr(g), ptr(acc), rows, cols, ld, layout)
+
+    def _bwd_begin(self):
         if getattr(self, "_pack_ev", None) is not None:             # the transposed data-gradient operands / stem helper of begin_step
             torch.cuda.current_stream().wait_event(self._pack_ev)
             self._pack_ev = None
@@ -937,6 +1000,16 @@ class HipEngine:
         self._foldq = []
         self._foldq2 = []
 
+    def _bwd_join(self, ev_text=None):
+        self._flush_wgq()                          # (both queues are empty here: every token-side section ends in seg())
+        fq, self._foldq = self._foldq, []
+        K.fold_group(fq)
+        self._join_off_path()
+        if ev_text is not None:
+            torch.cuda.current_stream().wait_event(ev_text)
+        self._keep = []                           # main is now ordered after every side-stream reader: plain frees are safe
+
+    def _seg_fn(self, on_segment):
         def seg(name):
             """Report a finished gradient segment.  The bucket may be all-reduced once everything enqueued so far on the CURRENT
             stream and on the weight-gradient side stream has run: hand both events to the reducer (its communication stream
@@ -955,18 +1028,44 @@ class HipEngine:
             if self.wgrad_stream and self.two_streams and self.side2 is not None:
                 e2 = torch.cuda.Event(); e2.record(self.side2); evs.append(e2)
             on_segment(name, evs)
-        dl = dlogits.to(T).contiguous() if dlogits.dtype != T else dlogits.contiguous()
+        return seg
 
-        # ---- head
+    def _head_bwd(self, tape, dlogits, G, seg):
+        if dlogits is None:
+            return None
+        T = self.dtype
+        dl = dlogits.to(T).contiguous() if dlogits.dtype != T else dlogits.contiguous()
         hdr = tape["head"]; c = "answer_head.classifier"
         dz = self._act_bwd(dl, None, c + ".6.bias", G, 0.0, 0, off_chain=self.chain_trim)
         dz = self._lin_act_bwd(dz, hdr["h2"], c + ".6.weight", c + ".3.bias", G, hdr["p"])
         dz = self._lin_act_bwd(dz, hdr["h1"], c + ".3.weight", c + ".0.bias", G, hdr["p"])
         dfused = self._lin_bwd(dz, hdr["fused"], c + ".0.weight", G)
         seg("answer_head")
+        return dfused
 
+    def _fusion_bwd(self, tape, dfused, G, seg, taps=None):
+        """Returns (dfeat, denc, dq, add_dq): dq is the query-path text gradient; add_dq: it is still to be added to denc (on the
+        text stream, chain_trim)."""
+        cfg, T = self.cfg, self.dtype
+        B = tape["B"]
+        taps = taps or {}
         # ---- fusion tail: output norm, gate, pools
         pr = tape["pool"]; d, L = pr["d"], pr["L"]
+        # dfused may come from autograd in any layout (an expanded or transposed gradient): the kernels below read it row-major, and
+        # a caller's tensor is never written (the fused tap accumulates into a copy)
+        if dfused is not None and tuple(dfused.shape) != tuple(pr["fused_pre"].shape):
+            raise RuntimeError(f"dfused of shape {tuple(dfused.shape)}, expected {tuple(pr['fused_pre'].shape)}")
+        if dfused is None:
+            dfused = torch.zeros_like(pr["fused_pre"])
+        elif dfused.dtype != T:
+            src, dfused = dfused.contiguous(), torch.empty_like(pr["fused_pre"])
+            call("vqa_convert", dt(src), dt(T), ptr(src), ptr(dfused), dfused.numel())
+        elif taps.get("fused") is not None:
+            dfused = dfused.clone(memory_format=torch.contiguous_format)
+        else:
+            dfused = dfused.contiguous()
+        if taps.get("fused") is not None:
+            self._tap(taps["fused"], dfused, B, d, d)
         dfp = self._ln_bwd(dfused, pr["fused_pre"], "fusion.output_norm", pr["fst"], G)
         dcat = torch.empty_like(pr["cat"])
         if cfg["use_gating"]:
@@ -976,37 +1075,77 @@ class HipEngine:
             dcat = self._lin_bwd(dzg, pr["cat"], "fusion.gate.gate.0.weight", G, addend=dcat)
         else:
             dcat[:, :d] = dfp; dcat[:, d:] = dfp
+        if taps.get("attended_pooled") is not None:
+            self._tap(taps["attended_pooled"], dcat, B, d, 2 * d)
+        if taps.get("text_pooled") is not None:
+            self._tap(taps["text_pooled"], dcat[:, d:], B, d, 2 * d)
         dq = torch.empty_like(pr["q"])
         denc = torch.empty_like(pr["enc"])
         call("vqa_masked_pool_pair_bwd", dt(T), ptr(dcat), ptr(pr["maskf"]), ptr(dq), ptr(denc), B, L, d)
         # ---- cross-attention layers (reverse); image-token gradient accumulates across layers
         dimg, ev_img = None, None
         side_ok = self.hoist_cross and self.two_streams and self.side is not None
+        dprobs = taps.get("cross_attention_weights")
         for li in range(len(tape["clayers"]) - 1, -1, -1):
+            dpl = None if dprobs is None else dprobs[li]
+            if dpl is not None:
+                dpl = dpl.detach().to(device=dcat.device, dtype=torch.float32).contiguous()
+                if dpl.numel() != tape["clayers"][li]["probs"].numel():
+                    raise RuntimeError(f"aux gradient of cross_attention_weights[{li}] has {dpl.numel()} elements, "
+                                       f"expected {tape['clayers'][li]['probs'].numel()}")
             dq, dimg, ev_img = self._attn_block_bwd(tape["clayers"][li], dq, G, dkv_addend=dimg, kv_side=side_ok and li >= 1,
-                                                    addend_event=ev_img)
+                                                    addend_event=ev_img, dprobs=dpl)
         if ev_img is not None:                                    # (a single layer never takes the side path; kept for safety)
             torch.cuda.current_stream().wait_event(ev_img)
+        rp = tape["proj"]
+        if dimg is None:                                          # no cross-attention layer: the image tokens feed nothing but the aux tap
+            dimg = torch.zeros((B * rp["ntok"], d), device=dcat.device, dtype=T)
+        if taps.get("image_projected") is not None:
+            self._tap(taps["image_projected"], dimg, B * rp["ntok"], d, d)
         # dq is now the gradient wrt text features through the query path: it joins the pooled-text gradient on the text stream below
         # (only the text encoder's backward reads the sum; the projector / CNN chain does not wait for it)
         add_on_side = self.chain_trim and self.two_streams and self.side is not None
         if not add_on_side:
             call("vqa_add", dt(T), ptr(denc), ptr(dq), ptr(denc), denc.numel())
         # ---- projector
-        pj = "fusion.image_projector.projection"; rp = tape["proj"]
+        pj = "fusion.image_projector.projection"
         dpos = self._gslice(G, "fusion.image_projector.position_embedding")
         dpz = self._ln_bwd(dimg, rp["pz"], pj + ".1", rp["st"], G, p=rp["p"], seed=rp["seed"], dadd=dpos, period=rp["ntok"])
         dpz = self._act_bwd(dpz, None, pj + ".0.bias", G, 0.0, 0, off_chain=self.chain_trim)
         dfeat = self._lin_bwd(dpz, rp["feat"], pj + ".0.weight", G)
         seg("fusion")
+        return dfeat, denc, dq, add_on_side
 
+    def _encoders_bwd(self, tape, dfeat, denc, dq, G, seg, taps=None, add_dq=False):
+        """Text encoder (side stream) and CNN backward; returns the text stream's completion event (or None)."""
+        cfg, T = self.cfg, self.dtype
+        training = tape["training"]
+        B = tape["B"]
+        taps = taps or {}
+        d = cfg["embed_dim"]
+        ft = tape["feat"]
+        ntok, Cf = ft["Hf"] * ft["Wf"], ft["Cf"]
+        dev = self.flat.device
+        rows = tape["embed"]["ids"].numel()
+        for name, t, shape in (("dfeat", dfeat, (B * ntok, Cf)), ("denc", denc, (rows, d))):
+            if t is not None and (tuple(t.shape) != shape or t.dtype != T):
+                raise RuntimeError(f"{name}: expected {shape} in {T}, got {tuple(t.shape)} in {t.dtype}")
+        # a caller's tensor is never written: a tap accumulates into a copy
+        own = lambda t, key: t.clone(memory_format=torch.contiguous_format) if taps.get(key) is not None else t.contiguous()
+        dfeat = torch.zeros((B * ntok, Cf), device=dev, dtype=T) if dfeat is None else own(dfeat, "image_features")
+        denc = torch.zeros((rows, d), device=dev, dtype=T) if denc is None else own(denc, "text_features")
+        if taps.get("image_features") is not None:
+            self._tap(taps["image_features"], dfeat, B * ntok, Cf, ntok, layout=1)
+        if taps.get("text_features") is not None:
+            self._tap(taps["text_features"], denc, denc.shape[0], d, d)
+        add_on_side = add_dq
         # ---- text encoder backward on the side stream, concurrently with the CNN backward below
         main = torch.cuda.current_stream()
         use_side = self.two_streams and self.side is not None
         if use_side:
             evf = torch.cuda.Event(); evf.record(main)
             self.side.wait_event(evf)
-            self._keep.extend([denc, dq])                 # allocated on main, consumed on the side stream: alive until the join below
+            self._keep.extend([t for t in (denc, dq) if t is not None])     # allocated on main, consumed on the side stream: alive until the join below
         with torch.cuda.stream(self.side if use_side else main):
             if add_on_side:
                 call("vqa_add", dt(T), ptr(denc), ptr(dq), ptr(denc), denc.numel())
@@ -1077,13 +1216,7 @@ class HipEngine:
         # ---- stem
         self._stem_bwd(tape, dxc, G, training, after_reduce=lambda: (self._flush_deferred_and_report(seg)))
         seg("image_encoder.stem")
-        self._flush_wgq()                          # (both queues are empty here: every token-side section ends in seg())
-        fq, self._foldq = self._foldq, []
-        K.fold_group(fq)
-        self._join_off_path()
-        if use_side:
-            main.wait_event(ev_tb)
-        self._keep = []                           # main is now ordered after every side-stream reader: plain frees are safe
+        return ev_tb if use_side else None
 
     def _flush_deferred_and_report(self, seg):
         had_deferred = bool(self._deferred)
