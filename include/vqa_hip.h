@@ -61,12 +61,8 @@ int vqa_pack_transpose_batch(int dtype, const float* flat, void* out, const long
  * dst_off (elements of wout), bias_off (floats of bout), blk0}.  vqa_igemm's relu argument: 1 = ReLU before the addend,
  * 2 = ReLU after the addend (relu(conv + bias + residual)). */
 int vqa_fold_bn_batch(int dtype, const float* flat, void* wout, float* bout, const long long* desc, int nd, int total_blocks, float eps, hipStream_t stream);
-/* stage-1 3x3/1 conv, 64->64 channels, bf16, LDS-resident input patch (models/cnn_backbone.py:182-187 at Cin=Cout=64):
- * forward (w = [Cout][R][S][Cin]) and data gradient (w = flipped+transposed pack, out += addend*(addmask>0)); weight gradient. */
-int vqa_conv3x3_c64_blocks(int B, int H, int W);
-int vqa_conv3x3_c64(const void* x, const void* w, void* out, float* stats, const void* addend, const void* addmask,
-                    int B, int H, int W, hipStream_t stream);
-/* same conv (forward, or data gradient with the flipped pack) without epilogue inputs: 8-wave persistent kernel, 8 output rows per
+/* stage-1 3x3/1 conv, 64->64 channels, bf16, LDS-resident input patch (models/cnn_backbone.py:182-187 at Cin=Cout=64): forward
+ * (w = [Cout][R][S][Cin]) or data gradient (w = flipped+transposed pack) without epilogue inputs: 8-wave persistent kernel, 8 output rows per
  * block, input patches by LDS-DMA, weights in registers; stats [vqa_conv3x3_c64p_blocks][2][64] or NULL.  H % 8 == 0, W % 8 == 0. */
 int vqa_conv3x3_c64p_blocks(int B, int H, int W);
 /* ... and the data gradient of a residual block's conv1 (w = flipped + transposed pack) with the identity path in the epilogue:
@@ -199,8 +195,6 @@ int vqa_bn_bwd_apply(int dtype, const void* dout, const void* outact, const void
 
 /* ---- stem tail: BN + ReLU + MaxPool2d(3,2,1) fused (models/cnn_backbone.py:351-353) ----------------------------- */
 int vqa_stem_pool_fwd(int dtype, const void* y, const float* coef, void* out, uint8_t* idx, int B, int H, int W, int C, hipStream_t stream);
-int vqa_stem_bwd_reduce(int dtype, const void* dpool, const uint8_t* idx, const void* y, const float* coef, float* slab,
-                        int B, int H, int W, int C, hipStream_t stream);
 int vqa_stem_bwd_apply(int dtype, const void* dpool, const uint8_t* idx, const void* y, const float* coef, const float* bcoef,
                        void* dy, int B, int H, int W, int C, hipStream_t stream);
 

@@ -31,8 +31,6 @@ SIGNATURES = {
     "vqa_pack_transpose": [I, P, P, I, I, I, I, I, I, P],
     "vqa_pack_transpose_batch": [I, P, P, P, I, I, P],
     "vqa_fold_bn_batch": [I, P, P, P, P, I, I, F, P],
-    "vqa_conv3x3_c64_blocks": [I, I, I],
-    "vqa_conv3x3_c64": [P, P, P, P, P, P, I, I, I, P],
     "vqa_conv3x3_c64p_blocks": [I, I, I],
     "vqa_conv3x3_c64p": [P, P, P, P, I, I, I, I, P],
     "vqa_conv3x3_c64p_epi": [P, P, P, P, P, P, I, I, I, P],
@@ -71,7 +69,6 @@ SIGNATURES = {
     "vqa_bn_bwd_finalize": [P, I, I, I, D, P, P, I, P, P, P, P],
     "vqa_bn_bwd_apply": [I, P, P, P, P, P, P, P, P, LL, I, P, P],
     "vqa_stem_pool_fwd": [I, P, P, P, P, I, I, I, I, P],
-    "vqa_stem_bwd_reduce": [I, P, P, P, P, P, I, I, I, I, P],
     "vqa_stem_bwd_apply": [I, P, P, P, P, P, P, I, I, I, I, P],
     "vqa_se_fwd": [I, P, P, P, P, P, P, P, I, I, I, I, P, I, P],
     "vqa_se_bwd": [I, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, P, P, P, I, P],
@@ -116,7 +113,7 @@ SIGNATURES = {
     "vqa_adamw": [P, P, P, P, LL, F, F, F, F, F, LL, P, F, F, P, P, P, P],
 }
 _RET_LL = {"vqa_image_resize_ws", "vqa_wgrad_group_ws", "vqa_spatial_bwd_scratch", "vqa_se_bwd_scratch", "vqa_layernorm_bwd_ws", "vqa_bias_act_bwd_ws"}                       # return a size (long long)
-_NO_STATUS = _RET_LL | {"vqa_wgrad3x3_c64_blocks", "vqa_bn_acc_words", "vqa_bn_apply_pool_chunks", "vqa_se_bwd_blocks", "vqa_wgrad3x3_c128_blocks", "vqa_layernorm_bwd_folds", "vqa_bias_act_bwd_fold_rows", "vqa_conv3x3_c64p_blocks", "vqa_stem_wgrad_blocks", "vqa_igemm_mtiles", "vqa_igemm_variant", "vqa_bn_bwd_blocks", "vqa_stem_conv_blocks", "vqa_conv3x3_c64_blocks", "vqa_stem_conv_pool_ok", "vqa_wgrad3x3_c64_bn_ok", "vqa_conv8p_ok"}   # return a count, not a status
+_NO_STATUS = _RET_LL | {"vqa_wgrad3x3_c64_blocks", "vqa_bn_acc_words", "vqa_bn_apply_pool_chunks", "vqa_se_bwd_blocks", "vqa_wgrad3x3_c128_blocks", "vqa_layernorm_bwd_folds", "vqa_bias_act_bwd_fold_rows", "vqa_conv3x3_c64p_blocks", "vqa_stem_wgrad_blocks", "vqa_igemm_mtiles", "vqa_igemm_variant", "vqa_bn_bwd_blocks", "vqa_stem_conv_blocks", "vqa_stem_conv_pool_ok", "vqa_wgrad3x3_c64_bn_ok", "vqa_conv8p_ok"}   # return a count, not a status
 
 _lib = None
 

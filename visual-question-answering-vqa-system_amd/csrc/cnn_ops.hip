@@ -474,38 +474,6 @@ __global__ __launch_bounds__(256) void stem_pool_fwd_kernel(const T* __restrict_
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void stem_bwd_reduce_kernel(const T* __restrict__ dpool, const uint8_t* __restrict__ idx, const T* __restrict__ y,
-                                                              const float* __restrict__ coef, float* __restrict__ slab,
-                                                              int B, int H, int W, int C, int Ho, int Wo) {
-  constexpr int VEC = Vec16<T>::N;
-  const int cv = C / VEC, lanes_r = 256 / cv;
-  const int myv = threadIdx.x % cv, myr = threadIdx.x / cv, c0 = myv * VEC;
-  const size_t rows = (size_t)B * H * W;
-  float sg[VEC], sx[VEC], g[VEC], sc[VEC], sh[VEC], mean[VEC], inv[VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) { sg[j] = sx[j] = 0.f; sc[j] = coef[c0 + j]; sh[j] = coef[C + c0 + j]; mean[j] = coef[2 * C + c0 + j]; inv[j] = coef[3 * C + c0 + j]; }
-  if (myr < lanes_r)
-    for (size_t r = (size_t)blockIdx.x * lanes_r + myr; r < rows; r += (size_t)gridDim.x * lanes_r) {
-      const int w = (int)(r % W); size_t q = r / W; const int h = (int)(q % H); const int b = (int)(q / H);
-      Vec16<T> yy = ldg16(y + r * C + c0);
-      stem_route<T>(dpool, idx, yy, sc, sh, b, h, w, c0, C, Ho, Wo, g);
-#pragma unroll
-      for (int j = 0; j < VEC; ++j) { sg[j] += g[j]; sx[j] += g[j] * (yy.get(j) - mean[j]) * inv[j]; }
-    }
-  extern __shared__ float shm[];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) { shm[(0 * 256 + threadIdx.x) * VEC + j] = sg[j]; shm[(1 * 256 + threadIdx.x) * VEC + j] = sx[j]; }
-  __syncthreads();
-  for (int o = threadIdx.x; o < 2 * C; o += 256) {
-    const int k = o / C, c = o - k * C, v = c / VEC, j = c - v * VEC;
-    float s = 0.f;
-    for (int r = 0; r < lanes_r; ++r) s += shm[(k * 256 + r * cv + v) * VEC + j];
-    slab[((size_t)blockIdx.x * 3 + k) * C + c] = s;
-    if (k == 0) slab[((size_t)blockIdx.x * 3 + 2) * C + c] = 0.f;
-  }
-}
-
-template <typename T>
 __global__ void stem_bwd_apply_kernel(const T* __restrict__ dpool, const uint8_t* __restrict__ idx, const T* __restrict__ y,
                                       const float* __restrict__ coef, const float* __restrict__ bc, T* __restrict__ dy,
                                       int B, int H, int W, int C, int Ho, int Wo) {
@@ -1343,15 +1311,6 @@ int vqa_stem_pool_fwd(int dtype, const void* y, const float* coef, void* out, ui
      hipLaunchKernelGGL(stem_pool_fwd_kernel<bf16_t>, dim3((unsigned)tiles), dim3(threads), 0, st, (const bf16_t*)y, coef, (bf16_t*)out, idx, B, H, W, C, Ho, Wo, trows));
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
-int vqa_stem_bwd_reduce(int dtype, const void* dpool, const uint8_t* idx, const void* y, const float* coef, float* slab, int B, int H, int W, int C, hipStream_t st) {
-  const int VEC = dtype ? 8 : 4, Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
-  if (C % 8 || 256 % (C / VEC)) return VQA_EARG;
-  const int nb = vqa_bn_bwd_blocks((long long)B * H * W);
-  const size_t shm = (size_t)2 * 256 * VEC * 4;
-  DT(hipLaunchKernelGGL(stem_bwd_reduce_kernel<float>, dim3(nb), dim3(256), shm, st, (const float*)dpool, idx, (const float*)y, coef, slab, B, H, W, C, Ho, Wo),
-     hipLaunchKernelGGL(stem_bwd_reduce_kernel<bf16_t>, dim3(nb), dim3(256), shm, st, (const bf16_t*)dpool, idx, (const bf16_t*)y, coef, slab, B, H, W, C, Ho, Wo));
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
 int vqa_stem_bwd_apply(int dtype, const void* dpool, const uint8_t* idx, const void* y, const float* coef, const float* bc, void* dy, int B, int H, int W, int C, hipStream_t st) {
   const int VEC = dtype ? 8 : 4, Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
   const size_t total = (size_t)B * H * W * (C / VEC);
@@ -1410,7 +1369,7 @@ int vqa_se_bwd(int dtype, const void* dout, const void* x, const float* w1, cons
 #define SE_FUSED_KT(R_, NR, NL, TM) do { \
       const size_t shl = ((shm2 + 15) & ~(size_t)15) + (size_t)(NL) * nt * 17 + ((TM) ? (size_t)ntail * nt : 0); \
       auto kfn = se_bwd_fused_kernel<bf16_t, R_, NR, NL, TM>; \
-      if (shl > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shl); \
+      (void)vqa_ensure_lds(reinterpret_cast<const void*>(kfn), shl); \
       hipLaunchKernelGGL(kfn, dim3(B), dim3(nt), shl, st, (const bf16_t*)dout, (const bf16_t*)x, w1, w2, hidden, scale, dz2, dh, dpool, (bf16_t*)dx, \
                          HW, C, Cr, mask_out, (const bf16_t*)bn_y, bn_coef, (unsigned long long*)bn_slab); } while (0)
 #define SE_FUSED_D(R_) do { if (nreg == 2) SE_FUSED_K(R_, 2, 0); else if (nlds == 0) SE_FUSED_K(R_, 4, 0); else if (nlds == 2) SE_FUSED_K(R_, 4, 2); \

@@ -5,6 +5,9 @@
 
 #include <stdlib.h>
 
+#include <atomic>
+#include <mutex>
+
 // Measurement / ablation switches (tile choices, and the VQA_*_DBG phase switches that give WRONG results on purpose) are
 // environment variables only in builds made with -DVQA_ABLATION (tools/build_ablation.py makes its own libvqa_hip_ablation.so).
 // The product library ignores the environment: every switch is its shipped default, folded at compile time.
@@ -174,3 +177,46 @@ __device__ __forceinline__ void bn_acc_coef(const BnAcc& f, int C, int c, double
 }
 
 #define VQA_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
+
+// ------------------------------------------------------------------------------------------------------------------
+// Dynamic LDS above the default limit: every launch site calls vqa_ensure_lds(kernel, bytes) before its launch.  The largest size
+// set so far is remembered per (kernel, device) in a fixed lock-free table, so the common case is one hipGetDevice and a few atomic
+// loads; only a size larger than the recorded one takes the mutex and calls hipFuncSetAttribute, and under the mutex the recorded
+// size only grows, so racing threads never leave a smaller limit set last.  (Table full or device index out of range: the
+// attribute is set on every call, still correct.)  Returns the HIP error; launch sites keep VQA_LAUNCH_CHECK.
+// ------------------------------------------------------------------------------------------------------------------
+#define VQA_LDS_SLOTS 256
+#define VQA_LDS_DEVICES 16
+struct VqaLdsSlot { std::atomic<const void*> kernel; std::atomic<size_t> bytes[VQA_LDS_DEVICES]; };
+inline VqaLdsSlot vqa_lds_slots[VQA_LDS_SLOTS];       // zero-initialised, shared by every translation unit of the library
+inline std::mutex vqa_lds_mutex;
+
+static inline VqaLdsSlot* vqa_lds_find(const void* kernel, bool insert) {
+  const size_t h = (size_t)(reinterpret_cast<uintptr_t>(kernel) >> 4) % VQA_LDS_SLOTS;
+  for (size_t i = 0; i < VQA_LDS_SLOTS; ++i) {
+    VqaLdsSlot& s = vqa_lds_slots[(h + i) % VQA_LDS_SLOTS];
+    const void* k = s.kernel.load(std::memory_order_acquire);
+    if (k == kernel) return &s;
+    if (!k) {                                          // slots are only ever claimed under the mutex (insert == true)
+      if (insert) s.kernel.store(kernel, std::memory_order_release);
+      return insert ? &s : nullptr;
+    }
+  }
+  return nullptr;
+}
+static inline hipError_t vqa_ensure_lds(const void* kernel, size_t bytes) {
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  const bool cached = dev >= 0 && dev < VQA_LDS_DEVICES;
+  if (cached) {
+    const VqaLdsSlot* s = vqa_lds_find(kernel, false);
+    if (s && s->bytes[dev].load(std::memory_order_acquire) >= bytes) return hipSuccess;
+  }
+  std::lock_guard<std::mutex> lock(vqa_lds_mutex);
+  VqaLdsSlot* s = cached ? vqa_lds_find(kernel, true) : nullptr;
+  if (s && s->bytes[dev].load(std::memory_order_relaxed) >= bytes) return hipSuccess;
+  e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  if (e == hipSuccess && s) s->bytes[dev].store(bytes, std::memory_order_release);
+  return e;
+}

@@ -1,22 +1,20 @@
 // 3x3 / stride 1 / pad 1 convolution with 64 input and 64 output channels (stage 1 of the ResNet, bf16):
 // forward (models/cnn_backbone.py:182-187 with Cin=Cout=64), its data gradient (same kernel, flipped weights) and its
 // weight gradient, written around an LDS-resident INPUT PATCH instead of the generic implicit-GEMM gather:
-//   * a workgroup walks (image, 2 output rows) blocks persistently; the 4 x (W+2) x 64 input patch of a block is loaded
+//   * a workgroup walks (image, output rows) blocks persistently; the (rows+2) x (W+2) x 64 input patch of a block is loaded
 //     once (zero padded by the buffer range check), stored XOR-swizzled in LDS and reused by all 9 filter taps;
-//   * forward/dgrad: every wave keeps its 36 weight fragments (its 32 output channels x K=576) in registers for the
-//     whole launch; A fragments are ds_read_b128 straight out of the patch (implicit im2col in LDS);
+//   * forward/dgrad (8-wave kernel): every wave keeps the weight fragments of its output channels in registers for the
+//     whole launch; A fragments are read straight out of the patch (implicit im2col in LDS);
 //   * wgrad: contraction over pixels, both operands via ds_read_b64_tr_b16, 64x576 partial dW in registers over the
-//     whole walk, one atomic flush per workgroup.
+//     whole walk, one flush per workgroup.
 // These layers are HBM-bound in bf16 (288 flop/byte); the patch cuts L2/HBM reads ~9x versus a per-tap gather.
 #include <cstdlib>
 #include <utility>
 #include "common.h"
 
 namespace {
-constexpr int RBF = 2;            // output rows per block, forward / data gradient
-constexpr int RBG = 4;            // output rows per block, weight gradient
+constexpr int RBG = 4;            // output rows per block, 4-wave weight-gradient kernel
 constexpr int CH = 64;            // channels (in and out)
-constexpr int LDE = 32 + 8;       // epilogue staging row stride (elements)
 constexpr int OOBV = (int)0x80000000;
 
 // element offset of (patch row, patch col, channel chunk) in the swizzled patch: 16-byte chunks XOR (col & 7)
@@ -99,141 +97,6 @@ __device__ __forceinline__ void pre_bn_coef(int mode, const float* pre_coef, con
     else { cf[tid] = pre_coef[tid]; cf[64 + tid] = pre_coef[64 + tid]; }
   }
 }
-}
-
-__global__ __launch_bounds__(256) void conv3x3_c64_kernel(C64Params p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int PWc = p.W + 2;
-  const int patch_elems = (RBF + 2) * PWc * CH;
-  bf16_t* patch0 = reinterpret_cast<bf16_t*>(smem);
-  bf16_t* patch1 = patch0 + patch_elems;
-  bf16_t* Est = patch1 + patch_elems;                       // [4 waves][16][LDE]
-  float* red = reinterpret_cast<float*>(Est + 4 * 16 * LDE); // [2 m-waves][64][2]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
-  const int wn = wave & 1, wm = wave >> 1;                   // wave owns channels [32*wn, 32*wn+32), m tiles wm, wm+2, ...
-  const int rblocks = p.H / RBF, nblocks = p.B * rblocks;
-  const int mtiles = RBF * p.W / 16;
-  const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.x), 0, (int)p.x_bytes, 0x00020000);
-
-  // ---- weight fragments: w[n][(r,s,c)] (576 per row), resident for the whole launch
-  bf16x8 bfr[18][2];
-#pragma unroll
-  for (int kk = 0; kk < 18; ++kk)
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
-      bfr[kk][nt] = *reinterpret_cast<const bf16x8*>(p.w + (size_t)(wn * 32 + nt * 16 + li) * 576 + kk * 32 + g * 8);
-
-  // ---- patch staging descriptors, computed once: chunk id -> LDS offset, offset relative to the block's first pixel,
-  //      patch row (for the per-block vertical range check).  No integer division inside the block loop.
-  constexpr int MAXV = 8;
-  const int nchunks = (RBF + 2) * PWc * 8;
-  const float inv_pw = 1.0f / (float)PWc, inv_w = 1.0f / (float)p.W;
-  int s_lds[MAXV], s_rel[MAXV]; unsigned long long s_prow = 0;
-#pragma unroll
-  for (int i = 0; i < MAXV; ++i) {
-    const int id = tid + 256 * i;
-    s_lds[i] = -1; s_rel[i] = OOBV;
-    if (id < nchunks) {
-      const int chunk = id & 7, q = id >> 3, prow = (int)(((float)q + 0.5f) * inv_pw), pcol = q - prow * PWc;
-      s_lds[i] = patch_off(prow, pcol, chunk, PWc);
-      const int iw = pcol - 1;
-      if ((unsigned)iw < (unsigned)p.W) s_rel[i] = (((prow - 1) * p.W + iw) * CH + chunk * 8) * 2;
-      s_prow |= (unsigned long long)prow << (4 * i);
-    }
-  }
-  u32x4 pre[MAXV];
-  auto pload = [&](int blk) {
-    const int b = blk / rblocks, oh0 = (blk - b * rblocks) * RBF;
-    const int base = ((b * p.H + oh0) * p.W) * CH * 2;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-      const int ih = oh0 - 1 + (int)((s_prow >> (4 * i)) & 15);
-      const int off = ((unsigned)ih < (unsigned)p.H && s_rel[i] != OOBV) ? base + s_rel[i] : OOBV;
-      pre[i] = __builtin_amdgcn_raw_buffer_load_b128(rsX, off, 0, 0);
-    }
-  };
-  auto pstore = [&](bf16_t* dst) {
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i)
-      if (s_lds[i] >= 0) *reinterpret_cast<u32x4*>(dst + s_lds[i]) = pre[i];
-  };
-
-  float ssum[2] = {0.f, 0.f}, ssq[2] = {0.f, 0.f};
-  bf16_t* myst = Est + wave * 16 * LDE;
-  int blk = blockIdx.x, buf = 0;
-  if (blk < nblocks) { pload(blk); pstore(patch0); }
-  __syncthreads();
-  for (; blk < nblocks; blk += gridDim.x, buf ^= 1) {
-    const int nxt = blk + gridDim.x;
-    if (nxt < nblocks) pload(nxt);
-    const bf16_t* pt = buf ? patch1 : patch0;
-    const int b = blk / rblocks, oh0 = (blk - b * rblocks) * RBF;
-    for (int mt = wm; mt < mtiles; mt += 2) {
-      const int px = mt * 16 + li, orow = (int)(((float)px + 0.5f) * inv_w), ow = px - orow * p.W;
-      // per-tile address terms: e[s][half] = offset of (row orow, col ow+s, swizzled chunk half*4+g); taps add r*PWc*64
-      int e[3][2];
-#pragma unroll
-      for (int s = 0; s < 3; ++s) {
-        const int col = ow + s, cb = (orow * PWc + col) * 64;
-        e[s][0] = cb + ((g ^ (col & 7)) << 3);
-        e[s][1] = cb + (((4 + g) ^ (col & 7)) << 3);
-      }
-      const int rowstep = PWc * 64;
-      f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-#pragma unroll
-      for (int kk = 0; kk < 18; ++kk) {
-        const int tap = kk >> 1, r = tap / 3, s = tap - r * 3;
-        const bf16x8 af = *reinterpret_cast<const bf16x8*>(pt + e[s][kk & 1] + r * rowstep);
-        acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfr[kk][0], acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfr[kk][1], acc[1], 0, 0, 0);
-      }
-      // epilogue: 16 pixels x 32 channels of this wave -> LDS -> one 16-byte store per lane (+ optional addend)
-#pragma unroll
-      for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-        for (int rr = 0; rr < 4; ++rr) {
-          const float v = acc[nt][rr];
-          ssum[nt] += v; ssq[nt] += v * v;
-          myst[(g * 4 + rr) * LDE + nt * 16 + li] = f2bf(v);
-        }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      {
-        const int pxl = lane >> 2, cv = lane & 3;
-        const int pxo = mt * 16 + pxl, orow2 = (int)(((float)pxo + 0.5f) * inv_w), ow2 = pxo - orow2 * p.W;
-        const size_t off = (((size_t)b * p.H + oh0 + orow2) * p.W + ow2) * CH + wn * 32 + cv * 8;
-        Vec16<bf16_t> v; v.raw = *reinterpret_cast<const u32x4*>(&myst[pxl * LDE + cv * 8]);
-        if (p.addend) {
-          Vec16<bf16_t> av = ldg16(p.addend + off);
-          if (p.addmask) {
-            Vec16<bf16_t> mv = ldg16(p.addmask + off);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v.set(j, v.get(j) + (mv.get(j) > 0.f ? av.get(j) : 0.f));
-          } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v.set(j, v.get(j) + av.get(j));
-          }
-        }
-        stg16(p.out + off, v);
-      }
-      asm volatile("" ::: "memory");
-    }
-    if (nxt < nblocks) pstore(buf ? patch0 : patch1);
-    __syncthreads();
-  }
-  if (p.stats) {
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      float s = ssum[nt], q = ssq[nt];
-      s += __shfl_xor(s, 16, 64); q += __shfl_xor(q, 16, 64);
-      s += __shfl_xor(s, 32, 64); q += __shfl_xor(q, 32, 64);
-      if (lane < 16) { red[(wm * 64 + wn * 32 + nt * 16 + lane) * 2] = s; red[(wm * 64 + wn * 32 + nt * 16 + lane) * 2 + 1] = q; }
-    }
-    __syncthreads();
-    if (tid < 64) {
-      p.stats[((size_t)blockIdx.x * 2) * 64 + tid] = red[tid * 2] + red[(64 + tid) * 2];
-      p.stats[((size_t)blockIdx.x * 2 + 1) * 64 + tid] = red[tid * 2 + 1] + red[(64 + tid) * 2 + 1];
-    }
-  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1030,30 +893,12 @@ extern "C" int vqa_slab_reduce(const float* ws, float* dw, int nslabs, long long
 
 extern "C" {
 
-// persistent grid size (= rows of the BN statistics slab) or 0 when the shape is unsupported
-int vqa_conv3x3_c64_blocks(int B, int H, int W) {
-  if (H % RBG || (RBF * W) % 16 || W > 126 || B * (H / RBG) <= 0) return 0;
-  if (((RBF + 2) * (W + 2) * 8 + 255) / 256 > 8 || ((RBG + 2) * (W + 2) * 8 + 255) / 256 > 12 || (RBG * W * 8 + 255) / 256 > 8) return 0;
+// persistent grid of the 4-wave weight-gradient kernel (wgrad3x3_c64_kernel), 0 when it does not take the shape
+static int c64_wgrad4_blocks(int B, int H, int W) {
+  if (H % RBG || W % 8 || W > 126 || B * (H / RBG) <= 0) return 0;
+  if (((RBG + 2) * (W + 2) * 8 + 255) / 256 > 12 || (RBG * W * 8 + 255) / 256 > 8) return 0;
   const int nb = B * (H / RBG);
   return nb < 512 ? nb : 512;
-}
-// x NHWC bf16 [B][H][W][64]; w [64][(r,s,c)] bf16 (forward: [Cout][R][S][Cin]; data gradient: flipped+transposed pack);
-// out NHWC bf16; stats [blocks][2][64] or NULL; out += addend * (addmask > 0) (identity-path gradient) when given.
-int vqa_conv3x3_c64(const void* x, const void* w, void* out, float* stats, const void* addend, const void* addmask,
-                    int B, int H, int W, hipStream_t st) {
-  const int grid = vqa_conv3x3_c64_blocks(B, H, W);
-  if (!x || !w || !out || grid <= 0) return VQA_EARG;
-  C64Params p;
-  p.x = (const bf16_t*)x; p.w = (const bf16_t*)w; p.out = (bf16_t*)out; p.stats = stats;
-  p.addend = (const bf16_t*)addend; p.addmask = (const bf16_t*)addmask; p.outmask = nullptr; p.bn_y = nullptr; p.bn_coef = nullptr; p.bn_facc = nullptr; p.B = B; p.H = H; p.W = W; p.dbg = 0; p.stats_mode = 0; p.pre_mode = 0; p.pre_coef = nullptr;
-  const size_t xb = (size_t)B * H * W * CH * 2;
-  if (xb >= 0x7fffffffull) return VQA_EARG;
-  p.x_bytes = (unsigned)xb;
-  const size_t shm = (size_t)2 * (RBF + 2) * (W + 2) * CH * 2 + 4 * 16 * LDE * 2 + 2 * 64 * 2 * 4;
-  static size_t attr = 0;
-  if (shm > attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_c64_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); attr = shm; }
-  hipLaunchKernelGGL(conv3x3_c64_kernel, dim3(grid), dim3(256), shm, st, p);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
 }
 // persistent grid of the 8-wave LDS-DMA patch kernel (= rows of its statistics slab), 0 when the shape is unsupported
 static int c64p_rows(int H, int W) {         // output rows per block of the 8-wave patch kernel for this shape, 0: unsupported
@@ -1082,15 +927,12 @@ static int c64p_launch(C64Params& p, const void* x, const void* w, void* out, fl
   p.x_bytes = (unsigned)xb;
   const int rbp = c64p_rows(H, W);
   const size_t shm = (size_t)2 * (rbp + 2) * (W + 2) * CH * 2 + 4 * 64 * 2 * 4 + 4 * 64 * 4;
-  static size_t attr8 = 0, attr4 = 0;
-  static size_t attr[6] = {0, 0, 0, 0, 0, 0};
-#define C64P_GO(RB, EP, SLOT) do { auto kfn = conv3x3_c64p_kernel<RB, EP>; \
-    if (shm > attr[SLOT]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); attr[SLOT] = shm; } \
+#define C64P_GO(RB, EP) do { auto kfn = conv3x3_c64p_kernel<RB, EP>; (void)vqa_ensure_lds(reinterpret_cast<const void*>(kfn), shm); \
     hipLaunchKernelGGL(kfn, dim3(grid), dim3(512), shm, st, p); } while (0)
   if (p.addend && p.bn_y) return VQA_EARG;
-  if (p.addend) { if (rbp == 8) C64P_GO(8, 1, 2); else C64P_GO(4, 1, 3); }
-  else if (p.bn_y) { if (rbp == 8) C64P_GO(8, 2, 4); else C64P_GO(4, 2, 5); }
-  else { if (rbp == 8) C64P_GO(8, 0, 0); else C64P_GO(4, 0, 1); }
+  if (p.addend) { if (rbp == 8) C64P_GO(8, 1); else C64P_GO(4, 1); }
+  else if (p.bn_y) { if (rbp == 8) C64P_GO(8, 2); else C64P_GO(4, 2); }
+  else { if (rbp == 8) C64P_GO(8, 0); else C64P_GO(4, 0); }
 #undef C64P_GO
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
@@ -1137,8 +979,6 @@ int vqa_conv3x3_c64p_bn(const void* y, const unsigned long long* acc, const floa
   p.pre_inv_count = 1.0 / count; p.pre_unbias = count > 1 ? count / (count - 1) : 1.0; p.pre_momentum = momentum; p.pre_eps = eps;
   return c64p_launch(p, y, w, out, stats, B, H, W, stats_mode, st);
 }
-// dw [64][576] fp32 (+=).  ws: scratch of >= vqa_conv3x3_c64_blocks(B,H,W) * 64*576 floats for the deterministic two-pass
-// accumulation (NULL or too small: fp32 atomics)
 // Stage-2 shape only (3x3 / 1 / pad 1, 128 -> 128 channels, 28 x 28 maps, bf16): slabs needed (= workgroups) or 0 when unsupported
 int vqa_wgrad3x3_c128_blocks(int B, int H, int W) {
   const int en = vqa_env_int("VQA_C128WP", 1);
@@ -1154,8 +994,7 @@ int vqa_wgrad3x3_c128(const void* x, const void* dy, float* dw, int B, int H, in
   C128WgradParams p;
   p.x = (const bf16_t*)x; p.dy = (const bf16_t*)dy; p.ws = ws; p.B = B; p.bytes = (unsigned)((size_t)B * H * W * 128 * 2);
   const size_t shm = (size_t)2 * C128_BUF;
-  static bool attr = false;
-  if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3x3_c128p_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); attr = true; }
+  (void)vqa_ensure_lds(reinterpret_cast<const void*>(&wgrad3x3_c128p_kernel), shm);
   hipLaunchKernelGGL(wgrad3x3_c128p_kernel, dim3(grid), dim3(512), shm, st, p);
   hipLaunchKernelGGL(wgrad_c128p_reduce_kernel, dim3(128 * 576 / 4 / 64, 2), dim3(64, 16), 0, st, ws, dw, grid / 2);
   VQA_LAUNCH_CHECK();
@@ -1174,14 +1013,14 @@ static int c64wp_rows(int H, int W, size_t* shm_out) {
 // slabs ([64][576] floats each) vqa_wgrad3x3_c64 needs in `ws` for this shape; 0: neither kernel takes it
 int vqa_wgrad3x3_c64_blocks(int B, int H, int W) {
   if (B <= 0 || H <= 0 || W <= 0) return 0;
-  const int g4 = vqa_conv3x3_c64_blocks(B, H, W);
+  const int g4 = c64_wgrad4_blocks(B, H, W);
   const int rbw = c64wp_rows(H, W, nullptr);
   const int nblk = rbw ? B * (H / rbw) : 0, gp = nblk < 256 ? nblk : 256;
   return g4 > gp ? g4 : gp;
 }
 static int c64_wgrad_launch(const void* x, const float* pre_coef, const void* dy, float* dw, int B, int H, int W, float* ws, long long ws_floats,
                             hipStream_t st) {
-  const int grid = vqa_conv3x3_c64_blocks(B, H, W);            // the 4-wave kernel's persistent grid (0: it does not take the shape)
+  const int grid = c64_wgrad4_blocks(B, H, W);            // the 4-wave kernel's persistent grid (0: it does not take the shape)
   size_t shm_p = 0;
   const int rbw = c64wp_rows(H, W, &shm_p);
   const int nblk_p = rbw ? B * (H / rbw) : 0, grid_p = nblk_p < 256 ? nblk_p : 256;
@@ -1198,12 +1037,11 @@ static int c64_wgrad_launch(const void* x, const float* pre_coef, const void* dy
   if (wp_env && ws && grid_p > 0 && ws_floats >= (long long)grid_p * 64 * 576) {
     p.ws = ws;
     shm_p += 2 * 64 * 4;                                        // cf[2][64] behind the two buffers
-    static size_t attr4 = 0, attr2 = 0;
     if (rbw == 4) {
-      if (shm_p > attr4) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3x3_c64p_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_p); attr4 = shm_p; }
+      (void)vqa_ensure_lds(reinterpret_cast<const void*>(&wgrad3x3_c64p_kernel<4>), shm_p);
       hipLaunchKernelGGL(wgrad3x3_c64p_kernel<4>, dim3(grid_p), dim3(512), shm_p, st, p);
     } else {
-      if (shm_p > attr2) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3x3_c64p_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_p); attr2 = shm_p; }
+      (void)vqa_ensure_lds(reinterpret_cast<const void*>(&wgrad3x3_c64p_kernel<2>), shm_p);
       hipLaunchKernelGGL(wgrad3x3_c64p_kernel<2>, dim3(grid_p), dim3(512), shm_p, st, p);
     }
     VQA_LAUNCH_CHECK();
@@ -1213,8 +1051,7 @@ static int c64_wgrad_launch(const void* x, const float* pre_coef, const void* dy
   p.ws = (ws && ws_floats >= (long long)grid * 64 * 576) ? ws : nullptr;
   const int MP = (RBG * W + 31) / 32 * 32;
   const size_t shm = (size_t)(RBG + 2) * (W + 2) * CH * 2 + (size_t)MP * (CH + 4) * 2;
-  static size_t attr = 0;
-  if (shm > attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3x3_c64_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); attr = shm; }
+  (void)vqa_ensure_lds(reinterpret_cast<const void*>(&wgrad3x3_c64_kernel), shm);
   hipLaunchKernelGGL(wgrad3x3_c64_kernel, dim3(grid), dim3(256), shm, st, p);
   VQA_LAUNCH_CHECK();
   return p.ws ? vqa_slab_reduce(p.ws, dw, grid, 64 * 576, st) : VQA_OK;
@@ -1222,6 +1059,8 @@ static int c64_wgrad_launch(const void* x, const float* pre_coef, const void* dy
 int vqa_wgrad3x3_c64_bn_ok(int B, int H, int W) {               // 1: vqa_wgrad3x3_c64_bn takes this shape (the 8-wave kernel does)
   return B > 0 && H > 0 && c64wp_rows(H, W, nullptr) > 0 && vqa_env_int("VQA_C64WP", 1) && (size_t)B * H * W * CH * 2 < 0x7fffffffull;
 }
+// dw [64][576] fp32 (+=).  ws: vqa_wgrad3x3_c64_blocks(B, H, W) * 64*576 floats for the deterministic two-pass accumulation (the 4-wave
+// kernel falls back to fp32 atomics when it is NULL or too small)
 int vqa_wgrad3x3_c64(const void* x, const void* dy, float* dw, int B, int H, int W, float* ws, long long ws_floats, hipStream_t st) {
   return c64_wgrad_launch(x, nullptr, dy, dw, B, H, W, ws, ws_floats, st);
 }

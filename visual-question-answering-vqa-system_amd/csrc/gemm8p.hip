@@ -819,23 +819,16 @@ int vqa_gemm4w(const void* A, const void* B, void* C, int M, int N, int K, hipSt
   p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = (bf16_t*)C; p.M = M; p.N = N; p.K = K;
   p.a_bytes = (unsigned)ab; p.b_bytes = (unsigned)bb;
   p.tiles_n = N / G8_BN; p.ntiles = (M / G8_BM) * p.tiles_n;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm4w_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS);
-#ifdef VQA_ABLATION
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm4w_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm4w_kernel<12>), hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm4w_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS);
-#endif
-    attr = true;
-  }
+#define G4W_GO(NP3) do { (void)vqa_ensure_lds(reinterpret_cast<const void*>(&gemm4w_kernel<NP3>), G8_LDS); \
+    hipLaunchKernelGGL(gemm4w_kernel<NP3>, dim3(p.ntiles), dim3(256), G8_LDS, st, p); } while (0)
 #ifdef VQA_ABLATION
   const int np3 = vqa_env_int("VQA_G4_NP3", 8);
-  if (np3 == 4) { hipLaunchKernelGGL(gemm4w_kernel<4>, dim3(p.ntiles), dim3(256), G8_LDS, st, p); VQA_LAUNCH_CHECK(); return VQA_OK; }
-  if (np3 == 12) { hipLaunchKernelGGL(gemm4w_kernel<12>, dim3(p.ntiles), dim3(256), G8_LDS, st, p); VQA_LAUNCH_CHECK(); return VQA_OK; }
-  if (np3 == 16) { hipLaunchKernelGGL(gemm4w_kernel<16>, dim3(p.ntiles), dim3(256), G8_LDS, st, p); VQA_LAUNCH_CHECK(); return VQA_OK; }
+  if (np3 == 4) { G4W_GO(4); VQA_LAUNCH_CHECK(); return VQA_OK; }
+  if (np3 == 12) { G4W_GO(12); VQA_LAUNCH_CHECK(); return VQA_OK; }
+  if (np3 == 16) { G4W_GO(16); VQA_LAUNCH_CHECK(); return VQA_OK; }
 #endif
-  hipLaunchKernelGGL(gemm4w_kernel<8>, dim3(p.ntiles), dim3(256), G8_LDS, st, p);
+  G4W_GO(8);
+#undef G4W_GO
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
 int vqa_gemm8p(const void* A, const void* B, void* C, int M, int N, int K, hipStream_t st) {
@@ -846,8 +839,7 @@ int vqa_gemm8p(const void* A, const void* B, void* C, int M, int N, int K, hipSt
   p.A = (const bf16_t*)A; p.B = (const bf16_t*)B; p.C = (bf16_t*)C; p.M = M; p.N = N; p.K = K;
   p.a_bytes = (unsigned)ab; p.b_bytes = (unsigned)bb;
   p.tiles_n = N / G8_BN; p.ntiles = (M / G8_BM) * p.tiles_n;
-  static bool attr = false;
-  if (!attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm8p_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, G8_LDS); attr = true; }
+  (void)vqa_ensure_lds(reinterpret_cast<const void*>(&gemm8p_kernel), G8_LDS);
   hipLaunchKernelGGL(gemm8p_kernel, dim3(p.ntiles), dim3(512), G8_LDS, st, p);
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
@@ -894,15 +886,9 @@ int vqa_conv8p(const void* x, const void* w, void* out, unsigned long long* stat
   p.ntiles = tiles_m * p.tiles_n;
   p.cpk_shift = 0;
   while ((64 << p.cpk_shift) < C) ++p.cpk_shift;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv8p_kernel<2, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C8Geo<2, 4>::LDS);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv8p_kernel<4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)C8Geo<4, 2>::LDS);
-    attr = true;
-  }
   constexpr int lds_w = C8Geo<2, 4>::LDS, lds_n = C8Geo<4, 2>::LDS;
-  if (wide) hipLaunchKernelGGL((conv8p_kernel<2, 4>), dim3(p.ntiles), dim3(512), lds_w, st, p);
-  else hipLaunchKernelGGL((conv8p_kernel<4, 2>), dim3(p.ntiles), dim3(512), lds_n, st, p);
+  if (wide) { (void)vqa_ensure_lds(reinterpret_cast<const void*>(&conv8p_kernel<2, 4>), lds_w); hipLaunchKernelGGL((conv8p_kernel<2, 4>), dim3(p.ntiles), dim3(512), lds_w, st, p); }
+  else { (void)vqa_ensure_lds(reinterpret_cast<const void*>(&conv8p_kernel<4, 2>), lds_n); hipLaunchKernelGGL((conv8p_kernel<4, 2>), dim3(p.ntiles), dim3(512), lds_n, st, p); }
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
 }

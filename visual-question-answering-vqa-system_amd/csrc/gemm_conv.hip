@@ -1340,16 +1340,10 @@ __global__ void fold_bn_batch_kernel(const float* __restrict__ flat, T* __restri
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
-// (the static attr_set flags below are per PROCESS: one process drives one GPU -- the launch model of this library, bench.py and
-// torch.distributed; a process that drove several devices would have to set the attribute per device)
 template <typename T, int BM, int BN, int LOADER, int NW = 4, int BK = GT<T>::BK, int OCC = 2, int ST = 2, int WIN = 0>
 static int launch_igemm(const IGemmParams& p, hipStream_t st) {
   constexpr int SMEM = IGemmCfg<T, BM, BN, BK, ST, WIN>::SMEM;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_kernel<T, BM, BN, LOADER, NW, BK, OCC, ST, WIN>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    attr_set = true;
-  }
+  (void)vqa_ensure_lds(reinterpret_cast<const void*>(&igemm_kernel<T, BM, BN, LOADER, NW, BK, OCC, ST, WIN>), SMEM);
   const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
   hipLaunchKernelGGL((igemm_kernel<T, BM, BN, LOADER, NW, BK, OCC, ST, WIN>), dim3(tiles), dim3(NW * 64), SMEM, st, p);
   VQA_LAUNCH_CHECK();
@@ -1424,11 +1418,7 @@ template <typename T, int BMW, int BNW, int LOADER>
 static int launch_wgrad(const WgradParams& p, int nsplit, hipStream_t st) {
   constexpr int VEC = GT<T>::VEC;
   constexpr int SMEM = 2 * GT<T>::BKM * (BMW + BNW + (sizeof(T) == 2 ? 0 : 2 * VEC)) * (int)sizeof(T);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<T, BMW, BNW, LOADER>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    attr_set = true;
-  }
+  (void)vqa_ensure_lds(reinterpret_cast<const void*>(&wgrad_kernel<T, BMW, BNW, LOADER>), SMEM);
   const int tiles = ((p.N + BMW - 1) / BMW) * ((p.Kw + BNW - 1) / BNW);
   hipLaunchKernelGGL((wgrad_kernel<T, BMW, BNW, LOADER>), dim3(tiles, nsplit), dim3(256), SMEM, st, p);
   VQA_LAUNCH_CHECK();
@@ -1439,11 +1429,7 @@ template <typename T>
 static int launch_wgrad_group(const WgradGroup& g, const ReduceGroup& r, hipStream_t st) {
   constexpr int VEC = GT<T>::VEC;
   constexpr int SMEM = 2 * GT<T>::BKM * (128 + 128 + (sizeof(T) == 2 ? 0 : 2 * VEC)) * (int)sizeof(T);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_group_kernel<T, 128, 128, LOADER_NHWC>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    attr_set = true;
-  }
+  (void)vqa_ensure_lds(reinterpret_cast<const void*>(&wgrad_group_kernel<T, 128, 128, LOADER_NHWC>), SMEM);
   hipLaunchKernelGGL((wgrad_group_kernel<T, 128, 128, LOADER_NHWC>), dim3(g.blk0[g.n]), dim3(256), SMEM, st, g);
   if (r.blk0[r.n] > 0) hipLaunchKernelGGL(wgrad_reduce_group_kernel, dim3(r.blk0[r.n]), dim3(256), 0, st, r);
   VQA_LAUNCH_CHECK();
@@ -1462,11 +1448,7 @@ static int launch_reduce(const WgradParams& p, int nsplit, hipStream_t st) {
 template <int TN, int TK, int NS>
 static int launch_wgrad_dma(const WgradParams& p, int nsplit, hipStream_t st) {
   using Cfg = WgradDmaCfg<TN, TK, NS>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_dma_kernel<TN, TK, NS>), hipFuncAttributeMaxDynamicSharedMemorySize, Cfg::SMEM);
-    attr_set = true;
-  }
+  (void)vqa_ensure_lds(reinterpret_cast<const void*>(&wgrad_dma_kernel<TN, TK, NS>), Cfg::SMEM);
   const int tiles = ((p.N + TN - 1) / TN) * ((p.Kw + TK - 1) / TK);
   hipLaunchKernelGGL((wgrad_dma_kernel<TN, TK, NS>), dim3(tiles, nsplit), dim3(512), Cfg::SMEM, st, p);
   VQA_LAUNCH_CHECK();
@@ -1673,7 +1655,7 @@ int vqa_dgrad_s2(int dtype, const void* dy, const void* dyd, const void* wt, voi
   const int bn = N <= 64 ? 64 : 128;
   const int tiles = 4 * ((class_rows + 127) / 128) * ((N + bn - 1) / bn);
   auto go = [&](auto kern, int smem) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    (void)vqa_ensure_lds(reinterpret_cast<const void*>(kern), smem);
     hipLaunchKernelGGL(kern, dim3(tiles), dim3(256), smem, st, p);
   };
   if (dtype) { if (bn == 64) go(&igemm_kernel<bf16_t, 128, 64, LOADER_DGRAD2>, IGemmCfg<bf16_t, 128, 64>::SMEM);

@@ -531,8 +531,7 @@ int vqa_stem_conv(const float* img, const void* wstem, void* out, float* stats, 
   if (!img || !wstem || !out || nb <= 0 || (size_t)B * 3 * H * W * 4 >= 0x7fffffffull) return VQA_EARG;      // 32-bit buffer offsets into the image
   const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1, PW = 2 * Wo + 8;
   const size_t shm = (size_t)(3 * PR * PW + 64 * LDW) * 2 + 4 * 64 * 2 * 4;
-  static size_t attr = 0;
-  if (shm > attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_conv_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); attr = shm; }
+  (void)vqa_ensure_lds(reinterpret_cast<const void*>(&stem_conv_kernel), shm);
   hipLaunchKernelGGL(stem_conv_kernel, dim3(nb), dim3(256), shm, st, img, (const bf16_t*)wstem, (bf16_t*)out, stats, H, W, Ho, Wo);
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
@@ -558,8 +557,7 @@ int vqa_stem_conv_pool(const float* img, const void* wstem, const float* coef, v
   const size_t shm = stem_conv_pool_shm(H, W, &ctiles, &PW);
   if (!img || !wstem || !coef || !out || !vqa_stem_conv_pool_ok(B, H, W)) return VQA_EARG;
   const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1, Hp = (Ho + 2 - 3) / 2 + 1, Wp = (Wo + 2 - 3) / 2 + 1;
-  static size_t attr = 0;
-  if (shm > attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_conv_pool_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); attr = shm; }
+  (void)vqa_ensure_lds(reinterpret_cast<const void*>(&stem_conv_pool_kernel), shm);
   hipLaunchKernelGGL(stem_conv_pool_kernel, dim3(B * (Hp / PRB)), dim3(256), shm, st, img, (const bf16_t*)wstem, coef, (bf16_t*)out,
                      B, H, W, Ho, Wo, Hp, Wp, ctiles, PW, vqa_env_int("VQA_STEMCP_DBG", 0));
   VQA_LAUNCH_CHECK(); return VQA_OK;
@@ -582,8 +580,7 @@ int vqa_stem_wgrad(const float* img, const void* dy, float* dw, int B, int H, in
   const int PW = 2 * Wo + 8, MP = (Wo / nsplit + 31) / 32 * 32;
   const size_t shm = (size_t)(3 * PRW * PW + MP * LDA + MP * LDD) * 2;
   if (shm > 160 * 1024) return VQA_EARG;
-  static size_t attr = 0;
-  if (shm > attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_wgrad_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); attr = shm; }
+  (void)vqa_ensure_lds(reinterpret_cast<const void*>(&stem_wgrad_kernel<false>), shm);
   int nblocks = B * (Ho / RBW);
   const int cap = 256 * (int)((160 * 1024) / shm > 4 ? 4 : (160 * 1024) / shm);
   int grid = nblocks < cap ? nblocks : cap;
@@ -604,8 +601,7 @@ int vqa_stem_wgrad_fused(const float* img, const void* y, const void* dpool, con
   const int PW = 2 * Wo + 8, MP = (Wo / nsplit + 31) / 32 * 32;
   const size_t shm = (size_t)(3 * PRW * PW + MP * LDA + MP * LDD) * 2;
   if (shm > 160 * 1024) return VQA_EARG;
-  static size_t attr = 0;
-  if (shm > attr) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_wgrad_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); attr = shm; }
+  (void)vqa_ensure_lds(reinterpret_cast<const void*>(&stem_wgrad_kernel<true>), shm);
   int nblocks = B * (Ho / RBW);
   const int cap = 256 * (int)((160 * 1024) / shm > 4 ? 4 : (160 * 1024) / shm);
   int grid = nblocks < cap ? nblocks : cap;

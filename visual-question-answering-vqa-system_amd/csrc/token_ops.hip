@@ -828,8 +828,7 @@ static int attention_bwd_valu(int dtype, const void* dctx, int ldc, const void* 
   const size_t shm = ((size_t)(2 * Lq + 2 * Lk) * (hd + 1) + (size_t)2 * Lq * (Lk + 1)) * 4;
   if (shm > 160 * 1024) return VQA_EARG;
   const float scale = sqrtf((float)hd);
-  if (dtype) { if (shm > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<bf16_t, DPR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); }
-  else { if (shm > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<float, DPR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); }
+  (void)vqa_ensure_lds(dtype ? reinterpret_cast<const void*>(&attn_bwd_kernel<bf16_t, DPR>) : reinterpret_cast<const void*>(&attn_bwd_kernel<float, DPR>), shm);
   DT(hipLaunchKernelGGL((attn_bwd_kernel<float, DPR>), dim3(B * H), dim3(256), shm, st, (const float*)dctx, ldc, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, probs, (float*)dq, (float*)dk, (float*)dv, lddq, lddk, lddv, H, Lq, Lk, hd, scale, p, seed, dprobs),
      hipLaunchKernelGGL((attn_bwd_kernel<bf16_t, DPR>), dim3(B * H), dim3(256), shm, st, (const bf16_t*)dctx, ldc, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, probs, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, lddq, lddk, lddv, H, Lq, Lk, hd, scale, p, seed, dprobs));
   VQA_LAUNCH_CHECK(); return VQA_OK;
@@ -849,9 +848,7 @@ int vqa_embed_bwd(int dtype, const long long* ids, const void* dout, float* demb
   if (D > 2048 || rows <= 0 || rows >= (1 << 27) || V <= 0) return VQA_EARG;
   const size_t shm = (size_t)EMB_VB * D * 4;
   const dim3 grid((V + EMB_VB - 1) / EMB_VB);
-  static size_t attr_f = 0, attr_b = 0;
-  if (!dtype && shm > 65536 - 4200 && shm > attr_f) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&embed_bwd_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); attr_f = shm; }
-  if (dtype && shm > 65536 - 4200 && shm > attr_b) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&embed_bwd_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); attr_b = shm; }
+  (void)vqa_ensure_lds(dtype ? reinterpret_cast<const void*>(&embed_bwd_kernel<bf16_t>) : reinterpret_cast<const void*>(&embed_bwd_kernel<float>), shm);
   DT(hipLaunchKernelGGL(embed_bwd_kernel<float>, grid, dim3(256), shm, st, ids, (const float*)dout, demb, rows, D, V, scale, p, seed),
      hipLaunchKernelGGL(embed_bwd_kernel<bf16_t>, grid, dim3(256), shm, st, ids, (const bf16_t*)dout, demb, rows, D, V, scale, p, seed));
   VQA_LAUNCH_CHECK(); return VQA_OK;
@@ -939,8 +936,7 @@ int vqa_attention_fwd(int dtype, const void* q, const void* k, const void* v, in
   const size_t shm = ((size_t)(Lq + 2 * Lk) * (hd + 1) + (size_t)Lq * (Lk + 1)) * 4;
   if (shm > 160 * 1024) return VQA_EARG;
   const float scale = sqrtf((float)hd);
-  if (dtype) { if (shm > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); }
-  else { if (shm > 65536) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_fwd_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm); }
+  (void)vqa_ensure_lds(dtype ? reinterpret_cast<const void*>(&attn_fwd_kernel<bf16_t>) : reinterpret_cast<const void*>(&attn_fwd_kernel<float>), shm);
   DT(hipLaunchKernelGGL(attn_fwd_kernel<float>, dim3(B * H), dim3(256), shm, st, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, kmask, probs, (float*)ctx, ldc, H, Lq, Lk, hd, scale, p, seed),
      hipLaunchKernelGGL(attn_fwd_kernel<bf16_t>, dim3(B * H), dim3(256), shm, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, kmask, probs, (bf16_t*)ctx, ldc, H, Lq, Lk, hd, scale, p, seed));
   VQA_LAUNCH_CHECK(); return VQA_OK;
@@ -1243,7 +1239,7 @@ extern "C" int vqa_attention_fwd_mfma(const void* q, const void* k, const void* 
   const int BH = B * H;
   auto go = [&](auto kern, int nkt, int wpb) {
     const size_t shm = (size_t)wpb * (nkt * 32) * hd * 2 + (size_t)wpb * 32 * (nkt * 32 + 1) * 4;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    (void)vqa_ensure_lds(reinterpret_cast<const void*>(kern), shm);
     hipLaunchKernelGGL(kern, dim3((BH + wpb - 1) / wpb), dim3(wpb * 64), shm, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv,
                        kmask, probs, (bf16_t*)ctx, ldc, BH, H, Lq, Lk, p, seed);
   };
@@ -1449,7 +1445,7 @@ static int attention_bwd_mfma(const void* dctx, int ldc, const void* q, const vo
   const int BH = B * H;
   auto go = [&](auto kern, int nkt, int wpb) {
     const size_t shm = (size_t)wpb * ((nkt * 32 + 32 + 32) * hd * 2 + 32 * (nkt * 32 + 1) * 4 + 32 * 4 + (DPR ? 32 * (nkt * 32 + 1) * 4 : 0));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    (void)vqa_ensure_lds(reinterpret_cast<const void*>(kern), shm);
     hipLaunchKernelGGL(kern, dim3((BH + wpb - 1) / wpb), dim3(wpb * 64), shm, st, (const bf16_t*)dctx, ldc, (const bf16_t*)q, (const bf16_t*)k,
                        (const bf16_t*)v, ldq, ldk, ldv, probs, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, lddq, lddk, lddv, BH, H, Lq, Lk, p, seed, dprobs);
   };

@@ -82,19 +82,12 @@ class HipEngine:
         self._wt_table = None
         self._wt_buf = None
         # schedule switches: plain attributes (tools/ flip them for A/B measurements); the product never reads the environment
-        self.defer_tail = True
         self._deferred = []
         self._keep = []
         self._wgq = []
-        self.group_wgrad = True
         self._foldq = []                          # deferred folds of the LayerNorm / bias parameter gradients (K.fold_group at segment end)
         self._foldq2 = []
-        self.defer_folds = True
-        self.bias_offpath = False
-        self.chain_trim = False                   # backward: pure bias column sums of the head / gate / projector and the text-gradient add leave the main-stream chain (measured neutral: 12.11 vs 12.09 ms, off)
         self.fuse_act_dgrad = True                # ReLU(+dropout) backward of a Linear -> ReLU -> Dropout -> Linear pair applied by the data-gradient GEMM's epilogue; the bias column sums leave the chain
-        self.use_c64_fwd = False                  # 4-wave stage-1 patch kernel for forward / data gradient (superseded by the 8-wave one)
-        self.use_c64p = True                      # 8-wave weights-resident stage-1 conv kernel
         self.fuse_se_pool = True                  # SE global-average-pool sums leave the last block's bn_apply (one read of the stage output less)
         self.fuse_se_bnred = True                 # the last block's bn2-backward column sums leave the SE backward apply pass (ditto)
         # BatchNorm finalize folded into the consumers (bf16 training schedule): statistics / backward sums travel as fixed-point
@@ -115,8 +108,6 @@ class HipEngine:
         self.pack_off_main = True                 # begin_step's backward operands (transposed weights, stem helper) are packed on the weight-gradient stream
         self.hoist_cross = True                   # cross-attention: layer 0's query projection beside the CNN, layers >= 1's K / V path (fwd + bwd) on the text stream
         self.use_c64p_epi = True                  # stage-1 conv1 data gradients (identity addend + masks) on the 8-wave patch kernel
-        self.fuse_hand_reduce = False             # ... and the previous block's bn2 (+ shortcut BN) backward sums in the epilogue of conv1's data gradient:
-                                                  # measured neutral (12.21-12.27 vs 12.21-12.23 ms/step: two more epilogue streams cost what the pass saves) -> off
         self.fuse_bn1_reduce = True               # bn1-backward column sums in the epilogue of conv2's data gradient (conv8p, stage 1: the patch kernel)
         self.use_conv8p_bwd = True                # ... also for the data gradients (they run beside the weight-gradient stream)
         self._accbuf = None
@@ -129,7 +120,6 @@ class HipEngine:
         # the CNN weight gradients run on a second side stream (off the critical path)
         self.side, self.side2 = pick_concurrent_streams(flat.device, 2) if flat.is_cuda else (None, None)
         self.two_streams = True
-        self.wgrad_stream = True
         # test hook (tests/test_gpu_insitu.py): a dict here receives, per residual block, the intermediate gradients of its backward
         # (dout, dy2, dyd, da1, dy1, dx) so that every layer of a LIVE full-size bf16 step can be checked locally against fp32 math
         self.capture = None
@@ -303,11 +293,9 @@ class HipEngine:
         return (self.P(prefix + ".weight"), self.P(prefix + ".bias"), self.buf[prefix + ".running_mean"], self.buf[prefix + ".running_var"],
                 self.buf[prefix + ".num_batches_tracked"])
 
-    def _c64_ok(self, B, H, W, Cin, Cout, R, stride, wgrad=False):
-        if not wgrad and not self.use_c64_fwd:
-            return False          # since the LDS-DMA rewrite the generic implicit GEMM is as fast for forward / data gradient
-        ok = self.dtype == torch.bfloat16 and Cin == 64 and Cout == 64 and R == 3 and stride == 1
-        return ok and (K.c64w_blocks(B, H, W) if wgrad else K.c64_blocks(B, H, W)) > 0
+    def _c64w_ok(self, B, H, W, Cin, Cout, R, stride):
+        """64 -> 64 channel 3x3/1 weight gradient on the stage-1 patch kernels (vqa_wgrad3x3_c64: 8-wave LDS-DMA form, else the 4-wave one)."""
+        return (self.dtype == torch.bfloat16 and Cin == 64 and Cout == 64 and R == 3 and stride == 1 and K.c64w_blocks(B, H, W) > 0)
 
     def _c128w_ok(self, B, H, W, Cin, Cout, stride):
         """128 -> 128 channel 3x3/1 conv on 28 x 28 maps (stage 2): the 8-wave LDS-DMA weight-gradient kernel."""
@@ -316,8 +304,7 @@ class HipEngine:
     def _c64p_ok(self, B, H, W, Cin, Cout, R, stride):
         """64 -> 64 channel 3x3/1 conv without epilogue inputs: the 8-wave LDS-DMA patch kernel (156 vs 215 us forward, 152 vs 188 us
         data gradient at B=512)."""
-        return (self.dtype == torch.bfloat16 and Cin == 64 and Cout == 64 and R == 3 and stride == 1 and K.c64p_blocks(B, H, W) > 0
-                and self.use_c64p)
+        return self.dtype == torch.bfloat16 and Cin == 64 and Cout == 64 and R == 3 and stride == 1 and K.c64p_blocks(B, H, W) > 0
 
     def _c8p_ok(self, B, H, W, Cin, Cout, R, stride, pad, bwd=False):
         """3x3 / pad 1 conv (stride 1 or 2) or stride-1 data gradient routed to the 8-phase tile: bf16, output channels a multiple of 256
@@ -340,9 +327,6 @@ class HipEngine:
             a = self._acc(K.L.count("vqa_bn_acc_words", 2, Cout)) if (acc and stats) else None
             y, st, mt = K.conv3x3_c64p(x, self.Wm(wname), B, H, W, want_stats=stats, stats_acc=a)
             return y, st, (-1 if a is not None else mt), geom, Ho, Wo
-        if self._c64_ok(B, H, W, Cin, Cout, R, stride):
-            y, st, mt = K.conv3x3_c64(x, self.Wm(wname), B, H, W, want_stats=stats)
-            return y, st, mt, geom, Ho, Wo
         if self._c8p_ok(B, H, W, Cin, Cout, R, stride, pad) and (acc or not stats):
             a = self._acc(K.L.count("vqa_bn_acc_words", 2, Cout)) if stats else None
             y = K.conv8p(x, self.Wm(wname), B, H, W, Cin, Cout, stride=stride, stats_acc=a)
@@ -399,7 +383,7 @@ class HipEngine:
     #      workgroup, latency-bound launch on its own.  The queue is flushed on the stream that produced its operands (when it is
     #      full, before a gradient segment is reported, before the stream context changes) and holds references to dz / x until then.
     def _wgrad_linear(self, dz, x_in, dw, M, N, Kin):
-        if self.group_wgrad and K.wgrad_group_ok(self.dtype, M, N, Kin):
+        if K.wgrad_group_ok(self.dtype, M, N, Kin):
             self._wgq.append((dz, x_in, dw, M, N, Kin))
             if len(self._wgq) == 8:
                 self._flush_wgq()
@@ -467,11 +451,11 @@ class HipEngine:
                 ws = None
                 if dbias is not None:      # fixed-order column sums (bit-reproducible): per-workgroup rows + index-order fold
                     ws = torch.empty((K.reduce_ws("vqa_bias_act_bwd_ws", dt(dout), M, N),), device=dout.device, dtype=torch.float32)
-                defer = int(ws is not None and self.defer_folds)
+                defer = int(ws is not None)
                 call("vqa_bias_act_bwd", dt(dout), ptr(dout), ptr(outact), ptr(dz), ptr(dbias), M, N, float(p), int(seed), ptr(ws), defer)
                 if defer:                  # the bias gradient is only read by the optimizer: fold it with the rest of the segment
                     (self._foldq if on_chain else self._foldq2).append((ws, 0, K.L.count("vqa_bias_act_bwd_fold_rows", dt(dout), M, N), N, N, dbias, N, None))
-            on_chain = need_dz or not (self.bias_offpath or off_chain)
+            on_chain = need_dz or not off_chain
             if on_chain:
                 launch()
             else:                          # a pure column sum (no mask, no dropout): a side output, off the data-gradient chain
@@ -486,16 +470,16 @@ class HipEngine:
         eg, eb = self.E[prefix + ".weight"], self.E[prefix + ".bias"]
         return K.layernorm_bwd(dout, x, self.P(prefix + ".weight"), stats, G[eg.offset: eg.offset + eg.numel],
                                G[eb.offset: eb.offset + eb.numel], addend=addend, drop_p=p, seed=seed, dadd=dadd, period=period,
-                               foldq=self._foldq if self.defer_folds else None)
+                               foldq=self._foldq)
 
     def _off_path(self, tensors, fn, defer=False):
         """Run fn (a weight-gradient launch) on the second side stream: it only needs `tensors` (already produced on the
         current stream) and writes its own slice of G, so it may overlap the data-gradient chain.
         defer: keep it back until _flush_deferred() -- the last residual block's weight gradients are released when the stem
         backward starts, so that the (latency-bound) fused stem weight-gradient kernel does not run alone at the end of the step."""
-        if not (self.wgrad_stream and self.two_streams and self.side2 is not None):
+        if not (self.two_streams and self.side2 is not None):
             return fn()
-        if defer and self.defer_tail:
+        if defer:
             self._deferred.append((tensors, fn))
             return
         cur = torch.cuda.current_stream()
@@ -518,7 +502,7 @@ class HipEngine:
 
     def _join_off_path(self):
         self._flush_deferred()
-        if self.wgrad_stream and self.two_streams and self.side2 is not None:
+        if self.two_streams and self.side2 is not None:
             ev = torch.cuda.Event(); ev.record(self.side2)
             torch.cuda.current_stream().wait_event(ev)
 
@@ -937,8 +921,8 @@ class HipEngine:
         self._bwd_begin()
         seg = self._seg_fn(on_segment)
         dfused = self._head_bwd(tape, dlogits, G, seg)
-        dfeat, denc, dq, add_dq = self._fusion_bwd(tape, dfused, G, seg)
-        ev_tb = self._encoders_bwd(tape, dfeat, denc, dq, G, seg, add_dq=add_dq)
+        dfeat, denc = self._fusion_bwd(tape, dfused, G, seg)
+        ev_tb = self._encoders_bwd(tape, dfeat, denc, G, seg)
         self._bwd_join(ev_tb)
 
     # The same backward in three separately callable parts, split where it reports its segments (graph-connected aux outputs:
@@ -958,9 +942,7 @@ class HipEngine:
         taps: fused / attended_pooled / text_pooled ([B][d]), image_projected ([B][ntok][d]), cross_attention_weights (per layer
         [B][H][L][ntok] or None)."""
         self._bwd_begin()
-        dfeat, denc, dq, add_dq = self._fusion_bwd(self._tape_part(tape, "pool"), dfused, G, self._seg_fn(on_segment), taps or {})
-        if add_dq:
-            call("vqa_add", dt(self.dtype), ptr(denc), ptr(dq), ptr(denc), denc.numel())
+        dfeat, denc = self._fusion_bwd(self._tape_part(tape, "pool"), dfused, G, self._seg_fn(on_segment), taps or {})
         self._bwd_join()
         for k in ("pool", "clayers", "proj", "caw"):
             tape.pop(k, None)
@@ -971,7 +953,7 @@ class HipEngine:
         """(dfeat, denc) -> parameter gradients of the text encoder, the CNN stages and the stem.
         taps: image_features (fp32 NCHW [B][Cf][Hf][Wf]) -> dfeat, text_features (fp32 [B][L][d]) -> denc."""
         self._bwd_begin()
-        ev_tb = self._encoders_bwd(self._tape_part(tape, "stages"), dfeat, denc, None, G, self._seg_fn(on_segment), taps or {}, add_dq=False)
+        ev_tb = self._encoders_bwd(self._tape_part(tape, "stages"), dfeat, denc, G, self._seg_fn(on_segment), taps or {})
         self._bwd_join(ev_tb)
         for k in ("stages", "stem", "tlayers", "final_norm", "embed", "feat"):
             tape.pop(k, None)
@@ -1025,7 +1007,7 @@ class HipEngine:
             evs = []
             cur = torch.cuda.current_stream()
             e = torch.cuda.Event(); e.record(cur); evs.append(e)
-            if self.wgrad_stream and self.two_streams and self.side2 is not None:
+            if self.two_streams and self.side2 is not None:
                 e2 = torch.cuda.Event(); e2.record(self.side2); evs.append(e2)
             on_segment(name, evs)
         return seg
@@ -1036,7 +1018,7 @@ class HipEngine:
         T = self.dtype
         dl = dlogits.to(T).contiguous() if dlogits.dtype != T else dlogits.contiguous()
         hdr = tape["head"]; c = "answer_head.classifier"
-        dz = self._act_bwd(dl, None, c + ".6.bias", G, 0.0, 0, off_chain=self.chain_trim)
+        dz = self._act_bwd(dl, None, c + ".6.bias", G, 0.0, 0)
         dz = self._lin_act_bwd(dz, hdr["h2"], c + ".6.weight", c + ".3.bias", G, hdr["p"])
         dz = self._lin_act_bwd(dz, hdr["h1"], c + ".3.weight", c + ".0.bias", G, hdr["p"])
         dfused = self._lin_bwd(dz, hdr["fused"], c + ".0.weight", G)
@@ -1044,8 +1026,7 @@ class HipEngine:
         return dfused
 
     def _fusion_bwd(self, tape, dfused, G, seg, taps=None):
-        """Returns (dfeat, denc, dq, add_dq): dq is the query-path text gradient; add_dq: it is still to be added to denc (on the
-        text stream, chain_trim)."""
+        """Returns (dfeat, denc): the gradients at the image features and at the text encoder's output (query path included)."""
         cfg, T = self.cfg, self.dtype
         B = tape["B"]
         taps = taps or {}
@@ -1071,7 +1052,7 @@ class HipEngine:
         if cfg["use_gating"]:
             dzg = torch.empty_like(pr["z"])
             call("vqa_gate_bwd", dt(T), ptr(dfp), ptr(pr["z"]), ptr(pr["cat"]), ptr(dzg), ptr(dcat), B, d)
-            dzg = self._act_bwd(dzg, None, "fusion.gate.gate.0.bias", G, 0.0, 0, off_chain=self.chain_trim)
+            dzg = self._act_bwd(dzg, None, "fusion.gate.gate.0.bias", G, 0.0, 0)
             dcat = self._lin_bwd(dzg, pr["cat"], "fusion.gate.gate.0.weight", G, addend=dcat)
         else:
             dcat[:, :d] = dfp; dcat[:, d:] = dfp
@@ -1102,21 +1083,18 @@ class HipEngine:
             dimg = torch.zeros((B * rp["ntok"], d), device=dcat.device, dtype=T)
         if taps.get("image_projected") is not None:
             self._tap(taps["image_projected"], dimg, B * rp["ntok"], d, d)
-        # dq is now the gradient wrt text features through the query path: it joins the pooled-text gradient on the text stream below
-        # (only the text encoder's backward reads the sum; the projector / CNN chain does not wait for it)
-        add_on_side = self.chain_trim and self.two_streams and self.side is not None
-        if not add_on_side:
-            call("vqa_add", dt(T), ptr(denc), ptr(dq), ptr(denc), denc.numel())
+        # dq is now the gradient wrt text features through the query path: it joins the pooled-text gradient
+        call("vqa_add", dt(T), ptr(denc), ptr(dq), ptr(denc), denc.numel())
         # ---- projector
         pj = "fusion.image_projector.projection"
         dpos = self._gslice(G, "fusion.image_projector.position_embedding")
         dpz = self._ln_bwd(dimg, rp["pz"], pj + ".1", rp["st"], G, p=rp["p"], seed=rp["seed"], dadd=dpos, period=rp["ntok"])
-        dpz = self._act_bwd(dpz, None, pj + ".0.bias", G, 0.0, 0, off_chain=self.chain_trim)
+        dpz = self._act_bwd(dpz, None, pj + ".0.bias", G, 0.0, 0)
         dfeat = self._lin_bwd(dpz, rp["feat"], pj + ".0.weight", G)
         seg("fusion")
-        return dfeat, denc, dq, add_on_side
+        return dfeat, denc
 
-    def _encoders_bwd(self, tape, dfeat, denc, dq, G, seg, taps=None, add_dq=False):
+    def _encoders_bwd(self, tape, dfeat, denc, G, seg, taps=None):
         """Text encoder (side stream) and CNN backward; returns the text stream's completion event (or None)."""
         cfg, T = self.cfg, self.dtype
         training = tape["training"]
@@ -1138,17 +1116,14 @@ class HipEngine:
             self._tap(taps["image_features"], dfeat, B * ntok, Cf, ntok, layout=1)
         if taps.get("text_features") is not None:
             self._tap(taps["text_features"], denc, denc.shape[0], d, d)
-        add_on_side = add_dq
         # ---- text encoder backward on the side stream, concurrently with the CNN backward below
         main = torch.cuda.current_stream()
         use_side = self.two_streams and self.side is not None
         if use_side:
             evf = torch.cuda.Event(); evf.record(main)
             self.side.wait_event(evf)
-            self._keep.extend([t for t in (denc, dq) if t is not None])     # allocated on main, consumed on the side stream: alive until the join below
+            self._keep.append(denc)               # allocated on main, consumed on the side stream: alive until the join below
         with torch.cuda.stream(self.side if use_side else main):
-            if add_on_side:
-                call("vqa_add", dt(T), ptr(denc), ptr(dq), ptr(denc), denc.numel())
             fn = tape["final_norm"]
             dx = self._ln_bwd(denc, fn["x"], "text_encoder.final_norm", fn["st"], G)
             for rec in reversed(tape["tlayers"]):
@@ -1202,13 +1177,12 @@ class HipEngine:
                 masked = False
                 se_pre = None
             nb = len(srec["blocks"])
-            pre = se_pre         # BatchNorm-backward sums of the next block's bn2, already reduced by the pass that produced dxc
             for bi in range(nb - 1, -1, -1):
                 rec = srec["blocks"][bi]
-                # the gradient handed to the previous block of the stage is masked by THAT block's ReLU in this block's epilogue,
-                # which also reduces that block's bn2-backward sums (it holds the finished gradient tile anyway)
+                # the gradient handed to the previous block of the stage is masked by THAT block's ReLU in this block's epilogue
                 hand = srec["blocks"][bi - 1] if (bi > 0 and "yd" not in rec) else None
-                dxc, pre = self._block_bwd(rec, dxc, G, training, masked=masked, hand=hand, pre=pre)
+                # the last block's bn2-backward sums may already have been reduced by the SE backward that produced dxc
+                dxc = self._block_bwd(rec, dxc, G, training, masked=masked, hand=hand, pre=se_pre if bi == nb - 1 else None)
                 masked = hand is not None
             if not self._deferred:                # stage 1: its held-back weight gradients are released below, report it there
                 seg(f"image_encoder.stage{s}")
@@ -1257,14 +1231,13 @@ class HipEngine:
         if fused:
             # dy (B x 112 x 112 x 64) is never written: the weight-gradient kernel rebuilds it row by row
             dwv = self._gslice(G, "image_encoder.stem.0.weight")
-            if K.PROFILE is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True); e0.record()
+            e0 = K.prof_begin()
             ws, wsf = K.stem_wgrad_scratch(dxc.device, B, IH, IW)
             call("vqa_stem_wgrad_fused", ptr(st["images"]), ptr(st["y"]), ptr(dxc), ptr(st["idx"]), ptr(st["coef"]), ptr(bc), ptr(dwv), B, IH, IW,
                  ptr(ws), wsf)
-            if K.PROFILE is not None:
-                e1.record(); K.PROFILE.append(("stem_wgrad_kernel<true>", 2.0 * B * H1 * W1 * 64 * 147, e0, e1,
-                                                            B * 3 * IH * IW * 4 + B * H1 * W1 * 64 * 2 + dxc.numel() * 3))
+            if e0 is not None:
+                K.prof_end(e0, "stem_wgrad_kernel<true>", 2.0 * B * H1 * W1 * 64 * 147,
+                           B * 3 * IH * IW * 4 + B * H1 * W1 * 64 * 2 + dxc.numel() * 3)
         else:
             dy = torch.empty_like(st["y"])
             call("vqa_stem_bwd_apply", dt(T), ptr(dxc), ptr(st["idx"]), ptr(st["y"]), ptr(st["coef"]), ptr(bc), ptr(dy), B, H1, W1, 64)
@@ -1272,10 +1245,10 @@ class HipEngine:
                     loader=K.LOADER_STEM)
 
     def _block_bwd(self, rec, dout, G, training, masked=False, hand=None, pre=None):
-        """ResidualBlock backward (reference forward: models/cnn_backbone.py:164-197).  Returns (dx, pre-reduced bn2 sums for `hand`).
+        """ResidualBlock backward (reference forward: models/cnn_backbone.py:164-197).  Returns dx.
         masked: `dout` was already multiplied by (out > 0) by its producer, so the block output is never re-read here.
         hand: tape record of the PREVIOUS block of the stage (this block's input is its post-ReLU output): the returned gradient
-              is masked by that ReLU and the previous block's bn2-backward column sums are reduced in the same epilogue.
+              is masked by that ReLU.
         pre: (slab, rows) of this block's bn2-backward sums when the producer of `dout` already reduced them."""
         outmask = hand["out"] if hand is not None else None
         T = self.dtype
@@ -1295,23 +1268,20 @@ class HipEngine:
                             slab=pre[0] if (pre and not pre_acc) else None, nb=pre[1] if (pre and not pre_acc) else 0,
                             facc=(pre[0] if pre_acc else (self._acc(K.L.count("vqa_bn_acc_words", 3, Cout)) if bacc else None)), facc_filled=pre_acc)
         g2 = rec["g2"]; B, Ho, Wo = g2[0], g2[1], g2[2]
-        c64_2 = self._c64_ok(B, Ho, Wo, Cout, Cout, 3, 1)
         if rec["a1"] is None:                                 # conv2 ran on relu(bn1(y1)) built in LDS (fuse_bn_conv): so does its weight gradient
             self._off_path([dy2], lambda: K.wgrad3x3_c64_bn(rec["y1"], rec["c1"], dy2, LY.mat_of(G, self.E[p + ".conv2.weight"]), B, Ho, Wo), defer=last)
-        elif self._c64_ok(B, Ho, Wo, Cout, Cout, 3, 1, wgrad=True):
+        elif self._c64w_ok(B, Ho, Wo, Cout, Cout, 3, 1):
             self._off_path([dy2], lambda: K.wgrad3x3_c64(rec["a1"], dy2, LY.mat_of(G, self.E[p + ".conv2.weight"]), B, Ho, Wo), defer=last)
         elif self._c128w_ok(B, Ho, Wo, Cout, Cout, 1):
             self._off_path([dy2], lambda: K.wgrad3x3_c128(rec["a1"], dy2, LY.mat_of(G, self.E[p + ".conv2.weight"]), B, Ho, Wo))
         else:
             self._off_path([dy2], lambda: K.wgrad(dy2, rec["a1"], LY.mat_of(G, self.E[p + ".conv2.weight"]), M, Cout, 9 * Cout, g2, dtype=T))
-        slab1, nb1, facc1, handed_pre = None, 0, None, None
+        facc1 = None
         if self._c64p_ok(B, Ho, Wo, Cout, Cout, 3, 1) and bacc and self.fuse_bn1_reduce:
             facc1 = self._acc(K.L.count("vqa_bn_acc_words", 3, Cout))      # (as below for conv8p: bn1's backward sums leave this launch)
             da1 = K.conv3x3_c64p_bnred(dy2, self._wflip(p + ".conv2.weight"), B, Ho, Wo, rec["y1"], rec["c1"], facc1)
         elif self._c64p_ok(B, Ho, Wo, Cout, Cout, 3, 1):
             da1, _, _ = K.conv3x3_c64p(dy2, self._wflip(p + ".conv2.weight"), B, Ho, Wo)
-        elif c64_2:
-            da1, _, _ = K.conv3x3_c64(dy2, self._wflip(p + ".conv2.weight"), B, Ho, Wo)
         elif self.use_conv8p_bwd and self._c8p_ok(B, Ho, Wo, Cout, Cout, 3, 1, 1, bwd=True):
             if bacc and self.fuse_bn1_reduce:     # bn1's backward column sums leave the data-gradient epilogue: no bn_bwd_reduce pass over (da1, y1)
                 facc1 = self._acc(K.L.count("vqa_bn_acc_words", 3, Cout))
@@ -1322,11 +1292,10 @@ class HipEngine:
             da1, _, _ = K.igemm(dy2, self.Wt(p + ".conv2.weight"), M, Cout, 9 * Cout, geom_d2, dtype=T, transposed=1)
         dy1, _ = K.bn_bwd(da1, None, rec["y1"], rec["c1"], self.P(p + ".bn1.weight"), Cout, training,
                           gs(p + ".bn1.weight"), gs(p + ".bn1.bias"), self_mask=True,      # a1 > 0 recomputed from y1: a1 is not read
-                          slab=slab1, nb=nb1, facc=facc1 if facc1 is not None else (self._acc(K.L.count("vqa_bn_acc_words", 3, Cout)) if bacc else None),
+                          facc=facc1 if facc1 is not None else (self._acc(K.L.count("vqa_bn_acc_words", 3, Cout)) if bacc else None),
                           facc_filled=facc1 is not None)
         g1 = rec["g1"]; H, W, stride = g1[1], g1[2], g1[8]
-        c64_1 = self._c64_ok(B, H, W, Cin, Cout, 3, stride)
-        if self._c64_ok(B, H, W, Cin, Cout, 3, stride, wgrad=True):
+        if self._c64w_ok(B, H, W, Cin, Cout, 3, stride):
             self._off_path([dy1], lambda: K.wgrad3x3_c64(rec["x"], dy1, LY.mat_of(G, self.E[p + ".conv1.weight"]), B, H, W), defer=last)
         elif self._c128w_ok(B, H, W, Cin, Cout, stride):
             self._off_path([dy1], lambda: K.wgrad3x3_c128(rec["x"], dy1, LY.mat_of(G, self.E[p + ".conv1.weight"]), B, H, W))
@@ -1346,24 +1315,14 @@ class HipEngine:
                 geom_dd = (B, Ho, Wo, Cout, H, W, 1, 1, stride, 0)
                 dxd, _, _ = K.igemm(dyd, self.Wt(p + ".downsample.0.weight"), Md, Cin, Cout, geom_dd, dtype=T, transposed=1)
                 dx, _, _ = K.igemm(dy1, self.Wt(p + ".conv1.weight"), Md, Cin, 9 * Cout, geom_d1, dtype=T, transposed=1, addend=dxd)
-        elif c64_1 and not masked and outmask is None:
-            dx, _, _ = K.conv3x3_c64(dy1, self._wflip(p + ".conv1.weight"), B, H, W, addend=dout, addmask=rec["out"])
         elif self.use_c64p_epi and self._c64p_ok(B, H, W, Cout, Cin, 3, stride):
             # stage 1: the patch kernel with the identity-path gradient and the ReLU masks in its per-tile epilogue (was the 128 x 64 igemm tile)
             dx = K.conv3x3_c64p_epi(dy1, self._wflip(p + ".conv1.weight"), B, H, W, addend=dout, addmask=out_act, outmask=outmask)
         elif self.use_conv8p_bwd and stride == 1 and self._c8p_ok(B, H, W, Cout, Cin, 3, stride, 1, bwd=True):
-            bnred = None
-            if hand is not None and bacc and self.fuse_hand_reduce:
-                # dx is the gradient entering the previous block's bn2 (and its shortcut BatchNorm), already masked by that block's
-                # ReLU (outmask): their backward column sums leave this epilogue and that block skips its bn_bwd_reduce pass
-                hfacc = self._acc(K.L.count("vqa_bn_acc_words", 3, Cin))
-                bnred = (hand["y2"], hand["c2"], hfacc, False, hand.get("yd"), hand.get("cd"))
-                handed_pre = (hfacc, -1)
-            dx = K.conv8p(dy1, self.Wt(p + ".conv1.weight"), B, H, W, Cout, Cin, transposed=1, addend=dout, addmask=out_act, outmask=outmask,
-                          bnred=bnred)
+            dx = K.conv8p(dy1, self.Wt(p + ".conv1.weight"), B, H, W, Cout, Cin, transposed=1, addend=dout, addmask=out_act, outmask=outmask)
         else:
             dx, _, _ = K.igemm(dy1, self.Wt(p + ".conv1.weight"), Md, Cin, 9 * Cout, geom_d1, dtype=T, transposed=1,
                                addend=dout, addmask=out_act, outmask=outmask)
         if self.capture is not None:
             self.capture[p] = dict(dout=dout, masked=masked, handed=hand is not None, dy2=dy2, dyd=dyd, da1=da1, dy1=dy1, dx=dx)
-        return dx, handed_pre
+        return dx

@@ -16,11 +16,28 @@ from ._lib import call, dt, ptr
 
 LOADER_NHWC, LOADER_STEM = 0, 1
 
-# Optional live profiling (bench.py): when PROFILE is a list, igemm/wgrad bracket their launch with events on the
-# launch stream and append (kernel symbol, algorithmic FLOPs, start event, end event, algorithmic bytes).
+# Optional live profiling (bench.py): when PROFILE is a list, the wrappers bracket their launch with events on the
+# launch stream (prof_begin / prof_end) and append (kernel symbol, algorithmic FLOPs, start event, end event, algorithmic bytes).
 PROFILE = None
 PROFILE_VARIANTS = []        # (symbol, variant label, FLOPs, start event, end event) of launches whose symbol covers several code paths
 PROFILE_STAGED = {}      # symbol -> bytes staged through LDS-DMA by its profiled launches (conv8p)
+
+
+def prof_begin():
+    """Start of a profiled launch: a recorded timing event while PROFILE is a list, else None (no event is created)."""
+    if PROFILE is None:
+        return None
+    e0 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    return e0
+
+
+def prof_end(e0, sym, flops, nbytes):
+    """End of the launch prof_begin() opened (e0 not None): appends (sym, flops, e0, e1, nbytes) to PROFILE; returns e1."""
+    e1 = torch.cuda.Event(enable_timing=True)
+    e1.record()
+    PROFILE.append((sym, flops, e0, e1, nbytes))
+    return e1
 
 # HBM-bound entries (no FLOPs worth counting): algorithmic bytes of one call from its C-ABI argument list -- the tensors the op
 # must read and write once (SURVEY 8(d)); recorded as ("hbm:<class>:<entry>", 0, e0, e1, bytes) while PROFILE is a list.
@@ -68,20 +85,12 @@ HBM_BYTES = {
 
 
 def _hbm_hook(name, args):
-    if PROFILE is None:
-        return None
-    ent = HBM_BYTES.get(name)
+    ent = HBM_BYTES.get(name) if PROFILE is not None else None
     if ent is None:
         return None
     cls, fn = ent
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    prof = PROFILE
-
-    def done():
-        e1.record()
-        prof.append((f"hbm:{cls}:{name[4:]}", 0.0, e0, e1, float(fn(args))))
-    return done
+    e0 = prof_begin()
+    return lambda: prof_end(e0, f"hbm:{cls}:{name[4:]}", 0.0, float(fn(args)))
 
 
 L._HOOK[0] = _hbm_hook
@@ -128,25 +137,6 @@ def pack_transpose(w3d: torch.Tensor, dtype, out=None, ldo=None, col0=0, flip=Fa
     return out
 
 
-def c64_blocks(B, H, W) -> int:
-    return L.count("vqa_conv3x3_c64_blocks", B, H, W)
-
-
-def conv3x3_c64(x, w, B, H, W, *, want_stats=False, addend=None, addmask=None):
-    """bf16 3x3/1 conv, 64->64 channels, LDS-patch kernel.  Returns (out [B*H*W, 64], stats slab | None, blocks)."""
-    nb = c64_blocks(B, H, W)
-    out = torch.empty((B * H * W, 64), device=x.device, dtype=torch.bfloat16)
-    stats = torch.empty((nb, 2, 64), device=x.device, dtype=torch.float32) if want_stats else None
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-    call("vqa_conv3x3_c64", ptr(x), ptr(w), ptr(out), ptr(stats), ptr(addend), ptr(addmask), B, H, W)
-    if PROFILE is not None:
-        e1.record()
-        PROFILE.append(("conv3x3_c64_kernel", 2.0 * B * H * W * 64 * 576, e0, e1, 2 * B * H * W * 64 * 2))
-    return out, stats, nb
-
-
 def c64p_blocks(B, H, W) -> int:
     return L.count("vqa_conv3x3_c64p_blocks", B, H, W)
 
@@ -163,13 +153,10 @@ def conv3x3_c64p(x, w, B, H, W, *, want_stats=False, stats_acc=None):
     nb = c64p_blocks(B, H, W)
     out = torch.empty((B * H * W, 64), device=x.device, dtype=torch.bfloat16)
     stats = torch.empty((nb, 2, 64), device=x.device, dtype=torch.float32) if (want_stats and stats_acc is None) else stats_acc
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = prof_begin()
     call("vqa_conv3x3_c64p", ptr(x), ptr(w), ptr(out), ptr(stats), B, H, W, int(stats_acc is not None))
-    if PROFILE is not None:
-        e1.record()
-        PROFILE.append((_c64p_sym(H, W, 0), 2.0 * B * H * W * 64 * 576, e0, e1, 2 * B * H * W * 64 * 2))
+    if e0 is not None:
+        prof_end(e0, _c64p_sym(H, W, 0), 2.0 * B * H * W * 64 * 576, 2 * B * H * W * 64 * 2)
     return out, stats, nb
 
 
@@ -177,13 +164,10 @@ def conv3x3_c64p_bnred(x, w, B, H, W, bn_y, bn_coef, bn_facc):
     """conv3x3_c64p (data gradient, w = the flipped pack) whose output is the gradient entering relu(BatchNorm(bn_y)): also adds that
     BatchNorm's backward column sums (sum g | sum g * xhat, g = out * [bn_y * scale + shift > 0]) to the zeroed accumulator bn_facc."""
     out = torch.empty((B * H * W, 64), device=x.device, dtype=torch.bfloat16)
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = prof_begin()
     call("vqa_conv3x3_c64p_bnred", ptr(x), ptr(w), ptr(out), ptr(bn_y), ptr(bn_coef), ptr(bn_facc), B, H, W)
-    if PROFILE is not None:
-        e1.record()
-        PROFILE.append((_c64p_sym(H, W, 2), 2.0 * B * H * W * 64 * 576, e0, e1, 3 * B * H * W * 64 * 2))
+    if e0 is not None:
+        prof_end(e0, _c64p_sym(H, W, 2), 2.0 * B * H * W * 64 * 576, 3 * B * H * W * 64 * 2)
     return out
 
 
@@ -191,13 +175,10 @@ def conv3x3_c64p_epi(x, w, B, H, W, *, addend, addmask=None, outmask=None):
     """Data gradient of a 64 -> 64 channel 3x3/1 conv (w = the flipped pack) with the residual block's identity path in the epilogue:
     (conv + addend * (addmask > 0)) * (outmask > 0) on the bf16 conv value (vqa_igemm's epilogue), 8-wave LDS-DMA patch kernel."""
     out = torch.empty((B * H * W, 64), device=x.device, dtype=torch.bfloat16)
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = prof_begin()
     call("vqa_conv3x3_c64p_epi", ptr(x), ptr(w), ptr(out), ptr(addend), ptr(addmask), ptr(outmask), B, H, W)
-    if PROFILE is not None:
-        e1.record()
-        PROFILE.append((_c64p_sym(H, W, 1), 2.0 * B * H * W * 64 * 576, e0, e1, (3 + (addmask is not None) + (outmask is not None)) * B * H * W * 64 * 2))
+    if e0 is not None:
+        prof_end(e0, _c64p_sym(H, W, 1), 2.0 * B * H * W * 64 * 576, (3 + (addmask is not None) + (outmask is not None)) * B * H * W * 64 * 2)
     return out
 
 
@@ -209,14 +190,11 @@ def conv3x3_c64p_bn(y, acc, bn, w, B, H, W, count, *, want_stats=False, stats_ac
     coef = torch.empty((4, 64), device=y.device, dtype=torch.float32)
     stats = torch.empty((nb, 2, 64), device=y.device, dtype=torch.float32) if (want_stats and stats_acc is None) else stats_acc
     g, b_, rm, rv, nbt = bn
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = prof_begin()
     call("vqa_conv3x3_c64p_bn", ptr(y), ptr(acc), ptr(g), ptr(b_), ptr(rm), ptr(rv), ptr(nbt), ptr(coef), ptr(w), ptr(out), ptr(stats), B, H, W,
          int(stats_acc is not None), float(count), momentum, eps)
-    if PROFILE is not None:
-        e1.record()
-        PROFILE.append((_c64p_sym(H, W, 0), 2.0 * B * H * W * 64 * 576, e0, e1, 2 * B * H * W * 64 * 2))
+    if e0 is not None:
+        prof_end(e0, _c64p_sym(H, W, 0), 2.0 * B * H * W * 64 * 576, 2 * B * H * W * 64 * 2)
     return out, stats, nb, coef
 
 
@@ -226,15 +204,12 @@ def c64w_bn_ok(B, H, W) -> bool:
 
 def wgrad3x3_c64_bn(y, coef, dy, dw, B, H, W):
     """dw += dy^T gather(relu(y * coef[0] + coef[1])): weight gradient of the conv that conv3x3_c64p_bn ran (8-wave kernel)."""
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = prof_begin()
     wsf = c64w_blocks(B, H, W) * 64 * 576
     ws = torch.empty(wsf, device=y.device, dtype=torch.float32)
     call("vqa_wgrad3x3_c64_bn", ptr(y), ptr(coef), ptr(dy), ptr(dw), B, H, W, ptr(ws), wsf)
-    if PROFILE is not None:
-        e1.record()
-        PROFILE.append(("wgrad3x3_c64", 2.0 * B * H * W * 64 * 576, e0, e1, 2 * B * H * W * 64 * 2))
+    if e0 is not None:
+        prof_end(e0, "wgrad3x3_c64", 2.0 * B * H * W * 64 * 576, 2 * B * H * W * 64 * 2)
 
 
 def conv8p_ok(B, H, W, C, N) -> bool:
@@ -245,29 +220,26 @@ def conv8p(x, w, B, H, W, C, N, *, transposed=0, stride=1, stats_acc=None, out=N
     """3x3 / 1 / pad 1 conv (or its stride-1 data gradient) on the 8-phase 224(196) x 256 x 64 tile (csrc/gemm8p.hip).  bf16 NHWC."""
     if out is None:
         out = torch.empty((B * ((H - 1) // stride + 1) * ((W - 1) // stride + 1), N), device=x.device, dtype=torch.bfloat16)
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = prof_begin()
     # fused BatchNorm-backward column sums of the stored tile: (y, coef, facc) with the ReLU mask recomputed from y, or
     # (y, coef, facc, False, y2 | None, coef2 | None) for an already masked tile (+ the shortcut BatchNorm sharing the gradient)
     bn_y, bn_coef, bn_facc, bn_self, bn_y2, bn_coef2 = (tuple(bnred) + (True, None, None))[:6] if bnred is not None else (None, None, None, True, None, None)
     call("vqa_conv8p", ptr(x), ptr(w), ptr(out), ptr(stats_acc), ptr(addend), ptr(addmask), ptr(outmask), ptr(bn_y), ptr(bn_coef), ptr(bn_facc),
          int(bool(bn_self)), ptr(bn_y2), ptr(bn_coef2),
          B, H, W, C, N, int(transposed), int(stride))
-    if PROFILE is not None:
-        e1.record()
+    if e0 is not None:
         sym = "conv8p_kernel<2, 4>" if N % 256 == 0 else "conv8p_kernel<4, 2>"      # the symbol rocprofv3 prints (the C dispatch: 256 | N)
+        flops = 2.0 * out.shape[0] * N * 9 * C
+        e1 = prof_end(e0, sym, flops,
+                      (B * H * W * C + out.shape[0] * N * (1 + sum(t is not None for t in (addend, addmask, outmask, bn_y, bn_y2))) + N * 9 * C) * 2)
         # (the same symbol runs with and without epilogue inputs -- identity-path gradient / masks / the fused BatchNorm-backward sums:
         #  PROFILE_VARIANTS lets bench.py show the two groups of launches apart)
         PROFILE_VARIANTS.append((sym, "with epilogue inputs" if (addend is not None or outmask is not None or bnred is not None) else "plain",
-                                 2.0 * out.shape[0] * N * 9 * C, e0, e1))
+                                 flops, e0, e1))
         # bytes the launch stages through LDS-DMA (tiles x K tiles x (tile rows + tile columns) x 128): what prices its K loop (DESIGN section 7)
         bmp, bn = (224, 256) if N % 256 == 0 else (448, 128)
         rpt = bmp * 7 // 8 if out.shape[0] % (bmp * 7 // 8) == 0 else bmp
         PROFILE_STAGED[sym] = PROFILE_STAGED.get(sym, 0) + (-(-out.shape[0] // rpt)) * (N // bn) * (9 * C // 64) * (bmp + bn) * 128
-        PROFILE.append((sym,
-                        2.0 * out.shape[0] * N * 9 * C, e0, e1,
-                        (B * H * W * C + out.shape[0] * N * (1 + sum(t is not None for t in (addend, addmask, outmask, bn_y, bn_y2))) + N * 9 * C) * 2))
     return out
 
 
@@ -277,15 +249,12 @@ def c64w_blocks(B, H, W) -> int:
 
 
 def wgrad3x3_c64(x, dy, dw, B, H, W):
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = prof_begin()
     wsf = c64w_blocks(B, H, W) * 64 * 576                     # one partial dW per persistent workgroup, reduced in a fixed order
     ws = torch.empty(wsf, device=x.device, dtype=torch.float32)
     call("vqa_wgrad3x3_c64", ptr(x), ptr(dy), ptr(dw), B, H, W, ptr(ws), wsf)
-    if PROFILE is not None:
-        e1.record()
-        PROFILE.append(("wgrad3x3_c64", 2.0 * B * H * W * 64 * 576, e0, e1, 2 * B * H * W * 64 * 2))   # prefix of both kernels (4-wave / 8-wave DMA)
+    if e0 is not None:
+        prof_end(e0, "wgrad3x3_c64", 2.0 * B * H * W * 64 * 576, 2 * B * H * W * 64 * 2)   # prefix of both kernels (4-wave / 8-wave DMA)
 
 
 def c128_wgrad_blocks(B, H, W):
@@ -294,43 +263,34 @@ def c128_wgrad_blocks(B, H, W):
 
 def wgrad3x3_c128(x, dy, dw, B, H, W):
     """Stage-2 shape (128 -> 128 channels, 28 x 28): 8-wave LDS-DMA weight-gradient kernel, per-workgroup slabs + fixed-order reduce."""
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = prof_begin()
     wsf = c128_wgrad_blocks(B, H, W) * 128 * 576
     ws = torch.empty(wsf, device=x.device, dtype=torch.float32)
     call("vqa_wgrad3x3_c128", ptr(x), ptr(dy), ptr(dw), B, H, W, ptr(ws), wsf)
-    if PROFILE is not None:
-        e1.record()
-        PROFILE.append(("wgrad3x3_c128p_kernel", 2.0 * B * H * W * 128 * 1152, e0, e1, 2 * B * H * W * 128 * 2))
+    if e0 is not None:
+        prof_end(e0, "wgrad3x3_c128p_kernel", 2.0 * B * H * W * 128 * 1152, 2 * B * H * W * 128 * 2)
 
 
 def dgrad_s2(dy, dyd, wt, B, H, W, C, Ho, Wo, N, R, pad, *, dtype):
     """Data gradient of a stride-2 conv (+ optional 1x1/2 shortcut) with rows grouped by parity class."""
     out = torch.empty((B * Ho * Wo, N), device=dy.device, dtype=dtype)
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = prof_begin()
     call("vqa_dgrad_s2", dt(dtype), ptr(dy), ptr(dyd), ptr(wt), ptr(out), B, H, W, C, Ho, Wo, N, R, pad)
-    if PROFILE is not None:
-        e1.record()
+    if e0 is not None:
         flops = 2.0 * B * H * W * C * N * (R * R + (1 if dyd is not None else 0))
-        PROFILE.append((f"igemm_kernel<{_tname(dtype)}, 128, {64 if N <= 64 else 128}, 2, 4, {_bk(dtype)}, 2, 2, 0>", flops, e0, e1,
-                        (B * H * W * C * (2 if dyd is not None else 1) + B * Ho * Wo * N) * 2))
+        prof_end(e0, f"igemm_kernel<{_tname(dtype)}, 128, {64 if N <= 64 else 128}, 2, 4, {_bk(dtype)}, 2, 2, 0>", flops,
+                 (B * H * W * C * (2 if dyd is not None else 1) + B * Ho * Wo * N) * 2)
     return out
 
 
 def stem_wgrad(img, dy, dw, B, H, W):
     """bf16 stem weight gradient: dw [64][7][7][3] fp32 += dy^T im2col(img)."""
     Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = prof_begin()
     ws, wsf = stem_wgrad_scratch(img.device, B, H, W)
     call("vqa_stem_wgrad", ptr(img), ptr(dy), ptr(dw), B, H, W, ptr(ws), wsf)
-    if PROFILE is not None:
-        e1.record()
-        PROFILE.append(("stem_wgrad_kernel<false>", 2.0 * B * Ho * Wo * 64 * 147, e0, e1, B * 3 * H * W * 4 + B * Ho * Wo * 64 * 2))
+    if e0 is not None:
+        prof_end(e0, "stem_wgrad_kernel<false>", 2.0 * B * Ho * Wo * 64 * 147, B * 3 * H * W * 4 + B * Ho * Wo * 64 * 2)
 
 
 def stem_wgrad_scratch(device, B, H, W):
@@ -349,13 +309,10 @@ def stem_conv(img, wstem, B, H, W, want_stats):
     Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
     y = torch.empty((B * Ho * Wo, 64), device=img.device, dtype=torch.bfloat16)
     stats = torch.empty((nb, 2, 64), device=img.device, dtype=torch.float32) if want_stats else None
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = prof_begin()
     call("vqa_stem_conv", ptr(img), ptr(wstem), ptr(y), ptr(stats), B, H, W)
-    if PROFILE is not None:
-        e1.record()
-        PROFILE.append(("stem_conv_kernel", 2.0 * B * Ho * Wo * 64 * 147, e0, e1, B * 3 * H * W * 4 + B * Ho * Wo * 64 * 2))
+    if e0 is not None:
+        prof_end(e0, "stem_conv_kernel", 2.0 * B * Ho * Wo * 64 * 147, B * 3 * H * W * 4 + B * Ho * Wo * 64 * 2)
     return y, stats, nb
 
 
@@ -367,13 +324,10 @@ def stem_conv_pool(img, wstem, coef, B, H, W):
     Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
     Hp, Wp = (Ho + 2 - 3) // 2 + 1, (Wo + 2 - 3) // 2 + 1
     x = torch.empty((B * Hp * Wp, 64), device=img.device, dtype=torch.bfloat16)
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = prof_begin()
     call("vqa_stem_conv_pool", ptr(img), ptr(wstem), ptr(coef), ptr(x), B, H, W)
-    if PROFILE is not None:
-        e1.record()
-        PROFILE.append(("stem_conv_pool_kernel", 2.0 * B * Ho * Wo * 64 * 147, e0, e1, B * 3 * H * W * 4 + B * Hp * Wp * 64 * 2))
+    if e0 is not None:
+        prof_end(e0, "stem_conv_pool_kernel", 2.0 * B * Ho * Wo * 64 * 147, B * 3 * H * W * 4 + B * Hp * Wp * 64 * 2)
     return x
 
 
@@ -389,19 +343,16 @@ def igemm(a, w, M, N, Kw, geom, *, dtype, loader=LOADER_NHWC, bias=None, addend=
     if want_stats and stats_acc is None:
         mt = L.count("vqa_igemm_mtiles", M, N, loader)
         stats = torch.empty((mt, 2, N), device=a.device, dtype=torch.float32)
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = prof_begin()
     call("vqa_igemm", dt(dtype), loader, ptr(a), ptr(w), ptr(out), ptr(bias), ptr(addend), ptr(addmask), ptr(outmask), ptr(stats),
          M, N, Kw, B, H, W, C, Ho, Wo, R, S, stride, pad, transposed, relu, float(drop_p), int(drop_seed), int(stats_acc is not None))
-    if PROFILE is not None:
-        e1.record()
+    if e0 is not None:
         var = igemm_variant(dtype, loader, M, N, Kw, geom)
         kreal = 147 if loader == LOADER_STEM else Kw
         flops = 2.0 * B * H * W * C * R * S * N if transposed else 2.0 * M * N * kreal
         es = 2 if dtype == torch.bfloat16 else 4
         nbytes = (B * H * W * C * (4 if loader == LOADER_STEM else es)) + (M * N + N * Kw) * es
-        PROFILE.append((igemm_symbol(dtype, loader, var), flops, e0, e1, nbytes))
+        prof_end(e0, igemm_symbol(dtype, loader, var), flops, nbytes)
     return out, stats, mt
 
 
@@ -409,15 +360,12 @@ def linear_dgrad_act(dz, wt, M, Kin, N, *, dtype, outact, drop_p, addend=None):
     """dx[M][Kin] = (dz[M][N] @ wt[Kin][N]^T + addend) * (outact > 0) / (1 - drop_p): a Linear's data gradient that leaves with the ReLU(+dropout)
     mask of the layer in front applied (vqa_linear_dgrad_act; bit-equal to igemm followed by vqa_bias_act_bwd)."""
     dx = torch.empty((M, Kin), device=dz.device, dtype=dtype)
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = prof_begin()
     call("vqa_linear_dgrad_act", dt(dtype), ptr(dz), ptr(wt), ptr(dx), ptr(addend), ptr(outact), float(drop_p), M, Kin, N)
-    if PROFILE is not None:
-        e1.record()
+    if e0 is not None:
         var = igemm_variant(dtype, LOADER_NHWC, M, Kin, N, linear_geom(M, N))
         es = 2 if dtype == torch.bfloat16 else 4
-        PROFILE.append((igemm_symbol(dtype, LOADER_NHWC, var), 2.0 * M * N * Kin, e0, e1, (M * N + 2 * M * Kin + N * Kin) * es))
+        prof_end(e0, igemm_symbol(dtype, LOADER_NHWC, var), 2.0 * M * N * Kin, (M * N + 2 * M * Kin + N * Kin) * es)
     return dx
 
 
@@ -442,15 +390,12 @@ def wgrad(dy, x, dw, M, N, Kw, geom, *, dtype, loader=LOADER_NHWC):
     B, H, W, C, Ho, Wo, R, S, stride, pad = geom
     kind, tn, tk, nsplit, wsf = wgrad_plan(dtype, loader, M, N, Kw, B, H, W, C, R, S)
     ws = torch.empty(wsf, device=dy.device, dtype=torch.float32) if wsf else None       # torch's caching allocator, stream-ordered
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = prof_begin()
     call("vqa_wgrad", dt(dtype), loader, ptr(dy), ptr(x), ptr(dw), M, N, Kw, B, H, W, C, Ho, Wo, R, S, stride, pad, ptr(ws), wsf)
-    if PROFILE is not None:
-        e1.record()
+    if e0 is not None:
         es = 2 if dtype == torch.bfloat16 else 4
         name = f"wgrad_dma_kernel<{tn}, {tk}, 2>" if kind else f"wgrad_kernel<{_tname(dtype)}, {tn}, {tk}, {loader}>"     # (timing includes the reduce launch)
-        PROFILE.append((name, 2.0 * M * N * Kw, e0, e1, (M * N + B * H * W * C) * es + N * Kw * 4))
+        prof_end(e0, name, 2.0 * M * N * Kw, (M * N + B * H * W * C) * es + N * Kw * 4)
 
 
 _GROUP_OK = {}
@@ -479,15 +424,12 @@ def wgrad_group(jobs, *, dtype):
     if wsf < 0:
         raise RuntimeError("wgrad_group: a job does not qualify (check wgrad_group_ok first)")
     ws = torch.empty(wsf, device=jobs[0][0].device, dtype=torch.float32) if wsf else None
-    if PROFILE is not None:
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+    e0 = prof_begin()
     call("vqa_wgrad_group", dt(dtype), n, dy, x, dw, Ms, Ns, Ks, ptr(ws), wsf)
-    if PROFILE is not None:
-        e1.record()
+    if e0 is not None:
         es = 2 if dtype == torch.bfloat16 else 4
-        PROFILE.append((f"wgrad_group_kernel<{_tname(dtype)}, 128, 128, 0>", sum(2.0 * j[3] * j[4] * j[5] for j in jobs), e0, e1,
-                        sum((j[3] * j[4] + j[3] * j[5]) * es + j[4] * j[5] * 4 for j in jobs)))
+        prof_end(e0, f"wgrad_group_kernel<{_tname(dtype)}, 128, 128, 0>", sum(2.0 * j[3] * j[4] * j[5] for j in jobs),
+                 sum((j[3] * j[4] + j[3] * j[5]) * es + j[4] * j[5] * 4 for j in jobs))
 
 
 def linear_geom(M, K):
