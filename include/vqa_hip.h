@@ -61,6 +61,21 @@ int vqa_pack_transpose_batch(int dtype, const float* flat, void* out, const long
  * dst_off (elements of wout), bias_off (floats of bout), blk0}.  vqa_igemm's relu argument: 1 = ReLU before the addend,
  * 2 = ReLU after the addend (relu(conv + bias + residual)). */
 int vqa_fold_bn_batch(int dtype, const float* flat, void* wout, float* bout, const long long* desc, int nd, int total_blocks, float eps, hipStream_t stream);
+/* MXFP8 eval path of the residual blocks (csrc/mxfp8.hip).  MXFP8 = OCP e4m3fn element codes + one E8M0 scale code per 32
+ * consecutive elements of the contraction axis (NHWC: 32 channels of one pixel; folded weights [Cout][R][S][Cin]: 32 input channels of
+ * one tap).  Quantization rule: amax == 0 -> scale 127, elements +0; amax finite -> X = clamp(floor(log2 amax) - 8, -127, 127), scale
+ * X + 127, q = e4m3fn RNE of clamp(x / 2^X, -448, 448); an Inf / NaN in the block -> scale 0xFF and every element 0x7F.
+ * vqa_mx_quant: in bf16 (dtype 1) / fp32 (dtype 0) [M][C], C % 32 == 0 -> q [M][C], s [M][C/32].
+ * vqa_fold_bn_mxfp8: vqa_fold_bn_batch's table and grid; codes at wq + dst_off, scales at ws + dst_off / 32 (dst_off % 32 == 0), bias as there.
+ * vqa_conv_mxfp8: NHWC implicit-GEMM conv (3x3 pad 1 or 1x1 pad 0, stride 1 / 2, C % 64 == 0, N % 64 == 0) of MXFP8 a / as and
+ * w / ws [N][R*S*C] with vqa_igemm's epilogue (bias fp32, bf16 addend, relu 1 before / 2 after the addend) into bf16 out and / or
+ * its MXFP8 copy oq [M][N] / os [M][N/32] (= vqa_mx_quant of the bf16 result). */
+int vqa_mx_quant(int dtype, const void* in, uint8_t* q, uint8_t* s, int M, int C, hipStream_t stream);
+int vqa_fold_bn_mxfp8(const float* flat, uint8_t* wq, uint8_t* ws, float* bout, const long long* desc, int nd, int total_blocks, float eps,
+                      hipStream_t stream);
+int vqa_conv_mxfp8(const uint8_t* a, const uint8_t* as, const uint8_t* w, const uint8_t* ws, const float* bias, const void* addend,
+                   void* out, uint8_t* oq, uint8_t* os, int M, int N, int B, int H, int W, int C, int Ho, int Wo, int R, int S,
+                   int stride, int pad, int relu, hipStream_t stream);
 /* stage-1 3x3/1 conv, 64->64 channels, bf16, LDS-resident input patch (models/cnn_backbone.py:182-187 at Cin=Cout=64): forward
  * (w = [Cout][R][S][Cin]) or data gradient (w = flipped+transposed pack) without epilogue inputs: 8-wave persistent kernel, 8 output rows per
  * block, input patches by LDS-DMA, weights in registers; stats [vqa_conv3x3_c64p_blocks][2][64] or NULL.  H % 8 == 0, W % 8 == 0. */

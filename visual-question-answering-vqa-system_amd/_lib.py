@@ -31,6 +31,9 @@ SIGNATURES = {
     "vqa_pack_transpose": [I, P, P, I, I, I, I, I, I, P],
     "vqa_pack_transpose_batch": [I, P, P, P, I, I, P],
     "vqa_fold_bn_batch": [I, P, P, P, P, I, I, F, P],
+    "vqa_mx_quant": [I, P, P, P, I, I, P],
+    "vqa_fold_bn_mxfp8": [P, P, P, P, P, I, I, F, P],
+    "vqa_conv_mxfp8": [P] * 9 + [I] * 13 + [P],
     "vqa_conv3x3_c64p_blocks": [I, I, I],
     "vqa_conv3x3_c64p": [P, P, P, P, I, I, I, I, P],
     "vqa_conv3x3_c64p_epi": [P, P, P, P, P, P, I, I, I, P],

@@ -370,6 +370,7 @@ class VQAModel(nn.Module):
         self.image_encoder.output_spatial_size = int(round(num_image_tokens ** 0.5))   # 7 in the reference (models/cnn_backbone.py:415)
         self.fusion.get_attention_visualization = self._attention_visualization
         self._engine = None
+        self._infer_precision = "bf16"             # residual-block convs of the eval (Conv+BN folded) path: set_inference_precision
         self._on_segment = None
         self._last_aux = None
         self._tapes: Dict[int, Any] = {}
@@ -429,7 +430,29 @@ class VQAModel(nn.Module):
                 raise RuntimeError("VQAModel (HIP) needs its parameters on the GPU: call model.to('cuda'); there is no CPU path")
             bufs = {n: b for n, b in self.named_buffers()}
             self._engine = self._pkg.engine.HipEngine(self.config, self._entries, self._flat, bufs, self.compute_dtype)
+        self._engine.infer_precision = self._infer_precision      # the setting lives here: .to() / _reflatten recreate the engine
         return self._engine
+
+    # ---- inference precision (extension)
+    INFERENCE_PRECISIONS = ("bf16", "mxfp8")
+
+    @property
+    def inference_precision(self) -> str:
+        return self._infer_precision
+
+    def set_inference_precision(self, precision: str) -> "VQAModel":
+        """Precision of the residual-block convolutions where the Conv+BN-folded eval path runs (eval mode without autograd: eager
+        eval forward, forward_graphed, predict, and return_aux / get_attention_maps under no_grad).  "bf16" (default) or "mxfp8"
+        (OCP MX: e4m3 elements, one E8M0 scale per 32 channels; activation scales computed per forward, weights quantized from the
+        fold on every forward).  Training, forwards under autograd, parameters, buffers and state_dict are unaffected."""
+        if precision not in self.INFERENCE_PRECISIONS:
+            raise ValueError(f"inference precision must be one of {self.INFERENCE_PRECISIONS}, got {precision!r}")
+        if precision == "mxfp8" and self.compute_dtype != torch.bfloat16:
+            raise ValueError("inference precision 'mxfp8' needs compute_dtype='bf16' (this model computes in fp32)")
+        self._infer_precision = precision
+        if self._engine is not None:
+            self._engine.infer_precision = precision
+        return self
 
     # ---- reference API
     def forward(self, images: torch.Tensor, token_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
@@ -483,7 +506,7 @@ class VQAModel(nn.Module):
         if not images.is_cuda:
             raise RuntimeError("VQAModel (HIP) got CPU inputs; this implementation only runs on an MI355X (no CPU fallback)")
         key = (tuple(images.shape), tuple(token_ids.shape), attention_mask is not None, self._flat.data_ptr(), self._ensure_engine().fold_eval,
-               getattr(self._engine, "fuse_stem_eval", None))
+               getattr(self._engine, "fuse_stem_eval", None), self._infer_precision)
         g = self._graphs.pop(key, None)
         if g is not None:
             self._graphs[key] = g                    # LRU: a hit moves the shape to the young end

@@ -115,6 +115,10 @@ class HipEngine:
         self._stem_fcoef = None
         self.fold_eval = True                     # inference (eval, no tape): Conv+BN folded, BN never runs as its own pass
         self._fold = None                         # (key, table, nd, blocks, wbuf, bbuf, views)
+        # residual-block convs of that folded path: "bf16" (vqa_igemm) or "mxfp8" (csrc/mxfp8.hip: block input quantized once, conv1
+        # writes only the MXFP8 a1, conv2 reads it; the 1x1 shortcut stays bf16).  Set by the drop-in's set_inference_precision.
+        self.infer_precision = "bf16"
+        self._foldmx = None                       # (fold key, codes, scales, bias) of the MXFP8 fold
         self.stem_w = None
         # the text encoder (many tiny, latency-bound launches) runs on its own stream beside the CNN, forward and backward;
         # the CNN weight gradients run on a second side stream (off the critical path)
@@ -204,6 +208,21 @@ class HipEngine:
         _, table, nd, blk, wbuf, bbuf, views = self._fold
         call("vqa_fold_bn_batch", K.dt(self.dtype), ptr(self.flat), ptr(wbuf), ptr(bbuf), ptr(table), nd, blk, 1e-5)
         return {w: (wbuf[wo: wo + n * k].view(n, k), bbuf[bo: bo + n]) for w, (wo, bo, n, k) in views.items()}
+
+    def _fold_mxfp8(self):
+        """MXFP8 form of the fold _fold_bn just issued (its table, one launch; the fold runs on every eval forward, so nothing goes
+        stale).  Returns {conv weight name: ((e4m3 codes [N][K], E8M0 codes [N][K/32]), bias [N])}."""
+        key, table, nd, blk, wbuf, bbuf, views = self._fold
+        if self._foldmx is None or self._foldmx[0] != key:
+            if any(wo % 32 or k % 32 for wo, _, _, k in views.values()):     # vqa_fold_bn_mxfp8's table contract
+                raise RuntimeError("MXFP8 fold: a weight offset or K is not a multiple of 32")
+            dev = self.flat.device
+            self._foldmx = (key, torch.empty(wbuf.numel(), device=dev, dtype=torch.uint8),
+                            torch.empty(wbuf.numel() // 32, device=dev, dtype=torch.uint8), torch.empty_like(bbuf))
+        _, wq, ws, bq = self._foldmx
+        K.fold_bn_mxfp8(self.flat, wq, ws, bq, table, nd, blk)
+        return {w: ((wq[wo: wo + n * k].view(n, k), ws[wo // 32: (wo + n * k) // 32].view(n, k // 32)), bq[bo: bo + n])
+                for w, (wo, bo, n, k) in views.items()}
 
     def _make_stem_fcoef(self):
         gam, bet = self.P("image_encoder.stem.1.weight"), self.P("image_encoder.stem.1.bias")
@@ -512,8 +531,10 @@ class HipEngine:
 
     # ------------------------------------------------------------------ forward
     def forward(self, images: torch.Tensor, token_ids: torch.Tensor, maskf: Optional[torch.Tensor], training: bool,
-                want_aux: bool = False, need_tape: bool = True, lowp_logits: bool = False):
-        """lowp_logits: return the logits in the compute dtype (the trainer's loss kernel reads bf16 and leaves the fp32 copy itself)."""
+                want_aux: bool = False, need_tape: bool = True, lowp_logits: bool = False, record: Optional[dict] = None):
+        """lowp_logits: return the logits in the compute dtype (the trainer's loss kernel reads bf16 and leaves the fp32 copy itself).
+        record: a dict that receives {residual block prefix: (input, output)} of the folded eval path, and under "mxfp8" also
+        {prefix + ".a1": MXFP8 a1 (codes, scales)} (tests)."""
         cfg, T = self.cfg, self.dtype
         self._site = 0
         if training:
@@ -595,6 +616,13 @@ class HipEngine:
 
         # ---- residual stages, A2-A5
         folded = self._fold_bn() if (self.fold_eval and not training and not need_tape) else None
+        foldmx, xq = None, None                   # MXFP8 folded weights; MXFP8 copy of the current block input (if one exists)
+        if folded is not None and self.infer_precision == "mxfp8":
+            if T != torch.bfloat16:
+                raise RuntimeError("infer_precision 'mxfp8' needs the bf16 compute dtype")
+            foldmx = self._fold_mxfp8()
+        elif self.infer_precision not in ("bf16", "mxfp8"):
+            raise ValueError(f"unknown infer_precision {self.infer_precision!r}")
         tape["stages"] = []
         for s, Cout in enumerate(LY.STAGE_CHANNELS, start=1):
             srec = {"blocks": []}
@@ -606,14 +634,30 @@ class HipEngine:
                     # inference: a1 = relu(conv1'(x) + b1); out = relu(conv2'(a1) + b2 + shortcut) -- two or three launches, no BN pass
                     Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
                     M = B * Ho * Wo
-                    w1, b1 = folded[p + ".conv1.weight"]
-                    w2, b2 = folded[p + ".conv2.weight"]
-                    a1, _, _ = K.igemm(x, w1, M, Cout, 9 * Cin, (B, H, W, Cin, Ho, Wo, 3, 3, stride, 1), dtype=T, bias=b1, relu=1)
+                    if foldmx is not None:
+                        # MXFP8: a1 exists only as MXFP8; block 0's conv2 also writes the MXFP8 copy block 1's conv1 reads
+                        if xq is None:
+                            xq = K.mx_quant(x)
+                        (w1, b1), (w2, b2) = foldmx[p + ".conv1.weight"], foldmx[p + ".conv2.weight"]
+                        _, a1q = K.conv_mxfp8(xq, w1, M, Cout, (B, H, W, Cin, Ho, Wo, 3, 3, stride, 1), bias=b1, relu=1,
+                                              want_bf16=False, want_mx=True)
+                    else:
+                        w1, b1 = folded[p + ".conv1.weight"]
+                        w2, b2 = folded[p + ".conv2.weight"]
+                        a1, _, _ = K.igemm(x, w1, M, Cout, 9 * Cin, (B, H, W, Cin, Ho, Wo, 3, 3, stride, 1), dtype=T, bias=b1, relu=1)
                     res = x
                     if (p + ".downsample.0.weight") in self.E:
                         wd, bd = folded[p + ".downsample.0.weight"]
                         res, _, _ = K.igemm(x, wd, M, Cout, Cin, (B, H, W, Cin, Ho, Wo, 1, 1, stride, 0), dtype=T, bias=bd)
-                    out, _, _ = K.igemm(a1, w2, M, Cout, 9 * Cout, (B, Ho, Wo, Cout, Ho, Wo, 3, 3, 1, 1), dtype=T, bias=b2, addend=res, relu=2)
+                    if foldmx is not None:
+                        out, xq = K.conv_mxfp8(a1q, w2, M, Cout, (B, Ho, Wo, Cout, Ho, Wo, 3, 3, 1, 1), bias=b2, addend=res, relu=2,
+                                               want_mx=(b == 0))
+                    else:
+                        out, _, _ = K.igemm(a1, w2, M, Cout, 9 * Cout, (B, Ho, Wo, Cout, Ho, Wo, 3, 3, 1, 1), dtype=T, bias=b2, addend=res, relu=2)
+                    if record is not None:
+                        record[p] = (x, out)
+                        if foldmx is not None:
+                            record[p + ".a1"] = a1q
                     x, H, W, C = out, Ho, Wo, Cout
                     continue
                 facc = training and self.fuse_bn_finalize and T == torch.bfloat16

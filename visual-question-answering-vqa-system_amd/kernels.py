@@ -356,6 +356,45 @@ def igemm(a, w, M, N, Kw, geom, *, dtype, loader=LOADER_NHWC, bias=None, addend=
     return out, stats, mt
 
 
+def mx_quant(x: torch.Tensor, out=None):
+    """MXFP8 copy of a bf16 / fp32 [M][C] tensor (C % 32 == 0): (e4m3 codes uint8 [M][C], E8M0 scale codes uint8 [M][C/32]).
+    The quantization rule is csrc/mxfp8.hip's (one scale per 32 consecutive elements of a row)."""
+    M, C = x.shape
+    q, s = out if out is not None else (torch.empty((M, C), device=x.device, dtype=torch.uint8),
+                                        torch.empty((M, C // 32), device=x.device, dtype=torch.uint8))
+    call("vqa_mx_quant", dt(x), ptr(x), ptr(q), ptr(s), M, C)
+    return q, s
+
+
+def fold_bn_mxfp8(flat, wq, ws, bias, table, nd, blocks, eps=1e-5):
+    """Eval Conv+BN fold of the pieces in `table` (vqa_fold_bn_batch's descriptor table) quantized to MXFP8: codes into wq, scales
+    into ws (at dst_off / 32), fp32 bias into bias.  Every piece needs dst_off % 32 == 0 and K % 32 == 0 (checked here when `table`
+    is still on the host; a device table is the caller's word -- the kernel leaves a piece that breaks it unwritten)."""
+    if not table.is_cuda:
+        t = table.view(-1, 10)
+        if bool(((t[:, 7] % 32) != 0).any()) or bool(((t[:, 6] % 32) != 0).any()):
+            raise ValueError("fold_bn_mxfp8: every piece needs dst_off % 32 == 0 and K % 32 == 0")
+        table = t.to(wq.device)
+    call("vqa_fold_bn_mxfp8", ptr(flat), ptr(wq), ptr(ws), ptr(bias), ptr(table), nd, blocks, float(eps))
+
+
+def conv_mxfp8(xq, w, M, N, geom, *, bias=None, addend=None, relu=0, want_bf16=True, want_mx=False):
+    """NHWC conv of the MXFP8 activation xq = (codes [B*H*W][C], scales [B*H*W][C/32]) with the MXFP8 weight w = (codes [N][R*S*C],
+    scales [N][R*S*C/32]); vqa_igemm's epilogue (bias, relu 1 before / 2 after the bf16 addend).  geom = (B, H, W, C, Ho, Wo, R, S,
+    stride, pad).  Returns (bf16 out [M][N] | None, its MXFP8 copy (codes, scales) | None)."""
+    B, H, W, C, Ho, Wo, R, S, stride, pad = geom
+    dev = xq[0].device
+    out = torch.empty((M, N), device=dev, dtype=torch.bfloat16) if want_bf16 else None
+    oq = (torch.empty((M, N), device=dev, dtype=torch.uint8), torch.empty((M, N // 32), device=dev, dtype=torch.uint8)) if want_mx else (None, None)
+    e0 = prof_begin()
+    call("vqa_conv_mxfp8", ptr(xq[0]), ptr(xq[1]), ptr(w[0]), ptr(w[1]), ptr(bias), ptr(addend), ptr(out), ptr(oq[0]), ptr(oq[1]),
+         M, N, B, H, W, C, Ho, Wo, R, S, stride, pad, relu)
+    if e0 is not None:
+        nbytes = B * H * W * C * 33 // 32 + N * R * S * C * 33 // 32 + M * N * (2 * int(want_bf16) + 2 * int(addend is not None))
+        prof_end(e0, f"conv_mxfp8_kernel<{128 if N % 128 == 0 else 64}>", 2.0 * M * N * R * S * C, nbytes)
+    return out, (oq if want_mx else None)
+
+
 def linear_dgrad_act(dz, wt, M, Kin, N, *, dtype, outact, drop_p, addend=None):
     """dx[M][Kin] = (dz[M][N] @ wt[Kin][N]^T + addend) * (outact > 0) / (1 - drop_p): a Linear's data gradient that leaves with the ReLU(+dropout)
     mask of the layer in front applied (vqa_linear_dgrad_act; bit-equal to igemm followed by vqa_bias_act_bwd)."""
