@@ -162,6 +162,19 @@ int vqa_stem_wgrad(const float* img, const void* dy, float* dw /* [64][7][7][3] 
 /* same, with the stem BN+ReLU+MaxPool backward apply fused in: dy is rebuilt per row from y, dpool, idx, coef, bcoef */
 int vqa_stem_wgrad_fused(const float* img, const void* y, const void* dpool, const uint8_t* idx, const float* coef,
                          const float* bcoef, float* dw, int B, int H, int W, float* ws, long long ws_floats, hipStream_t stream);
+/* Data gradient of the stem conv (the gradient with respect to the input image), an implicit GEMM over 2x2 image quads.  No atomics:
+ * every image element is written exactly once (bit-reproducible).
+ * vqa_stem_dgrad_pack: w_krsc [64][7][7][3] fp32 -> wpk, the packed [16][1024] operand in dtype (1: bf16, 0: fp32), 16*1024 elements.
+ * vqa_stem_dgrad: dy [B][Ho][Wo][64] in dtype (as vqa_stem_bwd_apply writes it) -> dimg NCHW fp32 [B][3][H][W] (overwritten).
+ *   Any H, W >= 7 the forward accepts; rows / columns past H-1 / W-1 are never written.
+ * vqa_stem_dgrad_fused: bf16 only; dy is rebuilt from y [B][Ho][Wo][64], dpool [B][Hp][Wp][64], idx, coef (4*64) and bcoef (3*64)
+ *   exactly as vqa_stem_bwd_apply computes it and never written.  vqa_stem_dgrad_fused_ok: 1 when the shape is supported (Wo even,
+ *   B*Ho*Wo*64*2 bytes addressable with 32-bit buffer offsets); otherwise vqa_stem_dgrad_fused returns VQA_EARG and launches nothing. */
+int vqa_stem_dgrad_pack(int dtype, const float* w_krsc, void* wpk, hipStream_t stream);
+int vqa_stem_dgrad(int dtype, const void* dy, const void* wpk, float* dimg, int B, int H, int W, hipStream_t stream);
+int vqa_stem_dgrad_fused_ok(int B, int H, int W);
+int vqa_stem_dgrad_fused(const void* y, const void* dpool, const uint8_t* idx, const float* coef, const float* bcoef, const void* wpk,
+                         float* dimg, int B, int H, int W, hipStream_t stream);
 
 /* ---- BatchNorm2d (nn.BatchNorm2d defaults; models/cnn_backbone.py:151,158,246,351) -----------------------------
  * coef = scale | shift | mean | invstd (4*C floats).  finalize also updates running_mean/var (momentum, unbiased var)

@@ -32,6 +32,7 @@ class _Node(nn.Module):
 # torch custom ops: the whole HIP forward and backward are registered in the `vqa_hip` namespace
 #   torch.ops.vqa_hip.vqa_forward(images, token_ids, mask, params, handle, training, want_aux) -> logits
 #   torch.ops.vqa_hip.vqa_backward(dlogits, handle, tape_id) -> flat gradient buffer (layout.py slots)
+#   torch.ops.vqa_hip.vqa_backward_input(dlogits, handle, tape_id, H, W) -> (flat gradient buffer, image gradient [B][3][H][W])
 # with a fake (shape-only) implementation and an autograd formula, so the node is visible to the dispatcher, autograd,
 # and FakeTensor tracing.  `handle` indexes a registry of live models (ops cannot carry Python objects); forward and
 # backward are explicit kernel sequences over the C ABI (engine.py).
@@ -80,13 +81,37 @@ def _(dlogits, handle, tape_id):
     return torch.empty_like(_MODELS[handle]._flat)
 
 
+@torch.library.custom_op("vqa_hip::vqa_backward_input", mutates_args=(), device_types="cuda")
+def _vqa_backward_input_op(dlogits: torch.Tensor, handle: int, tape_id: int, H: int, W: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """vqa_backward plus the gradient with respect to the images (fp32 NCHW [B][3][H][W]): the backward of a forward whose images
+    require grad.  The parameter gradients are computed either way (a frozen model's are dropped by autograd)."""
+    model = _MODELS[handle]
+    tape = model._tapes.pop(tape_id, None)
+    if tape is None:
+        raise RuntimeError(f"vqa_backward: the activations of forward #{tape_id} are gone -- either backward ran twice through it "
+                           f"(the reference needs retain_graph=True for that) or more than max_live_tapes = {model.max_live_tapes} "
+                           "training forwards were issued before its backward (raise VQAModel.max_live_tapes)")
+    G = torch.zeros_like(model._flat)
+    dimg = model._engine.backward(tape, dlogits.contiguous(), G, on_segment=model._on_segment, want_input_grad=True)
+    return G, dimg
+
+
+@_vqa_backward_input_op.register_fake
+def _(dlogits, handle, tape_id, H, W):
+    return torch.empty_like(_MODELS[handle]._flat), dlogits.new_empty((dlogits.shape[0], 3, H, W), dtype=torch.float32)
+
+
 def _setup_ctx(ctx, inputs, output):
     handle = inputs[4]
     ctx.handle = handle
     ctx.tape_id = _MODELS[handle]._tape_seq
+    ctx.image_hw = (inputs[0].shape[2], inputs[0].shape[3])
 
 
 def _backward(ctx, dlogits):
+    if ctx.needs_input_grad[0]:           # the images require grad: the stem's data gradient runs too
+        G, dimg = torch.ops.vqa_hip.vqa_backward_input(dlogits, ctx.handle, ctx.tape_id, *ctx.image_hw)
+        return dimg, None, None, G, None, None, None
     G = torch.ops.vqa_hip.vqa_backward(dlogits, ctx.handle, ctx.tape_id)
     return None, None, None, G, None, None, None
 
@@ -216,10 +241,10 @@ def _aux_encoders_bwd(ctx, dfeat, dtext):
         model._pkg._lib.call("vqa_nchw_to_nhwc", model._pkg._lib.dt(model.compute_dtype), g.data_ptr(), dfeat.data_ptr(), B, H * W, C)
     if dtext is not None:
         dtext = _from_f32(model, dtext).view(-1, dtext.shape[-1])
-    eng.backward_encoders(tape, dfeat, dtext, G, on_segment=model._on_segment)
+    dimg = eng.backward_encoders(tape, dfeat, dtext, G, on_segment=model._on_segment, want_input_grad=ctx.needs_input_grad[0])
     model._tapes.pop(ctx.tape_id, None)
     tape.pop("_G", None)
-    return None, None, None, G, None, None
+    return dimg, None, None, G, None, None
 
 
 torch.library.register_autograd("vqa_hip::vqa_aux_encoders", _aux_encoders_bwd, setup_context=_aux_encoders_setup)
@@ -464,10 +489,15 @@ class VQAModel(nn.Module):
         token_ids = token_ids.contiguous().long()
         maskf = None if attention_mask is None else attention_mask.contiguous().float()
         params = self._param_list()
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        if torch.is_grad_enabled() and (images.requires_grad or any(p.requires_grad for p in params)):
             # tapes are kept by id (gradient accumulation / loss1 + loss2: several forwards, then their backwards), oldest dropped
-            # beyond max_live_tapes
-            flat = _FlatParams.apply(self._flat, self._handle, *params)
+            # beyond max_live_tapes.  Images that require grad take this path even when no parameter does (a frozen model under
+            # saliency / adversarial attacks): the flat buffer then goes in untracked, so no parameter receives a .grad, and the
+            # forward is the taped one (never the captured graph nor the folded eval path; BatchNorm uses its running statistics)
+            if any(p.requires_grad for p in params):
+                flat = _FlatParams.apply(self._flat, self._handle, *params)
+            else:
+                flat = self._flat
             if return_aux:                   # aux tensors on the autograd graph (three chained ops, see vqa_aux_encoders above)
                 return self._forward_aux_graph(images, token_ids, maskf, flat)
             logits = torch.ops.vqa_hip.vqa_forward(images, token_ids, maskf, flat, self._handle, self.training, return_aux)

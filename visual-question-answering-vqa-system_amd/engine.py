@@ -959,15 +959,18 @@ class HipEngine:
         return dq_in, dkv_in, None
 
     # ------------------------------------------------------------------ backward
-    def backward(self, tape: dict, dlogits: torch.Tensor, G: torch.Tensor, on_segment: Optional[Callable[[str], None]] = None):
+    def backward(self, tape: dict, dlogits: torch.Tensor, G: torch.Tensor, on_segment: Optional[Callable[[str], None]] = None,
+                 want_input_grad: bool = False):
         """G: flat fp32 gradient buffer (same layout as the parameters), accumulated into (+=).  The three parts below (head,
-        fusion, encoders) run back to back without joining their side streams in between."""
+        fusion, encoders) run back to back without joining their side streams in between.  want_input_grad: also return the
+        gradient with respect to the images (fp32 NCHW [B][3][H][W], complete on the current stream); None otherwise."""
         self._bwd_begin()
         seg = self._seg_fn(on_segment)
         dfused = self._head_bwd(tape, dlogits, G, seg)
         dfeat, denc = self._fusion_bwd(tape, dfused, G, seg)
-        ev_tb = self._encoders_bwd(tape, dfeat, denc, G, seg)
+        ev_tb, dimg = self._encoders_bwd(tape, dfeat, denc, G, seg, want_input_grad=want_input_grad)
         self._bwd_join(ev_tb)
+        return dimg
 
     # The same backward in three separately callable parts, split where it reports its segments (graph-connected aux outputs:
     # dropin/models/vqa_model.py).  Each part joins its side streams, flushes its weight-gradient / fold queues, releases the tensors
@@ -993,14 +996,17 @@ class HipEngine:
         return dfeat, denc
 
     def backward_encoders(self, tape: dict, dfeat: Optional[torch.Tensor], denc: Optional[torch.Tensor], G: torch.Tensor, on_segment=None,
-                          taps: Optional[dict] = None):
+                          taps: Optional[dict] = None, want_input_grad: bool = False):
         """(dfeat, denc) -> parameter gradients of the text encoder, the CNN stages and the stem.
-        taps: image_features (fp32 NCHW [B][Cf][Hf][Wf]) -> dfeat, text_features (fp32 [B][L][d]) -> denc."""
+        taps: image_features (fp32 NCHW [B][Cf][Hf][Wf]) -> dfeat, text_features (fp32 [B][L][d]) -> denc.
+        want_input_grad: also return the image gradient (fp32 NCHW [B][3][H][W]); None otherwise."""
         self._bwd_begin()
-        ev_tb = self._encoders_bwd(self._tape_part(tape, "stages"), dfeat, denc, G, self._seg_fn(on_segment), taps or {})
+        ev_tb, dimg = self._encoders_bwd(self._tape_part(tape, "stages"), dfeat, denc, G, self._seg_fn(on_segment), taps or {},
+                                         want_input_grad=want_input_grad)
         self._bwd_join(ev_tb)
         for k in ("stages", "stem", "tlayers", "final_norm", "embed", "feat"):
             tape.pop(k, None)
+        return dimg
 
     @staticmethod
     def _tape_part(tape, key):
@@ -1138,8 +1144,9 @@ class HipEngine:
         seg("fusion")
         return dfeat, denc
 
-    def _encoders_bwd(self, tape, dfeat, denc, G, seg, taps=None):
-        """Text encoder (side stream) and CNN backward; returns the text stream's completion event (or None)."""
+    def _encoders_bwd(self, tape, dfeat, denc, G, seg, taps=None, want_input_grad=False):
+        """Text encoder (side stream) and CNN backward; returns (the text stream's completion event or None, the image gradient or
+        None)."""
         cfg, T = self.cfg, self.dtype
         training = tape["training"]
         B = tape["B"]
@@ -1232,9 +1239,10 @@ class HipEngine:
                 seg(f"image_encoder.stage{s}")
 
         # ---- stem
-        self._stem_bwd(tape, dxc, G, training, after_reduce=lambda: (self._flush_deferred_and_report(seg)))
+        dimg = self._stem_bwd(tape, dxc, G, training, after_reduce=lambda: (self._flush_deferred_and_report(seg)),
+                              want_dimg=want_input_grad)
         seg("image_encoder.stem")
-        return ev_tb if use_side else None
+        return (ev_tb if use_side else None), dimg
 
     def _flush_deferred_and_report(self, seg):
         had_deferred = bool(self._deferred)
@@ -1242,10 +1250,13 @@ class HipEngine:
         if had_deferred:
             seg("image_encoder.stage1")
 
-    def _stem_bwd(self, tape, dxc, G, training, after_reduce=None, fused=None):
+    def _stem_bwd(self, tape, dxc, G, training, after_reduce=None, fused=None, want_dimg=False):
         """Backward of conv7x7/2 -> BN -> ReLU -> MaxPool3x3/2 (models/cnn_backbone.py:349-354) given dxc = gradient of the
         pooled output [B*Hp*Wp, 64].  fused=None picks the fused weight-gradient kernel whenever the dedicated bf16 stem path
-        is active; fused=False forces the two-launch path (BN/ReLU/pool backward materialised, then the generic wgrad)."""
+        is active; fused=False forces the two-launch path (BN/ReLU/pool backward materialised, then the generic wgrad).
+        want_dimg: also compute and return the image gradient (fp32 NCHW [B][3][IH][IW]) on the current stream: beside the fused
+        weight gradient, the fused data-gradient kernel rebuilds dy from the same coefficients; on the two-launch path (fp32,
+        shapes the fused kernels reject) the generic one reads the dy that path materialises.  Returns it, or None."""
         T = self.dtype
         B = tape["B"]
         st = tape["stem"]
@@ -1272,6 +1283,10 @@ class HipEngine:
              int(training), ptr(self._gslice(G, bnp + ".weight")), ptr(self._gslice(G, bnp + ".bias")), ptr(bc))
         if after_reduce is not None:
             after_reduce()                        # stage-1 block-0 weight gradients run beside the stem weight gradient
+        # the data-gradient operand is packed here, once per backward that asks for it (not in begin_step: nothing changes for
+        # a backward without input gradients)
+        wpk = K.stem_dgrad_pack(self.P("image_encoder.stem.0.weight"), T) if want_dimg else None
+        dimg = None
         if fused:
             # dy (B x 112 x 112 x 64) is never written: the weight-gradient kernel rebuilds it row by row
             dwv = self._gslice(G, "image_encoder.stem.0.weight")
@@ -1282,11 +1297,21 @@ class HipEngine:
             if e0 is not None:
                 K.prof_end(e0, "stem_wgrad_kernel<true>", 2.0 * B * H1 * W1 * 64 * 147,
                            B * 3 * IH * IW * 4 + B * H1 * W1 * 64 * 2 + dxc.numel() * 3)
+            if want_dimg:
+                if K.stem_dgrad_fused_ok(B, IH, IW):
+                    dimg = K.stem_dgrad_fused(st["y"], dxc, st["idx"], st["coef"], bc, wpk, B, IH, IW)
+                else:                             # (a shape the fused data gradient rejects: its dy is materialised once)
+                    dy = torch.empty_like(st["y"])
+                    call("vqa_stem_bwd_apply", dt(T), ptr(dxc), ptr(st["idx"]), ptr(st["y"]), ptr(st["coef"]), ptr(bc), ptr(dy), B, H1, W1, 64)
+                    dimg = K.stem_dgrad(dy, wpk, B, IH, IW)
         else:
             dy = torch.empty_like(st["y"])
             call("vqa_stem_bwd_apply", dt(T), ptr(dxc), ptr(st["idx"]), ptr(st["y"]), ptr(st["coef"]), ptr(bc), ptr(dy), B, H1, W1, 64)
             K.wgrad(dy, st["images"], LY.mat_of(G, self.E["image_encoder.stem.0.weight"]), B * H1 * W1, 64, 147, st["geom"], dtype=T,
                     loader=K.LOADER_STEM)
+            if want_dimg:
+                dimg = K.stem_dgrad(dy, wpk, B, IH, IW)
+        return dimg
 
     def _block_bwd(self, rec, dout, G, training, masked=False, hand=None, pre=None):
         """ResidualBlock backward (reference forward: models/cnn_backbone.py:164-197).  Returns dx.

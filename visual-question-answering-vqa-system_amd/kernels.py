@@ -299,6 +299,46 @@ def stem_wgrad_scratch(device, B, H, W):
     return torch.empty(wsf, device=device, dtype=torch.float32), wsf
 
 
+def stem_dgrad_pack(w_krsc, dtype):
+    """Packed [16][1024] operand of the stem data gradient (compute dtype) from the fp32 KRSC master [64][7][7][3]."""
+    wpk = torch.empty(16 * 1024, device=w_krsc.device, dtype=dtype)
+    call("vqa_stem_dgrad_pack", dt(dtype), ptr(w_krsc), ptr(wpk))
+    return wpk
+
+
+def stem_dgrad_fused_ok(B, H, W) -> bool:
+    return L.count("vqa_stem_dgrad_fused_ok", B, H, W) > 0
+
+
+def _stem_dgrad_cost(B, H, W):
+    Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+    return Ho, Wo, 2.0 * B * Ho * Wo * 64 * 147
+
+
+def stem_dgrad(dy, wpk, B, H, W):
+    """Image gradient NCHW fp32 [B][3][H][W] from a materialised dy [B*Ho*Wo, 64] (fp32 or bf16, vqa_stem_bwd_apply)."""
+    dimg = torch.empty((B, 3, H, W), device=dy.device, dtype=torch.float32)
+    Ho, Wo, flops = _stem_dgrad_cost(B, H, W)
+    e0 = prof_begin()
+    call("vqa_stem_dgrad", dt(dy), ptr(dy), ptr(wpk), ptr(dimg), B, H, W)
+    if e0 is not None:
+        prof_end(e0, f"stem_dgrad_kernel<{'bf16' if dy.dtype == torch.bfloat16 else 'f32'},false>", flops,
+                 dy.numel() * dy.element_size() + dimg.numel() * 4)
+    return dimg
+
+
+def stem_dgrad_fused(y, dpool, idx, coef, bc, wpk, B, H, W):
+    """Image gradient NCHW fp32 [B][3][H][W] with the stem BN/ReLU/MaxPool backward folded in: dy is rebuilt from y (bf16 raw conv
+    output), dpool + idx (pooled gradient, argmax), coef and bc (BatchNorm backward coefficients) and never written."""
+    dimg = torch.empty((B, 3, H, W), device=y.device, dtype=torch.float32)
+    Ho, Wo, flops = _stem_dgrad_cost(B, H, W)
+    e0 = prof_begin()
+    call("vqa_stem_dgrad_fused", ptr(y), ptr(dpool), ptr(idx), ptr(coef), ptr(bc), ptr(wpk), ptr(dimg), B, H, W)
+    if e0 is not None:
+        prof_end(e0, "stem_dgrad_kernel<bf16,true>", flops, B * Ho * Wo * 64 * 2 + dpool.numel() * 3 + dimg.numel() * 4)
+    return dimg
+
+
 def stem_conv_blocks(B, H, W) -> int:
     return L.count("vqa_stem_conv_blocks", B, H, W)
 
