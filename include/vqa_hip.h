@@ -227,6 +227,7 @@ int vqa_stem_bwd_apply(int dtype, const void* dpool, const uint8_t* idx, const v
                        void* dy, int B, int H, int W, int C, hipStream_t stream);
 
 /* ---- SEAttention.forward (models/attention_modules.py:109-136) and its backward ---------------------------------- */
+/* C / (16 / sizeof element) must divide 256; the bottleneck 1 <= Cr <= C (any se_reduction), else VQA_EARG */
 int vqa_se_fwd(int dtype, const void* x, const float* w1, const float* w2, float* pooled, float* hidden, float* scale,
                void* out, int B, int HW, int C, int Cr,
                const float* pool_part /* or NULL: pool x here */, int pool_chunks /* = vqa_bn_apply_pool_chunks */, hipStream_t stream);
@@ -242,6 +243,7 @@ int vqa_se_bwd(int dtype, const void* dout, const void* x, const float* w1, cons
                const void* bn_y, const float* bn_coef, float* bn_slab /* or the u64 accumulator when bn_acc_mode = 1 */, int bn_acc_mode,
                hipStream_t stream);
 /* ---- SpatialAttention.forward (models/attention_modules.py:223-243) and its backward ----------------------------- */
+/* C / (16 / sizeof element) must divide 256, else VQA_EARG before anything is written; the max ignores NaN (torch propagates it) */
 int vqa_spatial_fwd(int dtype, const void* x, const float* w /* (1,2,7,7) */, float* pooled2, int* argmax, float* amap,
                     void* out, int B, int H, int W, int C, hipStream_t stream);
 long long vqa_spatial_bwd_scratch(int B, int H, int W);   /* floats of `scratch` below (3*B*H*W + the conv-weight partial sums) */

@@ -18,6 +18,7 @@ VARIANTS = [
     ("mask_none", dict(), 2, 64, 20, False, True),
     ("eval_mode_backward", dict(), 2, 64, 14, True, False),
     ("wide_head_dim64", dict(embed_dim=512, num_attention_heads=8, num_answers=24), 2, 64, 20, True, True),
+    ("se_reduction_1", dict(se_reduction=1), 2, 64, 12, True, True),
 ]
 
 
@@ -50,6 +51,26 @@ def test_variant_train_step_matches_oracle(tag, kw, B, isz, L, use_mask, trainin
     ref = np.array([float(tr.sd[n].grad.double().norm()) for n in names])
     rel = np.abs(got - ref) / np.maximum(ref, 1e-6 * ref.max())
     assert rel.max() < 3e-2, (tag, names[int(rel.argmax())], rel.max())
+
+
+def test_se_reduction_1_bf16_train_step_matches_oracle():
+    """The se_reduction_1 variant in the throughput dtype: a bottleneck as wide as the channels (Cr = 512 at stage 4, a 2 x 2 map
+    at 64 px, where the SE backward runs 256 threads per sample: Cr > threads), every gradient held to the bf16 noise floor of the
+    same model (tests/_bf16check.py)."""
+    from _bf16check import check_bf16_grads
+    cfg = O.full_config(dropout=0.0, answer_dropout=0.0, vocab_size=300, num_answers=40, embed_dim=64, se_reduction=1)
+    sd = O.init_state_dict(cfg, 31, jitter=True)
+    images, ids, mask, answers = O.synthetic_batch(2, seed=41, image_size=64, seq_len=12, vocab=300, num_answers=cfg["num_answers"])
+    m = pkg().load_dropin().VQAModel(**cfg, compute_dtype="bf16")
+    m.load_state_dict(sd)
+    m = m.to(DEV).train()
+    logits, _ = m(images.to(DEV), ids.to(DEV), mask.to(DEV))
+    loss = torch.nn.functional.cross_entropy(logits, answers.to(DEV))
+    loss.backward()
+    torch.cuda.synchronize()
+    noisy = {f"image_encoder.stage{s}.attention.se.fc1.weight" for s in (1, 2, 3)}
+    worst, lref = check_bf16_grads(m, sd, cfg, images, ids, mask, answers, noisy)
+    assert abs(loss.item() - lref) < 3e-2
 
 
 def test_stress_shape_384px_144_tokens_matches_oracle():

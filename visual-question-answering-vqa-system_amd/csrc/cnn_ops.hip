@@ -588,8 +588,20 @@ __global__ __launch_bounds__(256) void scale_kernel(const T* __restrict__ x, con
 // requests per workgroup at C = 512 / Cr = 32, which is what made the 7 x 7 x 512 stage's SE backward take 80 us for 157 MB.  Here
 // consecutive lanes read consecutive jr (thread = (channel group g, jr), G <= 64 groups), the G partials per jr are folded in group
 // order through LDS: one writer, fixed order (bit-reproducible).  part: >= NT floats of LDS free at this point; ends with a barrier.
+// Cr > NT (se_reduction < C / NT, e.g. se_reduction = 1 on a small map where vqa_se_bwd picks 256 threads): no room for even one
+// group of Cr threads, so a thread owns jr = tid, tid + NT, ... and sums all of c itself (G = 1, same order as the one-group fold).
 __device__ __forceinline__ void se_fc2_bwd(const float* __restrict__ z2, const float* __restrict__ w2, const float* __restrict__ hidden_b,
                                            float* __restrict__ dhs, float* __restrict__ dh_b, float* __restrict__ part, int C, int Cr, int NT) {
+  if (Cr > NT) {
+    for (int jr = threadIdx.x; jr < Cr; jr += NT) {
+      float t = 0.f;
+      for (int c = 0; c < C; ++c) t += z2[c] * w2[(size_t)c * Cr + jr];
+      t = hidden_b[jr] > 0.f ? t : 0.f;
+      dhs[jr] = t; dh_b[jr] = t;
+    }
+    __syncthreads();
+    return;
+  }
   const int G = min(NT / Cr, 64);
   const int jr = threadIdx.x % Cr, g = threadIdx.x / Cr;
   if (g < G) {
@@ -1322,7 +1334,7 @@ int vqa_stem_bwd_apply(int dtype, const void* dpool, const uint8_t* idx, const v
 int vqa_se_fwd(int dtype, const void* x, const float* w1, const float* w2, float* pooled, float* hidden, float* scale, void* out,
                int B, int HW, int C, int Cr, const float* pool_part, int pool_chunks, hipStream_t st) {
   const int VEC = dtype ? 8 : 4;
-  if (C % VEC || C / VEC > 256 || 256 % (C / VEC)) return VQA_EARG;
+  if (C % VEC || C / VEC > 256 || 256 % (C / VEC) || Cr < 1 || Cr > C) return VQA_EARG;
   if (pool_part && pool_chunks != vqa_bn_apply_pool_chunks(dtype, HW, C)) return VQA_EARG;
   const size_t shm = ((size_t)256 * VEC + C + Cr) * 4;
   DT(hipLaunchKernelGGL(se_pool_fc_kernel<float>, dim3(B), dim3(256), shm, st, (const float*)x, w1, w2, pooled, hidden, scale, HW, C, Cr, pool_part, pool_chunks),
@@ -1353,7 +1365,9 @@ int vqa_se_bwd(int dtype, const void* dout, const void* x, const float* w1, cons
                const float* scale, float* scratch, void* dx, float* dw1, float* dw2, int B, int HW, int C, int Cr, int mask_out,
                const void* bn_y, const float* bn_coef, float* bn_slab, int bn_acc_mode, hipStream_t st) {
   const int VEC = dtype ? 8 : 4;
-  if (C % VEC || C / VEC > 256 || 256 % (C / VEC)) return VQA_EARG;
+  // Cr <= C (the model's bottleneck is C / se_reduction) bounds the dynamic LDS of the launches below that do not raise the limit:
+  // shm <= shm2 <= (1024 * 8 + 4 * 2048) * 4 = 64 KB at bf16 C = 2048
+  if (C % VEC || C / VEC > 256 || 256 % (C / VEC) || Cr < 1 || Cr > C) return VQA_EARG;
   if ((bn_slab != nullptr) != (bn_y != nullptr) || (bn_slab != nullptr) != (bn_coef != nullptr)) return VQA_EARG;
   float* dz2 = scratch; float* dh = dz2 + (size_t)B * C; float* dpool = dh + (size_t)B * Cr;
   const int cvh = C / VEC;
@@ -1377,7 +1391,8 @@ int vqa_se_bwd(int dtype, const void* dout, const void* x, const float* w1, cons
     const int nit = (HW + nt / cvh - 1) / (nt / cvh);          // vectors a thread visits per phase
     const int nreg = !dtype || se_bwd_nreg_off() ? 0 : nit <= 2 ? 2 : 4;       // (8 / 12 kept vectors spill at the 128 registers a 1024-thread workgroup leaves a wave)
     // vectors parked in LDS on top (1024-thread form only: 16 KB each next to the 34 KB of scratch; 6 fill a CU's 160 KB)
-    const int nlds = (nreg == 4 && nt == 1024 && !se_bwd_nlds_off()) ? (nit <= 4 ? 0 : nit <= 6 ? 2 : nit <= 8 ? 4 : 6) : 0;
+    int nlds = (nreg == 4 && nt == 1024 && !se_bwd_nlds_off()) ? (nit <= 4 ? 0 : nit <= 6 ? 2 : nit <= 8 ? 4 : 6) : 0;
+    while (nlds > 0 && ((shm2 + 15) & ~(size_t)15) + (size_t)nlds * nt * 17 > 160 * 1024) nlds -= 2;    // (bf16 C = 2048 with a wide Cr: 6 would not fit)
     // one byte of [x > 0] per re-read vector and thread in LDS instead of the second read of x, where it fits beside the rest
     const int ntail = nit - nreg - nlds > 0 ? nit - nreg - nlds : 0;
     const bool tailm = nreg == 4 && mask_out && ntail > 0 && !se_bwd_nlds_off() &&
@@ -1409,13 +1424,12 @@ int vqa_se_bwd(int dtype, const void* dout, const void* x, const float* w1, cons
 
 int vqa_spatial_fwd(int dtype, const void* x, const float* w, float* pooled2, int* amax, float* amap, void* out, int B, int H, int W, int C, hipStream_t st) {
   const int VEC = dtype ? 8 : 4;
-  if (C % VEC) return VQA_EARG;
   const size_t npix = (size_t)B * H * W;
+  if (C <= 0 || C % VEC || npix >= (1ull << 28) || C / VEC > 256 || 256 % (C / VEC)) return VQA_EARG;      // before any launch: a refused call writes nothing
   const int pg = (int)((npix + 3) / 4 > 8192 ? 8192 : (npix + 3) / 4);
   DT(hipLaunchKernelGGL(spatial_pool_kernel<float>, dim3(pg), dim3(256), 0, st, (const float*)x, pooled2, amax, npix, C),
      hipLaunchKernelGGL(spatial_pool_kernel<bf16_t>, dim3(pg), dim3(256), 0, st, (const bf16_t*)x, pooled2, amax, npix, C));
   hipLaunchKernelGGL(spatial_conv_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, pooled2, w, amap, B, H, W);
-  if (npix >= (1ull << 28) || C / VEC > 256 || 256 % (C / VEC)) return VQA_EARG;
   DT(hipLaunchKernelGGL(scale_kernel<float>, dim3(px_grid(npix, C, VEC)), dim3(256), 0, st, (const float*)x, (const float*)nullptr, amap, (float*)out, (unsigned)npix, C, magic40(H * W)),
      hipLaunchKernelGGL(scale_kernel<bf16_t>, dim3(px_grid(npix, C, VEC)), dim3(256), 0, st, (const bf16_t*)x, (const float*)nullptr, amap, (bf16_t*)out, (unsigned)npix, C, magic40(H * W)));
   VQA_LAUNCH_CHECK(); return VQA_OK;
@@ -1426,14 +1440,13 @@ long long vqa_spatial_bwd_scratch(int B, int H, int W) { return 3ll * B * H * W 
 int vqa_spatial_bwd(int dtype, const void* dout, const void* x, const float* w, const float* pooled2, const int* amax, const float* amap,
                     float* scratch, void* dx, float* dw, int B, int H, int W, int C, hipStream_t st) {
   const int VEC = dtype ? 8 : 4;
-  if (C % VEC) return VQA_EARG;
   const size_t npix = (size_t)B * H * W;
+  if (C <= 0 || C % VEC || npix >= (1ull << 28) || C / VEC > 256 || 256 % (C / VEC)) return VQA_EARG;      // before any launch: a refused call writes nothing
   float* dpre = scratch; float* dpool2 = dpre + npix; float* wpart = dpool2 + 2 * npix;
   const int pg = (int)((npix + 3) / 4 > 8192 ? 8192 : (npix + 3) / 4);
   DT(hipLaunchKernelGGL(spatial_bwd_reduce_kernel<float>, dim3(pg), dim3(256), 0, st, (const float*)dout, (const float*)x, amap, dpre, npix, C),
      hipLaunchKernelGGL(spatial_bwd_reduce_kernel<bf16_t>, dim3(pg), dim3(256), 0, st, (const bf16_t*)dout, (const bf16_t*)x, amap, dpre, npix, C));
   hipLaunchKernelGGL(spatial_bwd_conv_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, dpre, w, dpool2, B, H, W);
-  if (npix >= (1ull << 28) || C / VEC > 256 || 256 % (C / VEC)) return VQA_EARG;
   DT(hipLaunchKernelGGL(spatial_bwd_apply_kernel<float>, dim3(px_grid(npix, C, VEC)), dim3(256), 0, st, (const float*)dout, amap, dpool2, amax, (float*)dx, (unsigned)npix, C),
      hipLaunchKernelGGL(spatial_bwd_apply_kernel<bf16_t>, dim3(px_grid(npix, C, VEC)), dim3(256), 0, st, (const bf16_t*)dout, amap, dpool2, amax, (bf16_t*)dx, (unsigned)npix, C));
   hipLaunchKernelGGL(spatial_wgrad_kernel, dim3(98, SPATIAL_WG_SLICES), dim3(256), 0, st, dpre, pooled2, wpart, B, H, W);
