@@ -282,6 +282,16 @@ int vqa_attention_fwd(int dtype, const void* q, const void* k, const void* v, in
 /* bf16 MFMA variant (Lq <= 32, Lk <= 64, hd 32|64): QK^T and PV as v_mfma_f32_32x32x16_bf16 tiles, softmax in registers */
 int vqa_attention_fwd_mfma(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const float* kmask, float* probs,
                            void* ctx, int ldc, int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t stream);
+/* cross-attention forward whose K / V rows (and kmask rows) for query batch b are those of image kv_index[b] (many questions per
+ * image from one cached image encoding): k, v hold n_kv images of Lk rows each; probs / ctx are per query batch as in
+ * vqa_attention_fwd(_mfma).  Inference only: no dropout.  A query batch whose index lies outside [0, n_kv) loads nothing and gets
+ * NaN in its probs and ctx rows.  The _mfma form has the limits of vqa_attention_fwd_mfma and takes no dtype (bf16). */
+int vqa_attention_fwd_idx(int dtype, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const int* kv_index,
+                          int n_kv, const float* kmask, float* probs, void* ctx, int ldc, int B, int H, int Lq, int Lk, int hd,
+                          hipStream_t stream);
+int vqa_attention_fwd_mfma_idx(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const int* kv_index, int n_kv,
+                               const float* kmask, float* probs, void* ctx, int ldc, int B, int H, int Lq, int Lk, int hd,
+                               hipStream_t stream);
 int vqa_attention_bwd(int dtype, const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
                       const float* probs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv, int B, int H, int Lq, int Lk,
                       int hd, float p, unsigned long long seed, hipStream_t stream);

@@ -92,6 +92,8 @@ SIGNATURES = {
     "vqa_layernorm_bwd_folds": [I, I, I, I, P],
     "vqa_attention_fwd": [I, P, P, P, I, I, I, P, P, P, I, I, I, I, I, I, F, ULL, P],
     "vqa_attention_fwd_mfma": [P, P, P, I, I, I, P, P, P, I, I, I, I, I, I, F, ULL, P],
+    "vqa_attention_fwd_idx": [I, P, P, P, I, I, I, P, I, P, P, P, I, I, I, I, I, I, P],
+    "vqa_attention_fwd_mfma_idx": [P, P, P, I, I, I, P, I, P, P, P, I, I, I, I, I, I, P],
     "vqa_attention_bwd": [I, P, I, P, P, P, I, I, I, P, P, P, P, I, I, I, I, I, I, I, I, F, ULL, P],
     "vqa_accuracy_update": [P, P, P, I, I, P],
     "vqa_attention_bwd_mfma": [P, I, P, P, P, I, I, I, P, P, P, P, I, I, I, I, I, I, I, I, F, ULL, P],

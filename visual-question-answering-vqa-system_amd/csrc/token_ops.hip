@@ -400,19 +400,31 @@ __global__ __launch_bounds__(512) void layernorm_bwd_bf16v_kernel(const bf16_t* 
 // ---------------------------------------------------------------------------------------------
 // Attention, one wave per (batch, head).  q/k/v/ctx are token-major with row strides ld* (elements);
 // head h occupies columns [h*hd, (h+1)*hd).  probs [B][H][Lq][Lk] fp32 holds softmax BEFORE dropout.
+// IDX (vqa_attention_fwd_idx, inference): the K / V / kmask rows of query batch b are those of image kv_index[b] (n_kv images of
+// Lk rows each); an index outside [0, n_kv) loads nothing and writes NaN to that batch's probs and ctx rows.
 // ---------------------------------------------------------------------------------------------
-template <typename T>
+template <typename T, bool IDX = false>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
                                                       int ldq, int ldk, int ldv, const float* __restrict__ kmask, float* __restrict__ probs,
-                                                      T* __restrict__ ctx, int ldc, int H, int Lq, int Lk, int hd, float scale, float p, uint64_t seed) {
+                                                      T* __restrict__ ctx, int ldc, int H, int Lq, int Lk, int hd, float scale, float p, uint64_t seed,
+                                                      const int* __restrict__ kv_index, int n_kv) {
   extern __shared__ float sm[];
   const int b = blockIdx.x / H, h = blockIdx.x - b * H, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ldh = hd + 1, ldp = Lk + 1;
+  int kb = b;                                                        // batch of the K / V / kmask rows
+  if constexpr (IDX) {
+    kb = kv_index[b];
+    if (kb < 0 || kb >= n_kv) {                                      // whole block leaves together (before any barrier)
+      for (int i = tid; i < Lq * Lk; i += 256) probs[((size_t)(b * H + h) * Lq) * Lk + i] = NAN;
+      for (int i = tid; i < Lq * hd; i += 256) { const int r = i / hd, d = i - r * hd; ctx[(size_t)(b * Lq + r) * ldc + h * hd + d] = from_f<T>(NAN); }
+      return;
+    }
+  }
   float* Qs = sm; float* Ks = Qs + Lq * ldh; float* Vs = Ks + Lk * ldh; float* Ps = Vs + Lk * ldh;
   for (int i = tid; i < Lq * hd; i += 256) { const int r = i / hd, d = i - r * hd; Qs[r * ldh + d] = to_f<T>(q[(size_t)(b * Lq + r) * ldq + h * hd + d]); }
   for (int i = tid; i < Lk * hd; i += 256) {
     const int r = i / hd, d = i - r * hd;
-    Ks[r * ldh + d] = to_f<T>(k[(size_t)(b * Lk + r) * ldk + h * hd + d]);
-    Vs[r * ldh + d] = to_f<T>(v[(size_t)(b * Lk + r) * ldv + h * hd + d]);
+    Ks[r * ldh + d] = to_f<T>(k[(size_t)(kb * Lk + r) * ldk + h * hd + d]);
+    Vs[r * ldh + d] = to_f<T>(v[(size_t)(kb * Lk + r) * ldv + h * hd + d]);
   }
   __syncthreads();
   for (int i = tid; i < Lq * Lk; i += 256) {
@@ -420,7 +432,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ q, 
     float s = 0.f;
     for (int d = 0; d < hd; ++d) s += Qs[r * ldh + d] * Ks[c * ldh + d];
     s = s / scale;                                                  // divide by sqrt(hd) before masking
-    if (kmask && kmask[b * Lk + c] == 0.f) s = -INFINITY;
+    if (kmask && kmask[kb * Lk + c] == 0.f) s = -INFINITY;
     Ps[r * ldp + c] = s;
   }
   __syncthreads();
@@ -937,8 +949,19 @@ int vqa_attention_fwd(int dtype, const void* q, const void* k, const void* v, in
   if (shm > 160 * 1024) return VQA_EARG;
   const float scale = sqrtf((float)hd);
   (void)vqa_ensure_lds(dtype ? reinterpret_cast<const void*>(&attn_fwd_kernel<bf16_t>) : reinterpret_cast<const void*>(&attn_fwd_kernel<float>), shm);
-  DT(hipLaunchKernelGGL(attn_fwd_kernel<float>, dim3(B * H), dim3(256), shm, st, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, kmask, probs, (float*)ctx, ldc, H, Lq, Lk, hd, scale, p, seed),
-     hipLaunchKernelGGL(attn_fwd_kernel<bf16_t>, dim3(B * H), dim3(256), shm, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, kmask, probs, (bf16_t*)ctx, ldc, H, Lq, Lk, hd, scale, p, seed));
+  DT(hipLaunchKernelGGL(attn_fwd_kernel<float>, dim3(B * H), dim3(256), shm, st, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, kmask, probs, (float*)ctx, ldc, H, Lq, Lk, hd, scale, p, seed, nullptr, 0),
+     hipLaunchKernelGGL(attn_fwd_kernel<bf16_t>, dim3(B * H), dim3(256), shm, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, kmask, probs, (bf16_t*)ctx, ldc, H, Lq, Lk, hd, scale, p, seed, nullptr, 0));
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+int vqa_attention_fwd_idx(int dtype, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const int* kv_index, int n_kv,
+                          const float* kmask, float* probs, void* ctx, int ldc, int B, int H, int Lq, int Lk, int hd, hipStream_t st) {
+  if (!kv_index || n_kv < 0) return VQA_EARG;
+  const size_t shm = ((size_t)(Lq + 2 * Lk) * (hd + 1) + (size_t)Lq * (Lk + 1)) * 4;
+  if (shm > 160 * 1024) return VQA_EARG;
+  const float scale = sqrtf((float)hd);
+  (void)vqa_ensure_lds(dtype ? reinterpret_cast<const void*>(&attn_fwd_kernel<bf16_t, true>) : reinterpret_cast<const void*>(&attn_fwd_kernel<float, true>), shm);
+  DT(hipLaunchKernelGGL((attn_fwd_kernel<float, true>), dim3(B * H), dim3(256), shm, st, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, kmask, probs, (float*)ctx, ldc, H, Lq, Lk, hd, scale, 0.f, 0ull, kv_index, n_kv),
+     hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, true>), dim3(B * H), dim3(256), shm, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, kmask, probs, (bf16_t*)ctx, ldc, H, Lq, Lk, hd, scale, 0.f, 0ull, kv_index, n_kv));
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
 int vqa_attention_bwd(int dtype, const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
@@ -1125,10 +1148,12 @@ typedef __attribute__((ext_vector_type(16))) float f32x16;
 
 // NKT = key tiles of 32 (2: Lk <= 64, the 49 image tokens / 20 text tokens; 5: Lk <= 160, the 144 image tokens of the 384x384
 // stress shape), WPB = waves (= (batch, head) problems) per workgroup: the wave-private LDS tiles of NKT = 5 fit two per CU.
-template <int HD, int NKT, int WPB>
+// IDX (vqa_attention_fwd_mfma_idx, inference): K / V / kmask rows of image kv_index[b] (n_kv images); out of range -> NaN rows.
+template <int HD, int NKT, int WPB, bool IDX = false>
 __global__ __launch_bounds__(WPB * 64, 1) void attn_fwd_mfma_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
                                                             int ldq, int ldk, int ldv, const float* __restrict__ kmask, float* __restrict__ probs,
-                                                            bf16_t* __restrict__ ctx, int ldc, int BH, int H, int Lq, int Lk, float p, uint64_t seed) {
+                                                            bf16_t* __restrict__ ctx, int ldc, int BH, int H, int Lq, int Lk, float p, uint64_t seed,
+                                                            const int* __restrict__ kv_index, int n_kv) {
   constexpr int LDV = HD;                       // V tile row stride (elements): 64 / 128 bytes, 8-byte aligned for the transposed reads
   constexpr int KR = NKT * 32;                  // key rows of the tiles
   constexpr int LDP = KR + 1;                   // probability staging row stride (floats)
@@ -1141,12 +1166,21 @@ __global__ __launch_bounds__(WPB * 64, 1) void attn_fwd_mfma_kernel(const bf16_t
   const int b = bh / H, h = bh - b * H;
   const int r = lane & 31, hh = lane >> 5;
   const float inv_scale = 1.0f / sqrtf((float)HD);
+  int kb = b;                                   // batch of the K / V / kmask rows
+  if constexpr (IDX) {
+    kb = __builtin_amdgcn_readfirstlane(kv_index[b]);
+    if (kb < 0 || kb >= n_kv) {                 // the whole wave leaves together
+      for (int i = lane; i < Lq * Lk; i += 64) probs[(size_t)bh * Lq * Lk + i] = NAN;
+      for (int i = lane; i < Lq * HD; i += 64) ctx[(size_t)(b * Lq + i / HD) * ldc + h * HD + i % HD] = f2bf(NAN);
+      return;
+    }
+  }
 
   // ---- V -> LDS (rows >= Lk zero), 16-byte vectors
   for (int i = lane; i < KR * (HD / 8); i += 64) {
     const int row = i / (HD / 8), cv = i - row * (HD / 8);
     u32x4 val = {0u, 0u, 0u, 0u};
-    if (row < Lk) val = *reinterpret_cast<const u32x4*>(v + (size_t)(b * Lk + row) * ldv + h * HD + cv * 8);
+    if (row < Lk) val = *reinterpret_cast<const u32x4*>(v + (size_t)(kb * Lk + row) * ldv + h * HD + cv * 8);
     *reinterpret_cast<u32x4*>(&Vs[row * LDV + cv * 8]) = val;
   }
   // ---- S^T = K Q^T
@@ -1162,7 +1196,7 @@ __global__ __launch_bounds__(WPB * 64, 1) void attn_fwd_mfma_kernel(const bf16_t
 #pragma unroll
     for (int t = 0; t < NKT; ++t) {
       bf16x8 kf = {};
-      if (32 * t + r < Lk) kf = *reinterpret_cast<const bf16x8*>(k + (size_t)(b * Lk + 32 * t + r) * ldk + h * HD + ks * 16 + 8 * hh);
+      if (32 * t + r < Lk) kf = *reinterpret_cast<const bf16x8*>(k + (size_t)(kb * Lk + 32 * t + r) * ldk + h * HD + ks * 16 + 8 * hh);
       st[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf, st[t], 0, 0, 0);
     }
   }
@@ -1174,7 +1208,7 @@ __global__ __launch_bounds__(WPB * 64, 1) void attn_fwd_mfma_kernel(const bf16_t
     for (int e = 0; e < 16; ++e) {
       const int key = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
       float s = st[t][e] * inv_scale;
-      if (key >= Lk || (kmask && kmask[b * Lk + key] == 0.f)) s = -INFINITY;
+      if (key >= Lk || (kmask && kmask[kb * Lk + key] == 0.f)) s = -INFINITY;
       st[t][e] = s;
       m = fmaxf(m, s);
     }
@@ -1241,10 +1275,26 @@ extern "C" int vqa_attention_fwd_mfma(const void* q, const void* k, const void* 
     const size_t shm = (size_t)wpb * (nkt * 32) * hd * 2 + (size_t)wpb * 32 * (nkt * 32 + 1) * 4;
     (void)vqa_ensure_lds(reinterpret_cast<const void*>(kern), shm);
     hipLaunchKernelGGL(kern, dim3((BH + wpb - 1) / wpb), dim3(wpb * 64), shm, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv,
-                       kmask, probs, (bf16_t*)ctx, ldc, BH, H, Lq, Lk, p, seed);
+                       kmask, probs, (bf16_t*)ctx, ldc, BH, H, Lq, Lk, p, seed, nullptr, 0);
   };
   if (Lk <= 64) { if (hd == 32) go(&attn_fwd_mfma_kernel<32, 2, 4>, 2, 4); else go(&attn_fwd_mfma_kernel<64, 2, 4>, 2, 4); }
   else { if (hd == 32) go(&attn_fwd_mfma_kernel<32, 5, 2>, 5, 2); else go(&attn_fwd_mfma_kernel<64, 5, 2>, 5, 2); }
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+
+extern "C" int vqa_attention_fwd_mfma_idx(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const int* kv_index, int n_kv,
+                                          const float* kmask, float* probs, void* ctx, int ldc, int B, int H, int Lq, int Lk, int hd, hipStream_t st) {
+  if (!q || !k || !v || !kv_index || n_kv < 0 || !probs || !ctx || Lq > 32 || Lk > 160 || (hd != 32 && hd != 64) || (ldq % 8) || (ldk % 8) || (ldv % 8))
+    return VQA_EARG;
+  const int BH = B * H;
+  auto go = [&](auto kern, int nkt, int wpb) {
+    const size_t shm = (size_t)wpb * (nkt * 32) * hd * 2 + (size_t)wpb * 32 * (nkt * 32 + 1) * 4;
+    (void)vqa_ensure_lds(reinterpret_cast<const void*>(kern), shm);
+    hipLaunchKernelGGL(kern, dim3((BH + wpb - 1) / wpb), dim3(wpb * 64), shm, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv,
+                       kmask, probs, (bf16_t*)ctx, ldc, BH, H, Lq, Lk, 0.f, 0ull, kv_index, n_kv);
+  };
+  if (Lk <= 64) { if (hd == 32) go(&attn_fwd_mfma_kernel<32, 2, 4, true>, 2, 4); else go(&attn_fwd_mfma_kernel<64, 2, 4, true>, 2, 4); }
+  else { if (hd == 32) go(&attn_fwd_mfma_kernel<32, 5, 2, true>, 5, 2); else go(&attn_fwd_mfma_kernel<64, 5, 2, true>, 5, 2); }
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
 

@@ -3,6 +3,8 @@
 Same constructor kwargs (:132-152), `forward(images, token_ids, attention_mask=None, return_aux=False)` (:243-311),
 `.predict` (:313-339), `.get_attention_maps` (:341-369), `.get_num_parameters` (:371-380), `.config` (:226-241),
 `create_vqa_model` (:383-407), `load_vqa_model` (:410-432) and the same 225 state_dict entries.
+Extension (inference only): many questions per image from one image encoding -- `forward(..., image_index=)`,
+`encode_images(images) -> ImageContext` and `answer(context, token_ids, ...)`.
 There is no CPU path: calling forward with CPU tensors, or without the built extension, raises.
 """
 from __future__ import annotations
@@ -14,6 +16,7 @@ from typing import Any, Dict, List, Optional, Tuple
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+import torch.optim.optimizer as _optim_hooks
 
 def _pkg():
     import sys
@@ -346,6 +349,34 @@ class _FlatParams(torch.autograd.Function):
         return (None, None) + tuple(lay.view_of(G, e) for e in model._param_entries)
 
 
+# torch.optim steps counted process-wide: an optimizer may write the parameters without bumping their version counters (its foreach
+# kernels work on aliases), so any step makes every ImageContext stale (a server that trains nothing in-process never pays for it)
+_OPT_STEPS = [0]
+
+
+def _count_optimizer_step(optimizer, args, kwargs):
+    _OPT_STEPS[0] += 1
+
+
+_optim_hooks.register_optimizer_step_post_hook(_count_optimizer_step)
+
+
+class ImageContext:
+    """The image half of the eval forward for U images (VQAModel.encode_images): every cross-attention layer's K | V per image token,
+    plus the NHWC features and projected tokens when made for aux.  Opaque; valid while the model's parameters, BatchNorm buffers
+    (through load_state_dict) and inference precision stay as they were when it was made -- answer() refuses it afterwards."""
+    __slots__ = ("num_images", "_eng", "_stamp", "_handle")
+
+    def __init__(self, num_images: int, eng_ctx: dict, stamp: tuple, handle: int):
+        self.num_images = num_images
+        self._eng = eng_ctx
+        self._stamp = stamp
+        self._handle = handle
+
+    def __repr__(self):
+        return f"ImageContext(num_images={self.num_images})"
+
+
 class VQAModel(nn.Module):
     def __init__(self, vocab_size: int = 10000, embed_dim: int = 256, num_answers: int = 1000,
                  use_se_attention: bool = True, use_spatial_attention: bool = True, se_reduction: int = 16,
@@ -401,6 +432,7 @@ class VQAModel(nn.Module):
         self._tapes: Dict[int, Any] = {}
         self._graphs: Dict[Any, Any] = {}           # captured inference graphs, one per input shape (forward_graphed)
         self._tape_seq = 0
+        self._ctx_epoch = 0                         # bumped by whatever invalidates an ImageContext torch cannot see (_ctx_stamp)
         self._handle = _NEXT_HANDLE[0]
         _NEXT_HANDLE[0] += 1
         _MODELS[self._handle] = self
@@ -439,6 +471,7 @@ class VQAModel(nn.Module):
                 p.grad = None
         self._flat = flat
         self._engine = None
+        self._ctx_epoch += 1
         self.__dict__.pop("_params_cache", None)
         if self._graphs:                             # captured graphs hold the OLD flat buffer's pointers
             torch.cuda.synchronize()
@@ -475,15 +508,27 @@ class VQAModel(nn.Module):
         if precision == "mxfp8" and self.compute_dtype != torch.bfloat16:
             raise ValueError("inference precision 'mxfp8' needs compute_dtype='bf16' (this model computes in fp32)")
         self._infer_precision = precision
+        self._ctx_epoch += 1
         if self._engine is not None:
             self._engine.infer_precision = precision
         return self
 
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        try:
+            return super().load_state_dict(state_dict, strict=strict, assign=assign)
+        finally:
+            self._ctx_epoch += 1                     # BatchNorm buffers are not views of the flat buffer: its version misses them
+
     # ---- reference API
     def forward(self, images: torch.Tensor, token_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
-                return_aux: bool = False) -> Tuple[torch.Tensor, Optional[Dict]]:
+                return_aux: bool = False, image_index: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[Dict]]:
+        """image_index (extension, inference only): images is [U, 3, H, W], token_ids [N, L] and question i is asked of image
+        image_index[i]; the result equals forward(images[image_index], token_ids, attention_mask) while the image half runs once per
+        image (see answer())."""
         if not images.is_cuda:
             raise RuntimeError("VQAModel (HIP) got CPU inputs; this implementation only runs on an MI355X (no CPU fallback)")
+        if image_index is not None:
+            return self._forward_indexed(images, token_ids, attention_mask, return_aux, image_index)
         eng = self._ensure_engine()
         images = images.contiguous().float()
         token_ids = token_ids.contiguous().long()
@@ -567,15 +612,161 @@ class VQAModel(nn.Module):
         graph.replay()
         return out
 
+    # ---- many questions per image (extension, inference only)
+    def _ctx_stamp(self, eng):
+        # what an ImageContext must still match: the flat buffer's version counter (load_state_dict, in-place writes through the
+        # parameters), the process-wide torch.optim step count, the engine's training-forward count (train-mode forwards move BatchNorm
+        # running statistics, and HipTrainer's AdamW writes the parameters through a raw pointer) and the model epoch
+        # (load_state_dict, .to(), set_inference_precision).  Four integers: answer() at N = 1 is a latency path
+        return (self._ctx_epoch, self._flat._version, _OPT_STEPS[0], eng.step_id)
+
+    def _inference_only(self, what, images=None):
+        if self.training:
+            raise RuntimeError(f"{what} is inference only: call model.eval() first")
+        if torch.is_grad_enabled() and ((images is not None and images.requires_grad)
+                                        or any(p.requires_grad for p in self._param_list())):
+            raise RuntimeError(f"{what} is inference only: run it under torch.no_grad() (or freeze the parameters)")
+
+    def _image_index(self, image_index, U: int, N: int, dev):
+        """int32 [N] device copy of a checked index, or None for the implied one (i -> i when N == U, every question on image 0 when
+        U == 1).  Range check: free for a CPU index, one device-to-host read for a device index."""
+        if image_index is None:
+            if N == U or U == 1:
+                return None
+            raise ValueError(f"image_index=None needs as many questions as images or one image; got {N} questions, {U} images")
+        if not isinstance(image_index, torch.Tensor):
+            image_index = torch.as_tensor(image_index)
+        if image_index.dim() != 1 or image_index.shape[0] != N:
+            raise ValueError(f"image_index must be 1-D with one entry per question ({N}); got shape {tuple(image_index.shape)}")
+        if image_index.dtype.is_floating_point or image_index.dtype.is_complex or image_index.dtype == torch.bool:
+            raise ValueError(f"image_index must hold integers, got {image_index.dtype}")
+        if N:
+            lo, hi = (int(v) for v in torch.stack(torch.aminmax(image_index)).tolist())
+            if lo < 0 or hi >= U:
+                raise IndexError(f"image_index holds {lo if lo < 0 else hi}, outside [0, {U}) for {U} images")
+        return image_index.to(device=dev, dtype=torch.int32)
+
+    def _implied_index(self, U: int, N: int, dev):
+        return torch.arange(N, device=dev, dtype=torch.int32) if U == N else torch.zeros(N, device=dev, dtype=torch.int32)
+
+    def _graph_put(self, key, g):
+        if len(self._graphs) >= self.graph_max_shapes:
+            torch.cuda.synchronize()                 # an evicted graph's private pool must outlive its last replay in flight
+            while len(self._graphs) >= self.graph_max_shapes:
+                self._graphs.pop(next(iter(self._graphs)))
+        self._graphs[key] = g
+
+    def _capture(self, fn):
+        """fn() twice on a side stream (warm-up), then captured into a HIP graph; returns (graph, fn's output in the graph's pool)."""
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):
+                fn()
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out = fn()
+        return graph, out
+
+    def _forward_indexed(self, images, token_ids, attention_mask, return_aux, image_index):
+        self._inference_only("forward(image_index=...)", images)
+        eng = self._ensure_engine()
+        images = images.contiguous().float()
+        token_ids = token_ids.contiguous().long()
+        U, N = images.shape[0], token_ids.shape[0]
+        idx = self._image_index(image_index, U, N, images.device)
+        if idx is None:
+            idx = self._implied_index(U, N, images.device)
+        maskf = None if attention_mask is None else attention_mask.contiguous().float()
+        if (self.graph_inference and not return_aux and 0 < N <= self.graph_max_batch and not torch.cuda.is_current_stream_capturing()):
+            key = ("image_index", tuple(images.shape), tuple(token_ids.shape), maskf is not None, self._flat.data_ptr(), eng.fold_eval,
+                   eng.fuse_stem_eval, self._infer_precision)
+            g = self._graphs.pop(key, None)
+            if g is None:
+                st_img, st_ids, st_idx = images.detach().clone(), token_ids.detach().clone(), idx.clone()
+                st_msk = None if maskf is None else maskf.detach().clone()
+                graph, out = self._capture(lambda: eng.answer(eng.encode_images(st_img), st_ids, st_msk, st_idx)[0])
+                g = (graph, st_img, st_ids, st_msk, st_idx, out)
+            self._graph_put(key, g)                  # (re)inserted at the young end of the LRU order
+            graph, st_img, st_ids, st_msk, st_idx, out = g
+            st_img.copy_(images); st_ids.copy_(token_ids); st_idx.copy_(idx)
+            if st_msk is not None:
+                st_msk.copy_(maskf)
+            graph.replay()
+            return out.clone(), None
+        logits, aux = eng.answer(eng.encode_images(images, want_aux=return_aux), token_ids, maskf, idx, want_aux=return_aux)
+        return (logits, aux) if return_aux else (logits, None)
+
+    def encode_images(self, images: torch.Tensor) -> ImageContext:
+        """Run the image half of the eval forward once per image (stem, residual stages, SE / spatial attention, projector and the
+        K / V projections of every cross-attention layer) and keep it for answer().  Inference only (eval mode, no autograd).  The
+        context keeps about 100 KB per image at the default configuration (49 tokens x 2 layers x K | V in bf16), and the NHWC features
+        plus projected tokens for return_aux (another ~75 KB)."""
+        if not images.is_cuda:
+            raise RuntimeError("VQAModel (HIP) got CPU inputs; this implementation only runs on an MI355X (no CPU fallback)")
+        self._inference_only("encode_images", images)
+        eng = self._ensure_engine()
+        ctx = eng.encode_images(images.contiguous().float(), want_aux=True)
+        return ImageContext(images.shape[0], ctx, self._ctx_stamp(eng), self._handle)
+
+    def answer(self, context: ImageContext, token_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
+               image_index: Optional[torch.Tensor] = None, return_aux: bool = False) -> Tuple[torch.Tensor, Optional[Dict]]:
+        """Logits of N questions over a context of encode_images(): question i is asked of image image_index[i] (None: i -> i when
+        N == context.num_images, or every question on image 0 when the context holds one image).  Equals forward(images[image_index],
+        token_ids, attention_mask) and costs only the question path.  Inference only.  Up to graph_max_batch questions (without aux) a
+        captured HIP graph of the question path is replayed, keyed on (images, questions, length, mask, parameters, precision); the
+        context's K / V are copied into the graph's buffers, so one graph serves every context of that shape.  A device image_index
+        costs one device-to-host read (the range check); a CPU one costs none.  Raises RuntimeError for a context made before the
+        parameters, BatchNorm buffers (load_state_dict) or inference precision changed, or before a train-mode forward."""
+        if not isinstance(context, ImageContext) or context._handle != self._handle:
+            raise ValueError("answer() needs an ImageContext made by this model's encode_images()")
+        self._inference_only("answer")
+        eng = self._ensure_engine()
+        if context._stamp != self._ctx_stamp(eng):
+            raise RuntimeError("stale ImageContext: the parameters, BatchNorm buffers or inference precision changed since "
+                               "encode_images() made it; encode the images again")
+        if not token_ids.is_cuda:
+            raise RuntimeError("VQAModel (HIP) got CPU inputs; this implementation only runs on an MI355X (no CPU fallback)")
+        token_ids = token_ids.contiguous().long()
+        U, (N, L) = context.num_images, token_ids.shape
+        dev = token_ids.device
+        idx = self._image_index(image_index, U, N, dev)
+        maskf = None if attention_mask is None else attention_mask.contiguous().float()
+        ec = context._eng
+        if (self.graph_inference and not return_aux and 0 < N <= self.graph_max_batch and not torch.cuda.is_current_stream_capturing()):
+            key = ("answer", U, N, L, maskf is not None, idx is None, self._flat.data_ptr(), self._infer_precision)
+            g = self._graphs.pop(key, None)
+            if g is None:
+                st_ids = token_ids.clone()
+                st_msk = None if maskf is None else maskf.clone()
+                st_idx = self._implied_index(U, N, dev) if idx is None else idx.clone()
+                st_ctx = {"kv": ec["kv"].clone(), "U": U, "ntok": ec["ntok"]}
+                graph, out = self._capture(lambda: eng.answer(st_ctx, st_ids, st_msk, st_idx)[0])
+                g = (graph, st_ctx, st_ids, st_msk, st_idx, out)
+            self._graph_put(key, g)
+            graph, st_ctx, st_ids, st_msk, st_idx, out = g
+            st_ctx["kv"].copy_(ec["kv"]); st_ids.copy_(token_ids)
+            if idx is not None:
+                st_idx.copy_(idx)
+            if st_msk is not None:
+                st_msk.copy_(maskf)
+            graph.replay()
+            return out.clone(), None
+        if idx is None:
+            idx = self._implied_index(U, N, dev)
+        logits, aux = eng.answer(ec, token_ids, maskf, idx, want_aux=return_aux)
+        return (logits, aux) if return_aux else (logits, None)
+
     graph_inference = True        # eval-mode no-grad forward()/predict() replay a captured HIP graph up to graph_max_batch
     graph_max_batch = 64          # (the serving case, api/inference.py:196-323: model(...) at B = 1 ... a few)
     graph_max_shapes = 16         # distinct input shapes kept captured (least recently used dropped first)
     max_live_tapes = 4            # training forwards whose backward has not run yet (each pins its activations)
 
-    def predict(self, images, token_ids, attention_mask=None, top_k: int = 5):
+    def predict(self, images, token_ids, attention_mask=None, top_k: int = 5, image_index=None):
         self.eval()
         with torch.no_grad():
-            logits, _ = self.forward(images, token_ids, attention_mask)    # (replays the HIP graph of this shape for B <= graph_max_batch)
+            logits, _ = self.forward(images, token_ids, attention_mask, image_index=image_index)    # (replays the HIP graph of this shape for B <= graph_max_batch)
             probs = F.softmax(logits, dim=-1)
             top_probs, top_indices = probs.topk(top_k, dim=-1)
         return top_indices, top_probs
@@ -585,8 +776,8 @@ class VQAModel(nn.Module):
         b, lq, _ = avg.shape
         return avg.view(b, lq, spatial_size, spatial_size)
 
-    def get_attention_maps(self, images, token_ids, attention_mask=None) -> Dict[str, torch.Tensor]:
-        _, aux = self.forward(images, token_ids, attention_mask, return_aux=True)
+    def get_attention_maps(self, images, token_ids, attention_mask=None, image_index=None) -> Dict[str, torch.Tensor]:
+        _, aux = self.forward(images, token_ids, attention_mask, return_aux=True, image_index=image_index)
         vis = self._attention_visualization(aux["cross_attention_weights"], self.image_encoder.output_spatial_size)
         return {"cross_attention": aux["cross_attention_weights"], "cross_attention_spatial": vis}
 

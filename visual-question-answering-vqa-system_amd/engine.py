@@ -841,10 +841,11 @@ class HipEngine:
         return nkv, stkv, self._lin(nkv, wk), self._lin(nkv, wv), d, False
 
     def _attn_block_fwd(self, q_in, kv_in, _unused, norm_q, norm_kv, attn, kmask, B, Lq, Lk, heads, hd, p, norm_f, fc1, fc2, self_attn,
-                        pre_q=None, pre_kv=None, probs=None):
+                        pre_q=None, pre_kv=None, probs=None, kv_index=None, n_kv=0):
         """pre-norm attention + FFN block (TransformerEncoderLayer.forward text_encoder.py:373-399 and
         MultiHeadCrossAttention.forward cross_attention.py:285-299).  pre_q / pre_kv: the results of _cross_q_path / _cross_kv_path when
-        the caller issued them earlier (on another stream, already joined)."""
+        the caller issued them earlier (on another stream, already joined).  kv_index (answer(), inference): int32 [B] on the device,
+        query batch b attends to the K / V rows of image kv_index[b] of the n_kv images in pre_kv."""
         T = self.dtype
         d = heads * hd
         wq, wk, wv = attn + ".W_q.weight", attn + ".W_k.weight", attn + ".W_v.weight"
@@ -865,7 +866,15 @@ class HipEngine:
             probs = torch.empty((B, heads, Lq, Lk), device=Q.device, dtype=torch.float32)
         ctx = torch.empty((B * Lq, d), device=Q.device, dtype=T)
         sa = self._seed()
-        if T == torch.bfloat16 and Lq <= 32 and Lk <= 160 and hd in (32, 64):
+        if kv_index is not None:
+            assert p == 0.0, "indexed attention is inference only"
+            if T == torch.bfloat16 and Lq <= 32 and Lk <= 160 and hd in (32, 64):
+                call("vqa_attention_fwd_mfma_idx", ptr(Q), ptr(Kt), ptr(V), ldq, ldkv, ldkv, ptr(kv_index), n_kv, ptr(kmask), ptr(probs), ptr(ctx),
+                     d, B, heads, Lq, Lk, hd)
+            else:
+                call("vqa_attention_fwd_idx", dt(T), ptr(Q), ptr(Kt), ptr(V), ldq, ldkv, ldkv, ptr(kv_index), n_kv, ptr(kmask), ptr(probs),
+                     ptr(ctx), d, B, heads, Lq, Lk, hd)
+        elif T == torch.bfloat16 and Lq <= 32 and Lk <= 160 and hd in (32, 64):
             call("vqa_attention_fwd_mfma", ptr(Q), ptr(Kt), ptr(V), ldq, ldkv, ldkv, ptr(kmask), ptr(probs), ptr(ctx), d, B, heads, Lq, Lk, hd,
                  float(p), sa)
         else:
@@ -881,6 +890,192 @@ class HipEngine:
                     probs=probs, ctx=ctx, sa=sa, so=so,
                     x1=x1, nf=nf, stf=stf, h=h, s1=s1, s2=s2, out=out, p=p, norm_q=norm_q, norm_kv=norm_kv, attn=attn, norm_f=norm_f,
                     fc1=fc1, fc2=fc2, self_attn=self_attn, B=B, Lq=Lq, Lk=Lk, heads=heads, hd=hd)
+
+    # ------------------------------------------------------------------ many questions per image (inference only)
+    def encode_images(self, images: torch.Tensor, want_aux: bool = False) -> dict:
+        """The image half of the eval forward, once per image: the one-launch stem, the Conv+BN-folded stages (bf16 or MXFP8,
+        infer_precision), SE / spatial attention, the projector (Linear + position embedding + LayerNorm) and norm_kv + W_k | W_v of
+        EVERY cross-attention layer.  Same launches and bits as forward(training=False, need_tape=False) issues for these tensors.
+        Returns the context answer() reads: {"kv": [ncl][U*ntok][2d] compute dtype (K | V per image token), "U", "ntok"} and, with
+        want_aux, "feat" (NHWC features [U*ntok][512]) and "img" (projected image tokens [U*ntok][d])."""
+        cfg, T = self.cfg, self.dtype
+        if not self.fold_eval:
+            raise RuntimeError("encode_images runs the Conv+BN-folded eval path (fold_eval = True)")
+        if self.infer_precision not in ("bf16", "mxfp8"):
+            raise ValueError(f"unknown infer_precision {self.infer_precision!r}")
+        self._site = 0
+        self.begin_step(for_backward=False)
+        U, _, IH, IW = images.shape
+        dev = images.device
+        # ---- stem (forward's inference form)
+        H1, W1 = (IH + 6 - 7) // 2 + 1, (IW + 6 - 7) // 2 + 1
+        M = U * H1 * W1
+        Hp, Wp = (H1 + 2 - 3) // 2 + 1, (W1 + 2 - 3) // 2 + 1
+        x = None
+        if self.fuse_stem_eval and self.stem_w2 is not None:
+            x = K.stem_conv_pool(images, self.stem_w2, self._bn_coef("image_encoder.stem.1", None, 0, 64, M, False), U, IH, IW)
+        if x is None:
+            if self.stem_w2 is not None and K.stem_conv_blocks(U, IH, IW) > 0:
+                y, st, mt = K.stem_conv(images, self.stem_w2, U, IH, IW, False)
+            else:
+                y, st, mt = K.igemm(images, self.stem_w, M, 64, self.stem_kp, (U, IH, IW, 3, H1, W1, 7, 7, 2, 3), dtype=T,
+                                    loader=K.LOADER_STEM, want_stats=False)
+            coef = self._bn_coef("image_encoder.stem.1", st, mt, 64, M, False)
+            x = torch.empty((U * Hp * Wp, 64), device=dev, dtype=T)
+            idx = torch.empty((U * Hp * Wp, 64), device=dev, dtype=torch.uint8)
+            call("vqa_stem_pool_fwd", dt(T), ptr(y), ptr(coef), ptr(x), ptr(idx), U, H1, W1, 64)
+        H, W, C = Hp, Wp, 64
+        # ---- residual stages (Conv+BN folded), SE, spatial attention
+        folded = self._fold_bn()
+        foldmx, xq = None, None
+        if self.infer_precision == "mxfp8":
+            if T != torch.bfloat16:
+                raise RuntimeError("infer_precision 'mxfp8' needs the bf16 compute dtype")
+            foldmx = self._fold_mxfp8()
+        for s, Cout in enumerate(LY.STAGE_CHANNELS, start=1):
+            for b in range(2):
+                p = f"image_encoder.stage{s}.blocks.{b}"
+                stride = 2 if (b == 0 and s > 1) else 1
+                Cin = C
+                Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
+                M = U * Ho * Wo
+                if foldmx is not None:
+                    if xq is None:
+                        xq = K.mx_quant(x)
+                    (w1, b1), (w2, b2) = foldmx[p + ".conv1.weight"], foldmx[p + ".conv2.weight"]
+                    _, a1q = K.conv_mxfp8(xq, w1, M, Cout, (U, H, W, Cin, Ho, Wo, 3, 3, stride, 1), bias=b1, relu=1, want_bf16=False, want_mx=True)
+                else:
+                    w1, b1 = folded[p + ".conv1.weight"]
+                    w2, b2 = folded[p + ".conv2.weight"]
+                    a1, _, _ = K.igemm(x, w1, M, Cout, 9 * Cin, (U, H, W, Cin, Ho, Wo, 3, 3, stride, 1), dtype=T, bias=b1, relu=1)
+                res = x
+                if (p + ".downsample.0.weight") in self.E:
+                    wd, bd = folded[p + ".downsample.0.weight"]
+                    res, _, _ = K.igemm(x, wd, M, Cout, Cin, (U, H, W, Cin, Ho, Wo, 1, 1, stride, 0), dtype=T, bias=bd)
+                if foldmx is not None:
+                    out, xq = K.conv_mxfp8(a1q, w2, M, Cout, (U, Ho, Wo, Cout, Ho, Wo, 3, 3, 1, 1), bias=b2, addend=res, relu=2, want_mx=(b == 0))
+                else:
+                    out, _, _ = K.igemm(a1, w2, M, Cout, 9 * Cout, (U, Ho, Wo, Cout, Ho, Wo, 3, 3, 1, 1), dtype=T, bias=b2, addend=res, relu=2)
+                x, H, W, C = out, Ho, Wo, Cout
+            ap = f"image_encoder.stage{s}.attention"
+            if (ap + ".se.fc1.weight") in self.E:
+                Cr = self.E[ap + ".se.fc1.weight"].shape[0]
+                pooled = torch.empty((U, C), device=dev, dtype=torch.float32)
+                hidden = torch.empty((U, Cr), device=dev, dtype=torch.float32)
+                scale = torch.empty((U, C), device=dev, dtype=torch.float32)
+                out = torch.empty_like(x)
+                call("vqa_se_fwd", dt(T), ptr(x), ptr(self.P(ap + ".se.fc1.weight")), ptr(self.P(ap + ".se.fc2.weight")),
+                     ptr(pooled), ptr(hidden), ptr(scale), ptr(out), U, H * W, C, Cr, None, 0)
+                x = out
+            if (ap + ".spatial.conv.weight") in self.E:
+                pooled2 = torch.empty((U * H * W, 2), device=dev, dtype=torch.float32)
+                amax = torch.empty((U * H * W,), device=dev, dtype=torch.int32)
+                amap = torch.empty((U * H * W,), device=dev, dtype=torch.float32)
+                out = torch.empty_like(x)
+                call("vqa_spatial_fwd", dt(T), ptr(x), ptr(self.P(ap + ".spatial.conv.weight")), ptr(pooled2), ptr(amax),
+                     ptr(amap), ptr(out), U, H, W, C)
+                x = out
+        feat, ntok, d = x, H * W, cfg["embed_dim"]
+        # ---- projector, then norm_kv + W_k | W_v of every cross layer (all read the same image tokens, cross_attention.py:357-361)
+        pj = "fusion.image_projector.projection"
+        pz = self._lin(feat, pj + ".0.weight", pj + ".0.bias")
+        sdp = self._seed()
+        posemb = self.P("fusion.image_projector.position_embedding")
+        if ntok * d > posemb.numel():
+            raise RuntimeError(f"{ntok} image tokens but position_embedding holds {posemb.numel() // d} (num_image_tokens)")
+        img, _ = self._ln(pz, pj + ".1", p=0.0, seed=sdp, addrow=posemb, period=ntok)
+        ncl = cfg["num_cross_layers"]
+        kv = torch.empty((ncl, U * ntok, 2 * d), device=dev, dtype=T)
+        for l in range(ncl):
+            a = f"fusion.cross_attention.layers.{l}"
+            nkv, _ = self._ln(img, a + ".norm_kv")
+            wk, wv = a + ".cross_attention.W_k.weight", a + ".cross_attention.W_v.weight"
+            if self._adjacent([wk, wv]):                 # the one [2d][d] GEMM _cross_kv_path issues, written into this layer's slot
+                e0 = self.E[wk]
+                w = self.wsrc[e0.offset: e0.offset + 2 * d * d].view(2 * d, d)
+                K.igemm(nkv, w, U * ntok, 2 * d, d, K.linear_geom(U * ntok, d), dtype=T, out=kv[l])
+            else:
+                kv[l, :, :d].copy_(self._lin(nkv, wk))
+                kv[l, :, d:].copy_(self._lin(nkv, wv))
+        ctx = {"kv": kv, "U": U, "ntok": ntok}
+        if want_aux:
+            ctx.update(feat=feat, img=img, Hf=H, Wf=W, Cf=C)
+        return ctx
+
+    def answer(self, ctx: dict, token_ids: torch.Tensor, maskf: Optional[torch.Tensor], kv_index: torch.Tensor, want_aux: bool = False):
+        """The question half of the eval forward over a context of encode_images(): text encoder, every cross layer's query path with
+        vqa_attention_fwd(_mfma)_idx over the cached K / V (question i attends to image kv_index[i]), the masked pools, the gate,
+        output_norm and the head.  kv_index: int32 [N] on the device, every entry in [0, ctx["U"]) (the caller checks).  All on the
+        current stream, no tape, no weight cast: the compute-dtype weights are those encode_images() cast (the drop-in refuses a context
+        once the parameters changed).  Returns (fp32 logits [N][num_answers], aux | None)."""
+        cfg, T = self.cfg, self.dtype
+        self._site = 0
+        d, heads = cfg["embed_dim"], cfg["num_attention_heads"]
+        hd = d // heads
+        N, L = token_ids.shape
+        U, ntok, kvs = ctx["U"], ctx["ntok"], ctx["kv"]
+        dev = token_ids.device
+        pe = self.buf["text_encoder.positional_encoding.pe"]
+        if L > pe.shape[1]:
+            raise RuntimeError(f"sequence length {L} exceeds max_question_length {pe.shape[1]}")
+        # ---- text encoder (forward's issue_text, dropout off)
+        emb_e = self.E["text_encoder.token_embedding.weight"]
+        sd0 = self._seed()
+        xt = torch.empty((N * L, d), device=dev, dtype=T)
+        call("vqa_embed_fwd", dt(T), ptr(token_ids), ptr(self.P(emb_e.name)), ptr(pe), ptr(xt), N * L, L, d, emb_e.shape[0], math.sqrt(d), 0.0, sd0)
+        for l in range(cfg["num_transformer_layers"]):
+            p = f"text_encoder.layers.{l}"
+            rec = self._attn_block_fwd(xt, xt, None, p + ".norm1", None, p + ".self_attention", maskf, N, L, L, heads, hd, 0.0,
+                                       p + ".norm2", p + ".ffn.fc1", p + ".ffn.fc2", self_attn=True)
+            xt = rec["out"]
+        enc, _ = self._ln(xt, "text_encoder.final_norm")
+        # ---- cross layers over the cached K / V
+        q = enc
+        ncl = cfg["num_cross_layers"]
+        caw = torch.empty((ncl, N, heads, L, ntok), device=dev, dtype=torch.float32) if (want_aux and ncl) else None
+        probs_all = []
+        for l in range(ncl):
+            p = f"fusion.cross_attention.layers.{l}"
+            pkv = (None, None, kvs[l], kvs[l][:, d:], 2 * d, True)
+            rec = self._attn_block_fwd(q, None, None, p + ".norm_query", p + ".norm_kv", p + ".cross_attention", None, N, L, ntok,
+                                       heads, hd, 0.0, p + ".norm_ffn", p + ".ffn.0", p + ".ffn.3", self_attn=False,
+                                       pre_kv=pkv, probs=None if caw is None else caw[l], kv_index=kv_index, n_kv=U)
+            probs_all.append(rec["probs"])
+            q = rec["out"]
+        # ---- pools, gate, output_norm, head (forward's tail, dropout off)
+        cat = torch.empty((N, 2 * d), device=dev, dtype=T)
+        call("vqa_masked_pool_pair_fwd", dt(T), ptr(q), ptr(enc), ptr(maskf), ptr(cat), N, L, d)
+        fused_pre = torch.empty((N, d), device=dev, dtype=T)
+        if cfg["use_gating"]:
+            z = self._lin(cat, "fusion.gate.gate.0.weight", "fusion.gate.gate.0.bias")
+            call("vqa_gate_fwd", dt(T), ptr(z), ptr(cat), ptr(fused_pre), N, d)
+        else:
+            att = cat[:, :d].contiguous(); txt = cat[:, d:].contiguous()
+            call("vqa_add", dt(T), ptr(att), ptr(txt), ptr(fused_pre), N * d)
+        fused, _ = self._ln(fused_pre, "fusion.output_norm")
+        c = "answer_head.classifier"
+        s1, s2 = self._seed(), self._seed()
+        h1 = self._lin(fused, c + ".0.weight", c + ".0.bias", relu=1, p=0.0, seed=s1)
+        h2 = self._lin(h1, c + ".3.weight", c + ".3.bias", relu=1, p=0.0, seed=s2)
+        logits = self._lin(h2, c + ".6.weight", c + ".6.bias")
+        logits_f = logits.float() if T != torch.float32 else logits
+        aux = None
+        if want_aux:
+            if "feat" not in ctx:
+                raise RuntimeError("aux outputs need a context made with want_aux=True")
+            Hf, Wf, Cf = ctx["Hf"], ctx["Wf"], ctx["Cf"]
+            feat_nchw = torch.empty((U, Cf, Hf, Wf), device=dev, dtype=torch.float32)
+            call("vqa_nhwc_to_nchw", dt(T), ptr(ctx["feat"]), ptr(feat_nchw), U, Hf * Wf, Cf)
+            aux = {
+                "image_features": feat_nchw,                               # one row per unique image
+                "text_features": enc.float().view(N, L, d),
+                "text_pooled": cat[:, d:].float(),
+                "fused": fused.float(),
+                "cross_attention_weights": probs_all,                      # per question
+                "image_projected": ctx["img"].float().view(U, ntok, d),    # one row per unique image
+                "attended_pooled": cat[:, :d].float(),
+            }
+        return logits_f, aux
 
     def _attn_block_bwd(self, rec, dout, G, dkv_addend=None, kv_side=False, addend_event=None, dprobs=None):
         """Returns (d q_in, d kv_in, event) ; for self-attention d kv_in is folded into d q_in.

@@ -76,6 +76,9 @@ HBM_BYTES = {
     "vqa_attention_bwd_mfma": ("attention", lambda a: 2 * (a[15] * (a[17] + 2 * a[18]) * a[1]) * 2 + a[15] * a[17] * a[1] * 2 + a[15] * a[16] * a[17] * a[18] * 4),
     "vqa_attention_fwd": ("attention", lambda a: (a[11] * (a[13] + 2 * a[14]) * a[10] + a[11] * a[13] * a[10]) * _ES(a[0]) + a[11] * a[12] * a[13] * a[14] * 4),
     "vqa_attention_bwd": ("attention", lambda a: 2 * (a[16] * (a[18] + 2 * a[19]) * a[2]) * _ES(a[0]) + a[16] * a[18] * a[2] * _ES(a[0]) + a[16] * a[17] * a[18] * a[19] * 4),
+    # indexed form (answer()): queries, ctx and probs per question, K / V once per image
+    "vqa_attention_fwd_mfma_idx": ("attention", lambda a: 2 * a[12] * a[14] * a[13] * a[16] * 2 + 2 * a[7] * a[15] * a[13] * a[16] * 2 + a[12] * a[13] * a[14] * a[15] * 4),
+    "vqa_attention_fwd_idx": ("attention", lambda a: (2 * a[13] * a[15] * a[14] * a[17] + 2 * a[8] * a[16] * a[14] * a[17]) * _ES(a[0]) + a[13] * a[14] * a[15] * a[16] * 4),
     "vqa_cross_entropy": ("token", lambda a: a[6] * a[7] * (_ES(a[0]) + 4)),
     # weight staging and the optimizer tail (H, N1): cast of the flat buffer, packed data-gradient operands, sum of squares, AdamW
     "vqa_convert": ("optimizer", lambda a: a[4] * (_ES(a[0]) + _ES(a[1]))),
