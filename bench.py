@@ -5,11 +5,13 @@ all-reduce + clip_grad_norm_(1.0) + AdamW) of the VQA model.
   python bench.py --gpus 1 --steps K --warmup W                      # BASELINE configs[2]: B=512/GPU, 224x224, 20 tokens, bf16 MFMA
   python bench.py ... --dump-outputs DIR                             # + the last timed step's loss, logits and a fixed sample of the
                                                                      #   updated parameters as DIR/<name>.npy (compare two builds)
+  python bench.py ... --full                                         # + the secondary measurements below (roofline, extras, cpu_baseline)
   python bench.py --config stress                                    # BASELINE configs[4]: B=256/GPU, 384x384 -> 144 image tokens,
                                                                      #   d=512, 8 text layers, 2000 answers, bf16
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line, in
+which `roofline`, `cpu_baseline` and `extras` are null.  With --full it also measures and carries
   roofline     : dominant GEMM-class kernel (by time) of a train step, algorithmic FLOP/s from live event timings vs the gfx950 MFMA
                  peak, plus `hbm_classes`: the HBM-bound kernel classes (BatchNorm passes, SE / spatial attention, stem pooling,
                  token-side elementwise, optimizer tail) with algorithmic bytes / time vs 8 TB/s
@@ -17,6 +19,7 @@ Prints ONE JSON line on rank 0 (contract in the task statement) including
                  the host cores on a bounded sample of the same workload (N=1 only); cores and CPU model stated
   extras       : forward-only pairs/s, and pairs/s through the restated loop of the UNCHANGED caller (training/train.py:168-212:
                  torch AdamW over the 164 parameter views, clip_grad_norm_, loss.item(), accuracy.update) on the drop-in model.
+--no-cpu-baseline / --no-extras leave those two out of a --full run.
 Inputs are synthetic (DemoVQADataset shapes, data/dataset.py:420-436) and resident in HBM before the timed region.
 
 --backend gloo lets N ranks share ONE GPU (tests/test_gpu_bench_ranks.py runs this whole file with 2 ranks on the 1-GPU test box);
@@ -179,8 +182,11 @@ def main(argv=None):
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo: ranks may share one GPU (rehearsal on a 1-GPU box)")
     ap.add_argument("--force-reducer", action="store_true", help="bucketed all-reduce choreography even with one rank")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the forward-only and drop-in-loop secondary measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline (two single-stream profiling steps), the forward-only and "
+                         "drop-in-loop extras and the CPU oracle baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the forward-only and drop-in-loop secondary measurements")
     ap.add_argument("--no-overlap", action="store_true", help="no RCCL/backward overlap")
     ap.add_argument("--serial", action="store_true", help="single-stream execution (no text-encoder / weight-gradient side streams)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -273,97 +279,99 @@ def _run(args, real_stdout):
     note(f"timed region done: {ms:.2f} ms/step")
     value = batch * world * args.steps / el
 
-    # ---- live per-kernel timing of one more step (events on the launch stream) -> roofline of the dominant kernel
+    # ---- --full only from here on: nothing below feeds `value` / `ms_per_step`, and a plain run does none of it.
+    # live per-kernel timing of one more step (events on the launch stream) -> roofline of the dominant kernel
     roof = None
-    K = pkg.kernels
-    # per-kernel durations are only meaningful without kernel concurrency: these two extra steps run single-stream
-    # (the timed region above used the side streams unless --serial); `rocprofv3 ... bench.py --serial` reproduces it.
-    # EVERY rank runs them (a step issues the bucket all-reduces: the collectives must stay matched); only rank 0 records events.
-    was = trainer.engine.two_streams
-    trainer.engine.two_streams = False
-    trainer.step(*data)
-    if rank == 0:
-        K.PROFILE = []
-        K.PROFILE_VARIANTS = []
-        K.PROFILE_STAGED = {}
-    trainer.step(*data)
-    torch.cuda.synchronize()
-    trainer.engine.two_streams = was
-    if rank == 0:
-        agg, hbm = {}, {}
-        for name, flops, e0, e1, nbytes in K.PROFILE:
-            tsec = e0.elapsed_time(e1) * 1e-3
-            if name.startswith("hbm:"):
-                _, cls, entry = name.split(":", 2)
-                h = hbm.setdefault(cls, [0.0, 0.0, 0, {}])
-                h[0] += tsec; h[1] += nbytes; h[2] += 1
-                pe = h[3].setdefault(entry, [0.0, 0.0, 0]); pe[0] += tsec; pe[1] += nbytes; pe[2] += 1
-                continue
-            a = agg.setdefault(name, [0.0, 0.0, 0, 0.0])
-            a[0] += tsec; a[1] += flops; a[2] += 1; a[3] += nbytes
-        variants = {}                           # launches of one symbol that run different code paths (kernels.PROFILE_VARIANTS)
-        for sym, label, flops, e0, e1 in K.PROFILE_VARIANTS:
-            v = variants.setdefault(sym, {}).setdefault(label, [0.0, 0.0, 0])
-            v[0] += e0.elapsed_time(e1) * 1e-3; v[1] += flops; v[2] += 1
-        K.PROFILE_VARIANTS = []
-        K.PROFILE = None
-        gemm_time = sum(a[0] for a in agg.values())
-        name, (tt, fl, n, nb) = max(agg.items(), key=lambda kv: kv[1][0])
-        ach = fl / tt / 1e12
-        traffic = None                      # HBM bytes per launch from rocprofv3 PMC passes (tools/hbm_traffic.py), if recorded
-        import glob
-        tag = "" if args.config == "default" else args.config + "_"
-        cands = sorted(glob.glob(os.path.join(REPO, "profiles", f"r*_{tag}hbm_traffic.json")))
-        if args.config == "default":
-            cands = [c for c in cands if "stress" not in os.path.basename(c)]
-        tpath = cands[-1] if cands else ""
-        tsrc = None
-        if tpath and batch == conf["batch"] and args.dtype == "bf16":
-            tb = tn = 0.0                           # the PROFILE name is a prefix of the full template instantiation(s):
-            for kname, v in json.load(open(tpath))["kernels"].items():      # launch-weighted mean over all of them
-                if name.rstrip('>') in kname:
-                    tb += v["hbm_bytes_per_launch"] * v["launches"]; tn += v["launches"]
-            if tn:
-                traffic = round(tb / tn)
-                tsrc = ("profiles/" + os.path.basename(tpath) + " (static: separate rocprofv3 --pmc passes of this command, "
-                        "tools/hbm_traffic.py; NOT measured in this run)")
-        hbm_time = sum(h[0] for h in hbm.values())
-        hbm_classes = {cls: {"ms": round(h[0] * 1e3, 3), "GB": round(h[1] / 1e9, 3), "GBps": round(h[1] / h[0] / 1e9, 1),
-                             "frac_of_hbm_peak": round(h[1] / h[0] / 1e9 / HBM_PEAK, 4), "launches": h[2],
-                             "entries": {k: {"ms": round(v[0] * 1e3, 3), "GBps": round(v[1] / v[0] / 1e9, 1), "n": v[2]}
-                                         for k, v in sorted(h[3].items(), key=lambda kv: -kv[1][0])}}
-                       for cls, h in sorted(hbm.items(), key=lambda kv: -kv[1][0])}
-        step_bytes = batch * act_bytes_pair + nparam * 4 * 7 + nparam * 4
-        roof = {"bound": "mfma", "kernel": name, "achieved": round(ach, 2), "peak": PEAK[args.dtype], "unit": "TFLOP/s",
-                "frac": round(ach / PEAK[args.dtype], 4), "traffic": traffic, "traffic_unit": "bytes/launch (2*FETCH_SIZE + WRITE_SIZE)", "traffic_source": tsrc,
-                "algorithmic_bytes_per_launch": round(nb / n), "launches_per_step": n,
-                "avg_launch_us": round(tt / n * 1e6, 2), "flop_per_launch": fl / n,
-                "measured": "live HIP events on the launch stream, one single-stream step after the timed region",
-                "launch_groups": {lab: {"n": v[2], "avg_launch_us": round(v[0] / v[2] * 1e6, 2), "tflops": round(v[1] / v[0] / 1e12, 1)}
-                                  for lab, v in variants.get(name, {}).items()},
-                "kernel_time_ms_per_step": round(tt * 1e3, 3), "all_gemm_time_ms_per_step": round(gemm_time * 1e3, 3),
-                "flop_per_pair": flop_pair, "step_tflops": round(value / world * flop_pair / 1e12, 2),
-                "step_frac_of_mfma_peak": round(value / world * flop_pair / 1e12 / PEAK[args.dtype], 4),
-                "per_kernel": {k: {"ms": round(v[0] * 1e3, 3), "tflops": round(v[1] / v[0] / 1e12, 1), "n": v[2]} for k, v in sorted(agg.items(), key=lambda kv: -kv[1][0])},
-                "hbm_bound_time_ms_per_step": round(hbm_time * 1e3, 3), "hbm_peak_GBps": HBM_PEAK, "hbm_classes": hbm_classes,
-                "step_algorithmic_bytes": round(step_bytes),
-                "step_algorithmic_GBps": round(step_bytes / (ms * 1e-3) / 1e9, 1),
-                "step_frac_of_hbm_peak": round(step_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK, 4)}
-        staged = K.PROFILE_STAGED.get(name)
-        if staged:
-            # bytes the dominant kernel stages through LDS-DMA and the per-CU rate that makes.  NOT its bound: with every piece moving 1/64 of its
-            # bytes (same instructions, waits, barriers) the launches are only 9-16 % faster, and without MFMAs the loop still takes 72-78 % of its
-            # time (profiles/r04_conv8p_diag.txt): the K loop is priced by its instruction / barrier skeleton
-            ncu = torch.cuda.get_device_properties(dev).multi_processor_count
-            roof["lds_dma_ingest"] = {"staged_bytes_per_launch": round(staged / n), "flop_per_staged_byte": round(fl / staged, 1),
-                                      "GBps_per_cu": round(staged / tt / 1e9 / ncu, 1), "cus": ncu,
-                                      "bound_by_these_bytes": False}
+    if args.full:
+        K = pkg.kernels
+        # per-kernel durations are only meaningful without kernel concurrency: these two extra steps run single-stream
+        # (the timed region above used the side streams unless --serial); `rocprofv3 ... bench.py --serial` reproduces it.
+        # EVERY rank runs them (a step issues the bucket all-reduces: the collectives must stay matched); only rank 0 records events.
+        was = trainer.engine.two_streams
+        trainer.engine.two_streams = False
+        trainer.step(*data)
+        if rank == 0:
+            K.PROFILE = []
+            K.PROFILE_VARIANTS = []
+            K.PROFILE_STAGED = {}
+        trainer.step(*data)
+        torch.cuda.synchronize()
+        trainer.engine.two_streams = was
+        if rank == 0:
+            agg, hbm = {}, {}
+            for name, flops, e0, e1, nbytes in K.PROFILE:
+                tsec = e0.elapsed_time(e1) * 1e-3
+                if name.startswith("hbm:"):
+                    _, cls, entry = name.split(":", 2)
+                    h = hbm.setdefault(cls, [0.0, 0.0, 0, {}])
+                    h[0] += tsec; h[1] += nbytes; h[2] += 1
+                    pe = h[3].setdefault(entry, [0.0, 0.0, 0]); pe[0] += tsec; pe[1] += nbytes; pe[2] += 1
+                    continue
+                a = agg.setdefault(name, [0.0, 0.0, 0, 0.0])
+                a[0] += tsec; a[1] += flops; a[2] += 1; a[3] += nbytes
+            variants = {}                           # launches of one symbol that run different code paths (kernels.PROFILE_VARIANTS)
+            for sym, label, flops, e0, e1 in K.PROFILE_VARIANTS:
+                v = variants.setdefault(sym, {}).setdefault(label, [0.0, 0.0, 0])
+                v[0] += e0.elapsed_time(e1) * 1e-3; v[1] += flops; v[2] += 1
+            K.PROFILE_VARIANTS = []
+            K.PROFILE = None
+            gemm_time = sum(a[0] for a in agg.values())
+            name, (tt, fl, n, nb) = max(agg.items(), key=lambda kv: kv[1][0])
+            ach = fl / tt / 1e12
+            traffic = None                      # HBM bytes per launch from rocprofv3 PMC passes (tools/hbm_traffic.py), if recorded
+            import glob
+            tag = "" if args.config == "default" else args.config + "_"
+            cands = sorted(glob.glob(os.path.join(REPO, "profiles", f"r*_{tag}hbm_traffic.json")))
+            if args.config == "default":
+                cands = [c for c in cands if "stress" not in os.path.basename(c)]
+            tpath = cands[-1] if cands else ""
+            tsrc = None
+            if tpath and batch == conf["batch"] and args.dtype == "bf16":
+                tb = tn = 0.0                           # the PROFILE name is a prefix of the full template instantiation(s):
+                for kname, v in json.load(open(tpath))["kernels"].items():      # launch-weighted mean over all of them
+                    if name.rstrip('>') in kname:
+                        tb += v["hbm_bytes_per_launch"] * v["launches"]; tn += v["launches"]
+                if tn:
+                    traffic = round(tb / tn)
+                    tsrc = ("profiles/" + os.path.basename(tpath) + " (static: separate rocprofv3 --pmc passes of this command, "
+                            "tools/hbm_traffic.py; NOT measured in this run)")
+            hbm_time = sum(h[0] for h in hbm.values())
+            hbm_classes = {cls: {"ms": round(h[0] * 1e3, 3), "GB": round(h[1] / 1e9, 3), "GBps": round(h[1] / h[0] / 1e9, 1),
+                                 "frac_of_hbm_peak": round(h[1] / h[0] / 1e9 / HBM_PEAK, 4), "launches": h[2],
+                                 "entries": {k: {"ms": round(v[0] * 1e3, 3), "GBps": round(v[1] / v[0] / 1e9, 1), "n": v[2]}
+                                             for k, v in sorted(h[3].items(), key=lambda kv: -kv[1][0])}}
+                           for cls, h in sorted(hbm.items(), key=lambda kv: -kv[1][0])}
+            step_bytes = batch * act_bytes_pair + nparam * 4 * 7 + nparam * 4
+            roof = {"bound": "mfma", "kernel": name, "achieved": round(ach, 2), "peak": PEAK[args.dtype], "unit": "TFLOP/s",
+                    "frac": round(ach / PEAK[args.dtype], 4), "traffic": traffic, "traffic_unit": "bytes/launch (2*FETCH_SIZE + WRITE_SIZE)", "traffic_source": tsrc,
+                    "algorithmic_bytes_per_launch": round(nb / n), "launches_per_step": n,
+                    "avg_launch_us": round(tt / n * 1e6, 2), "flop_per_launch": fl / n,
+                    "measured": "live HIP events on the launch stream, one single-stream step after the timed region",
+                    "launch_groups": {lab: {"n": v[2], "avg_launch_us": round(v[0] / v[2] * 1e6, 2), "tflops": round(v[1] / v[0] / 1e12, 1)}
+                                      for lab, v in variants.get(name, {}).items()},
+                    "kernel_time_ms_per_step": round(tt * 1e3, 3), "all_gemm_time_ms_per_step": round(gemm_time * 1e3, 3),
+                    "flop_per_pair": flop_pair, "step_tflops": round(value / world * flop_pair / 1e12, 2),
+                    "step_frac_of_mfma_peak": round(value / world * flop_pair / 1e12 / PEAK[args.dtype], 4),
+                    "per_kernel": {k: {"ms": round(v[0] * 1e3, 3), "tflops": round(v[1] / v[0] / 1e12, 1), "n": v[2]} for k, v in sorted(agg.items(), key=lambda kv: -kv[1][0])},
+                    "hbm_bound_time_ms_per_step": round(hbm_time * 1e3, 3), "hbm_peak_GBps": HBM_PEAK, "hbm_classes": hbm_classes,
+                    "step_algorithmic_bytes": round(step_bytes),
+                    "step_algorithmic_GBps": round(step_bytes / (ms * 1e-3) / 1e9, 1),
+                    "step_frac_of_hbm_peak": round(step_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK, 4)}
+            staged = K.PROFILE_STAGED.get(name)
+            if staged:
+                # bytes the dominant kernel stages through LDS-DMA and the per-CU rate that makes.  NOT its bound: with every piece moving 1/64 of its
+                # bytes (same instructions, waits, barriers) the launches are only 9-16 % faster, and without MFMAs the loop still takes 72-78 % of its
+                # time (profiles/r04_conv8p_diag.txt): the K loop is priced by its instruction / barrier skeleton
+                ncu = torch.cuda.get_device_properties(dev).multi_processor_count
+                roof["lds_dma_ingest"] = {"staged_bytes_per_launch": round(staged / n), "flop_per_staged_byte": round(fl / staged, 1),
+                                          "GBps_per_cu": round(staged / tt / 1e9 / ncu, 1), "cus": ncu,
+                                          "bound_by_these_bytes": False}
     if use_dist:
         dist.barrier()
 
-    # ---- secondary figures (1 rank only: neither issues collectives)
+    # ---- secondary figures (--full, 1 rank only: neither issues collectives)
     extras = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         eng = trainer.engine
         maskf = mask.float()
         n_f = max(5, min(20, args.steps))
@@ -385,7 +393,7 @@ def _run(args, real_stdout):
                   "dropin_loop_note": f"training/train.py:168-212 restated (non-AMP branch): model(...) through the vqa_hip custom ops + autograd, "
                                       f"torch.optim.AdamW over 164 views, clip_grad_norm_, loss.item(), argmax.cpu(); {n_d} steps"}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         note("timing the CPU oracle baseline (bounded sample)")
         cpu = cpu_baseline(conf)
     out = None
@@ -398,7 +406,7 @@ def _run(args, real_stdout):
                                       f"dropout on (BASELINE configs[{bidx}])",
                           "name": args.config, "batch_per_gpu": batch, "global_batch": batch * world, "parallelism": f"dp{world}",
                           "backend": (args.backend if use_dist else None), "reducer": ("forced" if args.force_reducer and world == 1 else ("on" if world > 1 else "off")),
-                          "bytes_allreduced_per_step": trainer.reducer.bytes_reduced // max(1, args.steps + args.warmup + 2) if trainer.reducer.active else 0},
+                          "bytes_allreduced_per_step": trainer.reducer.bytes_reduced // (args.steps + args.warmup + (2 if args.full else 0)) if trainer.reducer.active else 0},
                "final_loss": round(loss, 4), "roofline": roof, "cpu_baseline": cpu, "extras": extras}
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     if use_dist:

@@ -1,12 +1,12 @@
 """GPU: the N>1 code paths executed for real on the ONE GPU of the test box (north_star: "reported at 1, 2, 4 and 8 GPUs").
 
-* the WHOLE bench.py main() with 2 ranks -- fresh spawned processes sharing GPU 0, gloo transport: process-group init, warm-up,
-  timed loop with the bucketed gradient all-reduce, barriers, max-over-ranks time, the all-rank profiling steps, one JSON line on
-  rank 0, clean exit;
+* the WHOLE bench.py main() --full with 2 ranks -- fresh spawned processes sharing GPU 0, gloo transport: process-group init,
+  warm-up, timed loop with the bucketed gradient all-reduce, barriers, max-over-ranks time, the all-rank profiling steps, one JSON
+  line on rank 0, clean exit;
 * a world-size-1 RCCL ("nccl") group with the reducer forced on: HipTrainer.step issues every bucket as an async RCCL all-reduce on
   the communication stream behind the segment events and waits for them before clip + AdamW -- the exact stream choreography of an
   8-GPU job; its result must be bit-equal to the step without any reducer;
-* bench.py --force-reducer through the same RCCL group.
+* bench.py --force-reducer through the same RCCL group, with --full and as a plain run (no step beyond warm-up and timed ones).
 Every rank is a fresh child process (mp spawn): a process that has touched the GPU is never re-exec'ed.
 """
 import os
@@ -52,7 +52,7 @@ def _run_ranks(target, world, args, timeout=600):
 
 
 def test_whole_bench_main_with_two_ranks_on_one_gpu_over_gloo():
-    argv = ["--gpus", "2", "--backend", "gloo", "--batch", "8", "--steps", "3", "--warmup", "2", "--no-cpu-baseline"]
+    argv = ["--gpus", "2", "--backend", "gloo", "--batch", "8", "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline"]
     res = _run_ranks(_bench_worker, 2, (argv,))
     assert res[1] is None                                         # only rank 0 prints / returns the line
     out = res[0]
@@ -134,8 +134,23 @@ def test_forced_reducer_over_a_one_rank_rccl_group_is_bit_equal_to_no_reducer():
 
 
 def test_bench_force_reducer_through_rccl_world1():
-    argv = ["--gpus", "1", "--force-reducer", "--batch", "8", "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--no-extras"]
+    argv = ["--gpus", "1", "--force-reducer", "--batch", "8", "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-extras"]
     out = _run_ranks(_bench_worker, 1, (argv,))[0]
     assert out["n_gpus"] == 1 and out["config"]["reducer"] == "forced" and out["config"]["backend"] == "nccl"
     assert out["config"]["bytes_allreduced_per_step"] > 4 * 19_000_000
     assert out["value"] > 0 and out["roofline"]["frac"] > 0
+
+
+def test_plain_bench_runs_only_the_warmup_and_timed_steps():
+    """Without --full the line carries the headline alone: no profiling steps, extras or CPU baseline.  The forced reducer counts
+    every byte it all-reduces, so one step's worth over warm-up + timed steps proves that no other step ran."""
+    argv = ["--gpus", "1", "--force-reducer", "--batch", "8", "--steps", "3", "--warmup", "2"]
+    out = _run_ranks(_bench_worker, 1, (argv,))[0]
+    assert out["n_gpus"] == 1 and out["steps"] == 3 and out["warmup"] == 2 and out["config"]["reducer"] == "forced"
+    assert out["value"] > 0 and abs(out["value"] - 8 / (out["ms_per_step"] * 1e-3)) / out["value"] < 1e-3
+    assert out["roofline"] is None and out["extras"] is None and out["cpu_baseline"] is None
+    from _pkg import sub
+    from oracle import vqa_oracle as O
+    LY = sub("layout")
+    nflat = LY.flat_size(LY.build_entries(O.full_config()))
+    assert out["config"]["bytes_allreduced_per_step"] == 4 * nflat + 4
