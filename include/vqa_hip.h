@@ -308,6 +308,31 @@ int vqa_attention_bwd_dp(int dtype, const void* dctx, int ldc, const void* q, co
 int vqa_attention_bwd_mfma_dp(const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
                               const float* probs, const float* dprobs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv, int B, int H,
                               int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t stream);
+/* Many questions per image in training (VQAModel.forward_grouped, HipTrainer.step(image_index=)).
+ * vqa_index_csr: the questions of each image in ascending question order -- offsets [U+1], order [N] (image u's questions are
+ * order[offsets[u] .. offsets[u+1])).  Deterministic counting sort in one launch (U <= 32768), no host sync.  An index outside
+ * [0, U) writes -1 to every offsets and order entry (the backward kernels below then write NaN, never a wrong sum). */
+int vqa_index_csr(const int* kv_index, int N, int U, int* offsets, int* order, hipStream_t stream);
+/* vqa_attention_fwd(_mfma)_idx with dropout (p, seed): the mask of (question b, head, i, j) is the one vqa_attention_fwd(_mfma)
+ * draws for batch b, so an identity index is bit-equal to them. */
+int vqa_attention_fwd_idx_train(int dtype, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const int* kv_index,
+                                int n_kv, const float* kmask, float* probs, void* ctx, int ldc, int B, int H, int Lq, int Lk, int hd,
+                                float p, unsigned long long seed, hipStream_t stream);
+int vqa_attention_fwd_mfma_idx_train(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const int* kv_index, int n_kv,
+                                     const float* kmask, float* probs, void* ctx, int ldc, int B, int H, int Lq, int Lk, int hd, float p,
+                                     unsigned long long seed, hipStream_t stream);
+/* Backward of the _idx_train forwards: dq [B*Lq] per question, dk / dv [n_kv*Lk] per IMAGE = the sum over the image's questions
+ * (offsets / order of vqa_index_csr over the same index), accumulated in fp32 in CSR order and rounded once; no float atomics.
+ * One question per image: bit-equal to vqa_attention_bwd(_mfma).  An image without questions gets zeros.  The generic form needs
+ * Lk * hd <= 10240 besides the LDS limit of vqa_attention_bwd; the _mfma form has the limits of vqa_attention_bwd_mfma. */
+int vqa_attention_bwd_idx(int dtype, const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
+                          const float* probs, const int* offsets, const int* order, int n_kv, void* dq, void* dk, void* dv,
+                          int lddq, int lddk, int lddv, int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed,
+                          hipStream_t stream);
+int vqa_attention_bwd_mfma_idx(const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
+                               const float* probs, const int* offsets, const int* order, int n_kv, void* dq, void* dk, void* dv,
+                               int lddq, int lddk, int lddv, int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed,
+                               hipStream_t stream);
 /* Device-side accuracy counters: counters[3] (u64) += {top-1 correct, top-5 correct, samples} for fp32 logits [B][N] and i64 targets.
  * Replaces the argmax/topk + .cpu() + .item() of VQAAccuracy.update (utils/metrics.py:55-94); ties resolve to the lowest index. */
 int vqa_accuracy_update(const float* logits, const long long* targets, unsigned long long* counters, int B, int N, hipStream_t stream);

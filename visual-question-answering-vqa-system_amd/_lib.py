@@ -99,6 +99,11 @@ SIGNATURES = {
     "vqa_attention_bwd_mfma": [P, I, P, P, P, I, I, I, P, P, P, P, I, I, I, I, I, I, I, I, F, ULL, P],
     "vqa_attention_bwd_dp": [I, P, I, P, P, P, I, I, I, P, P, P, P, P, I, I, I, I, I, I, I, I, F, ULL, P],
     "vqa_attention_bwd_mfma_dp": [P, I, P, P, P, I, I, I, P, P, P, P, P, I, I, I, I, I, I, I, I, F, ULL, P],
+    "vqa_index_csr": [P, I, I, P, P, P],
+    "vqa_attention_fwd_idx_train": [I, P, P, P, I, I, I, P, I, P, P, P, I, I, I, I, I, I, F, ULL, P],
+    "vqa_attention_fwd_mfma_idx_train": [P, P, P, I, I, I, P, I, P, P, P, I, I, I, I, I, I, F, ULL, P],
+    "vqa_attention_bwd_idx": [I, P, I, P, P, P, I, I, I, P, P, P, I, P, P, P, I, I, I, I, I, I, I, I, F, ULL, P],
+    "vqa_attention_bwd_mfma_idx": [P, I, P, P, P, I, I, I, P, P, P, I, P, P, P, I, I, I, I, I, I, I, I, F, ULL, P],
     "vqa_masked_pool_fwd": [I, P, P, P, I, I, I, I, I, P],
     "vqa_masked_pool_bwd": [I, P, I, I, P, P, P, I, I, I, P],
     "vqa_masked_pool_pair_fwd": [I, P, P, P, P, I, I, I, P],

@@ -1550,3 +1550,442 @@ extern "C" int vqa_accuracy_update(const float* logits, const long long* targets
   hipLaunchKernelGGL(accuracy_kernel, dim3((B + 3) / 4), dim3(256), 0, st, logits, targets, counters, B, N);
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Many questions per image in TRAINING (VQAModel.forward_grouped, HipTrainer.step(image_index=)).
+//   vqa_index_csr              questions of each image in ascending question order (CSR), one workgroup, no host sync
+//   vqa_attention_fwd(_mfma)_idx_train   the indexed forwards with dropout: the mask of (question b, head, i, j) is the one
+//                              vqa_attention_fwd(_mfma) draws for batch b (identity index -> bit-equal)
+//   vqa_attention_bwd(_mfma)_idx         dQ per question, dK / dV per IMAGE: one workgroup (VALU) or wave (MFMA) per (image, head)
+//                              keeps the image's dK / dV in fp32 accumulators while it sweeps that image's questions in CSR order,
+//                              then rounds once and stores once.  No float atomics: the sums run in a fixed order (bit-reproducible).
+//                              One question per image: the products and their order are those of vqa_attention_bwd(_mfma)
+//                              (bit-equal); an image without questions gets zeros.
+// ---------------------------------------------------------------------------------------------
+
+// Counting sort of kv_index [N] into offsets [U+1] / order [N]; cur: U ints of dynamic LDS (counts, then per-image cursors).
+// Placement is stable: question i's slot = cursor of its image + #{earlier questions of the same image in its chunk of 1024}.
+// An index outside [0, U) writes -1 to every offset and order entry (the status the backward kernels check).
+__global__ __launch_bounds__(1024) void index_csr_kernel(const int* __restrict__ kv_index, int N, int U, int* __restrict__ offsets,
+                                                         int* __restrict__ order) {
+  extern __shared__ int cur[];
+  __shared__ int part[1024];
+  __shared__ int keys[1024];
+  __shared__ int bad;
+  const int tid = threadIdx.x;
+  if (tid == 0) bad = 0;
+  for (int u = tid; u < U; u += 1024) cur[u] = 0;
+  __syncthreads();
+  for (int i = tid; i < N; i += 1024) {
+    const int u = kv_index[i];
+    if (u < 0 || u >= U) bad = 1;
+    else atomicAdd(&cur[u], 1);                 // integer counts: order-independent
+  }
+  __syncthreads();
+  if (bad) {                                    // block-uniform
+    for (int u = tid; u <= U; u += 1024) offsets[u] = -1;
+    for (int i = tid; i < N; i += 1024) order[i] = -1;
+    return;
+  }
+  // exclusive scan of the counts: thread t owns images [u0, u1)
+  const int per = (U + 1023) / 1024, u0 = min(tid * per, U), u1 = min(u0 + per, U);
+  int s = 0;
+  for (int u = u0; u < u1; ++u) s += cur[u];
+  part[tid] = s;
+  __syncthreads();
+  for (int o = 1; o < 1024; o <<= 1) {          // inclusive scan of the 1024 partial sums
+    const int v = tid >= o ? part[tid - o] : 0;
+    __syncthreads();
+    part[tid] += v;
+    __syncthreads();
+  }
+  int run = part[tid] - s;
+  for (int u = u0; u < u1; ++u) { const int c = cur[u]; offsets[u] = run; cur[u] = run; run += c; }
+  if (tid == 1023) offsets[U] = part[1023];
+  __syncthreads();
+  for (int base = 0; base < N; base += 1024) {
+    const int i = base + tid, n = min(1024, N - base);
+    const int key = i < N ? kv_index[i] : -1;
+    keys[tid] = key;
+    __syncthreads();
+    int rank = 0;
+    bool last = true;
+    if (i < N) {
+      for (int j = 0; j < n; ++j)
+        if (keys[j] == key) { if (j < tid) ++rank; else if (j > tid) last = false; }
+      order[cur[key] + rank] = i;
+    }
+    __syncthreads();
+    if (i < N && last) cur[key] += rank + 1;
+    __syncthreads();
+  }
+}
+
+// VALU form: one workgroup per (image u, head h); NACC accumulators per thread and tensor (Lk * hd <= 256 * NACC).
+// Per question: the per-(batch, head) body of attn_bwd_kernel (DPR = false) with b = the question, K / V of image u.
+template <typename T, int NACC>
+__global__ __launch_bounds__(256) void attn_bwd_idx_kernel(const T* __restrict__ dctx, int ldc, const T* __restrict__ q, const T* __restrict__ k,
+                                                          const T* __restrict__ v, int ldq, int ldk, int ldv, const float* __restrict__ probs,
+                                                          T* __restrict__ dq, T* __restrict__ dk, T* __restrict__ dv, int lddq, int lddk, int lddv,
+                                                          int H, int Lq, int Lk, int hd, float scale, float p, uint64_t seed,
+                                                          const int* __restrict__ offsets, const int* __restrict__ order, int N) {
+  extern __shared__ float sm[];
+  const int u = blockIdx.x / H, h = blockIdx.x - u * H, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ldh = hd + 1, ldp = Lk + 1;
+  float* Qs = sm; float* Os = Qs + Lq * ldh; float* Ks = Os + Lq * ldh; float* Vs = Ks + Lk * ldh;
+  float* Ps = Vs + Lk * ldh; float* Ds = Ps + Lq * ldp;
+  const int nkd = Lk * hd;
+  int beg = offsets[u], end = offsets[u + 1];
+  if (beg < 0 || end < beg || end > N) {        // CSR status error (an index out of range): NaN, never a wrong sum
+    for (int i = tid; i < nkd; i += 256) {
+      const int c = i / hd, d = i - c * hd;
+      dk[(size_t)(u * Lk + c) * lddk + h * hd + d] = from_f<T>(NAN);
+      dv[(size_t)(u * Lk + c) * lddv + h * hd + d] = from_f<T>(NAN);
+    }
+    return;
+  }
+  for (int i = tid; i < nkd; i += 256) {
+    const int r = i / hd, d = i - r * hd;
+    Ks[r * ldh + d] = to_f<T>(k[(size_t)(u * Lk + r) * ldk + h * hd + d]);
+    Vs[r * ldh + d] = to_f<T>(v[(size_t)(u * Lk + r) * ldv + h * hd + d]);
+  }
+  float ak[NACC], av[NACC];
+#pragma unroll
+  for (int jj = 0; jj < NACC; ++jj) { ak[jj] = 0.f; av[jj] = 0.f; }
+  for (int jq = beg; jq < end; ++jq) {
+    const int b = order[jq];
+    if (b < 0 || b >= N) continue;              // block-uniform
+    __syncthreads();                            // the previous question's readers of Qs / Os / Ps / Ds are done
+    for (int i = tid; i < Lq * hd; i += 256) {
+      const int r = i / hd, d = i - r * hd;
+      Qs[r * ldh + d] = to_f<T>(q[(size_t)(b * Lq + r) * ldq + h * hd + d]);
+      Os[r * ldh + d] = to_f<T>(dctx[(size_t)(b * Lq + r) * ldc + h * hd + d]);
+    }
+    __syncthreads();
+    const float* pg = probs + ((size_t)(b * H + h) * Lq) * Lk;
+    for (int r = wave; r < Lq; r += 4) {
+      float t = 0.f;
+      for (int c = lane; c < Lk; c += 64) {
+        const float pr = pg[(size_t)r * Lk + c];
+        float ks = 1.f;
+        if (p > 0.f) ks = drop_keep32(drop_key(seed), (uint32_t)(((size_t)(b * H + h) * Lq + r) * Lk + c), p) ? 1.f / (1.f - p) : 0.f;
+        float dpd = 0.f;
+        for (int d = 0; d < hd; ++d) dpd += Os[r * ldh + d] * Vs[c * ldh + d];
+        const float dp = dpd * ks;
+        Ps[r * ldp + c] = pr * ks;
+        Ds[r * ldp + c] = dp;
+        t += dp * pr;
+      }
+      t = wave_sum(t);
+      for (int c = lane; c < Lk; c += 64) Ds[r * ldp + c] = pg[(size_t)r * Lk + c] * (Ds[r * ldp + c] - t) / scale;
+    }
+    __syncthreads();
+    for (int i = tid; i < Lq * hd; i += 256) {
+      const int r = i / hd, d = i - r * hd;
+      float a = 0.f;
+      for (int c = 0; c < Lk; ++c) a += Ds[r * ldp + c] * Ks[c * ldh + d];
+      dq[(size_t)(b * Lq + r) * lddq + h * hd + d] = from_f<T>(a);
+    }
+#pragma unroll
+    for (int jj = 0; jj < NACC; ++jj) {
+      const int i = tid + jj * 256;
+      if (i < nkd) {
+        const int c = i / hd, d = i - c * hd;
+        float a = ak[jj], e = av[jj];
+        for (int r = 0; r < Lq; ++r) { a += Ds[r * ldp + c] * Qs[r * ldh + d]; e += Ps[r * ldp + c] * Os[r * ldh + d]; }
+        ak[jj] = a; av[jj] = e;
+      }
+    }
+  }
+#pragma unroll
+  for (int jj = 0; jj < NACC; ++jj) {
+    const int i = tid + jj * 256;
+    if (i < nkd) {
+      const int c = i / hd, d = i - c * hd;
+      dk[(size_t)(u * Lk + c) * lddk + h * hd + d] = from_f<T>(ak[jj]);
+      dv[(size_t)(u * Lk + c) * lddv + h * hd + d] = from_f<T>(av[jj]);
+    }
+  }
+}
+
+// MFMA form: one wave per (image u, head h); the per-question body of attn_bwd_mfma_kernel (DPR = false).  The fp32 dK / dV
+// accumulators live in a wave-private LDS area in the MFMA accumulator layout, lane-private ([tile][c][e][lane]: no bank
+// conflicts, no cross-lane traffic); each question's orientation-2 MFMAs start from them instead of from zero.
+template <int HD, int NKT, int WPB>
+__global__ __launch_bounds__(WPB * 64, 1) void attn_bwd_mfma_idx_kernel(const bf16_t* __restrict__ dctx, int ldc, const bf16_t* __restrict__ q,
+                                                                const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int ldq, int ldk, int ldv,
+                                                                const float* __restrict__ probs, bf16_t* __restrict__ dq, bf16_t* __restrict__ dk,
+                                                                bf16_t* __restrict__ dv, int lddq, int lddk, int lddv, int UH, int H, int Lq, int Lk,
+                                                                float p, uint64_t seed, const int* __restrict__ offsets,
+                                                                const int* __restrict__ order, int N) {
+  constexpr int KR = NKT * 32;
+  constexpr int LDP = KR + 1;
+  constexpr int NACC = NKT * (HD / 32) * 16;    // accumulator registers per lane and tensor
+  constexpr int WAVE_BYTES = (KR + 32 + 32) * HD * 2 + 32 * LDP * 4 + 32 * 4 + 2 * NACC * 64 * 4;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int uh = blockIdx.x * WPB + wave;
+  if (uh >= UH) return;                         // whole wave exits together; only wave-private LDS, no block barrier below
+  char* base = smem + (size_t)wave * WAVE_BYTES;
+  bf16_t* Ks = reinterpret_cast<bf16_t*>(base);            // [KR][HD]
+  bf16_t* Qs = Ks + KR * HD;                               // [32][HD]
+  bf16_t* Os = Qs + 32 * HD;                               // [32][HD]  (dctx)
+  float* Ps = reinterpret_cast<float*>(Os + 32 * HD);      // [32][LDP]
+  float* Ts = Ps + 32 * LDP;                               // [32]
+  float* Ak = Ts + 32;                                     // [NACC][64] dK accumulators
+  float* Av = Ak + NACC * 64;                              // [NACC][64] dV accumulators
+  const int u = uh / H, h = uh - u * H;
+  const int r = lane & 31, hh = lane >> 5;
+  const int g2 = (lane >> 4) & 1, li = lane & 15, qd = li >> 2, pp = li & 3;
+  const float inv_scale = 1.0f / sqrtf((float)HD);
+  const float keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
+  const int beg = __builtin_amdgcn_readfirstlane(offsets[u]), end = __builtin_amdgcn_readfirstlane(offsets[u + 1]);
+  if (beg < 0 || end < beg || end > N) {        // CSR status error (an index out of range): NaN, never a wrong sum
+    for (int i = lane; i < Lk * HD; i += 64) {
+      const int c = i / HD, d = i - c * HD;
+      dk[(size_t)(u * Lk + c) * lddk + h * HD + d] = f2bf(NAN);
+      dv[(size_t)(u * Lk + c) * lddv + h * HD + d] = f2bf(NAN);
+    }
+    return;
+  }
+  for (int i = lane; i < KR * (HD / 8); i += 64) {
+    const int row = i / (HD / 8), cv = i - row * (HD / 8);
+    u32x4 val = {0u, 0u, 0u, 0u};
+    if (row < Lk) val = *reinterpret_cast<const u32x4*>(k + (size_t)(u * Lk + row) * ldk + h * HD + cv * 8);
+    *reinterpret_cast<u32x4*>(&Ks[row * HD + cv * 8]) = val;
+  }
+  for (int i = 0; i < NACC; ++i) { Ak[i * 64 + lane] = 0.f; Av[i * 64 + lane] = 0.f; }
+
+  for (int jq = beg; jq < end; ++jq) {
+    const int b = __builtin_amdgcn_readfirstlane(order[jq]);
+    if (b < 0 || b >= N) continue;              // wave-uniform
+    const int bh = b * H + h;                   // the question's (batch, head): probs, dropout index, dQ
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the previous question's LDS reads are complete
+    for (int i = lane; i < 32 * (HD / 8); i += 64) {
+      const int row = i / (HD / 8), cv = i - row * (HD / 8);
+      u32x4 a = {0u, 0u, 0u, 0u}, o = {0u, 0u, 0u, 0u};
+      if (row < Lq) {
+        a = *reinterpret_cast<const u32x4*>(q + (size_t)(b * Lq + row) * ldq + h * HD + cv * 8);
+        o = *reinterpret_cast<const u32x4*>(dctx + (size_t)(b * Lq + row) * ldc + h * HD + cv * 8);
+      }
+      *reinterpret_cast<u32x4*>(&Qs[row * HD + cv * 8]) = a;
+      *reinterpret_cast<u32x4*>(&Os[row * HD + cv * 8]) = o;
+    }
+    for (int i = lane; i < Lq * Lk; i += 64) { const int qi = i / Lk, kj = i - qi * Lk; Ps[qi * LDP + kj] = probs[(size_t)bh * Lq * Lk + i]; }
+
+    f32x16 d1[NKT], d2[NKT];
+#pragma unroll
+    for (int t = 0; t < NKT; ++t)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) { d1[t][e] = 0.f; d2[t][e] = 0.f; }
+#pragma unroll
+    for (int ks = 0; ks < HD / 16; ++ks) {
+      bf16x8 of = {};
+      if (r < Lq) of = *reinterpret_cast<const bf16x8*>(dctx + (size_t)(b * Lq + r) * ldc + h * HD + ks * 16 + 8 * hh);
+#pragma unroll
+      for (int t = 0; t < NKT; ++t) {
+        bf16x8 vf = {};
+        if (32 * t + r < Lk) vf = *reinterpret_cast<const bf16x8*>(v + (size_t)(u * Lk + 32 * t + r) * ldv + h * HD + ks * 16 + 8 * hh);
+        d1[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, of, d1[t], 0, 0, 0);
+        d2[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(of, vf, d2[t], 0, 0, 0);
+      }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+
+    // ---- orientation 1: row sums, dS, dQ = dS K
+    const size_t prow = ((size_t)bh * Lq + r) * Lk;
+    float tq = 0.f;
+#pragma unroll
+    for (int t = 0; t < NKT; ++t)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int key = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
+        const bool ok = r < Lq && key < Lk;
+        const float pr = ok ? Ps[r * LDP + key] : 0.f;
+        float ks = 1.f;
+        if (p > 0.f && ok) ks = drop_keep32(drop_key(seed), (uint32_t)(prow + key), p) ? keep : 0.f;
+        const float dp = ok ? d1[t][e] * ks : 0.f;
+        tq += dp * pr;
+        d1[t][e] = dp;
+      }
+    tq += __shfl_xor(tq, 32, 64);
+    if (hh == 0) Ts[r] = tq;
+#pragma unroll
+    for (int t = 0; t < NKT; ++t)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int key = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
+        const float pr = (r < Lq && key < Lk) ? Ps[r * LDP + key] : 0.f;
+        d1[t][e] = pr * (d1[t][e] - tq) * inv_scale;
+      }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    f32x16 oq[HD / 32];
+#pragma unroll
+    for (int c = 0; c < HD / 32; ++c)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) oq[c][e] = 0.f;
+#pragma unroll
+    for (int t = 0; t < NKT; ++t)
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        bf16x8 af;
+#pragma unroll
+        for (int jj = 0; jj < 8; ++jj) af[jj] = (__bf16)d1[t][8 * s2 + jj];
+#pragma unroll
+        for (int c = 0; c < HD / 32; ++c)
+          oq[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, attn_ldsB<HD>(Ks, 32 * t + 16 * s2, c, hh, g2, qd, pp), oq[c], 0, 0, 0);
+      }
+#pragma unroll
+    for (int c = 0; c < HD / 32; ++c)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int qi = (e & 3) + 8 * (e >> 2) + 4 * hh;
+        if (qi < Lq) dq[(size_t)(b * Lq + qi) * lddq + h * HD + c * 32 + r] = f2bf(oq[c][e]);
+      }
+
+    // ---- orientation 2: dK += dS^T Q, dV += Pd^T dctx, starting from the accumulators
+#pragma unroll
+    for (int t = 0; t < NKT; ++t) {
+      const int key = 32 * t + r;
+      f32x16 ds2, pd2;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int qi = (e & 3) + 8 * (e >> 2) + 4 * hh;
+        const bool ok = qi < Lq && key < Lk;
+        const float pr = ok ? Ps[qi * LDP + key] : 0.f;
+        float ks = 1.f;
+        if (p > 0.f && ok) ks = drop_keep32(drop_key(seed), (uint32_t)(((size_t)bh * Lq + qi) * Lk + key), p) ? keep : 0.f;
+        const float dp = ok ? d2[t][e] * ks : 0.f;
+        const float tt = ok ? Ts[qi] : 0.f;
+        ds2[e] = pr * (dp - tt) * inv_scale;
+        pd2[e] = pr * ks;
+      }
+      f32x16 okk[HD / 32], ovv[HD / 32];
+#pragma unroll
+      for (int c = 0; c < HD / 32; ++c)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int a = ((t * (HD / 32) + c) * 16 + e) * 64 + lane;
+          okk[c][e] = Ak[a]; ovv[c][e] = Av[a];
+        }
+#pragma unroll
+      for (int s2 = 0; s2 < 2; ++s2) {
+        bf16x8 as, ap;
+#pragma unroll
+        for (int jj = 0; jj < 8; ++jj) { as[jj] = (__bf16)ds2[8 * s2 + jj]; ap[jj] = (__bf16)pd2[8 * s2 + jj]; }
+#pragma unroll
+        for (int c = 0; c < HD / 32; ++c) {
+          okk[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as, attn_ldsB<HD>(Qs, 16 * s2, c, hh, g2, qd, pp), okk[c], 0, 0, 0);
+          ovv[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap, attn_ldsB<HD>(Os, 16 * s2, c, hh, g2, qd, pp), ovv[c], 0, 0, 0);
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < HD / 32; ++c)
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int a = ((t * (HD / 32) + c) * 16 + e) * 64 + lane;
+          Ak[a] = okk[c][e]; Av[a] = ovv[c][e];
+        }
+    }
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  for (int t = 0; t < NKT; ++t)
+#pragma unroll
+    for (int c = 0; c < HD / 32; ++c)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int kj = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
+        const int a = ((t * (HD / 32) + c) * 16 + e) * 64 + lane;
+        if (kj < Lk) {
+          dk[(size_t)(u * Lk + kj) * lddk + h * HD + c * 32 + r] = f2bf(Ak[a]);
+          dv[(size_t)(u * Lk + kj) * lddv + h * HD + c * 32 + r] = f2bf(Av[a]);
+        }
+      }
+}
+
+extern "C" {
+
+int vqa_index_csr(const int* kv_index, int N, int U, int* offsets, int* order, hipStream_t st) {
+  if (N < 0 || U < 0 || U > 32768 || !offsets || (N > 0 && (!kv_index || !order))) return VQA_EARG;
+  const size_t shm = (size_t)(U > 0 ? U : 1) * 4;
+  (void)vqa_ensure_lds(reinterpret_cast<const void*>(&index_csr_kernel), shm);
+  hipLaunchKernelGGL(index_csr_kernel, dim3(1), dim3(1024), shm, st, kv_index, N, U, offsets, order);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+
+int vqa_attention_fwd_idx_train(int dtype, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const int* kv_index,
+                                int n_kv, const float* kmask, float* probs, void* ctx, int ldc, int B, int H, int Lq, int Lk, int hd,
+                                float p, unsigned long long seed, hipStream_t st) {
+  if (!kv_index || n_kv < 0 || !(p >= 0.f && p < 1.f)) return VQA_EARG;
+  const size_t shm = ((size_t)(Lq + 2 * Lk) * (hd + 1) + (size_t)Lq * (Lk + 1)) * 4;
+  if (shm > 160 * 1024) return VQA_EARG;
+  const float scale = sqrtf((float)hd);
+  (void)vqa_ensure_lds(dtype ? reinterpret_cast<const void*>(&attn_fwd_kernel<bf16_t, true>) : reinterpret_cast<const void*>(&attn_fwd_kernel<float, true>), shm);
+  DT(hipLaunchKernelGGL((attn_fwd_kernel<float, true>), dim3(B * H), dim3(256), shm, st, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, kmask, probs, (float*)ctx, ldc, H, Lq, Lk, hd, scale, p, seed, kv_index, n_kv),
+     hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, true>), dim3(B * H), dim3(256), shm, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, kmask, probs, (bf16_t*)ctx, ldc, H, Lq, Lk, hd, scale, p, seed, kv_index, n_kv));
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+
+int vqa_attention_fwd_mfma_idx_train(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const int* kv_index, int n_kv,
+                                     const float* kmask, float* probs, void* ctx, int ldc, int B, int H, int Lq, int Lk, int hd, float p,
+                                     unsigned long long seed, hipStream_t st) {
+  if (!q || !k || !v || !kv_index || n_kv < 0 || !probs || !ctx || Lq > 32 || Lk > 160 || (hd != 32 && hd != 64) || (ldq % 8) || (ldk % 8) ||
+      (ldv % 8) || !(p >= 0.f && p < 1.f))
+    return VQA_EARG;
+  const int BH = B * H;
+  auto go = [&](auto kern, int nkt, int wpb) {
+    const size_t shm = (size_t)wpb * (nkt * 32) * hd * 2 + (size_t)wpb * 32 * (nkt * 32 + 1) * 4;
+    (void)vqa_ensure_lds(reinterpret_cast<const void*>(kern), shm);
+    hipLaunchKernelGGL(kern, dim3((BH + wpb - 1) / wpb), dim3(wpb * 64), shm, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv,
+                       kmask, probs, (bf16_t*)ctx, ldc, BH, H, Lq, Lk, p, seed, kv_index, n_kv);
+  };
+  if (Lk <= 64) { if (hd == 32) go(&attn_fwd_mfma_kernel<32, 2, 4, true>, 2, 4); else go(&attn_fwd_mfma_kernel<64, 2, 4, true>, 2, 4); }
+  else { if (hd == 32) go(&attn_fwd_mfma_kernel<32, 5, 2, true>, 5, 2); else go(&attn_fwd_mfma_kernel<64, 5, 2, true>, 5, 2); }
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+
+int vqa_attention_bwd_idx(int dtype, const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
+                          const float* probs, const int* offsets, const int* order, int n_kv, void* dq, void* dk, void* dv,
+                          int lddq, int lddk, int lddv, int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed,
+                          hipStream_t st) {
+  if (!dctx || !q || !k || !v || !probs || !offsets || (B > 0 && !order) || !dq || !dk || !dv || n_kv < 0 || B < 0 || H <= 0 ||
+      Lq <= 0 || Lk <= 0 || hd <= 0 || !(p >= 0.f && p < 1.f))
+    return VQA_EARG;
+  const size_t shm = ((size_t)(2 * Lq + 2 * Lk) * (hd + 1) + (size_t)2 * Lq * (Lk + 1)) * 4;
+  const long long nkd = (long long)Lk * hd;
+  if (shm > 160 * 1024 || nkd > 256 * 40) return VQA_EARG;
+  if (n_kv == 0) return VQA_OK;
+  const float scale = sqrtf((float)hd);
+  auto go = [&](auto kf, auto kb) {
+    (void)vqa_ensure_lds(dtype ? reinterpret_cast<const void*>(kb) : reinterpret_cast<const void*>(kf), shm);
+    DT(hipLaunchKernelGGL(kf, dim3(n_kv * H), dim3(256), shm, st, (const float*)dctx, ldc, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, probs, (float*)dq, (float*)dk, (float*)dv, lddq, lddk, lddv, H, Lq, Lk, hd, scale, p, seed, offsets, order, B),
+       hipLaunchKernelGGL(kb, dim3(n_kv * H), dim3(256), shm, st, (const bf16_t*)dctx, ldc, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, probs, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, lddq, lddk, lddv, H, Lq, Lk, hd, scale, p, seed, offsets, order, B));
+  };
+  if (nkd <= 256 * 16) go(&attn_bwd_idx_kernel<float, 16>, &attn_bwd_idx_kernel<bf16_t, 16>);
+  else go(&attn_bwd_idx_kernel<float, 40>, &attn_bwd_idx_kernel<bf16_t, 40>);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+
+int vqa_attention_bwd_mfma_idx(const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
+                               const float* probs, const int* offsets, const int* order, int n_kv, void* dq, void* dk, void* dv,
+                               int lddq, int lddk, int lddv, int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed,
+                               hipStream_t st) {
+  if (!dctx || !q || !k || !v || !probs || !offsets || (B > 0 && !order) || !dq || !dk || !dv || n_kv < 0 || B < 0 || H <= 0 ||
+      Lq <= 0 || Lq > 32 || Lk <= 0 || Lk > 160 || (hd != 32 && hd != 64) || (ldq % 8) || (ldk % 8) || (ldv % 8) || (ldc % 8) ||
+      !(p >= 0.f && p < 1.f))
+    return VQA_EARG;
+  if (n_kv == 0) return VQA_OK;
+  const int UH = n_kv * H;
+  auto go = [&](auto kern, int nkt, int wpb) {
+    const size_t nacc = (size_t)nkt * (hd / 32) * 16;
+    const size_t shm = (size_t)wpb * ((nkt * 32 + 32 + 32) * hd * 2 + 32 * (nkt * 32 + 1) * 4 + 32 * 4 + 2 * nacc * 64 * 4);
+    (void)vqa_ensure_lds(reinterpret_cast<const void*>(kern), shm);
+    hipLaunchKernelGGL(kern, dim3((UH + wpb - 1) / wpb), dim3(wpb * 64), shm, st, (const bf16_t*)dctx, ldc, (const bf16_t*)q, (const bf16_t*)k,
+                       (const bf16_t*)v, ldq, ldk, ldv, probs, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, lddq, lddk, lddv, UH, H, Lq, Lk, p, seed,
+                       offsets, order, B);
+  };
+  if (Lk <= 64) { if (hd == 32) go(&attn_bwd_mfma_idx_kernel<32, 2, 2>, 2, 2); else go(&attn_bwd_mfma_idx_kernel<64, 2, 2>, 2, 2); }
+  else { if (hd == 32) go(&attn_bwd_mfma_idx_kernel<32, 5, 1>, 5, 1); else go(&attn_bwd_mfma_idx_kernel<64, 5, 1>, 5, 1); }
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+
+}  // extern "C"

@@ -5,6 +5,8 @@ Same constructor kwargs (:132-152), `forward(images, token_ids, attention_mask=N
 `create_vqa_model` (:383-407), `load_vqa_model` (:410-432) and the same 225 state_dict entries.
 Extension (inference only): many questions per image from one image encoding -- `forward(..., image_index=)`,
 `encode_images(images) -> ImageContext` and `answer(context, token_ids, ...)`.
+Extension (training): `forward_grouped(images, token_ids, attention_mask, image_index)` runs one CNN pass per image and trains
+through it; `group_by_image(image_ids)` turns a batch's image ids into that form.
 There is no CPU path: calling forward with CPU tensors, or without the built extension, raises.
 """
 from __future__ import annotations
@@ -102,6 +104,63 @@ def _vqa_backward_input_op(dlogits: torch.Tensor, handle: int, tape_id: int, H: 
 @_vqa_backward_input_op.register_fake
 def _(dlogits, handle, tape_id, H, W):
     return torch.empty_like(_MODELS[handle]._flat), dlogits.new_empty((dlogits.shape[0], 3, H, W), dtype=torch.float32)
+
+
+# many questions per image in training (VQAModel.forward_grouped):
+#   torch.ops.vqa_hip.vqa_forward_grouped(images [U], token_ids [N], mask, image_index int32 [N], params, handle, training) -> logits [N]
+#   torch.ops.vqa_hip.vqa_backward_grouped_input(dlogits, handle, tape_id, U, H, W) -> (flat gradient, image gradient [U][3][H][W])
+# The backward without an image gradient is vqa_backward itself (the engine's tape carries the image index).
+@torch.library.custom_op("vqa_hip::vqa_forward_grouped", mutates_args=(), device_types="cuda")
+def _vqa_forward_grouped_op(images: torch.Tensor, token_ids: torch.Tensor, mask: Optional[torch.Tensor], image_index: torch.Tensor,
+                            flat_params: torch.Tensor, handle: int, training: bool) -> torch.Tensor:
+    model = _MODELS[handle]
+    logits, _, tape = model._engine.forward(images, token_ids, mask, training, False, need_tape=True, kv_index=image_index)
+    model._tape_seq += 1
+    model._tapes[model._tape_seq] = tape
+    while len(model._tapes) > model.max_live_tapes:
+        model._tapes.pop(next(iter(model._tapes)))
+    return logits
+
+
+@_vqa_forward_grouped_op.register_fake
+def _(images, token_ids, mask, image_index, flat_params, handle, training):
+    return images.new_empty((token_ids.shape[0], _MODELS[handle].num_answers), dtype=torch.float32)
+
+
+@torch.library.custom_op("vqa_hip::vqa_backward_grouped_input", mutates_args=(), device_types="cuda")
+def _vqa_backward_grouped_input_op(dlogits: torch.Tensor, handle: int, tape_id: int, U: int, H: int, W: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    model = _MODELS[handle]
+    tape = model._tapes.pop(tape_id, None)
+    if tape is None:
+        raise RuntimeError(f"vqa_backward: the activations of forward #{tape_id} are gone -- either backward ran twice through it "
+                           f"(the reference needs retain_graph=True for that) or more than max_live_tapes = {model.max_live_tapes} "
+                           "training forwards were issued before its backward (raise VQAModel.max_live_tapes)")
+    G = torch.zeros_like(model._flat)
+    dimg = model._engine.backward(tape, dlogits.contiguous(), G, on_segment=model._on_segment, want_input_grad=True)
+    return G, dimg
+
+
+@_vqa_backward_grouped_input_op.register_fake
+def _(dlogits, handle, tape_id, U, H, W):
+    return torch.empty_like(_MODELS[handle]._flat), dlogits.new_empty((U, 3, H, W), dtype=torch.float32)
+
+
+def _grouped_setup_ctx(ctx, inputs, output):
+    handle = inputs[5]
+    ctx.handle = handle
+    ctx.tape_id = _MODELS[handle]._tape_seq
+    ctx.image_shape = (inputs[0].shape[0], inputs[0].shape[2], inputs[0].shape[3])
+
+
+def _grouped_backward(ctx, dlogits):
+    if ctx.needs_input_grad[0]:
+        G, dimg = torch.ops.vqa_hip.vqa_backward_grouped_input(dlogits, ctx.handle, ctx.tape_id, *ctx.image_shape)
+        return dimg, None, None, None, G, None, None
+    G = torch.ops.vqa_hip.vqa_backward(dlogits, ctx.handle, ctx.tape_id)
+    return None, None, None, None, G, None, None
+
+
+torch.library.register_autograd("vqa_hip::vqa_forward_grouped", _grouped_backward, setup_context=_grouped_setup_ctx)
 
 
 def _setup_ctx(ctx, inputs, output):
@@ -698,6 +757,46 @@ class VQAModel(nn.Module):
         logits, aux = eng.answer(eng.encode_images(images, want_aux=return_aux), token_ids, maskf, idx, want_aux=return_aux)
         return (logits, aux) if return_aux else (logits, None)
 
+    def forward_grouped(self, images: torch.Tensor, token_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
+                        image_index: Optional[torch.Tensor] = None, return_aux: bool = False) -> Tuple[torch.Tensor, Optional[Dict]]:
+        """Many questions per image, training included: images [U, 3, H, W], token_ids / attention_mask [N, L], question i is asked of
+        image image_index[i] (None: the rules of answer()).  Computes
+            feat = image_encoder(images)            one CNN batch of the U images: train-mode BatchNorm statistics over U images,
+                                                    running statistics updated once from them
+            img  = image_projector(feat)            projector dropout drawn per image token (U rows)
+            text = text_encoder(token_ids, mask)    per question
+            cross-attention layer l: query batch i attends to norm_kv(img)[image_index[i]] (attention dropout per question)
+            pools, gate, output norm, answer head   per question
+        With dropout 0 this is fusion(image_encoder(images)[image_index], text, ...).  Gradients reach the parameters and, when
+        images.requires_grad, the images ([U, 3, H, W]); an image without a question still counts in the BatchNorm statistics and gets
+        a zero feature gradient.  With U = N and image_index = arange(N) every value (dropout included) is bit-equal to forward().
+        Eval mode without autograd delegates to forward(image_index=...).  return_aux=True raises NotImplementedError while autograd
+        records (no gradients through aux under grouping); otherwise aux has U image rows and N question rows.
+        Raises IndexError for an index outside [0, U), ValueError for a wrong shape or dtype."""
+        if not images.is_cuda:
+            raise RuntimeError("VQAModel (HIP) got CPU inputs; this implementation only runs on an MI355X (no CPU fallback)")
+        U, N = images.shape[0], token_ids.shape[0]
+        idx = self._image_index(image_index, U, N, images.device)
+        params = self._param_list()
+        recording = torch.is_grad_enabled() and (images.requires_grad or any(p.requires_grad for p in params))
+        if return_aux and recording:
+            raise NotImplementedError("forward_grouped(return_aux=True) under autograd: gradients through aux outputs are not supported "
+                                      "with an image index (run it under torch.no_grad())")
+        if not self.training and not recording:
+            return self.forward(images, token_ids, attention_mask, return_aux=return_aux, image_index=image_index)
+        eng = self._ensure_engine()
+        images = images.contiguous().float()
+        token_ids = token_ids.contiguous().long()
+        maskf = None if attention_mask is None else attention_mask.contiguous().float()
+        if idx is None:
+            idx = self._implied_index(U, N, images.device)
+        if recording:
+            flat = _FlatParams.apply(self._flat, self._handle, *params) if any(p.requires_grad for p in params) else self._flat
+            logits = torch.ops.vqa_hip.vqa_forward_grouped(images, token_ids, maskf, idx, flat, self._handle, self.training)
+            return logits, None
+        logits, aux, _ = eng.forward(images, token_ids, maskf, self.training, return_aux, need_tape=False, kv_index=idx)
+        return (logits, aux) if return_aux else (logits, None)
+
     def encode_images(self, images: torch.Tensor) -> ImageContext:
         """Run the image half of the eval forward once per image (stem, residual stages, SE / spatial attention, projector and the
         K / V projections of every cross-attention layer) and keep it for answer().  Inference only (eval mode, no autograd).  The
@@ -786,6 +885,25 @@ class VQAModel(nn.Module):
                   for k in ("image_encoder", "text_encoder", "fusion", "answer_head")}
         counts["total"] = sum(counts.values())
         return counts
+
+
+def group_by_image(image_ids) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Grouped form of a batch that carries each sample's image id (the reference dataset's sample info `image_id`):
+    returns (first, image_index), both int64.  `first` holds the batch position of the first occurrence of each distinct image, in
+    order of appearance; image_index[i] is the position in `first` of sample i's image.  So images[first] with image_index is what
+    forward_grouped / HipTrainer.step(image_index=) take, and images[first][image_index] equals images when samples of one image
+    carry the same image.  A tensor argument keeps its device."""
+    dev = image_ids.device if isinstance(image_ids, torch.Tensor) else torch.device("cpu")
+    ids = image_ids.tolist() if isinstance(image_ids, torch.Tensor) else list(image_ids)
+    slot: Dict[Any, int] = {}
+    first: List[int] = []
+    index: List[int] = []
+    for i, key in enumerate(ids):
+        if key not in slot:
+            slot[key] = len(first)
+            first.append(i)
+        index.append(slot[key])
+    return (torch.tensor(first, dtype=torch.long, device=dev), torch.tensor(index, dtype=torch.long, device=dev))
 
 
 def getattr_path(obj, dotted: str):

@@ -531,10 +531,15 @@ class HipEngine:
 
     # ------------------------------------------------------------------ forward
     def forward(self, images: torch.Tensor, token_ids: torch.Tensor, maskf: Optional[torch.Tensor], training: bool,
-                want_aux: bool = False, need_tape: bool = True, lowp_logits: bool = False, record: Optional[dict] = None):
+                want_aux: bool = False, need_tape: bool = True, lowp_logits: bool = False, record: Optional[dict] = None,
+                kv_index: Optional[torch.Tensor] = None):
         """lowp_logits: return the logits in the compute dtype (the trainer's loss kernel reads bf16 and leaves the fp32 copy itself).
         record: a dict that receives {residual block prefix: (input, output)} of the folded eval path, and under "mxfp8" also
-        {prefix + ".a1": MXFP8 a1 (codes, scales)} (tests)."""
+        {prefix + ".a1": MXFP8 a1 (codes, scales)} (tests).
+        kv_index (many questions per image, training included): int32 [N] on the device, every entry in [0, U) (the caller checks);
+        images holds U images, token_ids N questions, and question i attends to image kv_index[i].  The image half (CNN, projector,
+        norm_kv, K | V) runs at U images, the question half at N; the tape keeps the image index as CSR (vqa_index_csr) for the
+        backward, whose image-token gradient is then summed per image by vqa_attention_bwd(_mfma)_idx."""
         cfg, T = self.cfg, self.dtype
         self._site = 0
         if training:
@@ -542,7 +547,7 @@ class HipEngine:
         self.begin_step(for_backward=need_tape)
         if training and self.fuse_bn_finalize and T == torch.bfloat16:
             self._acc_reset()                     # one memset for every BatchNorm accumulator of this forward
-        tape: dict = {"training": training, "B": images.shape[0]}
+        tape: dict = {"training": training, "B": images.shape[0], "Bq": token_ids.shape[0]}     # image rows, question rows
         B, _, IH, IW = images.shape
         pdrop = cfg["dropout"] if training else 0.0
         phead = cfg["answer_dropout"] if training else 0.0
@@ -612,6 +617,14 @@ class HipEngine:
                     text["q0"] = self._cross_q_path(text["enc"], p0 + ".norm_query", p0 + ".cross_attention")
                 text["ev"] = torch.cuda.Event(); text["ev"].record()
 
+        csr = None
+        if kv_index is not None:
+            # questions of each image in ascending order, built once per step on this stream (the backward's attention reads it)
+            offsets = torch.empty((B + 1,), device=dev, dtype=torch.int32)
+            order = torch.empty((token_ids.shape[0],), device=dev, dtype=torch.int32)
+            call("vqa_index_csr", ptr(kv_index), token_ids.shape[0], B, ptr(offsets), ptr(order))
+            csr = (kv_index, offsets, order, B)
+            tape["csr"] = csr
         if self.mark: self.mark("forward: stem")
 
         # ---- residual stages, A2-A5
@@ -778,7 +791,8 @@ class HipEngine:
                 main.wait_event(ev_kv)
             rec = self._attn_block_fwd(q, img, None, p + ".norm_query", p + ".norm_kv", p + ".cross_attention", None, Bt, L, ntok,
                                        heads, hd, pdrop, p + ".norm_ffn", p + ".ffn.0", p + ".ffn.3", self_attn=False,
-                                       pre_q=text.get("q0") if l == 0 else None, pre_kv=pkv, probs=None if caw is None else caw[l])
+                                       pre_q=text.get("q0") if l == 0 else None, pre_kv=pkv, probs=None if caw is None else caw[l],
+                                       csr=csr)
             tape["clayers"].append(rec)
             probs_all.append(rec["probs"])
             q = rec["out"]
@@ -817,7 +831,7 @@ class HipEngine:
                 "text_pooled": cat[:, d:].float(),          # fusion's entry overrides the encoder's (vqa_model.py:303-309)
                 "fused": fused.float(),
                 "cross_attention_weights": probs_all,
-                "image_projected": img.float().view(Bt, ntok, d),
+                "image_projected": img.float().view(B, ntok, d),
                 "attended_pooled": cat[:, :d].float(),
             }
         if not need_tape:
@@ -841,11 +855,13 @@ class HipEngine:
         return nkv, stkv, self._lin(nkv, wk), self._lin(nkv, wv), d, False
 
     def _attn_block_fwd(self, q_in, kv_in, _unused, norm_q, norm_kv, attn, kmask, B, Lq, Lk, heads, hd, p, norm_f, fc1, fc2, self_attn,
-                        pre_q=None, pre_kv=None, probs=None, kv_index=None, n_kv=0):
+                        pre_q=None, pre_kv=None, probs=None, kv_index=None, n_kv=0, csr=None):
         """pre-norm attention + FFN block (TransformerEncoderLayer.forward text_encoder.py:373-399 and
         MultiHeadCrossAttention.forward cross_attention.py:285-299).  pre_q / pre_kv: the results of _cross_q_path / _cross_kv_path when
         the caller issued them earlier (on another stream, already joined).  kv_index (answer(), inference): int32 [B] on the device,
-        query batch b attends to the K / V rows of image kv_index[b] of the n_kv images in pre_kv."""
+        query batch b attends to the K / V rows of image kv_index[b] of the n_kv images in pre_kv.  csr (forward with kv_index,
+        training included): (kv_index, offsets, order, n_kv) of vqa_index_csr: the same indexed attention with dropout, kept on the
+        record for the backward."""
         T = self.dtype
         d = heads * hd
         wq, wk, wv = attn + ".W_q.weight", attn + ".W_k.weight", attn + ".W_v.weight"
@@ -866,7 +882,15 @@ class HipEngine:
             probs = torch.empty((B, heads, Lq, Lk), device=Q.device, dtype=torch.float32)
         ctx = torch.empty((B * Lq, d), device=Q.device, dtype=T)
         sa = self._seed()
-        if kv_index is not None:
+        if csr is not None:
+            kv_index, n_kv = csr[0], csr[3]
+            if T == torch.bfloat16 and Lq <= 32 and Lk <= 160 and hd in (32, 64):
+                call("vqa_attention_fwd_mfma_idx_train", ptr(Q), ptr(Kt), ptr(V), ldq, ldkv, ldkv, ptr(kv_index), n_kv, ptr(kmask), ptr(probs),
+                     ptr(ctx), d, B, heads, Lq, Lk, hd, float(p), sa)
+            else:
+                call("vqa_attention_fwd_idx_train", dt(T), ptr(Q), ptr(Kt), ptr(V), ldq, ldkv, ldkv, ptr(kv_index), n_kv, ptr(kmask),
+                     ptr(probs), ptr(ctx), d, B, heads, Lq, Lk, hd, float(p), sa)
+        elif kv_index is not None:
             assert p == 0.0, "indexed attention is inference only"
             if T == torch.bfloat16 and Lq <= 32 and Lk <= 160 and hd in (32, 64):
                 call("vqa_attention_fwd_mfma_idx", ptr(Q), ptr(Kt), ptr(V), ldq, ldkv, ldkv, ptr(kv_index), n_kv, ptr(kmask), ptr(probs), ptr(ctx),
@@ -889,7 +913,7 @@ class HipEngine:
         return dict(q_in=q_in, kv_in=kv_in, nq=nq, stq=stq, nkv=nkv, stkv=stkv, Q=Q, K=Kt, V=V, ldq=ldq, ldkv=ldkv, fused=fused,
                     probs=probs, ctx=ctx, sa=sa, so=so,
                     x1=x1, nf=nf, stf=stf, h=h, s1=s1, s2=s2, out=out, p=p, norm_q=norm_q, norm_kv=norm_kv, attn=attn, norm_f=norm_f,
-                    fc1=fc1, fc2=fc2, self_attn=self_attn, B=B, Lq=Lq, Lk=Lk, heads=heads, hd=hd)
+                    fc1=fc1, fc2=fc2, self_attn=self_attn, B=B, Lq=Lq, Lk=Lk, heads=heads, hd=hd, csr=csr)
 
     # ------------------------------------------------------------------ many questions per image (inference only)
     def encode_images(self, images: torch.Tensor, want_aux: bool = False) -> dict:
@@ -1096,18 +1120,30 @@ class HipEngine:
         wq, wk, wv = attn + ".W_q.weight", attn + ".W_k.weight", attn + ".W_v.weight"
         ldq, ldkv, fused = rec["ldq"], rec["ldkv"], rec["fused"]
         dev = dctx.device
+        csr = rec.get("csr")
+        Bk = B if csr is None else csr[3]             # K / V rows: one batch per query batch, or per image (indexed)
+        if csr is not None and dprobs is not None:
+            raise NotImplementedError("gradients through the attention weights are not supported with an image index")
         if fused and rec["self_attn"]:
             dqkv = torch.empty((B * Lq, 3 * d), device=dev, dtype=T)
             dQ, dK, dV = dqkv, dqkv[:, d:], dqkv[:, 2 * d:]
         elif fused:
             dQ = torch.empty((B * Lq, d), device=dev, dtype=T)
-            dkv = torch.empty((B * Lk, 2 * d), device=dev, dtype=T)
+            dkv = torch.empty((Bk * Lk, 2 * d), device=dev, dtype=T)
             dK, dV = dkv, dkv[:, d:]
         else:
-            dQ = torch.empty((B * Lq, d), device=dev, dtype=T); dK = torch.empty((B * Lk, d), device=dev, dtype=T); dV = torch.empty((B * Lk, d), device=dev, dtype=T)
+            dQ = torch.empty((B * Lq, d), device=dev, dtype=T); dK = torch.empty((Bk * Lk, d), device=dev, dtype=T); dV = torch.empty((Bk * Lk, d), device=dev, dtype=T)
         pr = (ptr(rec["probs"]),) if dprobs is None else (ptr(rec["probs"]), ptr(dprobs))
         dp = "" if dprobs is None else "_dp"
-        if T == torch.bfloat16 and Lq <= 32 and Lk <= 160 and hd in (32, 64):
+        if csr is not None:                           # dK / dV summed per image over its questions (fixed order, no atomics)
+            ix = (ptr(rec["probs"]), ptr(csr[1]), ptr(csr[2]), Bk)
+            if T == torch.bfloat16 and Lq <= 32 and Lk <= 160 and hd in (32, 64):
+                call("vqa_attention_bwd_mfma_idx", ptr(dctx), d, ptr(rec["Q"]), ptr(rec["K"]), ptr(rec["V"]), ldq, ldkv, ldkv, *ix,
+                     ptr(dQ), ptr(dK), ptr(dV), ldq, ldkv, ldkv, B, heads, Lq, Lk, hd, float(p), rec["sa"])
+            else:
+                call("vqa_attention_bwd_idx", dt(T), ptr(dctx), d, ptr(rec["Q"]), ptr(rec["K"]), ptr(rec["V"]), ldq, ldkv, ldkv, *ix,
+                     ptr(dQ), ptr(dK), ptr(dV), ldq, ldkv, ldkv, B, heads, Lq, Lk, hd, float(p), rec["sa"])
+        elif T == torch.bfloat16 and Lq <= 32 and Lk <= 160 and hd in (32, 64):
             call("vqa_attention_bwd_mfma" + dp, ptr(dctx), d, ptr(rec["Q"]), ptr(rec["K"]), ptr(rec["V"]), ldq, ldkv, ldkv, *pr,
                  ptr(dQ), ptr(dK), ptr(dV), ldq, ldkv, ldkv, B, heads, Lq, Lk, hd, float(p), rec["sa"])
         else:
@@ -1273,7 +1309,7 @@ class HipEngine:
     def _fusion_bwd(self, tape, dfused, G, seg, taps=None):
         """Returns (dfeat, denc): the gradients at the image features and at the text encoder's output (query path included)."""
         cfg, T = self.cfg, self.dtype
-        B = tape["B"]
+        B, Bq = tape["B"], tape.get("Bq", tape["B"])   # image rows (projector, image tokens), question rows (everything else)
         taps = taps or {}
         # ---- fusion tail: output norm, gate, pools
         pr = tape["pool"]; d, L = pr["d"], pr["L"]
@@ -1291,23 +1327,23 @@ class HipEngine:
         else:
             dfused = dfused.contiguous()
         if taps.get("fused") is not None:
-            self._tap(taps["fused"], dfused, B, d, d)
+            self._tap(taps["fused"], dfused, Bq, d, d)
         dfp = self._ln_bwd(dfused, pr["fused_pre"], "fusion.output_norm", pr["fst"], G)
         dcat = torch.empty_like(pr["cat"])
         if cfg["use_gating"]:
             dzg = torch.empty_like(pr["z"])
-            call("vqa_gate_bwd", dt(T), ptr(dfp), ptr(pr["z"]), ptr(pr["cat"]), ptr(dzg), ptr(dcat), B, d)
+            call("vqa_gate_bwd", dt(T), ptr(dfp), ptr(pr["z"]), ptr(pr["cat"]), ptr(dzg), ptr(dcat), Bq, d)
             dzg = self._act_bwd(dzg, None, "fusion.gate.gate.0.bias", G, 0.0, 0)
             dcat = self._lin_bwd(dzg, pr["cat"], "fusion.gate.gate.0.weight", G, addend=dcat)
         else:
             dcat[:, :d] = dfp; dcat[:, d:] = dfp
         if taps.get("attended_pooled") is not None:
-            self._tap(taps["attended_pooled"], dcat, B, d, 2 * d)
+            self._tap(taps["attended_pooled"], dcat, Bq, d, 2 * d)
         if taps.get("text_pooled") is not None:
-            self._tap(taps["text_pooled"], dcat[:, d:], B, d, 2 * d)
+            self._tap(taps["text_pooled"], dcat[:, d:], Bq, d, 2 * d)
         dq = torch.empty_like(pr["q"])
         denc = torch.empty_like(pr["enc"])
-        call("vqa_masked_pool_pair_bwd", dt(T), ptr(dcat), ptr(pr["maskf"]), ptr(dq), ptr(denc), B, L, d)
+        call("vqa_masked_pool_pair_bwd", dt(T), ptr(dcat), ptr(pr["maskf"]), ptr(dq), ptr(denc), Bq, L, d)
         # ---- cross-attention layers (reverse); image-token gradient accumulates across layers
         dimg, ev_img = None, None
         side_ok = self.hoist_cross and self.two_streams and self.side is not None

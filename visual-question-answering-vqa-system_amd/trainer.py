@@ -166,17 +166,25 @@ class HipTrainer:
                                          avoid_streams=[st for st in (self.engine.side, self.engine.side2) if st is not None])
         self.world = self.reducer.world
 
-    def step(self, images, token_ids, attention_mask, targets, metrics=None):
+    def step(self, images, token_ids, attention_mask, targets, metrics=None, image_index=None):
         """One full train step; returns (loss device scalar, logits fp32).  `metrics`: optional device-side accuracy tracker
-        (dropin/utils/metrics.py VQAAccuracy) updated from the logits without a host sync (train.py:211-212 does two)."""
+        (dropin/utils/metrics.py VQAAccuracy) updated from the logits without a host sync (train.py:211-212 does two).
+        image_index (many questions per image): images [U,3,H,W], token_ids / attention_mask [N,L], targets [N]; question i is asked of
+        image image_index[i] and the step trains VQAModel.forward_grouped's composition (one CNN pass per image, loss per question).
+        The range check is free for a CPU index (copied to the device without a sync) and costs one device-to-host read for a device
+        index.  None: exactly the plain step."""
         eng, T = self.engine, self.engine.dtype
         dev = self.G.device
         for name, t in (("images", images), ("token_ids", token_ids), ("targets", targets)):
             if not (isinstance(t, torch.Tensor) and t.device == dev):
                 raise RuntimeError(f"HipTrainer.step: `{name}` must be a tensor on {dev} (there is no CPU path)")
-        if images.dim() != 4 or images.shape[1] != 3 or token_ids.dim() != 2 or token_ids.shape[0] != images.shape[0] \
-                or targets.shape != (images.shape[0],):
-            raise RuntimeError("HipTrainer.step: expected images [B,3,H,W], token_ids [B,L], targets [B]")
+        Bq = token_ids.shape[0] if (image_index is not None and token_ids.dim() == 2) else images.shape[0]
+        if images.dim() != 4 or images.shape[1] != 3 or token_ids.dim() != 2 or token_ids.shape[0] != Bq or targets.shape != (Bq,):
+            raise RuntimeError("HipTrainer.step: expected images [B,3,H,W], token_ids [B,L], targets [B]"
+                               + ("" if image_index is None else " with B questions"))
+        kv_index = None
+        if image_index is not None:
+            kv_index = self._device_index(image_index, images.shape[0], Bq, dev)
         if attention_mask is not None and not (isinstance(attention_mask, torch.Tensor) and attention_mask.device == dev
                                                and attention_mask.shape == token_ids.shape):
             raise RuntimeError(f"HipTrainer.step: `attention_mask` must be a [B,L] tensor on {dev} (or None)")
@@ -189,7 +197,7 @@ class HipTrainer:
         if self._copy_sig is not None and eng.adamw_copy_target() is not None and self._copy_sig == self._param_sig():
             eng._wsrc_fresh = True                 # (one-shot, consumed by the begin_step of the forward below)
         maskf = None if attention_mask is None else attention_mask.contiguous().float()
-        logits, _, tape = eng.forward(images, token_ids, maskf, True, False, need_tape=True, lowp_logits=True)
+        logits, _, tape = eng.forward(images, token_ids, maskf, True, False, need_tape=True, lowp_logits=True, kv_index=kv_index)
         B, N = logits.shape
         # the loss kernel reads the logits in the compute dtype, writes d logits in it and leaves the fp32 logits the caller gets:
         # the same values as logits.float() -> loss -> d logits.to(bf16), two elementwise launches less between forward and backward
@@ -212,6 +220,16 @@ class HipTrainer:
         # the kernel wrote the bf16 operand copy too: the next step() skips the cast launch if nothing touched the parameters in between
         self._copy_sig = self._param_sig() if eng.adamw_copy_target() is not None else None
         return self.loss, logits_f
+
+    def _device_index(self, image_index, U, N, dev):
+        """int32 [N] device copy of a checked image index (VQAModel._image_index rules; None -> the implied index)."""
+        on_dev = isinstance(image_index, torch.Tensor) and image_index.device == dev
+        idx = self.model._image_index(image_index, U, N, dev if on_dev else torch.device("cpu"))
+        if idx is None:
+            return self.model._implied_index(U, N, dev)
+        if not on_dev:                                     # checked on the host: a pinned copy goes out without a sync
+            idx = idx.pin_memory().to(dev, non_blocking=True)
+        return idx
 
     def params_changed(self):
         """Tell the trainer that the parameters were written behind torch's back (through `.data`, a raw pointer, another C-ABI call):
