@@ -5,7 +5,7 @@ what must hold, per site with its own code path, is torch's dropout CONTRACT:
   same seed => same mask, different seed => different mask, and the backward regenerates the forward's mask
   (the gradient is zero exactly where the forward output was dropped).
 The attention site exposes no elementwise output, so the counter-based generator (csrc/common.h: mix32 / drop_key /
-drop_keep32) is restated here in numpy and both attention kernels (MFMA bf16, VALU fp32) are checked against the torch formula
+drop_keep32) is restated in numpy (tests/_dropmask.py) and both attention kernels (MFMA bf16, VALU fp32) are checked against the torch formula
 with that mask, forward and backward."""
 import math
 
@@ -13,28 +13,12 @@ import numpy as np
 import pytest
 import torch
 
+from _dropmask import keep_mask
 from _pkg import pkg, sub
 from oracle import vqa_oracle as O
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-M32 = np.uint64(0xFFFFFFFF)
-
-
-def _mix32(x):
-    x = x & M32
-    x ^= x >> np.uint64(16); x = (x * np.uint64(0x7feb352d)) & M32
-    x ^= x >> np.uint64(15); x = (x * np.uint64(0x846ca68b)) & M32
-    x ^= x >> np.uint64(16)
-    return x
-
-
-def keep_mask(seed: int, n: int, p: float) -> np.ndarray:
-    """numpy restatement of drop_keep32(drop_key(seed), idx, p) for idx in [0, n)."""
-    key = (_mix32(np.uint64(seed & 0xFFFFFFFF)) ^ ((np.uint64(seed >> 32) * np.uint64(0x9E3779B9)) & M32)) & M32
-    h = _mix32(np.arange(n, dtype=np.uint64) ^ key)
-    u = (h >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
-    return u >= np.float32(p)
 
 
 def _rate_ok(kept: int, n: int, p: float):

@@ -127,6 +127,9 @@ class HipEngine:
         # test hook (tests/test_gpu_insitu.py): a dict here receives, per residual block, the intermediate gradients of its backward
         # (dout, dy2, dyd, da1, dy1, dx) so that every layer of a LIVE full-size bf16 step can be checked locally against fp32 math
         self.capture = None
+        # test hook (tests/test_gpu_insitu.py): a dict here receives the gradients entering, inside and leaving every other backward
+        # section (stem, SE, spatial attention, attention blocks, fusion tail, projector, answer head), keyed by module prefix
+        self.capture_io = None
         self.fuse_stem_eval = True                # inference (no tape): conv7x7 + BN + ReLU + MaxPool of the stem in one launch
         self.mark = None                          # measurement hook (tools/phase_times.py): called with a label at forward boundaries
 
@@ -1157,6 +1160,9 @@ class HipEngine:
                 dnq = self._lin_bwd(dK, rec["nkv"], wk, G, addend=dnq)
                 dnq = self._lin_bwd(dV, rec["nkv"], wv, G, addend=dnq)
             dq_in = self._ln_bwd(dnq, rec["q_in"], rec["norm_q"], rec["stq"], G, addend=dx1)
+            if self.capture_io is not None:
+                self.capture_io[attn] = dict(dout=dout, dz2=dz2, dz1=dz1, dnf=dnf, dx1=dx1, dzo=dzo, dctx=dctx, dQ=dQ, dK=dK, dV=dV, dnq=dnq,
+                                             dnkv=None, dq=dq_in, dkv=None)
             return dq_in, None, None
         dnq = self._lin_bwd(dQ, rec["nq"], wq, G)
         main = torch.cuda.current_stream()
@@ -1177,6 +1183,9 @@ class HipEngine:
                 ev_kv = torch.cuda.Event(); ev_kv.record()
             self._keep.extend([dnkv, dkv_in])         # allocated there, read here (as the next layer's addend): alive until the join
             dq_in = self._ln_bwd(dnq, rec["q_in"], rec["norm_q"], rec["stq"], G, addend=dx1)
+            if self.capture_io is not None:
+                self.capture_io[attn] = dict(dout=dout, dz2=dz2, dz1=dz1, dnf=dnf, dx1=dx1, dzo=dzo, dctx=dctx, dQ=dQ, dK=dK, dV=dV, dnq=dnq,
+                                             dnkv=dnkv, dq=dq_in, dkv=dkv_in)
             return dq_in, dkv_in, ev_kv
         if fused:
             dnkv = self._lin_multi_bwd(dkv, rec["nkv"], [wk, wv], G)
@@ -1187,6 +1196,9 @@ class HipEngine:
         if addend_event is not None:
             main.wait_event(addend_event)             # (also orders the parameter-gradient folds queued by that layer before seg())
         dkv_in = self._ln_bwd(dnkv, rec["kv_in"], rec["norm_kv"], rec["stkv"], G, addend=dkv_addend)
+        if self.capture_io is not None:
+            self.capture_io[attn] = dict(dout=dout, dz2=dz2, dz1=dz1, dnf=dnf, dx1=dx1, dzo=dzo, dctx=dctx, dQ=dQ, dK=dK, dV=dV, dnq=dnq,
+                                         dnkv=dnkv, dq=dq_in, dkv=dkv_in)
         return dq_in, dkv_in, None
 
     # ------------------------------------------------------------------ backward
@@ -1301,8 +1313,12 @@ class HipEngine:
         hdr = tape["head"]; c = "answer_head.classifier"
         dz = self._act_bwd(dl, None, c + ".6.bias", G, 0.0, 0)
         dz = self._lin_act_bwd(dz, hdr["h2"], c + ".6.weight", c + ".3.bias", G, hdr["p"])
+        if self.capture_io is not None:
+            self.capture_io["answer_head"] = dict(dlogits=dl, dz3=dz)
         dz = self._lin_act_bwd(dz, hdr["h1"], c + ".3.weight", c + ".0.bias", G, hdr["p"])
         dfused = self._lin_bwd(dz, hdr["fused"], c + ".0.weight", G)
+        if self.capture_io is not None:
+            self.capture_io["answer_head"].update(dz0=dz, dfused=dfused)
         seg("answer_head")
         return dfused
 
@@ -1344,6 +1360,9 @@ class HipEngine:
         dq = torch.empty_like(pr["q"])
         denc = torch.empty_like(pr["enc"])
         call("vqa_masked_pool_pair_bwd", dt(T), ptr(dcat), ptr(pr["maskf"]), ptr(dq), ptr(denc), Bq, L, d)
+        if self.capture_io is not None:
+            self.capture_io["fusion"] = dict(dfused=dfused, dfp=dfp, dzg=dzg if cfg["use_gating"] else None, dcat=dcat, dq=dq,
+                                             denc_pool=denc.clone())
         # ---- cross-attention layers (reverse); image-token gradient accumulates across layers
         dimg, ev_img = None, None
         side_ok = self.hoist_cross and self.two_streams and self.side is not None
@@ -1372,6 +1391,9 @@ class HipEngine:
         dpz = self._ln_bwd(dimg, rp["pz"], pj + ".1", rp["st"], G, p=rp["p"], seed=rp["seed"], dadd=dpos, period=rp["ntok"])
         dpz = self._act_bwd(dpz, None, pj + ".0.bias", G, 0.0, 0)
         dfeat = self._lin_bwd(dpz, rp["feat"], pj + ".0.weight", G)
+        if self.capture_io is not None:
+            self.capture_io["fusion.image_projector"] = dict(dimg=dimg, dpz=dpz, dfeat=dfeat)
+            self.capture_io["fusion"]["denc"] = denc
         seg("fusion")
         return dfeat, denc
 
@@ -1434,6 +1456,8 @@ class HipEngine:
                 call("vqa_spatial_bwd", dt(T), ptr(dxc), ptr(r["x"]), ptr(self.P(ap + ".spatial.conv.weight")), ptr(r["pooled2"]),
                      ptr(r["amax"]), ptr(r["amap"]), ptr(scratch), ptr(dxn), ptr(self._gslice(G, ap + ".spatial.conv.weight")),
                      B, r["H"], r["W"], r["C"])
+                if self.capture_io is not None:
+                    self.capture_io[ap + ".spatial"] = dict(dout=dxc, dx=dxn)
                 dxc = dxn
             if "se" in srec:
                 r = srec["se"]
@@ -1453,6 +1477,8 @@ class HipEngine:
                      ptr(self._gslice(G, ap + ".se.fc1.weight")), ptr(self._gslice(G, ap + ".se.fc2.weight")), B, r["HW"], r["C"], r["Cr"], 1,
                      ptr(lastb["y2"]) if se_pre else None, ptr(lastb["c2"]) if se_pre else None, ptr(se_pre[0]) if se_pre else None,
                      int(bool(se_pre) and se_pre[1] < 0))
+                if self.capture_io is not None:
+                    self.capture_io[ap + ".se"] = dict(dout=dxc, dx=dxn)
                 dxc = dxn
                 masked = True                 # the SE input IS the last block's post-ReLU output: its mask was applied on the way out
             else:
@@ -1470,6 +1496,8 @@ class HipEngine:
                 seg(f"image_encoder.stage{s}")
 
         # ---- stem
+        if self.capture_io is not None:
+            self.capture_io["image_encoder.stem"] = dict(dxc=dxc)
         dimg = self._stem_bwd(tape, dxc, G, training, after_reduce=lambda: (self._flush_deferred_and_report(seg)),
                               want_dimg=want_input_grad)
         seg("image_encoder.stem")
