@@ -1,6 +1,8 @@
 """GPU: every layer of a LIVE bf16 train step, forward and backward, checked locally against fp32 / fp64 math -- at B = 64 (dropout
-off), at the benchmarked B = 512, 224x224 with dropout on (bench.py default) and at the stress shape B = 256, 384x384, d = 512, 8 text
-layers (bench.py --config stress).
+off), at the benchmarked B = 512, 224x224 with dropout on (bench.py default), at the stress shape B = 256, 384x384, d = 512, 8 text
+layers (bench.py --config stress), and grouped (forward with kv_index, many questions per image) at N = 512 questions, 224x224,
+dropout on: "g5" over U = 103 images (question i on image i // 5, tools/bench_grouped_train.py's q = 5) and "gmix" over U = 160
+images with 0 .. 12 questions each in shuffled order (images 0 and U - 1 have none).
 
 Why this test exists.  The end-to-end bf16 gradient check (tests/_bf16check.py) can only hold a CNN weight tensor to the noise floor
 of bf16 itself on this model -- relative error 0.4-0.55 per tensor against the fp32 oracle, the same for PyTorch's own CPU bf16
@@ -18,14 +20,14 @@ applied to the EXACT bf16 tensors that layer consumed in the live step, with the
 (tests/_insitu.py).  Per-image forward checks and data gradients of convolutions use the first and last 16 images (the last land
 in the tail tiles); weight gradients, BatchNorm statistics and their sums always use the full batch.
 
-Bounds (class: bound, global and per slice; measured worst over the three configurations):
+Bounds (class: bound, global and per slice; measured worst over the five configurations):
   bf16        4e-3   bf16-stored outputs of one op, forward and data gradients: the rounding of the stored value (2.4e-3 / 3.4e-3)
-  wgrad       2e-4   fp32 weight and bias gradients from the captured operands, 2.8e-5 / 1.7e-4 (the conv references sum chunks of
+  wgrad       2e-4   fp32 weight and bias gradients from the captured operands, 2.8e-5 / 6.3e-5 (the conv references sum chunks of
                      8 images in fp64: a single fp32 reduction over 1.6 M rows adds ~1e-3 of its own in channels whose sum cancels)
   bnparam     1e-3   BatchNorm and LayerNorm parameter gradients (7e-7 / 1.9e-5)
   fp32        1e-4   fp32-stored forward values (SE, spatial attention, BatchNorm coefficients, running buffers: 6.7e-5);
                      a batch mean and a BatchNorm shift are measured in standard deviations of their channel (a mean near 0 has no
-                     relative scale of its own): T_SIGMA 5e-4, measured 2.2e-4 (statistics summed from the fp32 conv output, the
+                     relative scale of its own): T_SIGMA 5e-4, measured 2.5e-4 (statistics summed from the fp32 conv output, the
                      reference from the stored bf16 y)
   probs       1e-6   attention probabilities, fp32 from bf16 Q / K (1.5e-7)
   attn        T_ATTN dQ / dK / dV of the attention backward (below)
@@ -41,6 +43,13 @@ Residual-block backward semantics (models/cnn_backbone.py:164-197, nn.BatchNorm2
     dx   = conv-input-gradient(dy1, W1) + [g | conv-input-gradient(dyd, Wd)]   (* (x > 0) when handed to the previous block masked)
 CPU time of the references (16 threads, measured): 11 s at B = 64, 41 s at B = 512, 71 s at the stress shape; the live step itself
 takes about a second.  The tape is copied block by block and freed as it goes.
+Grouped steps: the CNN, SE, spatial attention, stem and projector run (and are checked) at U image rows, the text encoder, pools, gate
+and head at N question rows.  The cross-attention references gather K / V by the image index, redraw the dropout mask per question,
+and sum the per-question dK / dV into image rows in fp64 (tests/_insitu.py attn_core_bwd); the K / V weight gradients, norm_kv and the
+image-token gradient chain then run over U * 49 rows.  Also checked: the CSR of the index against a stable argsort, exact zeros in
+every image-token gradient row of an image without questions, the grouped kernels in kernels.PROFILE, and the weight-gradient plans
+of the stage-2 entry conv and the stage-3 / 4 convs (U = 103: all on the 4-wave split kernel, which B = 512 never uses; U = 160: the
+non-entry stage-3 / 4 convs on the 8-wave DMA kernel).
 """
 import math
 import time
@@ -50,17 +59,13 @@ import torch
 import torch.nn.functional as F
 
 from _dropmask import keep_mask
-from _insitu import Checker, bn_bwd, channel_moments, nchw, rnd
+from _insitu import (T_ATTN, T_ATTN_SLICE, T_BF16, T_BNPARAM, T_FP32, T_PROBS, T_SIGMA, T_WGRAD, Checker, attn_core_bwd, attn_core_fwd,
+                     bn_bwd, channel_moments, check_csr, check_zero_rows, empty_images, nchw, rnd)
 from _pkg import pkg
 from oracle import vqa_oracle as O
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-T_BF16, T_WGRAD, T_BNPARAM, T_FP32 = 4e-3, 2e-4, 1e-3, 1e-4
-T_SIGMA = 5e-4                             # batch mean / BN shift error in standard deviations (measured 2.2e-4: stage-1 bn1 shift)
-T_PROBS = 1e-6                             # fp32 attention probabilities from bf16 Q / K (measured 1.5e-7)
-T_ATTN, T_ATTN_SLICE = 4e-3, 8e-3         # dQ / dK / dV of the attention backward: the kernel also feeds P and dS to its MFMAs in bf16
-                                           # (measured 2.6e-3 globally, 5.2e-3 in one feature column of cross-attention dQ)
 NSUB = 16                                  # per-image checks: the first and the last NSUB images
 
 CONFIGS = {
@@ -68,12 +73,19 @@ CONFIGS = {
     "b512": dict(B=512, image=224, model={}, dropout=True),
     "stress": dict(B=256, image=384, model=dict(embed_dim=512, num_transformer_layers=8, num_answers=2000, num_image_tokens=144),
                    dropout=True),
+    # grouped (forward with kv_index): B questions over U images
+    "g5": dict(B=512, U=103, image=224, model={}, dropout=True),       # tools/bench_grouped_train.py's q = 5: question i on image i // 5
+    "gmix": dict(B=512, U=160, image=224, model={}, dropout=True),     # 0 .. 12 questions per image, shuffled (_gmix_index)
 }
 # kernels that must have run in the B = 512 step (the top of profiles/r04_bench_b512_serial_kernel_stats.csv), as kernels.PROFILE
 # spells them
 B512_SYMBOLS = ("conv8p_kernel<2, 4>", "conv8p_kernel<4, 2>", "wgrad_dma_kernel<256, 256, 2>", "wgrad3x3_c128p_kernel",
                 "conv3x3_c64p_kernel<8, 0>", "conv3x3_c64p_kernel<8, 1>", "conv3x3_c64p_kernel<8, 2>", "stem_conv_kernel",
                 "stem_wgrad_kernel<true>")
+
+# the grouped step's own launches (as kernels.PROFILE spells them): the CSR of the image index, the indexed attention with dropout
+# and its backward that sums dK / dV per image
+GROUPED_SYMBOLS = ("hbm:token:index_csr", "hbm:attention:attention_fwd_mfma_idx_train", "hbm:attention:attention_bwd_mfma_idx")
 
 
 def _keep(seed, shape, p):
@@ -83,9 +95,41 @@ def _keep(seed, shape, p):
     return torch.from_numpy(keep_mask(seed, n, p)).view(*shape).double() / (1.0 - p)
 
 
+def _gmix_index(N=512, U=160, seed=11):
+    """N questions over U images, shuffled: images 0 and U - 1 (the tail tiles) and a few others get none, image 1 gets 9 and
+    image U // 2 gets 12, the rest 1 .. 6."""
+    g = torch.Generator().manual_seed(seed)
+    cnt = torch.randint(1, 7, (U,), generator=g)
+    fixed = {0: 0, U - 1: 0, 37: 0, 101: 0, 1: 9, U // 2: 12}
+    free = [u for u in range(U) if u not in fixed]
+    for u, v in fixed.items():
+        cnt[u] = v
+    k = 0
+    while int(cnt.sum()) != N:                 # bring the total to N within 1 .. 6 per free image
+        u = free[k % len(free)]
+        k += 1
+        if int(cnt.sum()) < N and cnt[u] < 6:
+            cnt[u] += 1
+        elif int(cnt.sum()) > N and cnt[u] > 1:
+            cnt[u] -= 1
+    idx = torch.repeat_interleave(torch.arange(U), cnt)
+    return idx[torch.randperm(N, generator=g)]
+
+
+def _image_index(name):
+    """The image index of a grouped configuration (long [B] on the CPU), or None."""
+    c = CONFIGS[name]
+    if "U" not in c:
+        return None
+    idx = torch.arange(c["B"]) // 5 if name == "g5" else _gmix_index(c["B"], c["U"])
+    assert int(idx.min()) >= 0 and int(idx.max()) < c["U"]
+    return idx
+
+
 def _live_step(name):
     """One training step through the engine exactly as bench.py configures the model (bf16, two streams), with the tape and the
-    capture kept and kernels.PROFILE recording the launches."""
+    capture kept and kernels.PROFILE recording the launches.  Grouped configurations run eng.forward(..., kv_index=) on the first
+    U images of the batch (as HipTrainer.step(..., image_index=) does).  run["B"]: image rows (U), run["Bq"]: question rows."""
     P = pkg()
     c = CONFIGS[name]
     kw = dict(c["model"])
@@ -100,12 +144,16 @@ def _live_step(name):
     B = c["B"]
     images, ids, mask, answers = (t.to(DEV) for t in O.synthetic_batch(B, seed=77, image_size=c["image"], num_answers=cfg["num_answers"]))
     maskf = mask.float()
+    index = _image_index(name)
+    U = B if index is None else c["U"]
+    images = images[:U].contiguous()
+    kv_index = None if index is None else index.to(device=DEV, dtype=torch.int32)
     K = P.kernels
     saved = (K.PROFILE, K.PROFILE_VARIANTS, K.PROFILE_STAGED)
     K.PROFILE, K.PROFILE_VARIANTS, K.PROFILE_STAGED = [], [], {}
     try:
         eng.capture, eng.capture_io = {}, {}
-        logits, _, tape = eng.forward(images, ids, maskf, True, False, need_tape=True)
+        logits, _, tape = eng.forward(images, ids, maskf, True, False, need_tape=True, kv_index=kv_index)
         dl = torch.empty_like(logits)
         loss = torch.zeros(1, device=DEV)
         P._lib.call("vqa_cross_entropy", 0, logits.data_ptr(), answers.data_ptr(), loss.data_ptr(), dl.data_ptr(), None, B, logits.shape[1],
@@ -118,8 +166,9 @@ def _live_step(name):
         cap = {**eng.capture, **eng.capture_io}      # (residual-block prefixes and section prefixes do not collide)
         eng.capture = eng.capture_io = None
         K.PROFILE, K.PROFILE_VARIANTS, K.PROFILE_STAGED = saved
-    return dict(m=m, eng=eng, cfg=cfg, sd=sd, B=B, images=images, ids=ids, maskf=maskf, logits=logits, tape=tape, cap=cap, G=G,
-                syms=syms)
+    assert tape["B"] == U and tape["Bq"] == B
+    return dict(m=m, eng=eng, cfg=cfg, sd=sd, B=U, Bq=B, index=index, images=images, ids=ids, maskf=maskf, logits=logits, tape=tape,
+                cap=cap, G=G, syms=syms)
 
 
 class _Params:
@@ -280,7 +329,10 @@ def _check_block(ck, run, W, s, rec):
     a1_t = rec["a1"]
     if fused12:              # stage 1: conv2 and its weight gradient rebuild relu(bn1(y1)) in LDS, the tensor is never stored;
                              # what they consumed is exactly this bf16 value (kernel-level bit-equality: tests/test_gpu_cnn_fused.py)
-        a1_t = torch.relu(rec["y1"].float() * rec["c1"][0] + rec["c1"][1]).to(rec["y1"].dtype)
+        # y1 * scale + shift is ONE fma in the kernels: the fp64 value rounded once to fp32 is that (torch's separate mul and add
+        # round twice, and where the shift cancels most of the product that moves a1 by one bf16 step -- 0.25% of one channel's
+        # elements at U = 103, a 4e-4 error in that input channel of dW2 that is the reference's own)
+        a1_t = torch.relu((rec["y1"].double() * rec["c1"][0].double() + rec["c1"][1].double()).float()).to(rec["y1"].dtype)
     x, y1, a1, y2, out = (nchw(t, B, h, w) for t, h, w in ((rec["x"], H, Wd_), (rec["y1"], Ho, Wo), (a1_t, Ho, Wo), (rec["y2"], Ho, Wo),
                                                             (rec["out"], Ho, Wo)))
     del a1_t
@@ -457,25 +509,26 @@ def _check_ln_grads(ck, W, tag, prefix, dg, db):
     ck.check(f"{tag} d{short}.bias", W.vec(prefix + ".bias", grad=True), db, T_BNPARAM, dims=(0,), cls="bnparam")
 
 
-def _attn_fwd_local(rec, loc, W, kmask):
-    """probs from the stored Q / K and ctx from the stored probs / V, fp64."""
+def _attn_fwd_local(rec, loc, W, kmask, index=None):
+    """probs from the stored Q / K and ctx from the stored probs / V, fp64.  index: image of every question (indexed attention:
+    K / V hold one batch per image; the dropout mask is drawn per question, as the plain kernel draws it per batch)."""
     B, Lq, Lk, H, hd, p = rec["B"], rec["Lq"], rec["Lk"], rec["heads"], rec["hd"], rec["p"]
     Qh = loc["Q"].view(B, Lq, H, hd).transpose(1, 2)
     Kh = loc["K"].view(-1, Lk, H, hd).transpose(1, 2)
     Vh = loc["V"].view(-1, Lk, H, hd).transpose(1, 2)
-    sc = Qh @ Kh.transpose(-1, -2) / math.sqrt(hd)
-    if kmask is not None:
-        sc = sc.masked_fill(kmask[:, None, None, :] == 0, float("-inf"))
     P = rec["probs"].cpu().double()
     keep = _keep(rec["sa"], (B, H, Lq, Lk), p)
-    ctx = ((P * keep) @ Vh).transpose(1, 2).reshape(B * Lq, -1)
-    return torch.softmax(sc, -1), ctx, (Qh, Kh, Vh, P, keep)
+    probs, ctx = attn_core_fwd(Qh, Kh, Vh, P, keep, kmask=kmask, index=index)
+    return probs, ctx.transpose(1, 2).reshape(B * Lq, -1), (Qh, Kh, Vh, P, keep)
 
 
-def _check_attn_block(ck, run, W, rec, tag, kmask, dkv_next):
-    """Every op of one attention + FFN block, forward and backward, from the stored / captured operands of THAT op."""
+def _check_attn_block(ck, run, W, rec, tag, kmask, dkv_next, index=None):
+    """Every op of one attention + FFN block, forward and backward, from the stored / captured operands of THAT op.  index: the
+    image of every question when K / V are per image (grouped cross-attention): dK / dV, the K / V weight gradients, norm_kv's
+    backward and the image-token gradient run over U * Lk rows."""
     c = run["cap"][rec["attn"]]
     B, Lq, H, hd, p = rec["B"], rec["Lq"], rec["heads"], rec["hd"], rec["p"]
+    ck.expect(f"{tag} indexed", (rec.get("csr") is not None) == (index is not None), "the tape and the test disagree on the index")
     d = H * hd
     attn, fc1, fc2 = rec["attn"], rec["fc1"], rec["fc2"]
     Wq, Wk, Wv, Wo = (W.lin_w(attn + f".W_{w}.weight") for w in "qkvo")
@@ -492,7 +545,7 @@ def _check_attn_block(ck, run, W, rec, tag, kmask, dkv_next):
     ck.check(f"{tag} Q", loc["Q"], loc["nq"] @ Wq.t(), T_BF16)
     ck.check(f"{tag} K", loc["K"], loc["nkv"] @ Wk.t(), T_BF16)
     ck.check(f"{tag} V", loc["V"], loc["nkv"] @ Wv.t(), T_BF16)
-    probs, ctx, (Qh, Kh, Vh, P, keep_a) = _attn_fwd_local(rec, loc, W, kmask)
+    probs, ctx, (Qh, Kh, Vh, P, keep_a) = _attn_fwd_local(rec, loc, W, kmask, index)
     ck.check(f"{tag} probs", rec["probs"].cpu(), probs, T_PROBS, cls="probs")
     ck.check(f"{tag} ctx", loc["ctx"], ctx, T_BF16)
     ck.check(f"{tag} x1", loc["x1"], loc["q_in"] + (loc["ctx"] @ Wo.t()) * k_o, T_BF16)
@@ -516,14 +569,18 @@ def _check_attn_block(ck, run, W, rec, tag, kmask, dkv_next):
     ck.check(f"{tag} dzo", g["dzo"], g["dx1"] * k_o, T_BF16)
     _check_lin_grads(ck, W, tag, attn + ".W_o.weight", None, g["dzo"], loc["ctx"])
     ck.check(f"{tag} dctx", g["dctx"], g["dzo"] @ Wo, T_BF16)
-    # attention core, closed form on the stored probabilities: dP = dctx V^T * keep, dS = P (dP - sum(dP P)), dQ = dS K / sqrt(hd), ...
+    # attention core, closed form on the stored probabilities (dK / dV summed per image over its questions when indexed)
     dC = g["dctx"].view(B, Lq, H, hd).transpose(1, 2)
-    dP = (dC @ Vh.transpose(-1, -2)) * keep_a
-    dS = P * (dP - (dP * P).sum(-1, keepdim=True)) / math.sqrt(hd)
+    dQ, dK, dV = attn_core_bwd(Qh, Kh, Vh, P, keep_a, dC, index=index, n_kv=Kh.shape[0])
     flat = lambda t: t.transpose(1, 2).reshape(-1, d)
-    ck.check(f"{tag} dQ", g["dQ"], flat(dS @ Kh), T_ATTN, cls="attn", slice_tol=T_ATTN_SLICE)
-    ck.check(f"{tag} dK", g["dK"], flat(dS.transpose(-1, -2) @ Qh), T_ATTN, cls="attn", slice_tol=T_ATTN_SLICE)
-    ck.check(f"{tag} dV", g["dV"], flat((P * keep_a).transpose(-1, -2) @ dC), T_ATTN, cls="attn", slice_tol=T_ATTN_SLICE)
+    ck.check(f"{tag} dQ", g["dQ"], flat(dQ), T_ATTN, cls="attn", slice_tol=T_ATTN_SLICE)
+    ck.check(f"{tag} dK", g["dK"], flat(dK), T_ATTN, cls="attn", slice_tol=T_ATTN_SLICE)
+    ck.check(f"{tag} dV", g["dV"], flat(dV), T_ATTN, cls="attn", slice_tol=T_ATTN_SLICE)
+    if index is not None:                      # the same per image (all Lk rows of an image as one slice)
+        ck.check(f"{tag} dK per image", g["dK"].reshape(Kh.shape[0], -1), flat(dK).reshape(Kh.shape[0], -1), T_ATTN, dims=(0,), cls="attn",
+                 slice_tol=T_ATTN_SLICE)
+        ck.check(f"{tag} dV per image", g["dV"].reshape(Kh.shape[0], -1), flat(dV).reshape(Kh.shape[0], -1), T_ATTN, dims=(0,), cls="attn",
+                 slice_tol=T_ATTN_SLICE)
     _check_lin_grads(ck, W, tag, attn + ".W_q.weight", None, g["dQ"], loc["nq"])
     _check_lin_grads(ck, W, tag, attn + ".W_k.weight", None, g["dK"], loc["nkv"])
     _check_lin_grads(ck, W, tag, attn + ".W_v.weight", None, g["dV"], loc["nkv"])
@@ -542,8 +599,9 @@ def _check_attn_block(ck, run, W, rec, tag, kmask, dkv_next):
 
 
 def _check_token_side(ck, run, W):
+    """Question rows (text, pools, gate, head) at B = run["Bq"], image-token rows (projector, norm_kv, K / V) at U = run["B"]."""
     eng, tape, cap, cfg = run["eng"], run["tape"], run["cap"], run["cfg"]
-    B, d = run["B"], cfg["embed_dim"]
+    B, U, d, index = run["Bq"], run["B"], cfg["embed_dim"], run["index"]
     ids, maskf = run["ids"].cpu(), run["maskf"].cpu().double()
     L = ids.shape[1]
     # ---- embedding + positional encoding + dropout
@@ -573,14 +631,14 @@ def _check_token_side(ck, run, W):
     pj = "fusion.image_projector.projection"
     Wp, bp = W.lin_w(pj + ".0.weight"), W.vec(pj + ".0.bias").double()
     pos = W.vec("fusion.image_projector.position_embedding").double().view(-1, d)[:ntok]
-    keep_p = _keep(pr["seed"], (B * ntok, d), pr["p"])
+    keep_p = _keep(pr["seed"], (U * ntok, d), pr["p"])
     ck.check("proj linear", pz, feat @ Wp.t() + bp, T_BF16)
-    ck.check("proj ln+dropout+pos", _cpu(tape["clayers"][0]["kv_in"]), _ln(pz, W, pj + ".1") * keep_p + pos.repeat(B, 1), T_BF16)
+    ck.check("proj ln+dropout+pos", _cpu(tape["clayers"][0]["kv_in"]), _ln(pz, W, pj + ".1") * keep_p + pos.repeat(U, 1), T_BF16)
     # ---- cross-attention layers (the K / V gradient of layer l includes those of the layers after it)
     ncl = len(tape["clayers"])
     for l, rec in enumerate(tape["clayers"]):
         nxt = cap[tape["clayers"][l + 1]["attn"]]["dkv"] if l + 1 < ncl else None
-        _check_attn_block(ck, run, W, rec, f"cross{l}", None, nxt)
+        _check_attn_block(ck, run, W, rec, f"cross{l}", None, nxt, index=index)
     # projector backward: dimg (the first cross layer's image-token gradient) -> LN + dropout -> Linear -> features
     cp = cap["fusion.image_projector"]
     dimg, dpz = _cpu(cp["dimg"]), _cpu(cp["dpz"])
@@ -589,11 +647,23 @@ def _check_token_side(ck, run, W):
     ck.check("proj dpz", dpz, dpz_ref, T_BF16)
     _check_ln_grads(ck, W, "proj", pj + ".1", dgp, dbp)
     ck.check("proj dpos", W.vec("fusion.image_projector.position_embedding", grad=True).view(-1, d)[:ntok],
-             dimg.view(B, ntok, d).sum(0), T_WGRAD, cls="wgrad")
+             dimg.view(U, ntok, d).sum(0), T_WGRAD, cls="wgrad")
     _check_lin_grads(ck, W, "proj", pj + ".0.weight", pj + ".0.bias", dpz, feat)
     ck.check("proj dfeat", _cpu(cp["dfeat"]), dpz @ Wp, T_BF16)
     if "image_encoder.stage4.attention.spatial" in cap:
         ck.expect("proj dfeat -> spatial", cap["image_encoder.stage4.attention.spatial"]["dout"] is cp["dfeat"], "not the same tensor")
+    if index is not None:
+        # an image without questions receives no image-token gradient anywhere: every one of its rows is exactly zero, from each
+        # cross layer's dK / dV down to the gradient entering the CNN (its BatchNorm statistics still count it: _check_bn_coef)
+        empty = empty_images(index, U)
+        for l, rec in enumerate(tape["clayers"]):
+            cl = cap[rec["attn"]]
+            for k in ("dK", "dV", "dnkv", "dkv"):
+                check_zero_rows(ck, f"cross{l} {k}", cl[k].cpu(), U, empty)
+        for k in ("dimg", "dpz", "dfeat"):
+            check_zero_rows(ck, f"proj {k}", cp[k].cpu(), U, empty)
+        if "image_encoder.stage4.attention.spatial" in cap:
+            check_zero_rows(ck, "stage4 spatial dout", cap["image_encoder.stage4.attention.spatial"]["dout"].cpu(), U, empty)
     # ---- masked pool pair, gate, output norm
     q_last = _cpu(pl["q"])
     m3 = maskf.view(B, L, 1)
@@ -647,10 +717,58 @@ def _check_token_side(ck, run, W):
     ck.expect("head dfused -> fusion", ch["dfused"] is cf["dfused"] or torch.equal(ch["dfused"], cf["dfused"]), "differs")
 
 
+def _wgrad_plans(run, at=None):
+    """{conv: (kind, tile n, tile k, nsplit)} of vqa_wgrad (kernels.wgrad_plan) for the conv weight gradients of this step that go
+    through kernels.wgrad -- the stage-2 entry conv and every 3x3 conv of stages 3 and 4 -- at its image batch, or at `at` images."""
+    K = pkg().kernels
+    plans = {}
+    for s in (2, 3, 4):
+        for rec in run["tape"]["stages"][s - 1]["blocks"]:
+            for conv, g in (("conv1", rec["g1"]), ("conv2", rec["g2"])):
+                if s == 2 and not (conv == "conv1" and "yd" in rec):
+                    continue                   # (the 128 -> 128 convs of stage 2 run the c128 patch kernel)
+                B, H, W_, C, Ho, Wo, R, S = g[:8]
+                if at is not None:
+                    B = at
+                plans[f"stage{s}.{rec['p'][-1]}.{conv}"] = K.wgrad_plan(torch.bfloat16, K.LOADER_NHWC, B * Ho * Wo, rec["Cout"], R * S * C, B, H,
+                                                                         W_, C, R, S)[:4]
+    return plans
+
+
+def _wgrad_symbol(plan):
+    """kernels.wgrad's PROFILE symbol of a bf16 plan."""
+    kind, tn, tk = plan[:3]
+    return f"wgrad_dma_kernel<{tn}, {tk}, 2>" if kind else f"wgrad_kernel<unsigned short, {tn}, {tk}, 0>"
+
+
+def _check_grouped(ck, run, name, syms):
+    """What only a grouped step has: the CSR of the image index, its own kernels, and the weight-gradient kernels its image batch
+    selects (the planner gives the 8-wave DMA kernel only to problems of >= 3e10 FLOP)."""
+    tape, index, U = run["tape"], run["index"], run["B"]
+    _, offsets, order, n_kv = tape["csr"]
+    ck.expect("csr images", n_kv == U, f"{n_kv} != {U}")
+    check_csr(ck, "csr", index, U, offsets, order)
+    missing = [s for s in GROUPED_SYMBOLS if s not in syms]
+    assert not missing, (missing, sorted(syms))
+    plans, plans512 = _wgrad_plans(run), _wgrad_plans(run, at=512)
+    print(f"{name}: wgrad plans (kind, tile n, tile k, nsplit) at U = {U}: {plans}; at 512: {plans512}")
+    missing = [(c, _wgrad_symbol(pl)) for c, pl in plans.items() if _wgrad_symbol(pl) not in syms]
+    assert not missing, (missing, sorted(syms))
+    if name == "g5":                           # U = 103: every one of them drops to the 4-wave split kernel, which B = 512 does not use
+        assert all(pl[0] == 0 for pl in plans.values()), plans
+        assert all(pl[0] == 1 for pl in plans512.values()), plans512
+    else:                                      # U = 160: the non-entry stage-3 / 4 convs (3.7e10 FLOP) keep the DMA kernel
+        assert {c for c, pl in plans.items() if pl[0] == 1} == {"stage3.1.conv1", "stage3.1.conv2", "stage3.0.conv2", "stage4.1.conv1",
+                                                                "stage4.1.conv2", "stage4.0.conv2"}, plans
+        cnt = torch.bincount(index, minlength=U)
+        assert int(cnt[0]) == 0 and int(cnt[U - 1]) == 0 and int(cnt.max()) >= 9, cnt
+        assert not bool((index[1:] >= index[:-1]).all())          # shuffled
+
+
 CPU_SECONDS = {}
 
 
-@pytest.mark.parametrize("name", ["b64", "b512", "stress"])
+@pytest.mark.parametrize("name", ["b64", "b512", "stress", "g5", "gmix"])
 def test_every_layer_of_a_live_bf16_step_matches_fp32_math_locally(name):
     torch.set_num_threads(16)
     t0 = time.perf_counter()
@@ -663,6 +781,8 @@ def test_every_layer_of_a_live_bf16_step_matches_fp32_math_locally(name):
         missing = [s for s in B512_SYMBOLS if s not in syms]
         assert not missing, (missing, sorted(syms))
     ck = Checker()
+    if run["index"] is not None:
+        _check_grouped(ck, run, name, syms)
     W = _Params(run)
     _check_stem(ck, run, W)
     n_handed = n_masked = n_fused12 = nblk = 0

@@ -79,6 +79,13 @@ HBM_BYTES = {
     # indexed form (answer()): queries, ctx and probs per question, K / V once per image
     "vqa_attention_fwd_mfma_idx": ("attention", lambda a: 2 * a[12] * a[14] * a[13] * a[16] * 2 + 2 * a[7] * a[15] * a[13] * a[16] * 2 + a[12] * a[13] * a[14] * a[15] * 4),
     "vqa_attention_fwd_idx": ("attention", lambda a: (2 * a[13] * a[15] * a[14] * a[17] + 2 * a[8] * a[16] * a[14] * a[17]) * _ES(a[0]) + a[13] * a[14] * a[15] * a[16] * 4),
+    # indexed form in training (forward_grouped): the same traffic with dropout; the backward reads Q, K, V, dctx and probs and writes
+    # dQ per question, dK / dV once per image; the CSR of the image index is N + U + 1 ints written from N read
+    "vqa_attention_fwd_mfma_idx_train": ("attention", lambda a: 2 * a[12] * a[14] * a[13] * a[16] * 2 + 2 * a[7] * a[15] * a[13] * a[16] * 2 + a[12] * a[13] * a[14] * a[15] * 4),
+    "vqa_attention_fwd_idx_train": ("attention", lambda a: (2 * a[13] * a[15] * a[14] * a[17] + 2 * a[8] * a[16] * a[14] * a[17]) * _ES(a[0]) + a[13] * a[14] * a[15] * a[16] * 4),
+    "vqa_attention_bwd_mfma_idx": ("attention", lambda a: (3 * a[18] * a[20] + 4 * a[11] * a[21]) * a[1] * 2 + a[18] * a[19] * a[20] * a[21] * 4),
+    "vqa_attention_bwd_idx": ("attention", lambda a: (3 * a[19] * a[21] + 4 * a[12] * a[22]) * a[2] * _ES(a[0]) + a[19] * a[20] * a[21] * a[22] * 4),
+    "vqa_index_csr": ("token", lambda a: (2 * a[1] + a[2] + 1) * 4),
     "vqa_cross_entropy": ("token", lambda a: a[6] * a[7] * (_ES(a[0]) + 4)),
     # weight staging and the optimizer tail (H, N1): cast of the flat buffer, packed data-gradient operands, sum of squares, AdamW
     "vqa_convert": ("optimizer", lambda a: a[4] * (_ES(a[0]) + _ES(a[1]))),
