@@ -238,7 +238,8 @@ int vqa_se_bwd_blocks(int dtype, int B, int HW, int C);
 long long vqa_se_bwd_scratch(int dtype, int B, int HW, int C, int Cr);   /* floats of `scratch` below */
 /* bn_acc_mode 1: bn_slab is the u64 fixed-point accumulator (vqa_bn_acc_words(3, C)) instead of a float slab */
 int vqa_se_bwd(int dtype, const void* dout, const void* x, const float* w1, const float* w2, const float* pooled,
-               const float* hidden, const float* scale, float* scratch /* vqa_se_bwd_scratch() floats */, void* dx, float* dw1, float* dw2,
+               const float* hidden, const float* scale, float* scratch /* vqa_se_bwd_scratch() floats */, void* dx,
+               float* dw1, float* dw2 /* both NULL: data gradient only, no weight-gradient launch */,
                int B, int HW, int C, int Cr, int mask_out /* dx *= (x > 0): x is a post-ReLU activation */,
                const void* bn_y, const float* bn_coef, float* bn_slab /* or the u64 accumulator when bn_acc_mode = 1 */, int bn_acc_mode,
                hipStream_t stream);
@@ -248,7 +249,8 @@ int vqa_spatial_fwd(int dtype, const void* x, const float* w /* (1,2,7,7) */, fl
                     void* out, int B, int H, int W, int C, hipStream_t stream);
 long long vqa_spatial_bwd_scratch(int B, int H, int W);   /* floats of `scratch` below (3*B*H*W + the conv-weight partial sums) */
 int vqa_spatial_bwd(int dtype, const void* dout, const void* x, const float* w, const float* pooled2, const int* argmax,
-                    const float* amap, float* scratch /* vqa_spatial_bwd_scratch() floats */, void* dx, float* dw, int B, int H, int W, int C,
+                    const float* amap, float* scratch /* vqa_spatial_bwd_scratch() floats */, void* dx,
+                    float* dw /* NULL: data gradient only */, int B, int H, int W, int C,
                     hipStream_t stream);
 int vqa_nhwc_to_nchw(int dtype, const void* in, float* out, int B, int HW, int C, hipStream_t stream);   /* aux['image_features'] */
 int vqa_nchw_to_nhwc(int dtype, const float* in, void* out, int B, int HW, int C, hipStream_t stream);
@@ -379,6 +381,18 @@ int vqa_adamw(float* p, const float* g, float* m, float* v, long long n, float l
               const int* skip, int* skipped,
               void* p_bf16 /* or NULL: also write the bf16 copy of the updated parameters (the operand buffer of the next forward) */,
               hipStream_t stream);
+
+/* The same over a device table of TRAINABLE ranges (fine-tuning with frozen parameters): elements outside them are never read or
+   written (parameters, moments and the bf16 copy stay put).  table: R <= 512 int64 rows (R = 0 with n = 0: nothing trains) {lo, hi, pos, lag index}: [lo, hi) of the flat
+   buffer, pos = its start in the concatenation of the ranges (ascending, pos[0] = 0); lo, hi, pos multiples of 4; n = total trainable
+   elements.  The norm folds in a fixed order.  Adam's step number of a range is calls - skipped[2] - lag[its lag index]: lag[j] (device
+   int per parameter) counts applied steps during which parameter j was frozen -- after an applied launch lag[frozen[k]] += 1 for the nf
+   frozen parameters listed, as torch.optim.AdamW advances a parameter's step only while it has a gradient. */
+int vqa_sumsq_ranges(const float* g, const long long* table, int R, long long n, float* out /* >= 2049 floats, as vqa_sumsq */,
+                     hipStream_t stream);
+int vqa_adamw_ranges(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n, float lr, float beta1,
+                     float beta2, float eps, float weight_decay, long long calls, const float* sumsq, float max_norm, float gscale,
+                     const int* skip, int* skipped, int* lag, const int* frozen, int nf, void* p_bf16, hipStream_t stream);
 
 /* ---- input pipeline on the GPU -----------------------------------------------------------------
  * vqa_image_normalize: torchvision ToTensor + Normalize of data/preprocess.py:34-35,117-121 -- uint8 HWC [B][H][W][3] ->

@@ -1369,6 +1369,7 @@ int vqa_se_bwd(int dtype, const void* dout, const void* x, const float* w1, cons
   // shm <= shm2 <= (1024 * 8 + 4 * 2048) * 4 = 64 KB at bf16 C = 2048
   if (C % VEC || C / VEC > 256 || 256 % (C / VEC) || Cr < 1 || Cr > C) return VQA_EARG;
   if ((bn_slab != nullptr) != (bn_y != nullptr) || (bn_slab != nullptr) != (bn_coef != nullptr)) return VQA_EARG;
+  if ((dw1 != nullptr) != (dw2 != nullptr)) return VQA_EARG;       // both NULL: data gradient only (frozen SE weights)
   float* dz2 = scratch; float* dh = dz2 + (size_t)B * C; float* dpool = dh + (size_t)B * Cr;
   const int cvh = C / VEC;
   const int nt = (1024 % cvh == 0 && (long long)HW * cvh >= (dtype ? 2048 : 4096)) ? 1024 : 256;      // threads per sample (tiny maps: 256 are plenty; bf16 7 x 7 x 512: 1024, so that a thread keeps all its 4 vectors)
@@ -1404,7 +1405,7 @@ int vqa_se_bwd(int dtype, const void* dout, const void* x, const float* w1, cons
 #undef SE_FUSED_KT
 #undef SE_FUSED_D
 #undef SE_FUSED
-    launch_se_wgrad(dz2, hidden, dh, pooled, dw1, dw2, B, C, Cr, st);
+    if (dw1) launch_se_wgrad(dz2, hidden, dh, pooled, dw1, dw2, B, C, Cr, st);
     VQA_LAUNCH_CHECK(); return VQA_OK;
   }
   DT(hipLaunchKernelGGL(se_bwd_reduce_kernel<float>, dim3(B), dim3(nt), shm, st, (const float*)dout, (const float*)x, w1, w2, hidden, scale, dz2, dh, dpool, HW, C, Cr),
@@ -1418,7 +1419,7 @@ int vqa_se_bwd(int dtype, const void* dout, const void* x, const float* w1, cons
   if (dtype) { if (bn_slab) SE_APPLY(bf16_t, true); else SE_APPLY(bf16_t, false); }
   else { if (bn_slab) SE_APPLY(float, true); else SE_APPLY(float, false); }
 #undef SE_APPLY
-  launch_se_wgrad(dz2, hidden, dh, pooled, dw1, dw2, B, C, Cr, st);
+  if (dw1) launch_se_wgrad(dz2, hidden, dh, pooled, dw1, dw2, B, C, Cr, st);
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
 
@@ -1449,8 +1450,10 @@ int vqa_spatial_bwd(int dtype, const void* dout, const void* x, const float* w, 
   hipLaunchKernelGGL(spatial_bwd_conv_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, dpre, w, dpool2, B, H, W);
   DT(hipLaunchKernelGGL(spatial_bwd_apply_kernel<float>, dim3(px_grid(npix, C, VEC)), dim3(256), 0, st, (const float*)dout, amap, dpool2, amax, (float*)dx, (unsigned)npix, C),
      hipLaunchKernelGGL(spatial_bwd_apply_kernel<bf16_t>, dim3(px_grid(npix, C, VEC)), dim3(256), 0, st, (const bf16_t*)dout, amap, dpool2, amax, (bf16_t*)dx, (unsigned)npix, C));
-  hipLaunchKernelGGL(spatial_wgrad_kernel, dim3(98, SPATIAL_WG_SLICES), dim3(256), 0, st, dpre, pooled2, wpart, B, H, W);
-  hipLaunchKernelGGL(spatial_wgrad_finish_kernel, dim3(1), dim3(128), 0, st, wpart, dw);
+  if (dw) {                                  // NULL: data gradient only (frozen conv weight)
+    hipLaunchKernelGGL(spatial_wgrad_kernel, dim3(98, SPATIAL_WG_SLICES), dim3(256), 0, st, dpre, pooled2, wpart, B, H, W);
+    hipLaunchKernelGGL(spatial_wgrad_finish_kernel, dim3(1), dim3(128), 0, st, wpart, dw);
+  }
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
 

@@ -829,6 +829,105 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
   }
 }
 
+// The same two kernels over a table of TRAINABLE ranges (fine-tuning with frozen parameters, trainer.py): elements outside every
+// range are never read or written.  table: int64 rows {lo, hi, pos, lag index} -- [lo, hi) of the flat buffer, pos = where the range
+// starts in the concatenation of all ranges (ascending); lo, hi, pos multiples of 4 (the layout's 8-element slots), so every float4
+// lies inside one range.  Threads stride over that concatenation: the grid is sized to the trainable count, not to the buffer.
+#define VQA_RANGES_MAX 512
+__device__ __forceinline__ int range_of(const long long* __restrict__ pos, int R, long long e) {
+  int lo = 0, hi = R - 1;                   // the last range whose pos <= e
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (pos[mid] <= e) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+__global__ __launch_bounds__(256) void sumsq_ranges_kernel(const float* __restrict__ g, const long long* __restrict__ table, int R, long long n,
+                                                           float* out) {
+  __shared__ long long s_lo[VQA_RANGES_MAX], s_pos[VQA_RANGES_MAX];
+  for (int r = threadIdx.x; r < R; r += blockDim.x) { s_lo[r] = table[4 * r]; s_pos[r] = table[4 * r + 2]; }
+  __syncthreads();
+  float s = 0.f;
+  const long long nv = n / 4;
+  for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nv; q += (long long)gridDim.x * blockDim.x) {
+    const long long e = 4 * q;
+    const int r = range_of(s_pos, R, e);
+    const float4 v = *reinterpret_cast<const float4*>(g + s_lo[r] + (e - s_pos[r]));
+    s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+  }
+  __shared__ float sh[4];
+  s = wave_sum(s);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) out[1 + blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+// clip + AdamW of adamw_kernel, per range: Adam's step number of range r is calls - skipped[2] - lag[table[r].lag index], where lag[j]
+// counts the applied steps during which parameter j was frozen (torch.optim.AdamW advances a parameter's `step` only when it has a
+// gradient).  Every parameter inside one range shares its lag (the caller merges only such neighbours).
+__global__ __launch_bounds__(256) void adamw_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, const long long* __restrict__ table, int R, long long n,
+                                                           float lr, float b1, float b2, float eps, float wd, long long calls,
+                                                           const float* __restrict__ sumsq, float max_norm, float gscale,
+                                                           const int* __restrict__ skip, int* __restrict__ skipped, const int* __restrict__ lag,
+                                                           bf16_t* __restrict__ p_bf16) {
+  if (skip && *skip != 0) {
+    if (skipped && blockIdx.x == 0 && threadIdx.x == 0) { skipped[0] += *skip; skipped[1] += 1; skipped[2] += 1; }
+    return;
+  }
+  __shared__ long long s_lo[VQA_RANGES_MAX], s_pos[VQA_RANGES_MAX];
+  __shared__ float s_step[VQA_RANGES_MAX], s_rbc2[VQA_RANGES_MAX];
+  const long long t0 = calls - (skipped ? (long long)skipped[2] : 0ll);
+  for (int r = threadIdx.x; r < R; r += blockDim.x) {
+    s_lo[r] = table[4 * r]; s_pos[r] = table[4 * r + 2];
+    const long long t = t0 - (lag ? (long long)lag[table[4 * r + 3]] : 0ll);
+    const float bc1 = (float)(1.0 - pow((double)b1, (double)t)), bc2 = (float)(1.0 - pow((double)b2, (double)t));
+    s_step[r] = lr / bc1; s_rbc2[r] = 1.f / sqrtf(bc2);
+  }
+  __syncthreads();
+  float coef = gscale;
+  if (sumsq && max_norm > 0.f) {
+    const float norm = sqrtf(*sumsq) * gscale;
+    const float c = max_norm / (norm + 1e-6f);
+    if (c < 1.f) coef *= c;
+  }
+  const long long nv = n / 4;
+  for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nv; q += (long long)gridDim.x * blockDim.x) {
+    const long long e = 4 * q;
+    const int r = range_of(s_pos, R, e);
+    const long long i = s_lo[r] + (e - s_pos[r]);
+    const float step = s_step[r], rbc2 = s_rbc2[r];
+    const float4 g4 = *reinterpret_cast<const float4*>(g + i);
+    float4 p4 = *reinterpret_cast<const float4*>(p + i);
+    float4 m4 = *reinterpret_cast<const float4*>(m + i);
+    float4 v4 = *reinterpret_cast<const float4*>(v + i);
+    float* pp = &p4.x; float* mm = &m4.x; float* vv = &v4.x; const float* gg = &g4.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float gr = gg[k] * coef;
+      float pi = pp[k] * (1.f - lr * wd);
+      const float mi = b1 * mm[k] + (1.f - b1) * gr;
+      const float vi = b2 * vv[k] + (1.f - b2) * gr * gr;
+      mm[k] = mi; vv[k] = vi;
+      pi -= step * mi / (sqrtf(vi) * rbc2 + eps);
+      pp[k] = pi;
+    }
+    *reinterpret_cast<float4*>(p + i) = p4;
+    *reinterpret_cast<float4*>(m + i) = m4;
+    *reinterpret_cast<float4*>(v + i) = v4;
+    if (p_bf16) {
+      uint2 w;
+      w.x = (uint32_t)f2bf(p4.x) | ((uint32_t)f2bf(p4.y) << 16);
+      w.y = (uint32_t)f2bf(p4.z) | ((uint32_t)f2bf(p4.w) << 16);
+      *reinterpret_cast<uint2*>(p_bf16 + i) = w;
+    }
+  }
+}
+// after an applied step: lag[frozen[k]] += 1 (one thread per frozen parameter; runs behind adamw_ranges_kernel on the same stream)
+__global__ void adamw_lag_kernel(int* __restrict__ lag, const int* __restrict__ frozen, int nf, const int* __restrict__ skip) {
+  if (skip && *skip != 0) return;
+  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < nf; k += gridDim.x * blockDim.x) lag[frozen[k]] += 1;
+}
+
 // ---------------------------------------------------------------------------------------------
 #define DT(call_f, call_b) do { if (dtype) { call_b; } else { call_f; } } while (0)
 static inline unsigned g1(size_t n) { return (unsigned)((n + 255) / 256); }
@@ -1130,6 +1229,24 @@ int vqa_adamw(float* p, const float* g, float* m, float* v, long long n, float l
   size_t blocks = ((size_t)n + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
   hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, (size_t)n, lr, b1, b2, eps, wd, calls, sumsq, max_norm, gscale,
                      skip, skipped, (bf16_t*)p_bf16);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+
+int vqa_sumsq_ranges(const float* g, const long long* table, int R, long long n, float* out, hipStream_t st) {
+  if (R < 0 || R > VQA_RANGES_MAX || n < 0 || n % 4 || (R == 0 && n != 0)) return VQA_EARG;
+  size_t blocks = ((size_t)n / 4 + 255) / 256; if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(sumsq_ranges_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g, table, R, n, out);
+  hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, st, out, (int)blocks);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+int vqa_adamw_ranges(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n, float lr, float b1, float b2,
+                     float eps, float wd, long long calls, const float* sumsq, float max_norm, float gscale, const int* skip, int* skipped,
+                     int* lag, const int* frozen, int nf, void* p_bf16, hipStream_t st) {
+  if (calls < 1 || R < 0 || R > VQA_RANGES_MAX || n < 0 || n % 4 || (R == 0 && n != 0) || nf < 0 || (nf > 0 && (!lag || !frozen))) return VQA_EARG;
+  size_t blocks = ((size_t)n / 4 + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(adamw_ranges_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, table, R, n, lr, b1, b2, eps, wd, calls, sumsq,
+                     max_norm, gscale, skip, skipped, (const int*)lag, (bf16_t*)p_bf16);
+  if (nf > 0) hipLaunchKernelGGL(adamw_lag_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, lag, frozen, nf, skip);
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
 

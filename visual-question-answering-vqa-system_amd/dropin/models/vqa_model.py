@@ -53,7 +53,8 @@ def _vqa_forward_op(images: torch.Tensor, token_ids: torch.Tensor, mask: Optiona
     # the 164 parameter views as a List[Tensor] cost ~0.6 ms of host time per call before the first kernel went out -- idle GPU time
     # for a caller that synchronises every step (training/train.py:211)
     model = _MODELS[handle]
-    logits, aux, tape = model._engine.forward(images, token_ids, mask, training, want_aux, need_tape=True)
+    plan, model._pending_plan = model._pending_plan, None
+    logits, aux, tape = model._engine.forward(images, token_ids, mask, training, want_aux, need_tape=True, plan=plan)
     model._last_aux = aux              # aux tensors are detached by construction (side channel, not graph outputs)
     model._tape_seq += 1
     model._tapes[model._tape_seq] = tape
@@ -114,7 +115,8 @@ def _(dlogits, handle, tape_id, H, W):
 def _vqa_forward_grouped_op(images: torch.Tensor, token_ids: torch.Tensor, mask: Optional[torch.Tensor], image_index: torch.Tensor,
                             flat_params: torch.Tensor, handle: int, training: bool) -> torch.Tensor:
     model = _MODELS[handle]
-    logits, _, tape = model._engine.forward(images, token_ids, mask, training, False, need_tape=True, kv_index=image_index)
+    plan, model._pending_plan = model._pending_plan, None
+    logits, _, tape = model._engine.forward(images, token_ids, mask, training, False, need_tape=True, kv_index=image_index, plan=plan)
     model._tape_seq += 1
     model._tapes[model._tape_seq] = tape
     while len(model._tapes) > model.max_live_tapes:
@@ -265,7 +267,8 @@ def _final_hw(h):
 def _aux_encoders_op(images: torch.Tensor, token_ids: torch.Tensor, mask: Optional[torch.Tensor], flat_params: torch.Tensor,
                      handle: int, training: bool) -> Tuple[torch.Tensor, torch.Tensor]:
     model = _MODELS[handle]
-    logits, aux, tape = model._engine.forward(images, token_ids, mask, training, True, need_tape=True)
+    plan, model._pending_plan = model._pending_plan, None
+    logits, aux, tape = model._engine.forward(images, token_ids, mask, training, True, need_tape=True, plan=plan)
     hw = (_final_hw(images.shape[2]), _final_hw(images.shape[3]))
     if tuple(aux["image_features"].shape[1:]) != (512,) + hw:              # the fake below derives the same shape from the geometry
         raise RuntimeError(f"image_features {tuple(aux['image_features'].shape)} disagrees with the stem / stage geometry {hw}")
@@ -487,6 +490,8 @@ class VQAModel(nn.Module):
         self._engine = None
         self._infer_precision = "bf16"             # residual-block convs of the eval (Conv+BN folded) path: set_inference_precision
         self._on_segment = None
+        self._pending_plan = None                   # fine-tuning plan handed to the next custom-op forward (finetune.Plan)
+        self._plan_cache: Dict[str, Any] = {}
         self._last_aux = None
         self._tapes: Dict[int, Any] = {}
         self._graphs: Dict[Any, Any] = {}           # captured inference graphs, one per input shape (forward_graphed)
@@ -511,6 +516,38 @@ class VQAModel(nn.Module):
             pl = [getattr_path(self, e.name) for e in self._param_entries]
             self.__dict__["_params_cache"] = pl
         return pl
+
+    def _part_modes(self):
+        """(image_encoder, text_encoder, fusion, answer_head) modes; NotImplementedError for a submodule whose mode differs from its
+        part's.  The module lists are cached: one attribute read per module on each call."""
+        mods = self.__dict__.get("_part_mods")
+        if mods is None:
+            mods = [(name, [(n, m) for n, m in getattr(self, name).named_modules(prefix=name)]) for name in self._pkg.finetune.PARTS]
+            self.__dict__["_part_mods"] = mods
+        out = []
+        for name, ms in mods:
+            mode = ms[0][1].training
+            for _, m in ms:
+                if m.training != mode:
+                    return self._pkg.finetune.part_modes(self)       # (raises, naming the module)
+            out.append(mode)
+        return tuple(out)
+
+    def _finetune_plan(self, params, images_grad: bool, training: bool):
+        """Fine-tuning plan of this forward (finetune.Plan), or None for the plain route: every parameter trains and every part runs
+        in mode `training`."""
+        modes = self._part_modes()
+        if modes != (training,) * 4 and len(set(modes)) == 1:
+            modes = (training,) * 4                  # (HipTrainer: the caller's mode when the parts agree)
+        return self._pkg.finetune.resolve(self._param_entries, params, modes, images_grad, self._plan_cache)
+
+    def _modes_plan(self, modes=None, taped=False):
+        """A plan that only sets the part modes (everything computed): for forwards without a tape, and the aux graph ops.  None when
+        the parts agree."""
+        modes = self._part_modes() if modes is None else modes
+        if len(set(modes)) == 1:
+            return None
+        return self._pkg.finetune.Plan(self._param_entries, (True,) * len(self._param_entries), modes, taped)
 
     def __del__(self):
         _MODELS.pop(getattr(self, "_handle", -1), None)
@@ -602,8 +639,12 @@ class VQAModel(nn.Module):
                 flat = _FlatParams.apply(self._flat, self._handle, *params)
             else:
                 flat = self._flat
+            # fine-tuning (frozen parameters, parts in different modes): the engine prunes what nothing needs (finetune.Plan)
+            plan = self._finetune_plan(params, images.requires_grad, self.training)
             if return_aux:                   # aux tensors on the autograd graph (three chained ops, see vqa_aux_encoders above)
+                self._pending_plan = None if plan is None else self._modes_plan(plan.modes, True)     # part modes only: nothing pruned
                 return self._forward_aux_graph(images, token_ids, maskf, flat)
+            self._pending_plan = plan
             logits = torch.ops.vqa_hip.vqa_forward(images, token_ids, maskf, flat, self._handle, self.training, return_aux)
             aux, self._last_aux = self._last_aux, None
         elif (self.graph_inference and not self.training and not return_aux and 0 < images.shape[0] <= self.graph_max_batch
@@ -613,7 +654,7 @@ class VQAModel(nn.Module):
             # logits); the result is copied out of the graph's static buffer so callers own what they get, like the reference
             logits, aux = self.forward_graphed(images, token_ids, attention_mask).clone(), None
         else:
-            logits, aux, _ = eng.forward(images, token_ids, maskf, self.training, return_aux, need_tape=False)
+            logits, aux, _ = eng.forward(images, token_ids, maskf, self.training, return_aux, need_tape=False, plan=self._modes_plan())
         return (logits, aux) if return_aux else (logits, None)
 
     def _forward_aux_graph(self, images, token_ids, maskf, flat):
@@ -792,9 +833,11 @@ class VQAModel(nn.Module):
             idx = self._implied_index(U, N, images.device)
         if recording:
             flat = _FlatParams.apply(self._flat, self._handle, *params) if any(p.requires_grad for p in params) else self._flat
+            self._pending_plan = self._finetune_plan(params, images.requires_grad, self.training)
             logits = torch.ops.vqa_hip.vqa_forward_grouped(images, token_ids, maskf, idx, flat, self._handle, self.training)
             return logits, None
-        logits, aux, _ = eng.forward(images, token_ids, maskf, self.training, return_aux, need_tape=False, kv_index=idx)
+        logits, aux, _ = eng.forward(images, token_ids, maskf, self.training, return_aux, need_tape=False, kv_index=idx,
+                                     plan=self._modes_plan())
         return (logits, aux) if return_aux else (logits, None)
 
     def encode_images(self, images: torch.Tensor) -> ImageContext:

@@ -87,6 +87,8 @@ class HipEngine:
         self._wgq = []
         self._foldq = []                          # deferred folds of the LayerNorm / bias parameter gradients (K.fold_group at segment end)
         self._foldq2 = []
+        self._plan = None                         # fine-tuning plan of the backward in flight (finetune.Plan), and its gradient buffer
+        self._bwd_G = None
         self.fuse_act_dgrad = True                # ReLU(+dropout) backward of a Linear -> ReLU -> Dropout -> Linear pair applied by the data-gradient GEMM's epilogue; the bias column sums leave the chain
         self.fuse_se_pool = True                  # SE global-average-pool sums leave the last block's bn_apply (one read of the stage output less)
         self.fuse_se_bnred = True                 # the last block's bn2-backward column sums leave the SE backward apply pass (ditto)
@@ -405,6 +407,8 @@ class HipEngine:
     #      workgroup, latency-bound launch on its own.  The queue is flushed on the stream that produced its operands (when it is
     #      full, before a gradient segment is reported, before the stream context changes) and holds references to dz / x until then.
     def _wgrad_linear(self, dz, x_in, dw, M, N, Kin):
+        if self._frozen_g(dw):
+            return
         if K.wgrad_group_ok(self.dtype, M, N, Kin):
             self._wgq.append((dz, x_in, dw, M, N, Kin))
             if len(self._wgq) == 8:
@@ -444,9 +448,10 @@ class HipEngine:
             Np = (N + 7) // 8 * 8
             dzp = torch.zeros((M, Np), device=dz.device, dtype=self.dtype)
             dzp[:, :N] = dz
-            dwp = torch.zeros((Np, Kin), device=dz.device, dtype=torch.float32)
-            K.wgrad(dzp, x_in, dwp, M, Np, Kin, K.linear_geom(M, Kin), dtype=self.dtype)
-            LY.mat_of(G, e).add_(dwp[:N])
+            if not self._frozen_g(LY.mat_of(G, e)):
+                dwp = torch.zeros((Np, Kin), device=dz.device, dtype=torch.float32)
+                K.wgrad(dzp, x_in, dwp, M, Np, Kin, K.linear_geom(M, Kin), dtype=self.dtype)
+                LY.mat_of(G, e).add_(dwp[:N])
             if not need_dx:
                 return None
             wp = torch.zeros((Np, 1, Kin), device=dz.device, dtype=torch.float32)
@@ -468,6 +473,8 @@ class HipEngine:
         if bname:
             e = self.E[bname]
             dbias = G[e.offset: e.offset + e.numel]
+            if self._frozen_g(dbias):
+                dbias = None
         if need_dz or dbias is not None:
             def launch():
                 ws = None
@@ -535,8 +542,12 @@ class HipEngine:
     # ------------------------------------------------------------------ forward
     def forward(self, images: torch.Tensor, token_ids: torch.Tensor, maskf: Optional[torch.Tensor], training: bool,
                 want_aux: bool = False, need_tape: bool = True, lowp_logits: bool = False, record: Optional[dict] = None,
-                kv_index: Optional[torch.Tensor] = None):
-        """lowp_logits: return the logits in the compute dtype (the trainer's loss kernel reads bf16 and leaves the fp32 copy itself).
+                kv_index: Optional[torch.Tensor] = None, plan=None):
+        """plan (fine-tuning with frozen parts, finetune.Plan; None: every part in mode `training`, everything taped): BatchNorm
+        and dropout follow each part's own mode, and a CNN with nothing to train and no image gradient runs without a tape -- the
+        Conv+BN-folded eval route in eval mode, the training forward (running statistics updated) without kept activations in train
+        mode.  The backward of such a tape prunes what nothing needs (see _plan_of).
+        lowp_logits: return the logits in the compute dtype (the trainer's loss kernel reads bf16 and leaves the fp32 copy itself).
         record: a dict that receives {residual block prefix: (input, output)} of the folded eval path, and under "mxfp8" also
         {prefix + ".a1": MXFP8 a1 (codes, scales)} (tests).
         kv_index (many questions per image, training included): int32 [N] on the device, every entry in [0, U) (the caller checks);
@@ -545,15 +556,25 @@ class HipEngine:
         backward, whose image-token gradient is then summed per image by vqa_attention_bwd(_mfma)_idx."""
         cfg, T = self.cfg, self.dtype
         self._site = 0
-        if training:
+        if plan is not None:
+            ctrain, ttrain, ftrain, htrain = plan.modes
+            cnn_tape = need_tape and plan.cnn_tape
+        else:
+            ctrain = ttrain = ftrain = htrain = training
+            cnn_tape = need_tape
+        if ctrain or ttrain or ftrain or htrain:
             self.step_id += 1
         self.begin_step(for_backward=need_tape)
-        if training and self.fuse_bn_finalize and T == torch.bfloat16:
+        if ctrain and self.fuse_bn_finalize and T == torch.bfloat16:
             self._acc_reset()                     # one memset for every BatchNorm accumulator of this forward
-        tape: dict = {"training": training, "B": images.shape[0], "Bq": token_ids.shape[0]}     # image rows, question rows
+        tape: dict = {"training": ctrain, "B": images.shape[0], "Bq": token_ids.shape[0]}     # image rows, question rows
+        if plan is not None and need_tape:
+            tape["plan"] = plan
+        training = ctrain                         # from here on `training` is the CNN's mode (BatchNorm)
         B, _, IH, IW = images.shape
-        pdrop = cfg["dropout"] if training else 0.0
-        phead = cfg["answer_dropout"] if training else 0.0
+        pdrop = cfg["dropout"] if ttrain else 0.0          # text encoder
+        pfus = cfg["dropout"] if ftrain else 0.0           # projector and cross-attention layers
+        phead = cfg["answer_dropout"] if htrain else 0.0
         dev = images.device
 
         # The stem's three launches go out FIRST (0.6 ms of GPU work): a caller that synchronises every step (training/train.py:211
@@ -569,7 +590,7 @@ class HipEngine:
         sgeom = (B, IH, IW, 3, H1, W1, 7, 7, 2, 3)
         Hp, Wp = (H1 + 2 - 3) // 2 + 1, (W1 + 2 - 3) // 2 + 1
         x = None
-        if self.fuse_stem_eval and not training and not need_tape and self.stem_w2 is not None:
+        if self.fuse_stem_eval and not training and not cnn_tape and self.stem_w2 is not None:
             # inference: the whole stem in one launch, the 112 x 112 conv output is never stored (no argmax: there is no backward)
             x = K.stem_conv_pool(images, self.stem_w2, self._bn_coef("image_encoder.stem.1", None, 0, 64, M, False), B, IH, IW)
         if x is None:
@@ -581,7 +602,8 @@ class HipEngine:
             x = torch.empty((B * Hp * Wp, 64), device=dev, dtype=T)
             idx = torch.empty((B * Hp * Wp, 64), device=dev, dtype=torch.uint8)
             call("vqa_stem_pool_fwd", dt(T), ptr(y), ptr(coef), ptr(x), ptr(idx), B, H1, W1, 64)
-            tape["stem"] = dict(images=images, y=y, coef=coef, idx=idx, geom=sgeom, H1=H1, W1=W1)
+            if cnn_tape:
+                tape["stem"] = dict(images=images, y=y, coef=coef, idx=idx, geom=sgeom, H1=H1, W1=W1)
         H, W, C = Hp, Wp, 64
         # ---- text encoder, A6-A8 (on the side stream; joined before fusion).  Issued behind stage 1: by then the GPU holds > 1 ms of
         #      queued work, which covers the millisecond the host spends on these ~100 launches (see the stem note above).
@@ -631,7 +653,7 @@ class HipEngine:
         if self.mark: self.mark("forward: stem")
 
         # ---- residual stages, A2-A5
-        folded = self._fold_bn() if (self.fold_eval and not training and not need_tape) else None
+        folded = self._fold_bn() if (self.fold_eval and not training and not cnn_tape) else None
         foldmx, xq = None, None                   # MXFP8 folded weights; MXFP8 copy of the current block input (if one exists)
         if folded is not None and self.infer_precision == "mxfp8":
             if T != torch.bfloat16:
@@ -679,7 +701,7 @@ class HipEngine:
                 facc = training and self.fuse_bn_finalize and T == torch.bfloat16
                 y1, st1, mt1, g1, Ho, Wo = self._conv(x, B, H, W, Cin, p + ".conv1.weight", Cout, 3, stride, 1, training, acc=facc)
                 M = B * Ho * Wo
-                fuse12 = (mt1 < 0 and self.fuse_bn_conv and need_tape and self._c64p_ok(B, Ho, Wo, Cout, Cout, 3, 1)
+                fuse12 = (mt1 < 0 and self.fuse_bn_conv and cnn_tape and self._c64p_ok(B, Ho, Wo, Cout, Cout, 3, 1)
                           and K.c64w_bn_ok(B, Ho, Wo))
                 if fuse12:                                   # conv2 normalises conv1's raw output in its LDS patch: a1 never exists
                     a1 = None
@@ -747,7 +769,8 @@ class HipEngine:
                      ptr(amap), ptr(out), B, H, W, C)
                 srec["spatial"] = dict(x=x, pooled2=pooled2, amax=amax, amap=amap, H=H, W=W, C=C)
                 x = out
-            tape["stages"].append(srec)
+            if cnn_tape:                          # (without a tape the stage's activations are freed as the next stage runs)
+                tape["stages"].append(srec)
             if s == 1:
                 issue_text()
             if self.mark: self.mark(f"forward: stage{s}")
@@ -766,8 +789,8 @@ class HipEngine:
         posemb = self.P("fusion.image_projector.position_embedding")
         if ntok * d > posemb.numel():            # the reference fails the same way (broadcast error at models/fusion.py:110)
             raise RuntimeError(f"{ntok} image tokens but position_embedding holds {posemb.numel() // d} (num_image_tokens)")
-        img, img_st = self._ln(pz, pj + ".1", p=pdrop, seed=sdp, addrow=posemb, period=ntok)
-        tape["proj"] = dict(feat=feat, pz=pz, st=img_st, seed=sdp, p=pdrop, ntok=ntok)
+        img, img_st = self._ln(pz, pj + ".1", p=pfus, seed=sdp, addrow=posemb, period=ntok)
+        tape["proj"] = dict(feat=feat, pz=pz, st=img_st, seed=sdp, p=pfus, ntok=ntok)
         q = enc
         tape["clayers"] = []
         probs_all = []
@@ -793,7 +816,7 @@ class HipEngine:
                 pkv, ev_kv = pre_kv[l]
                 main.wait_event(ev_kv)
             rec = self._attn_block_fwd(q, img, None, p + ".norm_query", p + ".norm_kv", p + ".cross_attention", None, Bt, L, ntok,
-                                       heads, hd, pdrop, p + ".norm_ffn", p + ".ffn.0", p + ".ffn.3", self_attn=False,
+                                       heads, hd, pfus, p + ".norm_ffn", p + ".ffn.0", p + ".ffn.3", self_attn=False,
                                        pre_q=text.get("q0") if l == 0 else None, pre_kv=pkv, probs=None if caw is None else caw[l],
                                        csr=csr)
             tape["clayers"].append(rec)
@@ -1208,12 +1231,32 @@ class HipEngine:
         fusion, encoders) run back to back without joining their side streams in between.  want_input_grad: also return the
         gradient with respect to the images (fp32 NCHW [B][3][H][W], complete on the current stream); None otherwise."""
         self._bwd_begin()
-        seg = self._seg_fn(on_segment)
-        dfused = self._head_bwd(tape, dlogits, G, seg)
-        dfeat, denc = self._fusion_bwd(tape, dfused, G, seg)
-        ev_tb, dimg = self._encoders_bwd(tape, dfeat, denc, G, seg, want_input_grad=want_input_grad)
-        self._bwd_join(ev_tb)
+        plan = tape.get("plan")
+        if plan is not None and want_input_grad and not plan.images_grad:
+            raise RuntimeError("backward: an image gradient was asked of a forward planned without one")
+        self._plan, self._bwd_G = plan, G
+        try:
+            seg = self._seg_fn(on_segment)
+            dfused = self._head_bwd(tape, dlogits, G, seg)
+            if plan is not None and not plan.fusion_bwd:      # nothing below the head trains: the other segments are reported as is
+                for name in ("fusion", "text_encoder") + tuple(f"image_encoder.stage{s}" for s in (4, 3, 2, 1)) + ("image_encoder.stem",):
+                    seg(name)
+                ev_tb, dimg = None, None
+            else:
+                dfeat, denc = self._fusion_bwd(tape, dfused, G, seg)
+                ev_tb, dimg = self._encoders_bwd(tape, dfeat, denc, G, seg, want_input_grad=want_input_grad)
+            self._bwd_join(ev_tb)
+        finally:
+            self._plan, self._bwd_G = None, None
         return dimg
+
+    def _frozen_g(self, t):
+        """True when the gradient slice t (of the current backward's flat buffer) belongs to frozen parameters only: its weight-gradient
+        launch is skipped (finetune.Plan; the plain route has no plan and skips nothing)."""
+        pl = self._plan
+        if pl is None:
+            return False
+        return pl.frozen((t.data_ptr() - self._bwd_G.data_ptr()) // 4, t.numel())
 
     # The same backward in three separately callable parts, split where it reports its segments (graph-connected aux outputs:
     # dropin/models/vqa_model.py).  Each part joins its side streams, flushes its weight-gradient / fold queues, releases the tensors
@@ -1316,7 +1359,8 @@ class HipEngine:
         if self.capture_io is not None:
             self.capture_io["answer_head"] = dict(dlogits=dl, dz3=dz)
         dz = self._lin_act_bwd(dz, hdr["h1"], c + ".3.weight", c + ".0.bias", G, hdr["p"])
-        dfused = self._lin_bwd(dz, hdr["fused"], c + ".0.weight", G)
+        pl = self._plan
+        dfused = self._lin_bwd(dz, hdr["fused"], c + ".0.weight", G, need_dx=pl is None or pl.need_dfused)
         if self.capture_io is not None:
             self.capture_io["answer_head"].update(dz0=dz, dfused=dfused)
         seg("answer_head")
@@ -1390,7 +1434,8 @@ class HipEngine:
         dpos = self._gslice(G, "fusion.image_projector.position_embedding")
         dpz = self._ln_bwd(dimg, rp["pz"], pj + ".1", rp["st"], G, p=rp["p"], seed=rp["seed"], dadd=dpos, period=rp["ntok"])
         dpz = self._act_bwd(dpz, None, pj + ".0.bias", G, 0.0, 0)
-        dfeat = self._lin_bwd(dpz, rp["feat"], pj + ".0.weight", G)
+        pl = self._plan
+        dfeat = self._lin_bwd(dpz, rp["feat"], pj + ".0.weight", G, need_dx=pl is None or pl.need_dfeat)
         if self.capture_io is not None:
             self.capture_io["fusion.image_projector"] = dict(dimg=dimg, dpz=dpz, dfeat=dfeat)
             self.capture_io["fusion"]["denc"] = denc
@@ -1409,6 +1454,9 @@ class HipEngine:
         ntok, Cf = ft["Hf"] * ft["Wf"], ft["Cf"]
         dev = self.flat.device
         rows = tape["embed"]["ids"].numel()
+        pl = self._plan
+        if pl is not None:                        # fine-tuning: the parts nothing needs are reported without running
+            return self._encoders_bwd_planned(tape, dfeat, denc, G, seg, pl, want_input_grad)
         for name, t, shape in (("dfeat", dfeat, (B * ntok, Cf)), ("denc", denc, (rows, d))):
             if t is not None and (tuple(t.shape) != shape or t.dtype != T):
                 raise RuntimeError(f"{name}: expected {shape} in {T}, got {tuple(t.shape)} in {t.dtype}")
@@ -1420,7 +1468,30 @@ class HipEngine:
             self._tap(taps["image_features"], dfeat, B * ntok, Cf, ntok, layout=1)
         if taps.get("text_features") is not None:
             self._tap(taps["text_features"], denc, denc.shape[0], d, d)
-        # ---- text encoder backward on the side stream, concurrently with the CNN backward below
+        ev_tb = self._text_bwd(tape, denc, G, seg)
+        dimg = self._cnn_bwd(tape, dfeat, G, seg, 0, want_input_grad)
+        return ev_tb, dimg
+
+    def _encoders_bwd_planned(self, tape, dfeat, denc, G, seg, pl, want_input_grad):
+        """_encoders_bwd under a fine-tuning plan: the text encoder's backward only when one of its parameters trains, the CNN's
+        down to the lowest level that needs a gradient (finetune.Plan.cnn_low); every segment is still reported, in the usual order."""
+        ev_tb = None
+        if pl.text:
+            ev_tb = self._text_bwd(tape, denc.contiguous(), G, seg)
+        else:
+            seg("text_encoder")
+        dimg = None
+        if pl.cnn_low is not None:
+            dimg = self._cnn_bwd(tape, dfeat.contiguous(), G, seg, pl.cnn_low, want_input_grad)
+        else:
+            for s in (4, 3, 2, 1):
+                seg(f"image_encoder.stage{s}")
+            seg("image_encoder.stem")
+        return ev_tb, dimg
+
+    def _text_bwd(self, tape, denc, G, seg):
+        """Text encoder backward on the side stream, concurrently with the CNN backward; returns the side stream's event (or None)."""
+        T, d = self.dtype, self.cfg["embed_dim"]
         main = torch.cuda.current_stream()
         use_side = self.two_streams and self.side is not None
         if use_side:
@@ -1433,11 +1504,18 @@ class HipEngine:
             for rec in reversed(tape["tlayers"]):
                 dx, _, _ = self._attn_block_bwd(rec, dx, G)
             em = tape["embed"]; emb_e = self.E["text_encoder.token_embedding.weight"]
-            call("vqa_embed_bwd", dt(T), ptr(em["ids"]), ptr(dx), ptr(self._gslice(G, emb_e.name)), dx.shape[0], d, emb_e.shape[0],
-                 math.sqrt(d), float(em["p"]), em["seed"])
+            if not self._frozen_g(self._gslice(G, emb_e.name)):
+                call("vqa_embed_bwd", dt(T), ptr(em["ids"]), ptr(dx), ptr(self._gslice(G, emb_e.name)), dx.shape[0], d, emb_e.shape[0],
+                     math.sqrt(d), float(em["p"]), em["seed"])
             seg("text_encoder")
             ev_tb = torch.cuda.Event(); ev_tb.record()
+        return ev_tb if use_side else None
 
+    def _cnn_bwd(self, tape, dfeat, G, seg, low, want_input_grad):
+        """CNN stages (reverse) down to stage `low` (0: and the stem); returns the image gradient or None."""
+        T = self.dtype
+        training = tape["training"]
+        B = tape["B"]
         # ---- CNN stages (reverse)
         bwd_acc = training and self.fuse_bn_finalize and T == torch.bfloat16
         self._bwd_acc = bwd_acc
@@ -1446,6 +1524,8 @@ class HipEngine:
         dxc = dfeat
         masked = False           # True: dxc already carries the ReLU mask of the block that consumes it (see _block_bwd)
         for s in (4, 3, 2, 1):
+            if s < low:                           # (fine-tuning: nothing below stage `low` needs a gradient)
+                break
             srec = tape["stages"][s - 1]
             ap = f"image_encoder.stage{s}.attention"
             if "spatial" in srec:
@@ -1453,8 +1533,9 @@ class HipEngine:
                 npix = B * r["H"] * r["W"]
                 scratch = torch.empty((K.L.count("vqa_spatial_bwd_scratch", B, r["H"], r["W"]),), device=dxc.device, dtype=torch.float32)
                 dxn = torch.empty_like(r["x"])
+                dws = self._gslice(G, ap + ".spatial.conv.weight")
                 call("vqa_spatial_bwd", dt(T), ptr(dxc), ptr(r["x"]), ptr(self.P(ap + ".spatial.conv.weight")), ptr(r["pooled2"]),
-                     ptr(r["amax"]), ptr(r["amap"]), ptr(scratch), ptr(dxn), ptr(self._gslice(G, ap + ".spatial.conv.weight")),
+                     ptr(r["amax"]), ptr(r["amap"]), ptr(scratch), ptr(dxn), None if self._frozen_g(dws) else ptr(dws),
                      B, r["H"], r["W"], r["C"])
                 if self.capture_io is not None:
                     self.capture_io[ap + ".spatial"] = dict(dout=dxc, dx=dxn)
@@ -1472,9 +1553,12 @@ class HipEngine:
                         se_pre = (self._acc(K.L.count("vqa_bn_acc_words", 3, r["C"])), -1)      # fixed-point accumulator: the block's apply pass finalizes it
                     elif nblk > 0:
                         se_pre = (torch.empty((nblk, 3, r["C"]), device=dxc.device, dtype=torch.float32), nblk)
+                dw1, dw2 = self._gslice(G, ap + ".se.fc1.weight"), self._gslice(G, ap + ".se.fc2.weight")
+                if self._frozen_g(dw1) and self._frozen_g(dw2):
+                    dw1 = dw2 = None              # data gradient only
                 call("vqa_se_bwd", dt(T), ptr(dxc), ptr(r["x"]), ptr(self.P(ap + ".se.fc1.weight")), ptr(self.P(ap + ".se.fc2.weight")),
                      ptr(r["pooled"]), ptr(r["hidden"]), ptr(r["scale"]), ptr(scratch), ptr(dxn),
-                     ptr(self._gslice(G, ap + ".se.fc1.weight")), ptr(self._gslice(G, ap + ".se.fc2.weight")), B, r["HW"], r["C"], r["Cr"], 1,
+                     ptr(dw1), ptr(dw2), B, r["HW"], r["C"], r["Cr"], 1,
                      ptr(lastb["y2"]) if se_pre else None, ptr(lastb["c2"]) if se_pre else None, ptr(se_pre[0]) if se_pre else None,
                      int(bool(se_pre) and se_pre[1] < 0))
                 if self.capture_io is not None:
@@ -1495,13 +1579,19 @@ class HipEngine:
             if not self._deferred:                # stage 1: its held-back weight gradients are released below, report it there
                 seg(f"image_encoder.stage{s}")
 
+        if low > 0:                               # (fine-tuning) the chain ends at stage `low`: the levels below are reported as is
+            self._flush_deferred_and_report(seg)
+            for s in range(low - 1, 0, -1):
+                seg(f"image_encoder.stage{s}")
+            seg("image_encoder.stem")
+            return None
         # ---- stem
         if self.capture_io is not None:
             self.capture_io["image_encoder.stem"] = dict(dxc=dxc)
         dimg = self._stem_bwd(tape, dxc, G, training, after_reduce=lambda: (self._flush_deferred_and_report(seg)),
                               want_dimg=want_input_grad)
         seg("image_encoder.stem")
-        return (ev_tb if use_side else None), dimg
+        return dimg
 
     def _flush_deferred_and_report(self, seg):
         had_deferred = bool(self._deferred)
@@ -1546,7 +1636,10 @@ class HipEngine:
         # a backward without input gradients)
         wpk = K.stem_dgrad_pack(self.P("image_encoder.stem.0.weight"), T) if want_dimg else None
         dimg = None
-        if fused:
+        skip_w = self._frozen_g(self._gslice(G, "image_encoder.stem.0.weight"))
+        if fused and skip_w:
+            pass                                  # (fine-tuning: the stem conv is frozen -- only the image gradient below)
+        elif fused:
             # dy (B x 112 x 112 x 64) is never written: the weight-gradient kernel rebuilds it row by row
             dwv = self._gslice(G, "image_encoder.stem.0.weight")
             e0 = K.prof_begin()
@@ -1556,6 +1649,7 @@ class HipEngine:
             if e0 is not None:
                 K.prof_end(e0, "stem_wgrad_kernel<true>", 2.0 * B * H1 * W1 * 64 * 147,
                            B * 3 * IH * IW * 4 + B * H1 * W1 * 64 * 2 + dxc.numel() * 3)
+        if fused:
             if want_dimg:
                 if K.stem_dgrad_fused_ok(B, IH, IW):
                     dimg = K.stem_dgrad_fused(st["y"], dxc, st["idx"], st["coef"], bc, wpk, B, IH, IW)
@@ -1566,8 +1660,9 @@ class HipEngine:
         else:
             dy = torch.empty_like(st["y"])
             call("vqa_stem_bwd_apply", dt(T), ptr(dxc), ptr(st["idx"]), ptr(st["y"]), ptr(st["coef"]), ptr(bc), ptr(dy), B, H1, W1, 64)
-            K.wgrad(dy, st["images"], LY.mat_of(G, self.E["image_encoder.stem.0.weight"]), B * H1 * W1, 64, 147, st["geom"], dtype=T,
-                    loader=K.LOADER_STEM)
+            if not skip_w:
+                K.wgrad(dy, st["images"], LY.mat_of(G, self.E["image_encoder.stem.0.weight"]), B * H1 * W1, 64, 147, st["geom"], dtype=T,
+                        loader=K.LOADER_STEM)
             if want_dimg:
                 dimg = K.stem_dgrad(dy, wpk, B, IH, IW)
         return dimg
@@ -1587,6 +1682,9 @@ class HipEngine:
         out_act = None if masked else rec["out"]
         bacc = getattr(self, "_bwd_acc", False)
         pre_acc = pre is not None and pre[1] < 0             # the SE backward already filled a fixed-point accumulator for bn2
+        # fine-tuning: the weight gradient of a frozen conv is not launched
+        tw1, tw2 = (not self._frozen_g(gs(p + ".conv1.weight"))), (not self._frozen_g(gs(p + ".conv2.weight")))
+        twd = has_ds and not self._frozen_g(gs(p + ".downsample.0.weight"))
         dy2, dyd = K.bn_bwd(dout, out_act, rec["y2"], rec["c2"], self.P(p + ".bn2.weight"), Cout, training,
                             gs(p + ".bn2.weight"), gs(p + ".bn2.bias"),
                             y2=rec.get("yd"), coef2=rec.get("cd"),
@@ -1596,7 +1694,9 @@ class HipEngine:
                             slab=pre[0] if (pre and not pre_acc) else None, nb=pre[1] if (pre and not pre_acc) else 0,
                             facc=(pre[0] if pre_acc else (self._acc(K.L.count("vqa_bn_acc_words", 3, Cout)) if bacc else None)), facc_filled=pre_acc)
         g2 = rec["g2"]; B, Ho, Wo = g2[0], g2[1], g2[2]
-        if rec["a1"] is None:                                 # conv2 ran on relu(bn1(y1)) built in LDS (fuse_bn_conv): so does its weight gradient
+        if not tw2:
+            pass
+        elif rec["a1"] is None:                               # conv2 ran on relu(bn1(y1)) built in LDS (fuse_bn_conv): so does its weight gradient
             self._off_path([dy2], lambda: K.wgrad3x3_c64_bn(rec["y1"], rec["c1"], dy2, LY.mat_of(G, self.E[p + ".conv2.weight"]), B, Ho, Wo), defer=last)
         elif self._c64w_ok(B, Ho, Wo, Cout, Cout, 3, 1):
             self._off_path([dy2], lambda: K.wgrad3x3_c64(rec["a1"], dy2, LY.mat_of(G, self.E[p + ".conv2.weight"]), B, Ho, Wo), defer=last)
@@ -1623,7 +1723,9 @@ class HipEngine:
                           facc=facc1 if facc1 is not None else (self._acc(K.L.count("vqa_bn_acc_words", 3, Cout)) if bacc else None),
                           facc_filled=facc1 is not None)
         g1 = rec["g1"]; H, W, stride = g1[1], g1[2], g1[8]
-        if self._c64w_ok(B, H, W, Cin, Cout, 3, stride):
+        if not tw1:
+            pass
+        elif self._c64w_ok(B, H, W, Cin, Cout, 3, stride):
             self._off_path([dy1], lambda: K.wgrad3x3_c64(rec["x"], dy1, LY.mat_of(G, self.E[p + ".conv1.weight"]), B, H, W), defer=last)
         elif self._c128w_ok(B, H, W, Cin, Cout, stride):
             self._off_path([dy1], lambda: K.wgrad3x3_c128(rec["x"], dy1, LY.mat_of(G, self.E[p + ".conv1.weight"]), B, H, W))
@@ -1633,7 +1735,8 @@ class HipEngine:
         geom_d1 = (B, Ho, Wo, Cout, H, W, 3, 3, stride, 1)
         if has_ds:
             gd = rec["gd"]
-            self._off_path([dyd], lambda: K.wgrad(dyd, rec["x"], LY.mat_of(G, self.E[p + ".downsample.0.weight"]), M, Cout, Cin, gd, dtype=T))
+            if twd:
+                self._off_path([dyd], lambda: K.wgrad(dyd, rec["x"], LY.mat_of(G, self.E[p + ".downsample.0.weight"]), M, Cout, Cin, gd, dtype=T))
             if stride == 2 and H % 2 == 0 and W % 2 == 0:
                 # conv1 (3x3/2) and shortcut (1x1/2) data gradients in ONE launch over parity classes: no redundant taps
                 wt = self._packT(p + ".dgrad2", [(self.E[p + ".conv1.weight"].offset, Cout, 9, Cin, 0, False),

@@ -1,0 +1,147 @@
+"""Fine-tuning with frozen parts: which parameters train, which mode each part runs in, and what the backward may skip.
+
+Pure host logic (no GPU): the drop-in model resolves a `Plan` from `requires_grad` and the `.training` flags of its parts, the engine
+reads it on the forward (BatchNorm / dropout per part, whether the CNN keeps a tape) and on the backward (which weight gradients and
+which part of the data-gradient chain run), and HipTrainer turns the trainable set into a device table of ranges for the optimizer.
+"""
+from __future__ import annotations
+
+from bisect import bisect_right
+from typing import Dict, List, Optional, Sequence, Tuple
+
+from . import layout as LY
+
+# the four top-level parts whose mode is read (VQAModel's children in the reference module tree)
+PARTS = ("image_encoder", "text_encoder", "fusion", "answer_head")
+STAGES = (1, 2, 3, 4)
+
+
+def part_modes(model) -> Tuple[bool, bool, bool, bool]:
+    """`.training` of image_encoder, text_encoder, fusion and answer_head.  A submodule whose mode differs from its part's
+    (model.image_encoder.stage3.eval() alone) raises NotImplementedError naming it: the engine runs one mode per part."""
+    modes = []
+    for name in PARTS:
+        part = getattr(model, name)
+        mode = part.training
+        for sub, mod in part.named_modules(prefix=name):
+            if mod.training != mode:
+                raise NotImplementedError(f"{sub} is in {'train' if mod.training else 'eval'} mode but {name} is in "
+                                          f"{'train' if mode else 'eval'} mode: the HIP engine runs one mode per part "
+                                          f"({', '.join(PARTS)}); set the whole part with {name}.train() / .eval()")
+        modes.append(mode)
+    return tuple(modes)
+
+
+def slot_end(e: LY.Entry) -> int:
+    return e.offset + (e.numel + LY.ALIGN - 1) // LY.ALIGN * LY.ALIGN
+
+
+def trainable_ranges(param_entries: Sequence[LY.Entry], trainable: Sequence[bool],
+                     lag_class: Optional[Sequence[int]] = None) -> List[Tuple[int, int, int]]:
+    """[(lo, hi, first parameter index)] over the parameters' 8-element slots: adjacent trainable parameters merged, except where
+    their lag classes differ (parameters frozen during different steps have different Adam step counts)."""
+    out: List[List[int]] = []
+    prev = None
+    for j, (e, t) in enumerate(zip(param_entries, trainable)):
+        if not t:
+            prev = None
+            continue
+        cls = 0 if lag_class is None else lag_class[j]
+        if prev is not None and out and out[-1][1] == e.offset and prev == cls:
+            out[-1][1] = slot_end(e)
+        else:
+            out.append([e.offset, slot_end(e), j])
+        prev = cls
+    return [tuple(r) for r in out]
+
+
+def range_table_rows(ranges: Sequence[Tuple[int, int, int]]) -> List[List[int]]:
+    """Rows {lo, hi, pos, lag index} of vqa_sumsq_ranges / vqa_adamw_ranges; pos = start of the range in their concatenation."""
+    rows, pos = [], 0
+    for lo, hi, j in ranges:
+        rows.append([lo, hi, pos, j])
+        pos += hi - lo
+    return rows
+
+
+def refine_classes(classes: Sequence[int], trainable: Sequence[bool]) -> List[int]:
+    """Split every lag class by this step's trainable bit (parameters in one class were frozen during exactly the same steps)."""
+    ids: Dict[Tuple[int, bool], int] = {}
+    return [ids.setdefault((c, bool(t)), len(ids)) for c, t in zip(classes, trainable)]
+
+
+class Plan:
+    """What a taped forward / its backward do for one trainable set and one set of part modes.
+
+    modes        (cnn, text, fusion, head) training flags
+    cnn_tape     the CNN keeps its activations (some image_encoder parameter trains, or the images require grad)
+    cnn_low      lowest CNN level the data-gradient chain reaches: None (no CNN backward), 4 ... 1 (stage), 0 (stem)
+    text         the text encoder's backward runs (some text_encoder parameter trains)
+    fusion_bwd   the fusion backward runs (a fusion parameter trains, or a gradient must pass it on)
+    need_dfused  the answer head hands a gradient to the fusion part
+    need_dfeat / need_denc   the fusion part hands a gradient to the CNN / the text encoder
+    """
+
+    def __init__(self, param_entries: Sequence[LY.Entry], trainable: Sequence[bool], modes: Tuple[bool, bool, bool, bool],
+                 images_grad: bool):
+        self.modes = tuple(bool(m) for m in modes)
+        self.trainable = tuple(bool(t) for t in trainable)
+        self.images_grad = bool(images_grad)
+        names = [e.name for e in param_entries]
+        tr = dict(zip(names, self.trainable))
+
+        def any_of(prefix):
+            return any(t for n, t in tr.items() if n.startswith(prefix))
+
+        self.cnn_tape = any_of("image_encoder.") or self.images_grad
+        if self.images_grad or any_of("image_encoder.stem."):
+            self.cnn_low: Optional[int] = 0
+        else:
+            self.cnn_low = next((s for s in STAGES if any_of(f"image_encoder.stage{s}.")), None)
+        self.text = any_of("text_encoder.")
+        self.need_dfeat = self.cnn_low is not None
+        self.need_denc = self.text
+        self.fusion_bwd = any_of("fusion.") or self.need_dfeat or self.need_denc
+        self.need_dfused = self.fusion_bwd
+        # frozen flat slots (sorted, disjoint): a weight-gradient launch whose output lies entirely inside them is skipped
+        spans = []
+        for e, t in zip(param_entries, self.trainable):
+            if not t:
+                if spans and spans[-1][1] == e.offset:
+                    spans[-1][1] = slot_end(e)
+                else:
+                    spans.append([e.offset, slot_end(e)])
+        self._flo = [s[0] for s in spans]
+        self._fhi = [s[1] for s in spans]
+
+    def frozen(self, lo: int, n: int) -> bool:
+        """True when the flat elements [lo, lo + n) belong to frozen parameters only."""
+        i = bisect_right(self._flo, lo) - 1
+        return i >= 0 and lo + n <= self._fhi[i]
+
+    def cnn_levels(self) -> List[str]:
+        """CNN segments whose backward runs, in backward order."""
+        if self.cnn_low is None:
+            return []
+        out = [f"image_encoder.stage{s}" for s in (4, 3, 2, 1) if s >= max(self.cnn_low, 1)]
+        if self.cnn_low == 0:
+            out.append("image_encoder.stem")
+        return out
+
+    def key(self):
+        return (self.modes, self.trainable, self.images_grad)
+
+
+def resolve(param_entries, params, modes, images_grad, cache: Optional[dict] = None) -> Optional[Plan]:
+    """The plan of a taped forward, or None for today's route (every parameter trains and every part runs in one mode).  `cache`
+    keeps the last plan: a step whose trainable set and modes did not change costs one pass over `params`."""
+    trainable = tuple(p.requires_grad for p in params)
+    if all(trainable) and len(set(modes)) == 1:
+        return None
+    key = (tuple(modes), trainable, bool(images_grad))
+    if cache is not None and cache.get("key") == key:
+        return cache["plan"]
+    plan = Plan(param_entries, trainable, modes, images_grad)
+    if cache is not None:
+        cache["key"], cache["plan"] = key, plan
+    return plan

@@ -91,6 +91,8 @@ HBM_BYTES = {
     "vqa_convert": ("optimizer", lambda a: a[4] * (_ES(a[0]) + _ES(a[1]))),
     "vqa_sumsq": ("optimizer", lambda a: a[1] * 4),
     "vqa_adamw": ("optimizer", lambda a: a[4] * 4 * 7),
+    "vqa_sumsq_ranges": ("optimizer", lambda a: a[3] * 4),
+    "vqa_adamw_ranges": ("optimizer", lambda a: a[6] * 4 * 7),
 }
 
 

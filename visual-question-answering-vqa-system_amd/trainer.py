@@ -14,6 +14,7 @@ from typing import List, Optional
 import torch
 import torch.distributed as dist
 
+from . import finetune as FT
 from . import layout as LY
 from ._lib import call, dt, ptr
 
@@ -72,7 +73,18 @@ class GradBucketReducer:
             self.comm_stream = pick_concurrent_streams(flat_grad.device, 1, avoid=avoid_streams)[0]
         self._works: List = []
         self.issued: List[str] = []
+        self._completed = 0
+        self._send = [True] * len(self.groups)
         self.bytes_reduced = 0
+
+    def set_trainable(self, ranges=None):
+        """Fine-tuning: `ranges` = [(lo, hi, ...)] of the trainable flat elements (None: everything trains).  A group that holds no
+        trainable parameter is not sent: its gradients are never read.  Like DDP, this needs the SAME trainable set on every rank --
+        a group sent by some ranks and not by others would leave the collectives unmatched."""
+        if ranges is None:
+            self._send = [True] * len(self.groups)
+        else:
+            self._send = [any(r[0] < hi and r[1] > lo for r in ranges) for _, lo, hi in self.groups]
 
     def _issue(self, tensor, events=()):
         if self.comm_stream is not None:
@@ -117,9 +129,11 @@ class GradBucketReducer:
             self._pending[gi] = (missing, evs)
             return
         self._pending.pop(gi, None)
-        self.issued.append("+".join(names))
-        self._issue(self.G[lo:hi], evs)
-        if len(self.issued) == len(self.groups):       # the last message of the step: the side tensors ride behind it
+        self._completed += 1
+        if self._send[gi]:
+            self.issued.append("+".join(names))
+            self._issue(self.G[lo:hi], evs)
+        if self._completed == len(self.groups):        # the last message of the step: the side tensors ride behind it
             for t in self._aux:
                 self._issue(t)
             self._aux = []
@@ -135,6 +149,7 @@ class GradBucketReducer:
             w.wait()
         self._works = []
         self.issued = []
+        self._completed = 0
         return 1.0 / self.world
 
 
@@ -165,6 +180,38 @@ class HipTrainer:
         self.reducer = GradBucketReducer(self.G, self.buckets, process_group, overlap, force=force_reducer,
                                          avoid_streams=[st for st in (self.engine.side, self.engine.side2) if st is not None])
         self.world = self.reducer.world
+        # fine-tuning (frozen parameters): the optimizer runs over a device table of trainable ranges (finetune.trainable_ranges),
+        # rebuilt only when the trainable set changes.  _lag_class groups parameters frozen during exactly the same steps; _lag[j]
+        # (device) counts the applied steps parameter j spent frozen, so each range forms torch.optim.AdamW's per-parameter step.
+        self._mask = None                          # trainable set of the current table (None: everything, the plain kernels)
+        self._ever_frozen = False                  # some parameter was frozen at some step: the plain kernels' global step is off
+        self._lag_class = [0] * len(model._param_entries)
+        self._ranges = None                        # (table, R, n, frozen indices, nf) on the device
+        self._lag = torch.zeros(len(model._param_entries), device=flat.device, dtype=torch.int32)
+
+    def _set_mask(self, trainable):
+        """Trainable set of this step (tuple of bools in layout order, or None for all): rebuild the range table when it changed."""
+        if trainable is not None and all(trainable):
+            trainable = None
+        if trainable == self._mask and (self._ranges is not None or not self._ever_frozen):
+            return
+        self._mask = trainable
+        tr = trainable if trainable is not None else (True,) * len(self._lag_class)
+        self._lag_class = FT.refine_classes(self._lag_class, tr)
+        self._ever_frozen = self._ever_frozen or trainable is not None
+        if not self._ever_frozen:
+            self._ranges = None
+            self.reducer.set_trainable(None)
+            return
+        ranges = FT.trainable_ranges(self.model._param_entries, tr, self._lag_class)
+        rows = FT.range_table_rows(ranges)
+        n = sum(hi - lo for lo, hi, _ in ranges)
+        dev = self.G.device
+        table = torch.tensor(rows if rows else [[0, 0, 0, 0]], dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        frozen = [j for j, t in enumerate(tr) if not t]
+        fidx = torch.tensor(frozen if frozen else [0], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+        self._ranges = (table, len(rows), n, fidx, len(frozen))
+        self.reducer.set_trainable(ranges)
 
     def step(self, images, token_ids, attention_mask, targets, metrics=None, image_index=None):
         """One full train step; returns (loss device scalar, logits fp32).  `metrics`: optional device-side accuracy tracker
@@ -197,7 +244,10 @@ class HipTrainer:
         if self._copy_sig is not None and eng.adamw_copy_target() is not None and self._copy_sig == self._param_sig():
             eng._wsrc_fresh = True                 # (one-shot, consumed by the begin_step of the forward below)
         maskf = None if attention_mask is None else attention_mask.contiguous().float()
-        logits, _, tape = eng.forward(images, token_ids, maskf, True, False, need_tape=True, lowp_logits=True, kv_index=kv_index)
+        # fine-tuning: requires_grad and the parts' modes, resolved on every step (finetune.Plan; None: the plain step)
+        plan = self.model._finetune_plan(self.model._param_list(), False, True)
+        self._set_mask(None if plan is None else plan.trainable)
+        logits, _, tape = eng.forward(images, token_ids, maskf, True, False, need_tape=True, lowp_logits=True, kv_index=kv_index, plan=plan)
         B, N = logits.shape
         # the loss kernel reads the logits in the compute dtype, writes d logits in it and leaves the fp32 logits the caller gets:
         # the same values as logits.float() -> loss -> d logits.to(bf16), two elementwise launches less between forward and backward
@@ -212,11 +262,18 @@ class HipTrainer:
             metrics.update(logits_f, targets)
         eng.backward(tape, dlogits, self.G, on_segment=self.reducer.on_segment if self.reducer.active else None)
         gscale = self.reducer.finish()
-        call("vqa_sumsq", ptr(self.G), self.G.numel(), ptr(self.sumsq))
         self.calls += 1
         b1, b2 = self.betas
-        call("vqa_adamw", ptr(self.model._flat), ptr(self.G), ptr(self.m), ptr(self.v), self.G.numel(), self.lr, b1, b2, self.eps,
-             self.wd, self.calls, ptr(self.sumsq), float(self.max_norm), gscale, ptr(self.bad_step), ptr(self._bad), ptr(eng.adamw_copy_target()))
+        if self._ranges is None:
+            call("vqa_sumsq", ptr(self.G), self.G.numel(), ptr(self.sumsq))
+            call("vqa_adamw", ptr(self.model._flat), ptr(self.G), ptr(self.m), ptr(self.v), self.G.numel(), self.lr, b1, b2, self.eps,
+                 self.wd, self.calls, ptr(self.sumsq), float(self.max_norm), gscale, ptr(self.bad_step), ptr(self._bad), ptr(eng.adamw_copy_target()))
+        else:                                      # frozen parameters: only the trainable ranges are read and written
+            table, R, n, fidx, nf = self._ranges
+            call("vqa_sumsq_ranges", ptr(self.G), ptr(table), R, n, ptr(self.sumsq))
+            call("vqa_adamw_ranges", ptr(self.model._flat), ptr(self.G), ptr(self.m), ptr(self.v), ptr(table), R, n, self.lr, b1, b2,
+                 self.eps, self.wd, self.calls, ptr(self.sumsq), float(self.max_norm), gscale, ptr(self.bad_step), ptr(self._bad),
+                 ptr(self._lag), ptr(fidx), nf, ptr(eng.adamw_copy_target()))
         # the kernel wrote the bf16 operand copy too: the next step() skips the cast launch if nothing touched the parameters in between
         self._copy_sig = self._param_sig() if eng.adamw_copy_target() is not None else None
         return self.loss, logits_f
