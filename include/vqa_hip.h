@@ -338,6 +338,25 @@ int vqa_attention_bwd_mfma_idx(const void* dctx, int ldc, const void* q, const v
 /* Device-side accuracy counters: counters[3] (u64) += {top-1 correct, top-5 correct, samples} for fp32 logits [B][N] and i64 targets.
  * Replaces the argmax/topk + .cpu() + .item() of VQAAccuracy.update (utils/metrics.py:55-94); ties resolve to the lowest index. */
 int vqa_accuracy_update(const float* logits, const long long* targets, unsigned long long* counters, int B, int N, hipStream_t stream);
+/* Soft answer scores (VQA v2, ten annotator answers per question; utils/metrics.py:12-19 acc(ans) = min(1, #agreeing annotators / 3)).
+ * vqa_answer_scores: answers [B][A] (i64 answer ids, -1 = not in the vocabulary, A <= 64) -> per row the distinct in-vocabulary ids in
+ *   order of first occurrence (ids), their number of occurrences (counts) and weights = min(1, count / 3) in fp32 (mode 0) or that
+ *   divided by the row's sum taken in slot order (mode 1; a row without an in-vocabulary answer stays zero).  Unused slots: -1 / 0 / 0.
+ *   An id < -1 or >= N: *err (may be NULL) += 1 per such row, the row becomes {N, -1, ...} / 0 / 0 so that the loss rejects it.
+ * vqa_cross_entropy_soft: vqa_cross_entropy with t[b][c] = sum of weights[b][k] over ids[b][k] == c (duplicates add up, -1 slots are
+ *   skipped), W[b] = sum_c t[b][c]:  loss += sum_b (W[b] * lse[b] - sum_k w[b][k] * x[b][ids[b][k]]) / B  (F.cross_entropy with
+ *   probability targets), dlogits = (W * softmax - t) * gscale / B (may be NULL).  An id < -1 or >= N is a bad target as there.
+ *   K = 1 with weight 1 gives the bits of vqa_cross_entropy.  counts + acc (both optional; acc without counts is an argument error):
+ *   acc[0] += min(3, votes for the row's arg-max) (integer thirds of the challenge accuracy), acc[1] += 1, per row, in the same pass.
+ * vqa_challenge_accuracy_update: those two counters alone, from fp32 logits (utils/metrics.py:136-184 VQAChallengeAccuracy without
+ *   the string comparison on the host); ties resolve to the lowest index. */
+int vqa_answer_scores(const long long* answers, int* ids, float* weights, int* counts, int B, int A, int N, int mode, int* err,
+                      hipStream_t stream);
+int vqa_cross_entropy_soft(int dtype, const void* logits, const int* ids, const float* weights, int K, float* loss, void* dlogits,
+                           float* logits_f32, int B, int N, float gscale, int* err, float* ws, const int* counts,
+                           unsigned long long* acc, hipStream_t stream);
+int vqa_challenge_accuracy_update(const float* logits, const int* ids, const int* counts, int K, unsigned long long* acc, int B, int N,
+                                  hipStream_t stream);
 /* masked mean over tokens (models/fusion.py:303-313, models/text_encoder.py:522-527) */
 /* both masked means of the fusion tail in one launch (round 4): out[B][2D] = [mean_m(x0) | mean_m(x1)] with the same mask, and the
  * matching backward dx{0,1}[b][l][:] = dcat[b][{0,D}:] * m[b][l] / cnt (models/fusion.py:281-296); per-element arithmetic of

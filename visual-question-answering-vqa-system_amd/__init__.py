@@ -24,6 +24,11 @@ def load_dropin_metrics():
     return _load_dropin_file("vqa_hip_dropin_utils_metrics", "utils", "metrics.py")
 
 
+def load_dropin_soft_targets():
+    """The drop-in `utils.soft_targets` (sparse soft answer scores: SoftTargets, answer_scores, SoftTargetCrossEntropy)."""
+    return _load_dropin_file("vqa_hip_dropin_utils_soft_targets", "utils", "soft_targets.py")
+
+
 def _load_dropin_file(name, *rel):
     import importlib.util
     import os

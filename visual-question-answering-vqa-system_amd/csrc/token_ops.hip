@@ -1669,6 +1669,182 @@ extern "C" int vqa_accuracy_update(const float* logits, const long long* targets
 }
 
 // ---------------------------------------------------------------------------------------------
+// Soft answer scores (VQA v2: ten annotator answers per question, acc(ans) = min(1, #agreeing annotators / 3),
+// utils/metrics.py:12-19, :136-184 VQAChallengeAccuracy).
+//   vqa_answer_scores              annotator ids [B][A] -> sparse soft targets {ids, counts, weights} [B][A], one wave per question
+//   vqa_cross_entropy_soft         cross_entropy_kernel with sum_k w_k * onehot(id_k) in place of the one-hot target; the challenge
+//                                  accuracy of the same rows rides along (the arg-max is the lowest index that holds the row maximum
+//                                  the softmax needs anyway)
+//   vqa_challenge_accuracy_update  the metric alone (evaluation)
+// The metric is counted in integer THIRDS: acc[0] += min(3, votes for the arg-max), acc[1] += 1 per question -- exact and
+// independent of the order the rows arrive in.  The four rows of a workgroup are added up in LDS first: one atomic pair per
+// workgroup instead of one per row (atomics on one address are serialised).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int lane_i(int v, int k) { return __builtin_amdgcn_readlane(v, k); }                    // k wave-uniform
+__device__ __forceinline__ float lane_f(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
+__device__ __forceinline__ int wave_min_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return v;
+}
+// votes for class `best` among the row's slots (lane k < K holds slot k), capped at 3; the same value in every lane
+__device__ __forceinline__ int row_thirds(int best, int id, int cnt, int K, int lane) {
+  int votes = (lane < K && id == best) ? cnt : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) votes += __shfl_xor(votes, o, 64);
+  return min(3, max(0, votes));
+}
+// every thread of the workgroup calls this (it holds a barrier); `thirds` < 0: this wave has no row
+__device__ __forceinline__ void block_add_thirds(unsigned long long* acc, int thirds) {
+  __shared__ int sh[4];
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = thirds;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t = 0ull, n = 0ull;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) if (sh[w] >= 0) { t += (unsigned long long)sh[w]; n += 1ull; }
+    if (n) { atomicAdd(acc + 0, t); atomicAdd(acc + 1, n); }
+  }
+}
+
+__global__ __launch_bounds__(256) void answer_scores_kernel(const long long* __restrict__ answers, int* __restrict__ ids, float* __restrict__ weights,
+                                                            int* __restrict__ counts, int B, int A, int N, int mode, int* err) {
+  const int lane = threadIdx.x & 63;
+  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (row >= B) return;
+  const long long a = lane < A ? answers[(size_t)row * A + lane] : -1ll;
+  const bool valid = a >= 0 && a < (long long)N;                       // -1: the annotator's answer is not in the vocabulary
+  const bool rowbad = __ballot(a < -1ll || a >= (long long)N) != 0ull;
+  const int ai = valid ? (int)a : -1;                                  // (a valid id is below N: it fits)
+  int cnt = 0, earlier = 0;
+  for (int j = 0; j < A; ++j) {
+    const int aj = lane_i(ai, j);                                      // read by EVERY lane: never under a divergent condition
+    const int same = (valid && aj == ai) ? 1 : 0;
+    cnt += same;
+    earlier += j < lane ? same : 0;
+  }
+  const bool first = valid && earlier == 0;
+  const unsigned long long firsts = __ballot(first);                  // distinct ids, in order of first occurrence
+  const int slot = __popcll(firsts & ((1ull << lane) - 1ull)), nslots = __popcll(firsts);
+  float w = first ? fminf(1.f, (float)cnt / 3.f) : 0.f;
+  if (mode == 1) {                                                     // rows sum to one: the sum is taken in slot order
+    float s = 0.f;
+    for (unsigned long long m = firsts; m; m &= m - 1ull) s += __shfl(w, __ffsll((long long)m) - 1, 64);
+    if (first && s > 0.f) w = w / s;
+  }
+  const size_t o = (size_t)row * A;
+  if (rowbad) {                                                        // slot 0 carries the id N: the loss kernel rejects the row
+    if (lane < A) { ids[o + lane] = lane == 0 ? N : -1; weights[o + lane] = 0.f; counts[o + lane] = 0; }
+    if (lane == 0 && err) atomicAdd(err, 1);
+    return;
+  }
+  if (first) { ids[o + slot] = (int)a; weights[o + slot] = w; counts[o + slot] = cnt; }
+  if (lane >= nslots && lane < A) { ids[o + lane] = -1; weights[o + lane] = 0.f; counts[o + lane] = 0; }
+}
+
+// cross_entropy_kernel's operation order (max, sum of exp, lse, the store loop); with K = 1 and weight 1 every value is the same bits
+template <typename T>
+__global__ __launch_bounds__(256) void cross_entropy_soft_kernel(const T* __restrict__ logits, const int* __restrict__ ids, const float* __restrict__ weights,
+                                                                 int K, float* loss, T* __restrict__ dlogits, float* __restrict__ logits_f32, int B, int N,
+                                                                 float gscale, int* err, float* part, const int* __restrict__ counts, unsigned long long* acc) {
+  const int lane = threadIdx.x & 63;
+  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  int thirds = -1;
+  if (row < B) {
+    const T* lr = logits + (size_t)row * N;
+    float m = -INFINITY;
+    for (int c = lane; c < N; c += 64) m = fmaxf(m, to_f<T>(lr[c]));
+    m = wave_max(m);
+    float s = 0.f;
+    int best = N;
+    for (int c = lane; c < N; c += 64) {
+      const float x = to_f<T>(lr[c]);
+      s += expf(x - m);
+      if (x == m) best = min(best, c);                                 // arg-max, ties -> lowest index (c ascends per lane)
+    }
+    s = wave_sum(s);
+    // lane k holds slot k: id -1 is an empty slot; an id < -1 or >= N is handled like a bad hard target (never read out of bounds,
+    // the row is counted in *err, its loss term and gradient row are NaN)
+    const int id = lane < K ? ids[(size_t)row * K + lane] : -1;
+    const bool used = id >= 0 && id < N;
+    const bool bad = __ballot(id < -1 || id >= N) != 0ull;
+    const float w = used ? weights[(size_t)row * K + lane] : 0.f;
+    const float xk = used ? to_f<T>(lr[id]) : 0.f;
+    float W = 0.f, dot = 0.f;
+    for (int k = 0; k < K; ++k) {                                      // slot order: W = sum_k w_k, dot = sum_k w_k * x[id_k]
+      const float wk = lane_f(w, k);
+      W += wk;
+      dot += wk * lane_f(xk, k);
+    }
+    const float lse = m + logf(s);
+    if (lane == 0) {
+      const float term = bad ? __builtin_nanf("") : (W * lse - dot) / (float)B;
+      if (part) part[row] = term;
+      else if (loss) atomicAdd(loss, term);
+      if (bad && err) atomicAdd(err, 1);
+    }
+    for (int c = lane; c < N; c += 64) {
+      const float x = to_f<T>(lr[c]);
+      if (logits_f32) logits_f32[(size_t)row * N + c] = x;
+      if (dlogits) {
+        float t = 0.f;
+        for (int k = 0; k < K; ++k) {                                  // duplicates add up
+          const int idk = lane_i(id, k);
+          const float wk = lane_f(w, k);
+          t += idk == c ? wk : 0.f;
+        }
+        dlogits[(size_t)row * N + c] = from_f<T>(bad ? __builtin_nanf("") : (W * expf(x - lse) - t) * gscale / (float)B);
+      }
+    }
+    if (acc) thirds = row_thirds(wave_min_i(best), id, lane < K ? counts[(size_t)row * K + lane] : 0, K, lane);
+  }
+  if (acc) block_add_thirds(acc, thirds);
+}
+
+__global__ __launch_bounds__(256) void challenge_accuracy_kernel(const float* __restrict__ logits, const int* __restrict__ ids, const int* __restrict__ counts,
+                                                                 int K, unsigned long long* acc, int B, int N) {
+  const int lane = threadIdx.x & 63;
+  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  int thirds = -1;
+  if (row < B) {
+    const float* x = logits + (size_t)row * N;
+    float m = -INFINITY;
+    for (int c = lane; c < N; c += 64) m = fmaxf(m, x[c]);
+    m = wave_max(m);
+    int best = N;
+    for (int c = lane; c < N; c += 64) if (x[c] == m) best = min(best, c);
+    thirds = row_thirds(wave_min_i(best), lane < K ? ids[(size_t)row * K + lane] : -1, lane < K ? counts[(size_t)row * K + lane] : 0, K, lane);
+  }
+  block_add_thirds(acc, thirds);
+}
+
+extern "C" int vqa_answer_scores(const long long* answers, int* ids, float* weights, int* counts, int B, int A, int N, int mode, int* err,
+                                 hipStream_t st) {
+  if (!answers || !ids || !weights || !counts || B <= 0 || A <= 0 || A > 64 || N <= 0 || (mode != 0 && mode != 1)) return VQA_EARG;
+  hipLaunchKernelGGL(answer_scores_kernel, dim3((B + 3) / 4), dim3(256), 0, st, answers, ids, weights, counts, B, A, N, mode, err);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+// vqa_cross_entropy with sparse soft targets; ws as there (B floats: the row terms are folded in row order, bit-reproducible)
+extern "C" int vqa_cross_entropy_soft(int dtype, const void* logits, const int* ids, const float* weights, int K, float* loss, void* dlogits,
+                                      float* logits_f32, int B, int N, float gscale, int* err, float* ws, const int* counts,
+                                      unsigned long long* acc, hipStream_t st) {
+  if (!logits || !ids || !weights || K <= 0 || K > 64 || B <= 0 || N <= 0 || (acc && !counts)) return VQA_EARG;
+  dim3 grid((B + 3) / 4);
+  DT(hipLaunchKernelGGL(cross_entropy_soft_kernel<float>, grid, dim3(256), 0, st, (const float*)logits, ids, weights, K, loss, (float*)dlogits, logits_f32,
+                        B, N, gscale, err, ws, counts, acc),
+     hipLaunchKernelGGL(cross_entropy_soft_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)logits, ids, weights, K, loss, (bf16_t*)dlogits, logits_f32,
+                        B, N, gscale, err, ws, counts, acc));
+  if (ws && loss) launch_fold(ws, B, 1, 1, loss, 1, nullptr, st);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+extern "C" int vqa_challenge_accuracy_update(const float* logits, const int* ids, const int* counts, int K, unsigned long long* acc, int B, int N,
+                                             hipStream_t st) {
+  if (!logits || !ids || !counts || !acc || K <= 0 || K > 64 || B <= 0 || N <= 0) return VQA_EARG;
+  hipLaunchKernelGGL(challenge_accuracy_kernel, dim3((B + 3) / 4), dim3(256), 0, st, logits, ids, counts, K, acc, B, N);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Many questions per image in TRAINING (VQAModel.forward_grouped, HipTrainer.step(image_index=)).
 //   vqa_index_csr              questions of each image in ascending question order (CSR), one workgroup, no host sync
 //   vqa_attention_fwd(_mfma)_idx_train   the indexed forwards with dropout: the mask of (question b, head, i, j) is the one

@@ -1,4 +1,5 @@
-"""`utils.metrics.VQAAccuracy` drop-in with device-resident counters (reference: utils/metrics.py:29-135).
+"""`utils.metrics.VQAAccuracy` and `VQAChallengeAccuracy` drop-ins with device-resident counters (reference:
+utils/metrics.py:29-135, :136-184).
 
 The reference's `update` moves argmax / top-5 indices to the host and calls `.item()` on every batch
 (utils/metrics.py:80-94): two device syncs per train step.  Here `update` launches one HIP kernel
@@ -92,3 +93,86 @@ class VQAAccuracy:
     def __str__(self) -> str:
         m = self.compute()
         return f"Accuracy: {m['accuracy']:.4f} | Top-5: {m['accuracy_top5']:.4f}"
+
+
+def _is_soft(x) -> bool:
+    """A utils.soft_targets.SoftTargets (by shape, not by class: the drop-in module may be imported under more than one name)."""
+    return isinstance(x, tuple) and hasattr(x, "ids") and hasattr(x, "weights") and hasattr(x, "counts")
+
+
+class VQAChallengeAccuracy:
+    """VQA v2 challenge accuracy, acc(ans) = min(1, #annotators who gave ans / 3) (utils/metrics.py:136-184), same interface:
+    reset / update / compute, attributes total_score and count.
+
+    `update(predictions, annotator_answers)` takes GPU logits [B, N] (or predicted indices [B]) with either the annotator ids
+    [B, A] (-1: not in the vocabulary) or a SoftTargets that carries `counts`.  Scores are kept in integer thirds in a 2-element
+    device buffer {thirds, questions}: exact, and nothing is read back before compute() / total_score / count.  The reference's own
+    call form, a list of predicted strings and a list of lists of annotator strings, is counted on the host as it does."""
+
+    def __init__(self):
+        self._counters: Optional[torch.Tensor] = None      # int64 {thirds, questions} on the GPU
+        self.reset()
+
+    def reset(self):                                          # utils/metrics.py:150-153
+        if self._counters is not None:
+            self._counters.zero_()
+        self._host = [0, 0]                                    # the string call form: {thirds, questions} counted on the host
+
+    def _fused_acc(self, device) -> torch.Tensor:
+        """The device counters (HipTrainer.step hands them to the loss launch: `vqa_cross_entropy_soft` counts/acc)."""
+        if self._counters is None or self._counters.device != device:
+            if self._counters is not None:
+                self._host = [h + int(v) for h, v in zip(self._host, self._counters.cpu())]
+            self._counters = torch.zeros(2, dtype=torch.int64, device=device)
+        return self._counters
+
+    def update(self, predictions, annotator_answers):
+        if not isinstance(predictions, torch.Tensor):          # utils/metrics.py:167-175, in thirds
+            for pred, answers in zip(predictions, annotator_answers):
+                self._host[0] += min(3, sum(1 for ans in answers if ans == pred))
+                self._host[1] += 1
+            return
+        if not predictions.is_cuda:
+            raise RuntimeError("VQAChallengeAccuracy (HIP) keeps its counters on the GPU: predictions must be a GPU tensor; there is no CPU path")
+        B, dev = predictions.shape[0], predictions.device
+        soft = _is_soft(annotator_answers)
+        if soft:
+            if annotator_answers.counts is None:
+                raise TypeError("VQAChallengeAccuracy.update: these SoftTargets carry no `counts` (votes per slot)")
+            annotator_answers.validate(B, dev)
+        elif not (isinstance(annotator_answers, torch.Tensor) and annotator_answers.dim() == 2 and annotator_answers.shape[0] == B):
+            raise TypeError("VQAChallengeAccuracy.update: annotator_answers must be annotator ids [B, A] or SoftTargets with counts")
+        c = self._fused_acc(dev)
+        if predictions.dim() == 2:
+            lg = predictions.detach()
+            lg = lg.float().contiguous() if lg.dtype != torch.float32 else lg.contiguous()
+            if not soft:
+                annotator_answers = _pkg().load_dropin_soft_targets().answer_scores(annotator_answers.to(dev), lg.shape[1])
+            ids, cnt = annotator_answers.ids, annotator_answers.counts
+            _pkg()._lib.call("vqa_challenge_accuracy_update", lg.data_ptr(), ids.data_ptr(), cnt.data_ptr(), ids.shape[1], c.data_ptr(),
+                             lg.shape[0], lg.shape[1])
+        else:                                                  # index predictions: still no host sync
+            pred = predictions.to(torch.int64)[:, None]
+            if soft:
+                votes = ((annotator_answers.ids.to(torch.int64) == pred) * annotator_answers.counts.to(torch.int64)).sum(1)
+            else:
+                a = annotator_answers.to(dev, torch.int64)
+                votes = ((a == pred) & (a >= 0)).sum(1)
+            c[0] += votes.clamp(max=3).sum()
+            c[1] += B
+
+    def _read(self):
+        dev = [0, 0] if self._counters is None else [int(v) for v in self._counters.cpu()]
+        return self._host[0] + dev[0], self._host[1] + dev[1]
+
+    @property
+    def total_score(self) -> float:
+        return self._read()[0] / 3.0
+
+    @property
+    def count(self) -> int:
+        return self._read()[1]
+
+    def compute(self) -> float:                               # utils/metrics.py:177-184
+        thirds, count = self._read()
+        return thirds / (3 * max(count, 1))

@@ -87,6 +87,10 @@ HBM_BYTES = {
     "vqa_attention_bwd_idx": ("attention", lambda a: (3 * a[19] * a[21] + 4 * a[12] * a[22]) * a[2] * _ES(a[0]) + a[19] * a[20] * a[21] * a[22] * 4),
     "vqa_index_csr": ("token", lambda a: (2 * a[1] + a[2] + 1) * 4),
     "vqa_cross_entropy": ("token", lambda a: a[6] * a[7] * (_ES(a[0]) + 4)),
+    # soft targets: the logits traffic of the hard kernel + ids, weights, counts [B][K]; the annotator ids are 8 bytes in, 12 out
+    "vqa_cross_entropy_soft": ("token", lambda a: a[8] * a[9] * (_ES(a[0]) + 4) + a[8] * a[4] * (8 + 4 * _P(a[13]))),
+    "vqa_challenge_accuracy_update": ("token", lambda a: a[5] * a[6] * 4 + a[5] * a[3] * 8),
+    "vqa_answer_scores": ("token", lambda a: a[4] * a[5] * 20),
     # weight staging and the optimizer tail (H, N1): cast of the flat buffer, packed data-gradient operands, sum of squares, AdamW
     "vqa_convert": ("optimizer", lambda a: a[4] * (_ES(a[0]) + _ES(a[1]))),
     "vqa_sumsq": ("optimizer", lambda a: a[1] * 4),

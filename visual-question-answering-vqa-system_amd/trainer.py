@@ -153,6 +153,11 @@ class GradBucketReducer:
         return 1.0 / self.world
 
 
+def _is_soft(targets) -> bool:
+    """A SoftTargets of the drop-in utils.soft_targets, recognised by its fields (that module can be imported under several names)."""
+    return isinstance(targets, tuple) and hasattr(targets, "ids") and hasattr(targets, "weights") and hasattr(targets, "counts")
+
+
 class HipTrainer:
     def __init__(self, model, lr=1e-4, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
                  process_group=None, overlap=True, force_reducer=False):
@@ -219,14 +224,25 @@ class HipTrainer:
         image_index (many questions per image): images [U,3,H,W], token_ids / attention_mask [N,L], targets [N]; question i is asked of
         image image_index[i] and the step trains VQAModel.forward_grouped's composition (one CNN pass per image, loss per question).
         The range check is free for a CPU index (copied to the device without a sync) and costs one device-to-host read for a device
-        index.  None: exactly the plain step."""
+        index.  None: exactly the plain step.
+        targets may be a SoftTargets (dropin/utils/soft_targets.py: sparse soft answer scores, ids / weights / counts [B, K]): the loss
+        is then F.cross_entropy with those probability-style targets (`vqa_cross_entropy_soft`), everything around it is the same step.
+        `metrics` must then be a VQAChallengeAccuracy (and the targets carry `counts`): it is counted inside the loss launch."""
         eng, T = self.engine, self.engine.dtype
         dev = self.G.device
-        for name, t in (("images", images), ("token_ids", token_ids), ("targets", targets)):
+        soft = _is_soft(targets)
+        if metrics is not None and soft != hasattr(metrics, "_fused_acc"):
+            raise TypeError("HipTrainer.step: soft targets are scored by VQAChallengeAccuracy, hard labels by VQAAccuracy "
+                            f"(got {type(metrics).__name__} with {'SoftTargets' if soft else 'a label tensor'})")
+        if metrics is not None and soft and targets.counts is None:
+            raise TypeError("HipTrainer.step: VQAChallengeAccuracy needs SoftTargets that carry `counts`")
+        for name, t in (("images", images), ("token_ids", token_ids)) + ((("targets", targets),) if not soft else ()):
             if not (isinstance(t, torch.Tensor) and t.device == dev):
                 raise RuntimeError(f"HipTrainer.step: `{name}` must be a tensor on {dev} (there is no CPU path)")
         Bq = token_ids.shape[0] if (image_index is not None and token_ids.dim() == 2) else images.shape[0]
-        if images.dim() != 4 or images.shape[1] != 3 or token_ids.dim() != 2 or token_ids.shape[0] != Bq or targets.shape != (Bq,):
+        if soft:
+            targets.validate(Bq, dev)
+        if images.dim() != 4 or images.shape[1] != 3 or token_ids.dim() != 2 or token_ids.shape[0] != Bq or (not soft and targets.shape != (Bq,)):
             raise RuntimeError("HipTrainer.step: expected images [B,3,H,W], token_ids [B,L], targets [B]"
                                + ("" if image_index is None else " with B questions"))
         kv_index = None
@@ -238,7 +254,8 @@ class HipTrainer:
         # the kernels read raw pointers: enforce the dtypes / contiguity VQAModel.forward enforces (vqa_model.py drop-in)
         images = images.contiguous().float()
         token_ids = token_ids.contiguous().long()
-        targets = targets.contiguous().long()
+        if not soft:
+            targets = targets.contiguous().long()
         self.G.zero_()
         self._scal.zero_()
         if self._copy_sig is not None and eng.adamw_copy_target() is not None and self._copy_sig == self._param_sig():
@@ -255,10 +272,16 @@ class HipTrainer:
         logits_f = torch.empty((B, N), device=images.device, dtype=torch.float32) if lowp else logits
         dlogits = torch.empty((B, N), device=images.device, dtype=logits.dtype)
         ce_ws = torch.empty((B,), device=images.device, dtype=torch.float32)
-        call("vqa_cross_entropy", dt(logits), ptr(logits), ptr(targets), ptr(self.loss), ptr(dlogits), ptr(logits_f) if lowp else None, B, N, 1.0,
-             ptr(self.bad_step), ptr(ce_ws))               # per-row loss terms, folded in row order (bit-reproducible)
+        if soft:                                           # the challenge accuracy rides in the same launch (counts + acc)
+            acc = None if metrics is None else metrics._fused_acc(dev)
+            call("vqa_cross_entropy_soft", dt(logits), ptr(logits), ptr(targets.ids), ptr(targets.weights), targets.ids.shape[1], ptr(self.loss),
+                 ptr(dlogits), ptr(logits_f) if lowp else None, B, N, 1.0, ptr(self.bad_step), ptr(ce_ws),
+                 None if acc is None else ptr(targets.counts), ptr(acc))
+        else:
+            call("vqa_cross_entropy", dt(logits), ptr(logits), ptr(targets), ptr(self.loss), ptr(dlogits), ptr(logits_f) if lowp else None, B, N, 1.0,
+                 ptr(self.bad_step), ptr(ce_ws))           # per-row loss terms, folded in row order (bit-reproducible)
         self.reducer.reduce_aux(self.bad_step)             # every rank must skip the update of a step ANY rank rejects
-        if metrics is not None:
+        if metrics is not None and not soft:
             metrics.update(logits_f, targets)
         eng.backward(tape, dlogits, self.G, on_segment=self.reducer.on_segment if self.reducer.active else None)
         gscale = self.reducer.finish()
