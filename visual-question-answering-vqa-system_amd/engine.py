@@ -58,6 +58,21 @@ def pick_concurrent_streams(device, n: int, avoid=(), tries: int = 12):
     return tuple(chosen)
 
 
+def stem_fcoef(gamma: torch.Tensor, beta: torch.Tensor) -> torch.Tensor:
+    """Coefficient block (0, 0, beta, 1/gamma) [4][C] that makes vqa_bn_bwd_reduce, fed with y := the POOLED stem output, form the
+    stem's BatchNorm-backward sums: where pooled > 0 it equals gamma*xhat + beta, so (pooled - beta) * (1/gamma) is xhat
+    (HipEngine._stem_bwd).  In bf16 the pooled value is rounded (8 significand bits: by at most 2^-8 |pooled|, half an ulp at the
+    bottom of a binade, 2^-9 |pooled| at its top), which moves d gamma by that times |dpool| / |gamma| per window.
+    tests/test_gpu_stem_tail_fp64.py holds the sum to sum |dpool| * [pooled > 0] * 2^-9 * |pooled| / |gamma| per channel and
+    records what was measured: up to 10 % of d gamma for a channel with beta / gamma = 30, nothing visible in fp32.
+    Deviation from the reference: a channel whose gamma is exactly 0 (|gamma| <= 1e-20) gets 1/gamma := 0, so its d gamma is 0,
+    where autograd gives sum g*xhat; its d beta and its dy (= 0) are exact, and nothing becomes inf or NaN."""
+    fcoef = torch.zeros((4, gamma.numel()), device=gamma.device, dtype=torch.float32)
+    fcoef[2] = beta
+    fcoef[3] = torch.where(gamma.abs() > 1e-20, 1.0 / gamma, torch.zeros_like(gamma))
+    return fcoef
+
+
 class HipEngine:
     def __init__(self, cfg: dict, entries: List[LY.Entry], flat: torch.Tensor, buffers: Dict[str, torch.Tensor],
                  compute_dtype: torch.dtype):
@@ -230,11 +245,7 @@ class HipEngine:
                 for w, (wo, bo, n, k) in views.items()}
 
     def _make_stem_fcoef(self):
-        gam, bet = self.P("image_encoder.stem.1.weight"), self.P("image_encoder.stem.1.bias")
-        fcoef = torch.zeros((4, 64), device=self.flat.device, dtype=torch.float32)
-        fcoef[2] = bet
-        fcoef[3] = torch.where(gam.abs() > 1e-20, 1.0 / gam, torch.zeros_like(gam))
-        return fcoef
+        return stem_fcoef(self.P("image_encoder.stem.1.weight"), self.P("image_encoder.stem.1.bias"))
 
     def begin_step(self, for_backward: bool = True):
         """Refresh the working copies of the weights (one cast of the whole flat buffer in bf16 mode)."""
