@@ -338,6 +338,18 @@ int vqa_attention_bwd_mfma_idx(const void* dctx, int ldc, const void* q, const v
 /* Device-side accuracy counters: counters[3] (u64) += {top-1 correct, top-5 correct, samples} for fp32 logits [B][N] and i64 targets.
  * Replaces the argmax/topk + .cpu() + .item() of VQAAccuracy.update (utils/metrics.py:55-94); ties resolve to the lowest index. */
 int vqa_accuracy_update(const float* logits, const long long* targets, unsigned long long* counters, int B, int N, hipStream_t stream);
+/* Top-k answers with their softmax probabilities in one launch (VQAModel.predict's softmax + topk; api/inference.py:228-246).
+ * logits: fp32 or bf16 [B][ld], ld >= N.  allowed: optional 0/1 bytes, allowed_ld == 0: one row [N] shared by every logits row, else
+ * [B][allowed_ld] with allowed_ld >= N.  y[j] = logits[j] where allowed (or without a mask), else -inf.
+ * Order: a before b when y[a] > y[b], or y[a] == y[b] and a < b; NaN ranks above every number, NaNs among themselves by index
+ *   (torch.sort(y, descending=True, stable=True)); decided on y itself, so idx [B][K] (i64) is exact.
+ * probs [B][K] (fp32) = exp(scale * y[idx] - m) / sum_j exp(scale * y[j] - m), m = max_j scale * y[j], scale = 1 / temperature:
+ *   softmax(y * scale) gathered at idx, IEEE arithmetic on special rows (a row holding a NaN, or with nothing allowed, gives NaN for all
+ *   K); scale == 1 changes no bit.  logits_f (optional, fp32 [B][N]) receives the RAW logits (not the masked ones).
+ * No atomics, no scratch; bit-reproducible.  Status 1000 without a launch: NULL logits / idx / probs; B, N or K < 1; K > 64; K > N;
+ * ld < N; allowed_ld neither 0 nor >= N; scale not finite or <= 0; dtype other than 0 (fp32) / 1 (bf16). */
+int vqa_softmax_topk(int dtype, const void* logits, long long ld, const unsigned char* allowed, long long allowed_ld, float scale,
+                     long long* idx, float* probs, float* logits_f, int B, int N, int K, hipStream_t stream);
 /* Soft answer scores (VQA v2, ten annotator answers per question; utils/metrics.py:12-19 acc(ans) = min(1, #agreeing annotators / 3)).
  * vqa_answer_scores: answers [B][A] (i64 answer ids, -1 = not in the vocabulary, A <= 64) -> per row the distinct in-vocabulary ids in
  *   order of first occurrence (ids), their number of occurrences (counts) and weights = min(1, count / 3) in fp32 (mode 0) or that

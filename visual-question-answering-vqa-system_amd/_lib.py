@@ -96,6 +96,7 @@ SIGNATURES = {
     "vqa_attention_fwd_mfma_idx": [P, P, P, I, I, I, P, I, P, P, P, I, I, I, I, I, I, P],
     "vqa_attention_bwd": [I, P, I, P, P, P, I, I, I, P, P, P, P, I, I, I, I, I, I, I, I, F, ULL, P],
     "vqa_accuracy_update": [P, P, P, I, I, P],
+    "vqa_softmax_topk": [I, P, LL, P, LL, F, P, P, P, I, I, I, P],
     "vqa_attention_bwd_mfma": [P, I, P, P, P, I, I, I, P, P, P, P, I, I, I, I, I, I, I, I, F, ULL, P],
     "vqa_attention_bwd_dp": [I, P, I, P, P, P, I, I, I, P, P, P, P, P, I, I, I, I, I, I, I, I, F, ULL, P],
     "vqa_attention_bwd_mfma_dp": [P, I, P, P, P, I, I, I, P, P, P, P, P, I, I, I, I, I, I, I, I, F, ULL, P],

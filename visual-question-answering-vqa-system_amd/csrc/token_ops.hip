@@ -1669,6 +1669,104 @@ extern "C" int vqa_accuracy_update(const float* logits, const long long* targets
 }
 
 // ---------------------------------------------------------------------------------------------
+// Top-k answers with their softmax probabilities (the tail of VQAModel.predict / api/inference.py:228-246: softmax + topk), one
+// launch, one wave per row.  y[j] = logits[j] where allowed (or without a mask), else -inf.  Index a ranks before b when
+// y[a] > y[b], or y[a] == y[b] and a < b (accuracy_kernel's lowest-index tie rule); NaN ranks above every number, NaNs among
+// themselves by index: torch.sort(y, descending=True, stable=True).  The order is decided on y alone, through an order-preserving
+// 32-bit key (NaN -> all ones, -0 == +0) joined with the reversed index into one 64-bit word, so a pick is an integer maximum.
+// probs = exp(scale * y - m) / sum_j exp(scale * y[j] - m), m = max_j scale * y[j] (NaNs skipped by the max, so a row that holds a
+// NaN, or nothing but -inf, gives NaN for every probability as torch.softmax does).  K rounds, each the best word strictly below the
+// previous pick: no per-row state, no atomics, no LDS.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t topk_key(float y) {
+  if (y != y) return 0xffffffffu;
+  uint32_t b = __float_as_uint(y);
+  if (b == 0x80000000u) b = 0u;
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float topk_val(uint32_t k) {          // inverse of topk_key (the all-ones key gives a NaN)
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+__device__ __forceinline__ unsigned long long topk_word(uint32_t key, int j) {
+  return ((unsigned long long)key << 32) | (unsigned long long)(0x7fffffffu - (uint32_t)j);
+}
+__device__ __forceinline__ float topk_arg(float scale, float y, float m) {      // scale * y - m with both roundings (never one fma)
+#pragma clang fp contract(off)
+  const float s = scale * y;
+  return s - m;
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const uint32_t hi = __shfl_xor((uint32_t)(v >> 32), o, 64), lo = __shfl_xor((uint32_t)v, o, 64);
+    const unsigned long long w = ((unsigned long long)hi << 32) | lo;
+    v = w > v ? w : v;
+  }
+  return v;
+}
+
+// The row is read again in each of the K + 2 passes (L2-resident: 4 KB at N = 1000).
+template <typename T>
+__global__ __launch_bounds__(256) void softmax_topk_kernel(const T* __restrict__ logits, long long ld, const unsigned char* __restrict__ allowed,
+                                                           long long allowed_ld, float scale, long long* __restrict__ idx,
+                                                           float* __restrict__ probs, float* __restrict__ logits_f, int B, int N, int K) {
+  const int lane = threadIdx.x & 63;
+  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (row >= B) return;
+  const T* x = logits + (size_t)row * ld;
+  const unsigned char* al = allowed ? allowed + (size_t)row * allowed_ld : nullptr;
+  float* xf = logits_f ? logits_f + (size_t)row * N : nullptr;
+  auto y_at = [&](int j) -> float {
+    const float v = to_f<T>(x[j]);
+    return (al && !al[j]) ? -INFINITY : v;
+  };
+  // pass 1: raw fp32 copy, row maximum of scale * y
+  float m = -INFINITY;
+  for (int j = lane; j < N; j += 64) {
+    if (xf) xf[j] = to_f<T>(x[j]);
+    m = fmaxf(m, scale * y_at(j));
+  }
+  m = wave_max(m);
+  // pass 2: denominator, per lane in index order, then the butterfly (a fixed order: bit-reproducible)
+  float sum = 0.f;
+  for (int j = lane; j < N; j += 64) sum += expf(topk_arg(scale, y_at(j), m));
+  sum = wave_sum(sum);
+  // K rounds of selection; lane r keeps pick r
+  unsigned long long prev = ~0ull, mine = 0ull;
+  for (int r = 0; r < K; ++r) {
+    unsigned long long best = 0ull;
+    for (int j = lane; j < N; j += 64) {
+      const unsigned long long c = topk_word(topk_key(y_at(j)), j);
+      if (c < prev && c > best) best = c;
+    }
+    best = wave_max_u64(best);
+    prev = best;
+    if (lane == r) mine = best;
+  }
+  if (lane < K) {
+    const float y = topk_val((uint32_t)(mine >> 32));
+    idx[(size_t)row * K + lane] = (long long)(0x7fffffffu - (uint32_t)mine);
+    probs[(size_t)row * K + lane] = expf(topk_arg(scale, y, m)) / sum;
+  }
+}
+
+template <typename T>
+static void launch_softmax_topk(const void* logits, long long ld, const unsigned char* allowed, long long allowed_ld, float scale, long long* idx,
+                                float* probs, float* logits_f, int B, int N, int K, hipStream_t st) {
+  hipLaunchKernelGGL(softmax_topk_kernel<T>, dim3((B + 3) / 4), dim3(256), 0, st, (const T*)logits, ld, allowed, allowed_ld, scale, idx, probs,
+                     logits_f, B, N, K);
+}
+
+extern "C" int vqa_softmax_topk(int dtype, const void* logits, long long ld, const unsigned char* allowed, long long allowed_ld, float scale,
+                                long long* idx, float* probs, float* logits_f, int B, int N, int K, hipStream_t st) {
+  if (!logits || !idx || !probs || B < 1 || N < 1 || K < 1 || K > 64 || K > N || ld < N || (allowed_ld != 0 && allowed_ld < N)
+      || !(scale > 0.f) || !(scale <= 3.402823466e38f) || (dtype != 0 && dtype != 1)) return VQA_EARG;
+  DT(launch_softmax_topk<float>(logits, ld, allowed, allowed_ld, scale, idx, probs, logits_f, B, N, K, st),
+     launch_softmax_topk<bf16_t>(logits, ld, allowed, allowed_ld, scale, idx, probs, logits_f, B, N, K, st));
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Soft answer scores (VQA v2: ten annotator answers per question, acc(ans) = min(1, #agreeing annotators / 3),
 // utils/metrics.py:12-19, :136-184 VQAChallengeAccuracy).
 //   vqa_answer_scores              annotator ids [B][A] -> sparse soft targets {ids, counts, weights} [B][A], one wave per question

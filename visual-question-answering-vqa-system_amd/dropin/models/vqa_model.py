@@ -7,13 +7,16 @@ Extension (inference only): many questions per image from one image encoding -- 
 `encode_images(images) -> ImageContext` and `answer(context, token_ids, ...)`.
 Extension (training): `forward_grouped(images, token_ids, attention_mask, image_index)` runs one CNN pass per image and trains
 through it; `group_by_image(image_ids)` turns a batch's image ids into that form.
+Extension (inference only): `predict_topk(...)` / `answer_topk(context, ...)` return the k best answers with their probabilities
+(`TopK`) from one extra launch inside the captured graph, with an optional answer whitelist and softmax temperature.
 There is no CPU path: calling forward with CPU tensors, or without the built extension, raises.
 """
 from __future__ import annotations
 
 import importlib
+import math
 import os
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Callable, Dict, List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -421,6 +424,22 @@ def _count_optimizer_step(optimizer, args, kwargs):
 
 
 _optim_hooks.register_optimizer_step_post_hook(_count_optimizer_step)
+
+
+class TopK(NamedTuple):
+    """The k best answers of N questions (VQAModel.predict_topk / answer_topk): best first, ties by the lower index."""
+    indices: torch.Tensor                    # int64 [N, k]
+    probs: torch.Tensor                      # float32 [N, k]
+    logits: Optional[torch.Tensor] = None    # float32 [N, num_answers] when return_logits=True
+
+    def to_records(self, decode: Callable[[int], str]) -> List[Dict]:
+        """Per question the dictionary of api/inference.py:236-253 without its 'question' key; decode maps an answer index to its
+        string (the answer vocabulary's decode).  Two read-backs for the whole batch (one .tolist() per tensor)."""
+        out = []
+        for irow, prow in zip(self.indices.tolist(), self.probs.tolist()):
+            answers = [{"answer": decode(i), "probability": p, "index": i} for i, p in zip(irow, prow)]
+            out.append({"answers": answers, "top_answer": answers[0]["answer"], "confidence": answers[0]["probability"]})
+        return out
 
 
 class ImageContext:
@@ -899,6 +918,142 @@ class VQAModel(nn.Module):
             idx = self._implied_index(U, N, dev)
         logits, aux = eng.answer(ec, token_ids, maskf, idx, want_aux=return_aux)
         return (logits, aux) if return_aux else (logits, None)
+
+    # ---- top-k answers with probabilities (extension, inference only)
+    def _topk_args(self, top_k, answer_mask, temperature, N: int, dev):
+        """Checked (k, mask | None, scale = fp32(1 / temperature)) of predict_topk / answer_topk; ValueError for what they refuse."""
+        A = self.num_answers
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or not 1 <= top_k <= min(64, A):
+            raise ValueError(f"top_k must be an integer in 1 ... {min(64, A)}, got {top_k!r}")
+        try:
+            t = float(temperature)
+        except (TypeError, ValueError):
+            raise ValueError(f"temperature must be a positive finite number, got {temperature!r}") from None
+        scale = torch.tensor(1.0 / t, dtype=torch.float32).item() if (math.isfinite(t) and t > 0.0) else 0.0
+        if not (math.isfinite(scale) and scale > 0.0):
+            raise ValueError(f"temperature must be finite and > 0 (with 1 / temperature a positive finite float32), got {temperature!r}")
+        if answer_mask is not None:
+            if (not isinstance(answer_mask, torch.Tensor) or answer_mask.dtype not in (torch.bool, torch.uint8)
+                    or tuple(answer_mask.shape) not in ((A,), (N, A))):
+                raise ValueError(f"answer_mask must be a bool or uint8 tensor of shape [{A}] or [{N}, {A}], got "
+                                 + (f"{answer_mask.dtype} {tuple(answer_mask.shape)}" if isinstance(answer_mask, torch.Tensor)
+                                    else type(answer_mask).__name__))
+            if answer_mask.device != dev:
+                raise ValueError(f"answer_mask must be on the model's device ({dev}), got {answer_mask.device}")
+            answer_mask = answer_mask.contiguous()
+        return top_k, answer_mask, scale
+
+    def _topk_route(self, base_key, N, init, feed, logits_fn, k, mask, scale, want):
+        """logits_fn(*inputs) (logits in the compute dtype), then vqa_softmax_topk.  Up to graph_max_batch rows both are ONE captured
+        graph, keyed on base_key + ("topk", k, mask shape, scale, want): init() makes the static inputs on a miss, feed (None = keep
+        what was captured) is copied into them, and copies of the static outputs are returned.  Larger batches: the same two steps
+        eagerly on feed.  The scale is part of the key (it is a launch argument frozen into the graph), so every new temperature is a
+        capture, and these graphs share the graph_max_shapes LRU with those of forward() / answer()."""
+        tk = self._pkg.kernels.softmax_topk
+
+        def tail(lg, msk):
+            idx, probs, lf = tk(lg, k, msk, scale, want_logits=want and lg.dtype != torch.float32)
+            return lg, idx, probs, lf
+
+        if self.graph_inference and 0 < N <= self.graph_max_batch and not torch.cuda.is_current_stream_capturing():
+            key = base_key + ("topk", k, None if mask is None else tuple(mask.shape), float(scale), bool(want))
+            g = self._graphs.pop(key, None)
+            fresh = g is None
+            if fresh:
+                st = init()                          # (clones of feed: nothing to copy in before this first replay)
+                st_mask = None if mask is None else mask.clone()
+                graph, out = self._capture(lambda: tail(logits_fn(*st), st_mask))
+                g = (graph, st, st_mask, out)
+            self._graph_put(key, g)                  # (re)inserted at the young end of the LRU order
+            graph, st, st_mask, (lg, idx, probs, lf) = g
+            if not fresh:
+                for s_, t in zip(st, feed):
+                    if t is not None:
+                        s_.copy_(t)
+                if st_mask is not None:
+                    st_mask.copy_(mask)
+            graph.replay()
+            return TopK(idx.clone(), probs.clone(), (lg if lf is None else lf).clone() if want else None)
+        lg, idx, probs, lf = tail(logits_fn(*feed), mask)
+        return TopK(idx, probs, (lg if lf is None else lf) if want else None)
+
+    def predict_topk(self, images: torch.Tensor, token_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, top_k: int = 5,
+                     image_index: Optional[torch.Tensor] = None, answer_mask: Optional[torch.Tensor] = None, temperature: float = 1.0,
+                     return_logits: bool = False) -> TopK:
+        """The top_k best answers of every question with their probabilities: kernels.softmax_topk(forward(...)[0], top_k, answer_mask,
+        1 / temperature) bit for bit, with the forward and the top-k launch in one captured HIP graph up to graph_max_batch questions
+        (keyed on the shapes, top_k, the mask's shape, the temperature and return_logits).  Inference only: eval mode (it is NOT set
+        for the caller: train mode raises RuntimeError), no autograd; image_index as in forward().  answer_mask: bool / uint8
+        [num_answers] or [N, num_answers] on the model's device, True = the answer may be given; a row with fewer than top_k allowed
+        answers ends with not-allowed ones at probability 0 (lowest index first), a row with none (or an all-padding question, whose
+        logits are NaN) gets NaN probabilities and indices 0 ... top_k-1.  Ties go to the lower index.  ValueError for top_k outside
+        1 ... min(64, num_answers), a temperature that is not finite and > 0, or a mask of another shape / dtype / device.
+        Keep to a few fixed temperatures on the graphed route: each distinct (top_k, mask shape, temperature, return_logits) is a graph
+        of its own -- two warm-up forwards, a capture and static copies of the inputs on first use -- in the same graph_max_shapes-entry
+        LRU as the graphs of forward() / answer(), which a stream of new values would evict.  A per-request temperature belongs on the
+        eager route (graph_inference = False, or kernels.softmax_topk on forward()'s logits)."""
+        if not images.is_cuda:
+            raise RuntimeError("VQAModel (HIP) got CPU inputs; this implementation only runs on an MI355X (no CPU fallback)")
+        self._inference_only("predict_topk", images)
+        eng = self._ensure_engine()
+        images = images.contiguous().float()
+        token_ids = token_ids.contiguous().long()
+        maskf = None if attention_mask is None else attention_mask.contiguous().float()
+        U, N = images.shape[0], token_ids.shape[0]
+        if image_index is None:
+            k, amask, scale = self._topk_args(top_k, answer_mask, temperature, U, images.device)
+            key = (tuple(images.shape), tuple(token_ids.shape), maskf is not None, self._flat.data_ptr(), eng.fold_eval,
+                   getattr(eng, "fuse_stem_eval", None), self._infer_precision)
+            feed = [images, token_ids, maskf]
+            graphed = self.graph_inference and 0 < U <= self.graph_max_batch and not torch.cuda.is_current_stream_capturing()
+            plan = None if graphed else self._modes_plan()           # (forward()'s two eval routes)
+            fn = lambda x, ids, msk: eng.forward(x, ids, msk, False, False, need_tape=False, lowp_logits=True, plan=plan)[0]
+            return self._topk_route(key, U, lambda: [None if t is None else t.detach().clone() for t in feed], feed, fn,
+                                    k, amask, scale, return_logits)
+        idx = self._image_index(image_index, U, N, images.device)
+        if idx is None:
+            idx = self._implied_index(U, N, images.device)
+        k, amask, scale = self._topk_args(top_k, answer_mask, temperature, N, images.device)
+        key = ("image_index", tuple(images.shape), tuple(token_ids.shape), maskf is not None, self._flat.data_ptr(), eng.fold_eval,
+               eng.fuse_stem_eval, self._infer_precision)
+        feed = [images, token_ids, maskf, idx]
+        fn = lambda x, ids, msk, ix: eng.answer(eng.encode_images(x), ids, msk, ix, lowp_logits=True)[0]
+        return self._topk_route(key, N, lambda: [None if t is None else t.detach().clone() for t in feed], feed, fn,
+                                k, amask, scale, return_logits)
+
+    def answer_topk(self, context: ImageContext, token_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, top_k: int = 5,
+                    image_index: Optional[torch.Tensor] = None, answer_mask: Optional[torch.Tensor] = None, temperature: float = 1.0,
+                    return_logits: bool = False) -> TopK:
+        """predict_topk over a context of encode_images(): kernels.softmax_topk(answer(context, ...)[0], ...) bit for bit, the question
+        path and the top-k launch in one captured graph up to graph_max_batch questions.  The rules of answer() (inference only, a
+        stale context raises RuntimeError) and the arguments of predict_topk()."""
+        if not isinstance(context, ImageContext) or context._handle != self._handle:
+            raise ValueError("answer_topk() needs an ImageContext made by this model's encode_images()")
+        self._inference_only("answer_topk")
+        eng = self._ensure_engine()
+        if context._stamp != self._ctx_stamp(eng):
+            raise RuntimeError("stale ImageContext: the parameters, BatchNorm buffers or inference precision changed since "
+                               "encode_images() made it; encode the images again")
+        if not token_ids.is_cuda:
+            raise RuntimeError("VQAModel (HIP) got CPU inputs; this implementation only runs on an MI355X (no CPU fallback)")
+        token_ids = token_ids.contiguous().long()
+        U, (N, L) = context.num_images, token_ids.shape
+        dev = token_ids.device
+        idx = self._image_index(image_index, U, N, dev)
+        maskf = None if attention_mask is None else attention_mask.contiguous().float()
+        k, amask, scale = self._topk_args(top_k, answer_mask, temperature, N, dev)
+        ec = context._eng
+        key = ("answer", U, N, L, maskf is not None, idx is None, self._flat.data_ptr(), self._infer_precision)
+        ntok = ec["ntok"]
+        fn = lambda kv, ids, msk, ix: eng.answer({"kv": kv, "U": U, "ntok": ntok}, ids, msk, ix, lowp_logits=True)[0]
+
+        def init():
+            return [ec["kv"].clone(), token_ids.clone(), None if maskf is None else maskf.clone(),
+                    self._implied_index(U, N, dev) if idx is None else idx.clone()]
+
+        graphed = self.graph_inference and 0 < N <= self.graph_max_batch and not torch.cuda.is_current_stream_capturing()
+        feed = [ec["kv"], token_ids, maskf, idx if (graphed or idx is not None) else self._implied_index(U, N, dev)]
+        return self._topk_route(key, N, init, feed, fn, k, amask, scale, return_logits)
 
     graph_inference = True        # eval-mode no-grad forward()/predict() replay a captured HIP graph up to graph_max_batch
     graph_max_batch = 64          # (the serving case, api/inference.py:196-323: model(...) at B = 1 ... a few)

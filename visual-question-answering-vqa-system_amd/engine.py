@@ -1063,12 +1063,14 @@ class HipEngine:
             ctx.update(feat=feat, img=img, Hf=H, Wf=W, Cf=C)
         return ctx
 
-    def answer(self, ctx: dict, token_ids: torch.Tensor, maskf: Optional[torch.Tensor], kv_index: torch.Tensor, want_aux: bool = False):
+    def answer(self, ctx: dict, token_ids: torch.Tensor, maskf: Optional[torch.Tensor], kv_index: torch.Tensor, want_aux: bool = False,
+               lowp_logits: bool = False):
         """The question half of the eval forward over a context of encode_images(): text encoder, every cross layer's query path with
         vqa_attention_fwd(_mfma)_idx over the cached K / V (question i attends to image kv_index[i]), the masked pools, the gate,
         output_norm and the head.  kv_index: int32 [N] on the device, every entry in [0, ctx["U"]) (the caller checks).  All on the
         current stream, no tape, no weight cast: the compute-dtype weights are those encode_images() cast (the drop-in refuses a context
-        once the parameters changed).  Returns (fp32 logits [N][num_answers], aux | None)."""
+        once the parameters changed).  Returns (fp32 logits [N][num_answers], aux | None); lowp_logits: the logits stay in the compute
+        dtype and the cast launch is skipped (forward's keyword; vqa_softmax_topk reads bf16 and leaves the fp32 copy itself)."""
         cfg, T = self.cfg, self.dtype
         self._site = 0
         d, heads = cfg["embed_dim"], cfg["num_attention_heads"]
@@ -1119,7 +1121,7 @@ class HipEngine:
         h1 = self._lin(fused, c + ".0.weight", c + ".0.bias", relu=1, p=0.0, seed=s1)
         h2 = self._lin(h1, c + ".3.weight", c + ".3.bias", relu=1, p=0.0, seed=s2)
         logits = self._lin(h2, c + ".6.weight", c + ".6.bias")
-        logits_f = logits.float() if T != torch.float32 else logits
+        logits_f = logits.float() if (T != torch.float32 and not lowp_logits) else logits
         aux = None
         if want_aux:
             if "feat" not in ctx:

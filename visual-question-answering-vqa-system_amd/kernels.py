@@ -683,3 +683,27 @@ def layernorm_bwd(dout, x, gamma, stats, dgamma, dbeta, *, addend=None, drop_p=0
             off, nr, st, nc, n0 = folds[1]
             foldq.append((ws, off, nr, st, nc, dadd, n0, None))
     return dx
+
+
+def softmax_topk(logits, k, allowed=None, scale=1.0, want_logits=False):
+    """The k best columns of every row of logits [B][N] (fp32 or bf16, unit column stride, any row stride >= N) with their softmax
+    probabilities, one launch (vqa_softmax_topk).  allowed: bool / uint8 [N] (shared) or [B][N], non-zero = the column may be picked
+    (the others count as -inf); scale = 1 / temperature.  Order: value descending, ties and NaNs (which rank first) by index -- a
+    stable descending sort.  Returns (indices int64 [B][k], probs fp32 [B][k], fp32 copy of the raw logits [B][N] | None)."""
+    B, N = logits.shape
+    if logits.stride(1) != 1 and N > 1:
+        raise ValueError("softmax_topk: logits need a unit column stride")
+    ld = logits.stride(0) if B > 1 else max(logits.stride(0), N)
+    ald = 0
+    if allowed is not None:
+        if allowed.dtype not in (torch.bool, torch.uint8) or tuple(allowed.shape) not in ((N,), (B, N)) or allowed.device != logits.device:
+            raise ValueError(f"softmax_topk: allowed must be bool / uint8 [{N}] or [{B}, {N}] on {logits.device}")
+        allowed = allowed.contiguous()
+        if allowed.dtype == torch.bool:
+            allowed = allowed.view(torch.uint8)
+        ald = N if allowed.dim() == 2 else 0
+    idx = torch.empty((B, k), device=logits.device, dtype=torch.int64)
+    probs = torch.empty((B, k), device=logits.device, dtype=torch.float32)
+    lf = torch.empty((B, N), device=logits.device, dtype=torch.float32) if want_logits else None
+    call("vqa_softmax_topk", dt(logits), ptr(logits), ld, ptr(allowed), ald, float(scale), ptr(idx), ptr(probs), ptr(lf), B, N, int(k))
+    return idx, probs, lf
