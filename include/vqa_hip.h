@@ -398,6 +398,23 @@ int vqa_fold_group(int njobs, const float* const* part, const int* nrows, const 
    never read out of bounds, they add NaN to the loss and get a NaN gradient row. */
 int vqa_cross_entropy(int dtype, const void* logits, const long long* targets, float* loss, void* dlogits, float* logits_f32,
                       int B, int N, float gscale, int* err, float* ws /* B floats, or NULL: float atomics on *loss */, hipStream_t stream);
+/* nn.CrossEntropyLoss(weight=, ignore_index=, label_smoothing=) mean: vqa_cross_entropy's arguments, then the options.
+ * class_weight [N] fp32 (NULL: all ones); has_ignore 0: no target is ignored; label_smoothing eps in [0, 1].
+ * keep[b] = target b != ignore_index (also when ignore_index lies in [0, N)), wy[b] = keep[b] * w[t_b], W = sum_b wy[b], Sw = sum_c w[c]:
+ *   loss    += [ (1-eps) * sum_b wy[b] * (-lp[b][t_b]) + eps/N * sum_b keep[b] * sum_c w[c] * (-lp[b][c]) ] / W       (lp = log_softmax)
+ *   dlogits  = [ (1-eps) * wy[b] * (p[b][c] - [c == t_b]) + eps/N * keep[b] * (Sw * p[b][c] - w[c]) ] * gscale / W    (may be NULL)
+ * = F.cross_entropy(logits, target, weight, ignore_index=, label_smoothing=, reduction="mean").  An ignored row adds no loss term,
+ * gets a zero gradient row and is never counted in *err; any other target outside [0, N) is a bad target as in vqa_cross_entropy
+ * (it counts in W with weight 1).  W == 0 (all rows ignored, or all kept rows of weight 0): the loss is NaN as in torch, dlogits
+ * is all ZERO (torch: zero without weights, NaN with weights -- this entry deviates on purpose) and *empty (may be NULL) += 1.
+ * acc (may be NULL): VQAAccuracy's {correct, correct_top5, total} += over the kept rows in the same pass, vqa_accuracy_update's
+ * rank rule (lowest index wins ties), a bad target counts in total as wrong.  W and Sw are summed by every wave in one fixed order:
+ * with ws (B floats) there is no float atomic and two launches give the same bits.  With class_weight NULL, eps 0 and no ignored
+ * target every output has the bits of vqa_cross_entropy.  Status 1000 without a launch: NULL logits / targets, B or N < 1, dtype
+ * not 0 / 1, label_smoothing outside [0, 1] or NaN, gscale not finite. */
+int vqa_cross_entropy_opts(int dtype, const void* logits, const long long* targets, float* loss, void* dlogits, float* logits_f32,
+                           int B, int N, float gscale, int* err, float* ws, const float* class_weight, long long ignore_index,
+                           int has_ignore, float label_smoothing, unsigned long long* acc, int* empty, hipStream_t stream);
 int vqa_convert(int dtype_in, int dtype_out, const void* in, void* out, long long n, hipStream_t stream);
 /* clip_grad_norm_(max_norm) + AdamW over flat fp32 buffers (training/train.py:204-208,127-132).
    skip (device int, may be NULL): when skip[0] != 0 the launch changes NOTHING (parameters, moments) and adds skip[0] to

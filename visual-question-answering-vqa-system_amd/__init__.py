@@ -29,6 +29,11 @@ def load_dropin_soft_targets():
     return _load_dropin_file("vqa_hip_dropin_utils_soft_targets", "utils", "soft_targets.py")
 
 
+def load_dropin_losses():
+    """The drop-in `utils.losses` (CrossEntropyLoss with weight / ignore_index / label_smoothing as one fused launch)."""
+    return _load_dropin_file("vqa_hip_dropin_utils_losses", "utils", "losses.py")
+
+
 def _load_dropin_file(name, *rel):
     import importlib.util
     import os

@@ -118,6 +118,7 @@ SIGNATURES = {
     "vqa_bias_act_bwd_fold_rows": [I, I, I],
     "vqa_fold_group": [I, P, P, P, P, P, P, P, P],
     "vqa_cross_entropy": [I, P, P, P, P, P, I, I, F, P, P, P],
+    "vqa_cross_entropy_opts": [I, P, P, P, P, P, I, I, F, P, P, P, LL, I, F, P, P, P],
     "vqa_answer_scores": [P, P, P, P, I, I, I, I, P, P],
     "vqa_cross_entropy_soft": [I, P, P, P, I, P, P, P, I, I, F, P, P, P, P, P],
     "vqa_challenge_accuracy_update": [P, P, P, I, P, I, I, P],

@@ -13,18 +13,34 @@ the reference's own ATen model.  What does win is `sys.modules`: an import state
      reference's own (`training/train.py:47-49`; the drop-in's `utils/` and `data/` hold only the device-side pieces and
      must not shadow them),
   3. appends the reference's `models/` directory to the bound package's `__path__`, so `models.cnn_backbone` & co. (not
-     used by any entry point, but importable in the reference) still resolve to the reference's files.
+     used by any entry point, but importable in the reference) still resolve to the reference's files,
+  4. registers a LAST-resort finder for the drop-in's additions to `utils` that the reference has no file for (`utils.losses`):
+     `from utils.losses import CrossEntropyLoss` imports the reference's own `utils` package and then, only because that package
+     holds no `losses.py`, the drop-in's file.  A project that has its own `utils/losses.py` keeps it.
 Nothing here touches the GPU (no HIP call, no `torch.cuda.is_available()`): `run()` may be followed by anything.
 """
 from __future__ import annotations
 
 import importlib
+import importlib.abc
+import importlib.util
 import os
 import runpy
 import sys
 from typing import List, Optional
 
 _BOUND_NAMES = ("models", "models.vqa_model")
+_DROPIN_ONLY = {"utils.losses": ("utils", "losses.py")}      # drop-in modules without a counterpart in the reference
+
+
+class _DropinOnlyFinder(importlib.abc.MetaPathFinder):
+    """Appended to sys.meta_path: asked only after every regular finder found nothing."""
+
+    def find_spec(self, fullname, path=None, target=None):
+        rel = _DROPIN_ONLY.get(fullname)
+        if rel is None:
+            return None
+        return importlib.util.spec_from_file_location(fullname, os.path.join(dropin_dir(), *rel))
 
 
 def dropin_dir() -> str:
@@ -62,6 +78,8 @@ def bind(project_root: Optional[str] = None, dtype: Optional[str] = None):
                 sys.path.remove(d)
         if not is_bound():                             # a stale finder cache or a `models` earlier on the path: refuse loudly
             raise RuntimeError(f"bind(): models.vqa_model resolved to {getattr(mod, '__file__', '?')}, not to the drop-in")
+    if not any(isinstance(f, _DropinOnlyFinder) for f in sys.meta_path):
+        sys.meta_path.append(_DropinOnlyFinder())
     if project_root is not None:
         ref_models = os.path.join(os.path.abspath(project_root), "models")
         pkg = sys.modules["models"]

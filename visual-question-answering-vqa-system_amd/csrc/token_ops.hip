@@ -1943,6 +1943,139 @@ extern "C" int vqa_challenge_accuracy_update(const float* logits, const int* ids
 }
 
 // ---------------------------------------------------------------------------------------------
+// Cross entropy with nn.CrossEntropyLoss's constructor options (training/train.py:120): class weights w[N], ignore_index and label
+// smoothing eps, reduction "mean".  keep[b] = target b is not ignore_index, wy[b] = keep[b] * w[t_b], W = sum_b wy[b],
+// Sw = sum_c w[c], lp = log_softmax(x):
+//   loss    += [ (1-eps) * sum_b wy[b] * (-lp[b][t_b]) + eps/N * sum_b keep[b] * sum_c w[c] * (-lp[b][c]) ] / W
+//   dlogits  = [ (1-eps) * wy[b] * (p[b][c] - [c == t_b]) + eps/N * keep[b] * (Sw * p[b][c] - w[c]) ] * gscale / W
+// One wave per row and cross_entropy_kernel's operation order; without weights, smoothing and ignored rows W is (float)B, the
+// factor (1-eps) * wy is 1.0f and the smoothing branch is not taken: the same bits as cross_entropy_kernel.
+// W and Sw are needed before the first gradient element: EVERY wave sums the B gathered weights and the N weights itself, lane c
+// taking the indices c, c + 64, ... in ascending order and then the butterfly -- one fixed order, the same bits in every wave, no
+// second launch and no host sync.  (Without weights W is a count of kept rows, taken in integers.)
+// sum_c w[c] * lp[c] = sum_c w[c] * (x[c] - m) - log(s) * Sw rides in the pass that forms s = sum exp(x - m); x - m instead of the
+// plain x keeps the cancellation against lse * Sw out of it when a row sits at +-300.  With weights or smoothing the whole row is
+// evaluated in that log-softmax form, lp = (x - m) - log(s), which stays at fp32 accuracy for rows far from zero; without them
+// the kernel keeps cross_entropy_kernel's lse = m + log(s), lse - x_t and exp(x - lse) for its bits (and its accuracy there).
+// A bad target (outside [0, N) and not ignore_index) is cross_entropy_kernel's: *err += 1, NaN term, NaN row; it counts in W with
+// weight 1 (unweighted: W = number of rows that are not ignored, so the default call divides by B like cross_entropy_kernel).
+// W == 0 (every row ignored, or every kept row has weight 0): the loss is NaN as in torch, dlogits is ZERO (torch: zero
+// unweighted, NaN weighted -- a deliberate deviation, the step then runs on a zero gradient) and *empty += 1.
+// acc = VQAAccuracy's {correct, correct_top5, total} over the kept rows with accuracy_kernel's rank rule, in the same pass.
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void cross_entropy_opts_kernel(const T* __restrict__ logits, const long long* __restrict__ targets,
+                                                                 const float* __restrict__ cw, long long ignore_index, int has_ignore, float eps,
+                                                                 float* loss, T* __restrict__ dlogits, float* __restrict__ logits_f32, int B, int N,
+                                                                 float gscale, int* err, float* part, unsigned long long* acc, int* empty) {
+  const int lane = threadIdx.x & 63;
+  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (row >= B) return;                                                 // (wave-uniform: a wave owns one row)
+  float W, Sw;
+  if (cw) {
+    float a = 0.f;
+    for (int b = lane; b < B; b += 64) {
+      const long long tb = targets[b];
+      float w = 0.f;
+      if (!(has_ignore && tb == ignore_index)) {
+        w = 1.f;                                                        // a bad target: never read out of bounds
+        if (tb >= 0 && tb < (long long)N) w = cw[tb];
+      }
+      a += w;
+    }
+    W = wave_sum(a);
+    a = 0.f;
+    for (int c = lane; c < N; c += 64) a += cw[c];
+    Sw = wave_sum(a);
+  } else {
+    int k = 0;
+    for (int b = lane; b < B; b += 64) k += (has_ignore && targets[b] == ignore_index) ? 0 : 1;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) k += __shfl_xor(k, o, 64);
+    W = (float)k;
+    Sw = (float)N;
+  }
+  const bool none = W == 0.f;
+  if (row == 0 && lane == 0 && none && empty) atomicAdd(empty, 1);
+  const T* lr = logits + (size_t)row * N;
+  const long long t64 = targets[row];
+  if (has_ignore && t64 == ignore_index) {                              // ignored: no loss term, a zero gradient row, not counted
+    if (lane == 0) {
+      const float term = none ? __builtin_nanf("") : 0.f;
+      if (part) part[row] = term;
+      else if (loss) atomicAdd(loss, term);
+    }
+    for (int c = lane; c < N; c += 64) {
+      if (logits_f32) logits_f32[(size_t)row * N + c] = to_f<T>(lr[c]);
+      if (dlogits) dlogits[(size_t)row * N + c] = from_f<T>(0.f);
+    }
+    return;
+  }
+  const bool bad = t64 < 0 || t64 >= (long long)N;
+  const int t = bad ? 0 : (int)t64;
+  const bool smooth = eps != 0.f;
+  const bool lsm = smooth || cw;                                        // log-softmax form (see above); else cross_entropy_kernel's
+  float m = -INFINITY;
+  for (int c = lane; c < N; c += 64) m = fmaxf(m, to_f<T>(lr[c]));
+  m = wave_max(m);
+  const float xt = to_f<T>(lr[t]);
+  float s = 0.f, wx = 0.f, rank = 0.f;
+  for (int c = lane; c < N; c += 64) {
+    const float x = to_f<T>(lr[c]);
+    s += expf(x - m);
+    if (smooth) wx += (cw ? cw[c] : 1.f) * (x - m);
+    if (acc) rank += (x > xt || (x == xt && c < t)) ? 1.f : 0.f;
+  }
+  s = wave_sum(s);
+  if (smooth) wx = wave_sum(wx);
+  if (acc) rank = wave_sum(rank);
+  const float logs = logf(s);
+  const float lse = m + logs;
+  const float c1 = (1.f - eps) * (bad || !cw ? 1.f : cw[t]);            // (1-eps) * wy
+  const float epsn = eps / (float)N;
+  if (lane == 0) {
+    float term = c1 * (lsm ? logs - (xt - m) : lse - xt);
+    if (smooth) term += epsn * (logs * Sw - wx);
+    term = (bad || none) ? __builtin_nanf("") : term / W;
+    if (part) part[row] = term;
+    else if (loss) atomicAdd(loss, term);
+    if (bad && err) atomicAdd(err, 1);
+    if (acc) {                                                          // a bad target counts as wrong, like accuracy_kernel
+      if (!bad && rank < 0.5f) atomicAdd(acc + 0, 1ull);
+      if (!bad && rank < 4.5f) atomicAdd(acc + 1, 1ull);
+      atomicAdd(acc + 2, 1ull);
+    }
+  }
+  for (int c = lane; c < N; c += 64) {
+    const float x = to_f<T>(lr[c]);
+    if (logits_f32) logits_f32[(size_t)row * N + c] = x;
+    if (dlogits) {
+      const float p = lsm ? expf((x - m) - logs) : expf(x - lse);
+      float g = c1 * (p - (c == t ? 1.f : 0.f));
+      if (smooth) g += epsn * (Sw * p - (cw ? cw[c] : 1.f));
+      g = g * gscale / W;
+      dlogits[(size_t)row * N + c] = from_f<T>(bad ? __builtin_nanf("") : (none ? 0.f : g));
+    }
+  }
+}
+
+// vqa_cross_entropy's arguments and ws (B floats or nullptr), then the options; class_weight nullptr = all ones, has_ignore 0 = no
+// target is ignored, acc / empty optional.  Nothing is launched on an argument error.
+extern "C" int vqa_cross_entropy_opts(int dtype, const void* logits, const long long* targets, float* loss, void* dlogits, float* logits_f32,
+                                      int B, int N, float gscale, int* err, float* ws, const float* class_weight, long long ignore_index,
+                                      int has_ignore, float label_smoothing, unsigned long long* acc, int* empty, hipStream_t st) {
+  if (!logits || !targets || B <= 0 || N <= 0 || (dtype != 0 && dtype != 1)) return VQA_EARG;
+  if (!(label_smoothing >= 0.f && label_smoothing <= 1.f) || !(fabsf(gscale) <= 3.402823466e38f)) return VQA_EARG;   // (NaN fails both)
+  dim3 grid((B + 3) / 4);
+  DT(hipLaunchKernelGGL(cross_entropy_opts_kernel<float>, grid, dim3(256), 0, st, (const float*)logits, targets, class_weight, ignore_index,
+                        has_ignore, label_smoothing, loss, (float*)dlogits, logits_f32, B, N, gscale, err, ws, acc, empty),
+     hipLaunchKernelGGL(cross_entropy_opts_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)logits, targets, class_weight, ignore_index,
+                        has_ignore, label_smoothing, loss, (bf16_t*)dlogits, logits_f32, B, N, gscale, err, ws, acc, empty));
+  if (ws && loss) launch_fold(ws, B, 1, 1, loss, 1, nullptr, st);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Many questions per image in TRAINING (VQAModel.forward_grouped, HipTrainer.step(image_index=)).
 //   vqa_index_csr              questions of each image in ascending question order (CSR), one workgroup, no host sync
 //   vqa_attention_fwd(_mfma)_idx_train   the indexed forwards with dropout: the mask of (question b, head, i, j) is the one

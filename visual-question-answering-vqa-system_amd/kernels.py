@@ -89,6 +89,8 @@ HBM_BYTES = {
     "vqa_cross_entropy": ("token", lambda a: a[6] * a[7] * (_ES(a[0]) + 4)),
     # soft targets: the logits traffic of the hard kernel + ids, weights, counts [B][K]; the annotator ids are 8 bytes in, 12 out
     "vqa_cross_entropy_soft": ("token", lambda a: a[8] * a[9] * (_ES(a[0]) + 4) + a[8] * a[4] * (8 + 4 * _P(a[13]))),
+    # options: the hard kernel's logits traffic + the targets and the class weights once (every wave re-reads them from cache)
+    "vqa_cross_entropy_opts": ("token", lambda a: a[6] * a[7] * (_ES(a[0]) + 4) + a[6] * 8 + a[7] * 4 * _P(a[11])),
     "vqa_challenge_accuracy_update": ("token", lambda a: a[5] * a[6] * 4 + a[5] * a[3] * 8),
     "vqa_answer_scores": ("token", lambda a: a[4] * a[5] * 20),
     # weight staging and the optimizer tail (H, N1): cast of the flat buffer, packed data-gradient operands, sum of squares, AdamW
@@ -707,3 +709,28 @@ def softmax_topk(logits, k, allowed=None, scale=1.0, want_logits=False):
     lf = torch.empty((B, N), device=logits.device, dtype=torch.float32) if want_logits else None
     call("vqa_softmax_topk", dt(logits), ptr(logits), ld, ptr(allowed), ald, float(scale), ptr(idx), ptr(probs), ptr(lf), B, N, int(k))
     return idx, probs, lf
+
+
+def cross_entropy_opts(logits, targets, *, class_weight=None, ignore_index=None, label_smoothing=0.0, loss=None, need_grad=True,
+                       logits_f32=None, gscale=1.0, err=None, fixed_order=True, acc=None, empty=None):
+    """F.cross_entropy(logits, targets, weight=class_weight, ignore_index=, label_smoothing=, reduction="mean") and its gradient in one
+    launch (vqa_cross_entropy_opts; include/vqa_hip.h has the formulas and the W == 0 rule).  logits [B][N] fp32 or bf16, contiguous;
+    targets int64 [B]; class_weight fp32 [N] on the device or None; ignore_index None: no target is ignored.
+    loss (fp32, one element) is accumulated into and created zeroed when None; err / empty: int32 device counters (+=) or None;
+    acc: VQAAccuracy's three int64 counters or None; logits_f32: an fp32 [B][N] tensor to fill or None.
+    fixed_order: the row terms are folded in row order (bit-reproducible); False -> float atomics on the loss.
+    Returns (loss, dlogits in the dtype of logits | None)."""
+    B, N = logits.shape
+    if not logits.is_contiguous() or targets.dtype != torch.int64 or tuple(targets.shape) != (B,) or not targets.is_contiguous():
+        raise ValueError("cross_entropy_opts: contiguous logits [B, N] and contiguous int64 targets [B] expected")
+    if class_weight is not None and (class_weight.dtype != torch.float32 or tuple(class_weight.shape) != (N,)
+                                     or class_weight.device != logits.device or not class_weight.is_contiguous()):
+        raise ValueError(f"cross_entropy_opts: class_weight must be a contiguous fp32 [{N}] tensor on {logits.device}")
+    if loss is None:
+        loss = torch.zeros((), device=logits.device, dtype=torch.float32)
+    dlogits = torch.empty_like(logits) if need_grad else None
+    ws = torch.empty((B,), device=logits.device, dtype=torch.float32) if fixed_order else None
+    call("vqa_cross_entropy_opts", dt(logits), ptr(logits), ptr(targets), ptr(loss), ptr(dlogits), ptr(logits_f32), B, N, float(gscale),
+         ptr(err), ptr(ws), ptr(class_weight), 0 if ignore_index is None else int(ignore_index), int(ignore_index is not None),
+         float(label_smoothing), ptr(acc), ptr(empty))
+    return loss, dlogits

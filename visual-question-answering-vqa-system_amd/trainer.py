@@ -160,9 +160,12 @@ def _is_soft(targets) -> bool:
 
 class HipTrainer:
     def __init__(self, model, lr=1e-4, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
-                 process_group=None, overlap=True, force_reducer=False):
+                 process_group=None, overlap=True, force_reducer=False, label_smoothing=0.0, class_weight=None, ignore_index=None):
         self.model = model
         self.engine = model._ensure_engine()
+        # nn.CrossEntropyLoss's constructor options for hard labels (all at their defaults: the plain loss launch, unchanged)
+        self.label_smoothing, self.ignore_index, self.class_weight = self._check_loss_opts(label_smoothing, class_weight, ignore_index)
+        self._loss_opts = self.label_smoothing != 0.0 or self.class_weight is not None or self.ignore_index is not None
         self.lr, self.wd, self.betas, self.eps, self.max_norm = lr, weight_decay, betas, eps, max_grad_norm
         flat = model._flat
         self.G = torch.zeros_like(flat)
@@ -179,6 +182,7 @@ class HipTrainer:
         # step number as calls - skipped-ever on the device: a skipped step never advances the bias corrections, check() or not)
         self._bad = torch.zeros(3, device=flat.device, dtype=torch.int32)
         self.bad_targets = self._bad[:2]
+        self._empty = torch.zeros(1, device=flat.device, dtype=torch.int32)   # steps whose batch had zero total weight since check()
         self.calls = 0
         self._copy_sig = None                      # parameter-version signature right after the last fused AdamW launch
         self.buckets = LY.bucket_ranges(model._entries)
@@ -193,6 +197,26 @@ class HipTrainer:
         self._lag_class = [0] * len(model._param_entries)
         self._ranges = None                        # (table, R, n, frozen indices, nf) on the device
         self._lag = torch.zeros(len(model._param_entries), device=flat.device, dtype=torch.int32)
+
+    def _check_loss_opts(self, label_smoothing, class_weight, ignore_index):
+        """Validated (label_smoothing float, ignore_index int | None, class_weight fp32 [num_answers] on the device | None); host
+        logic on the caller's values, before anything is launched."""
+        eps = float(label_smoothing)
+        if not 0.0 <= eps <= 1.0:                          # (NaN fails both comparisons)
+            raise ValueError(f"HipTrainer: label_smoothing must lie in [0, 1], got {label_smoothing!r}")
+        if ignore_index is not None:
+            if isinstance(ignore_index, bool) or int(ignore_index) != ignore_index:
+                raise ValueError(f"HipTrainer: ignore_index must be an integer or None, got {ignore_index!r}")
+            ignore_index = int(ignore_index)
+        if class_weight is not None:
+            n = self.model.num_answers
+            w = torch.as_tensor(class_weight).detach().to("cpu", torch.float32)
+            if w.dim() != 1 or w.shape[0] != n:
+                raise ValueError(f"HipTrainer: class_weight must have {n} entries (num_answers), got shape {tuple(w.shape)}")
+            if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+                raise ValueError("HipTrainer: class_weight must be finite and non-negative")
+            class_weight = w.contiguous().to(self.model._flat.device)
+        return eps, ignore_index, class_weight
 
     def _set_mask(self, trainable):
         """Trainable set of this step (tuple of bools in layout order, or None for all): rebuild the range table when it changed."""
@@ -227,10 +251,19 @@ class HipTrainer:
         index.  None: exactly the plain step.
         targets may be a SoftTargets (dropin/utils/soft_targets.py: sparse soft answer scores, ids / weights / counts [B, K]): the loss
         is then F.cross_entropy with those probability-style targets (`vqa_cross_entropy_soft`), everything around it is the same step.
-        `metrics` must then be a VQAChallengeAccuracy (and the targets carry `counts`): it is counted inside the loss launch."""
+        `metrics` must then be a VQAChallengeAccuracy (and the targets carry `counts`): it is counted inside the loss launch.
+        With label_smoothing / class_weight / ignore_index given to the constructor the loss is F.cross_entropy with those options
+        (`vqa_cross_entropy_opts`) and a VQAAccuracy is counted inside that launch over the rows that are not ignored; SoftTargets
+        then raise TypeError.  A batch of zero total weight (every target ignored, or every kept target of class weight 0) has a NaN
+        loss and a ZERO gradient: the step still runs AdamW on it (weight decay and the moments' decay apply), which is what the
+        reference loop does with torch when every target is ignored; torch's NaN gradient in the weighted case is not reproduced.
+        Such steps are counted on the device and check() raises ValueError for them."""
         eng, T = self.engine, self.engine.dtype
         dev = self.G.device
         soft = _is_soft(targets)
+        if soft and self._loss_opts:
+            raise TypeError("HipTrainer.step: label_smoothing / class_weight / ignore_index apply to hard labels; "
+                            "SoftTargets cannot be combined with them")
         if metrics is not None and soft != hasattr(metrics, "_fused_acc"):
             raise TypeError("HipTrainer.step: soft targets are scored by VQAChallengeAccuracy, hard labels by VQAAccuracy "
                             f"(got {type(metrics).__name__} with {'SoftTargets' if soft else 'a label tensor'})")
@@ -277,11 +310,17 @@ class HipTrainer:
             call("vqa_cross_entropy_soft", dt(logits), ptr(logits), ptr(targets.ids), ptr(targets.weights), targets.ids.shape[1], ptr(self.loss),
                  ptr(dlogits), ptr(logits_f) if lowp else None, B, N, 1.0, ptr(self.bad_step), ptr(ce_ws),
                  None if acc is None else ptr(targets.counts), ptr(acc))
+        elif self._loss_opts:                              # VQAAccuracy's counters ride in the same launch (kept rows only)
+            fused = metrics is not None and hasattr(metrics, "_buf")
+            call("vqa_cross_entropy_opts", dt(logits), ptr(logits), ptr(targets), ptr(self.loss), ptr(dlogits), ptr(logits_f) if lowp else None,
+                 B, N, 1.0, ptr(self.bad_step), ptr(ce_ws), ptr(self.class_weight), self.ignore_index or 0, int(self.ignore_index is not None),
+                 self.label_smoothing, ptr(metrics._buf(dev)) if fused else None, ptr(self._empty))
         else:
+            fused = False
             call("vqa_cross_entropy", dt(logits), ptr(logits), ptr(targets), ptr(self.loss), ptr(dlogits), ptr(logits_f) if lowp else None, B, N, 1.0,
                  ptr(self.bad_step), ptr(ce_ws))           # per-row loss terms, folded in row order (bit-reproducible)
         self.reducer.reduce_aux(self.bad_step)             # every rank must skip the update of a step ANY rank rejects
-        if metrics is not None and not soft:
+        if metrics is not None and not soft and not fused:
             metrics.update(logits_f, targets)
         eng.backward(tape, dlogits, self.G, on_segment=self.reducer.on_segment if self.reducer.active else None)
         gscale = self.reducer.finish()
@@ -332,9 +371,16 @@ class HipTrainer:
 
     def check(self):
         """Host-side error check (one sync; call it per logging interval, not per step): raises like nn.CrossEntropyLoss does
-        (training/train.py:120) if any step since the last check saw a target outside [0, num_answers)."""
+        (training/train.py:120) if any step since the last check saw a target outside [0, num_answers).  With loss options it also
+        raises ValueError if any step's batch had zero total weight (see step())"""
         n, skipped = (int(x) for x in self.bad_targets.tolist())
         if n:
             self.bad_targets.zero_()
             raise IndexError(f"{n} target(s) out of range [0, {self.model.num_answers}) since the last check: {skipped} step(s) were "
                              "skipped on every rank (parameters and optimizer state untouched; that step's loss and gradients are NaN)")
+        if self._loss_opts:
+            e = int(self._empty.item())
+            if e:
+                self._empty.zero_()
+                raise ValueError(f"{e} step(s) since the last check had a batch of zero total weight (every target ignored, or every kept "
+                                 "target of class weight 0): their loss is NaN and AdamW ran on a zero gradient")
