@@ -702,28 +702,14 @@ class VQAModel(nn.Module):
         key = (tuple(images.shape), tuple(token_ids.shape), attention_mask is not None, self._flat.data_ptr(), self._ensure_engine().fold_eval,
                getattr(self._engine, "fuse_stem_eval", None), self._infer_precision)
         g = self._graphs.pop(key, None)
-        if g is not None:
-            self._graphs[key] = g                    # LRU: a hit moves the shape to the young end
-        else:
+        if g is None:
             st_img = images.detach().clone().contiguous().float()
             st_ids = token_ids.detach().clone().contiguous().long()
             st_msk = None if attention_mask is None else attention_mask.detach().clone().contiguous().float()
             with torch.no_grad():
-                side = torch.cuda.Stream()
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):                       # warm-up off the default stream, as graph capture requires
-                    for _ in range(2):
-                        self._forward_eager_eval(st_img, st_ids, st_msk)
-                torch.cuda.current_stream().wait_stream(side)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    out = self._forward_eager_eval(st_img, st_ids, st_msk)
+                graph, out = self._capture(lambda: self._forward_eager_eval(st_img, st_ids, st_msk))
             g = (graph, st_img, st_ids, st_msk, out)
-            if len(self._graphs) >= self.graph_max_shapes:
-                torch.cuda.synchronize()             # an evicted graph's private pool must outlive its last replay in flight
-                while len(self._graphs) >= self.graph_max_shapes:
-                    self._graphs.pop(next(iter(self._graphs)))
-            self._graphs[key] = g
+        self._graph_put(key, g)                      # (re)inserted at the young end of the LRU order
         graph, st_img, st_ids, st_msk, out = g
         st_img.copy_(images); st_ids.copy_(token_ids)
         if st_msk is not None:

@@ -389,14 +389,14 @@ class HipEngine:
                             bias=self.P(bname) if bname else None, relu=relu, drop_p=p, drop_seed=seed, addend=addend)
         return out
 
-    def _lin_multi(self, x, wnames):
+    def _lin_multi(self, x, wnames, out=None):
         """One GEMM over several bias-free Linear weights that sit back to back in the flat buffer ([sum N][K] view)."""
         e0 = self.E[wnames[0]]
         Kin = e0.shape[1]
         N = sum(self.E[w].shape[0] for w in wnames)
         M = x.shape[0]
         w = self.wsrc[e0.offset: e0.offset + N * Kin].view(N, Kin)
-        out, _, _ = K.igemm(x, w, M, N, Kin, K.linear_geom(M, Kin), dtype=self.dtype)
+        out, _, _ = K.igemm(x, w, M, N, Kin, K.linear_geom(M, Kin), dtype=self.dtype, out=out)
         return out
 
     def _lin_multi_bwd(self, dz, x_in, wnames, G, addend=None):
@@ -564,8 +564,10 @@ class HipEngine:
         kv_index (many questions per image, training included): int32 [N] on the device, every entry in [0, U) (the caller checks);
         images holds U images, token_ids N questions, and question i attends to image kv_index[i].  The image half (CNN, projector,
         norm_kv, K | V) runs at U images, the question half at N; the tape keeps the image index as CSR (vqa_index_csr) for the
-        backward, whose image-token gradient is then summed per image by vqa_attention_bwd(_mfma)_idx."""
-        cfg, T = self.cfg, self.dtype
+        backward, whose image-token gradient is then summed per image by vqa_attention_bwd(_mfma)_idx.
+        The launches themselves live in the forward parts below (_stem_fwd ... _aux_of), which encode_images() and answer() compose
+        too; this method owns what is particular to it: the plan, the tape, the streams and the order the parts are issued in."""
+        cfg = self.cfg
         self._site = 0
         if plan is not None:
             ctrain, ttrain, ftrain, htrain = plan.modes
@@ -576,13 +578,13 @@ class HipEngine:
         if ctrain or ttrain or ftrain or htrain:
             self.step_id += 1
         self.begin_step(for_backward=need_tape)
-        if ctrain and self.fuse_bn_finalize and T == torch.bfloat16:
+        if ctrain and self.fuse_bn_finalize and self.dtype == torch.bfloat16:
             self._acc_reset()                     # one memset for every BatchNorm accumulator of this forward
         tape: dict = {"training": ctrain, "B": images.shape[0], "Bq": token_ids.shape[0]}     # image rows, question rows
         if plan is not None and need_tape:
             tape["plan"] = plan
         training = ctrain                         # from here on `training` is the CNN's mode (BatchNorm)
-        B, _, IH, IW = images.shape
+        B = images.shape[0]
         pdrop = cfg["dropout"] if ttrain else 0.0          # text encoder
         pfus = cfg["dropout"] if ftrain else 0.0           # projector and cross-attention layers
         phead = cfg["answer_dropout"] if htrain else 0.0
@@ -595,63 +597,29 @@ class HipEngine:
         use_side = self.two_streams and self.side is not None
         if use_side:
             ev0 = torch.cuda.Event(); ev0.record(main)
-        # ---- stem: conv7x7/2 (from the NCHW fp32 image) + BN + ReLU + maxpool, A1
-        H1, W1 = (IH + 6 - 7) // 2 + 1, (IW + 6 - 7) // 2 + 1
-        M = B * H1 * W1
-        sgeom = (B, IH, IW, 3, H1, W1, 7, 7, 2, 3)
-        Hp, Wp = (H1 + 2 - 3) // 2 + 1, (W1 + 2 - 3) // 2 + 1
-        x = None
-        if self.fuse_stem_eval and not training and not cnn_tape and self.stem_w2 is not None:
-            # inference: the whole stem in one launch, the 112 x 112 conv output is never stored (no argmax: there is no backward)
-            x = K.stem_conv_pool(images, self.stem_w2, self._bn_coef("image_encoder.stem.1", None, 0, 64, M, False), B, IH, IW)
-        if x is None:
-            if self.stem_w2 is not None and K.stem_conv_blocks(B, IH, IW) > 0:
-                y, st, mt = K.stem_conv(images, self.stem_w2, B, IH, IW, training)
-            else:
-                y, st, mt = K.igemm(images, self.stem_w, M, 64, self.stem_kp, sgeom, dtype=T, loader=K.LOADER_STEM, want_stats=training)
-            coef = self._bn_coef("image_encoder.stem.1", st, mt, 64, M, training)
-            x = torch.empty((B * Hp * Wp, 64), device=dev, dtype=T)
-            idx = torch.empty((B * Hp * Wp, 64), device=dev, dtype=torch.uint8)
-            call("vqa_stem_pool_fwd", dt(T), ptr(y), ptr(coef), ptr(x), ptr(idx), B, H1, W1, 64)
-            if cnn_tape:
-                tape["stem"] = dict(images=images, y=y, coef=coef, idx=idx, geom=sgeom, H1=H1, W1=W1)
-        H, W, C = Hp, Wp, 64
+        x, H, W, stem_rec = self._stem_fwd(images, training, cnn_tape)
+        if stem_rec is not None:
+            tape["stem"] = stem_rec
         # ---- text encoder, A6-A8 (on the side stream; joined before fusion).  Issued behind stage 1: by then the GPU holds > 1 ms of
         #      queued work, which covers the millisecond the host spends on these ~100 launches (see the stem note above).
-        d, heads = cfg["embed_dim"], cfg["num_attention_heads"]
-        hd = d // heads
         Bt, L = token_ids.shape
-        rows = Bt * L
-        pe = self.buf["text_encoder.positional_encoding.pe"]
-        if L > pe.shape[1]:
-            raise RuntimeError(f"sequence length {L} exceeds max_question_length {pe.shape[1]}")
+        self._pos_enc(L)                          # (a question that is too long fails here, before the stages are issued)
+        ncl = cfg["num_cross_layers"]
         text = {}
 
         def issue_text():
             if use_side:
                 self.side.wait_event(ev0)                # weights cast + everything earlier on main is visible to the side stream
             with torch.cuda.stream(self.side if use_side else main):
-                emb_e = self.E["text_encoder.token_embedding.weight"]
-                sd0 = self._seed()
-                xt = torch.empty((rows, d), device=dev, dtype=T)
-                call("vqa_embed_fwd", dt(T), ptr(token_ids), ptr(self.P(emb_e.name)), ptr(pe), ptr(xt), rows, L, d, emb_e.shape[0],
-                     math.sqrt(d), float(pdrop), sd0)
-                tape["embed"] = dict(ids=token_ids, seed=sd0, p=pdrop)
-                tape["tlayers"] = []
-                for l in range(cfg["num_transformer_layers"]):
-                    p = f"text_encoder.layers.{l}"
-                    rec = self._attn_block_fwd(xt, xt, None, p + ".norm1", None, p + ".self_attention", maskf, Bt, L, L, heads, hd, pdrop,
-                                               p + ".norm2", p + ".ffn.fc1", p + ".ffn.fc2", self_attn=True)
-                    tape["tlayers"].append(rec)
-                    xt = rec["out"]
-                text["enc"], enc_st = self._ln(xt, "text_encoder.final_norm")
-                tape["final_norm"] = dict(x=xt, st=enc_st)
-                if self.hoist_cross and cfg["num_cross_layers"] >= 1:
-                    # the first cross-attention layer's norm_query + W_q need the text features only: issued here, beside the CNN,
-                    # instead of behind the CNN on the fusion chain (the critical path between CNN forward and CNN backward)
-                    p0 = "fusion.cross_attention.layers.0"
-                    text["q0"] = self._cross_q_path(text["enc"], p0 + ".norm_query", p0 + ".cross_attention")
+                # the first cross-attention layer's norm_query + W_q need the text features only: issued here, beside the CNN,
+                # instead of behind the CNN on the fusion chain (the critical path between CNN forward and CNN backward)
+                text["enc"], text["q0"] = self._text_fwd(token_ids, maskf, pdrop, tape, hoist_q=self.hoist_cross and ncl >= 1)
                 text["ev"] = torch.cuda.Event(); text["ev"].record()
+
+        def after_stage(s):
+            if s == 1:
+                issue_text()
+            if self.mark: self.mark(f"forward: stage{s}")
 
         csr = None
         if kv_index is not None:
@@ -663,16 +631,88 @@ class HipEngine:
             tape["csr"] = csr
         if self.mark: self.mark("forward: stem")
 
-        # ---- residual stages, A2-A5
-        folded = self._fold_bn() if (self.fold_eval and not training and not cnn_tape) else None
+        # [B*Hf*Wf, 512] == tokens of the projector (NHWC makes the permute free)
+        feat, Hf, Wf, Cf, tape["stages"] = self._stages_fwd(x, B, H, W, training, cnn_tape, record=record, after_stage=after_stage)
+        ntok = Hf * Wf
+        tape["feat"] = dict(Hf=Hf, Wf=Wf, Cf=Cf)
+
+        # ---- fusion, A9-A11
+        enc = text["enc"]
+        if use_side:
+            main.wait_event(text["ev"])
+        img, tape["proj"] = self._projector_fwd(feat, ntok, pfus)
+        pre_kv = [None] * ncl
+        if self.hoist_cross and use_side and ncl > 1:
+            # every layer's K / V come from the SAME image tokens: layers >= 1 are projected on the (now idle) text stream while
+            # layer 0 runs here.  img lives on this stream and is read there; the results live there and are read here: both are
+            # ordered by the events below and kept alive by the tape (forward-only: freed after the last wait, see DESIGN section 3)
+            ev_img = torch.cuda.Event(); ev_img.record(main)
+            self.side.wait_event(ev_img)
+            with torch.cuda.stream(self.side):
+                for l in range(1, ncl):
+                    p = f"fusion.cross_attention.layers.{l}"
+                    pre_kv[l] = (self._cross_kv_path(img, p + ".norm_kv", p + ".cross_attention", cfg["embed_dim"]), torch.cuda.Event())
+                    pre_kv[l][1].record()
+
+        def kv_of(l):                             # layer l's hoisted K | V, joined just before that layer is issued
+            if pre_kv[l] is None:
+                return None
+            pkv, ev_kv = pre_kv[l]
+            main.wait_event(ev_kv)
+            return pkv
+
+        q, probs_all, caw = self._cross_layers_fwd(enc, img, Bt, L, ntok, pfus, want_aux, q0=text["q0"], kv_of=kv_of, csr=csr, tape=tape)
+        logits, cat, fused, tape["pool"], tape["head"] = self._tail_fwd(q, enc, maskf, Bt, L, phead, lowp_logits)
+        if caw is not None:
+            tape["caw"] = caw
+        aux = self._aux_of(feat, B, Hf, Wf, Cf, img, enc, cat, fused, probs_all) if want_aux else None
+        return logits, aux, (tape if need_tape else None)
+
+    # ------------------------------------------------------------------ forward parts
+    # Every launch of a forward is issued by exactly one of the methods below; forward(), encode_images() and answer() are
+    # compositions of them.  What varies between the routes comes in as plain arguments (a mode, dropout probabilities, a tape dict
+    # or None, a destination, an image index); streams, events, begin_step, step_id and the _site reset stay with the public methods.
+    def _stem_fwd(self, images, training, keep):
+        """conv7x7/2 (from the NCHW fp32 image) + BN + ReLU + maxpool, A1.  keep: the caller's tape wants the stem's activations (the
+        one-launch inference form keeps none).  Returns (pooled [B*Hp*Wp][64], Hp, Wp, tape record | None)."""
+        T, dev = self.dtype, images.device
+        B, _, IH, IW = images.shape
+        H1, W1 = (IH + 6 - 7) // 2 + 1, (IW + 6 - 7) // 2 + 1
+        M = B * H1 * W1
+        sgeom = (B, IH, IW, 3, H1, W1, 7, 7, 2, 3)
+        Hp, Wp = (H1 + 2 - 3) // 2 + 1, (W1 + 2 - 3) // 2 + 1
+        if self.fuse_stem_eval and not training and not keep and self.stem_w2 is not None:
+            # inference: the whole stem in one launch, the 112 x 112 conv output is never stored (no argmax: there is no backward)
+            x = K.stem_conv_pool(images, self.stem_w2, self._bn_coef("image_encoder.stem.1", None, 0, 64, M, False), B, IH, IW)
+            if x is not None:
+                return x, Hp, Wp, None
+        if self.stem_w2 is not None and K.stem_conv_blocks(B, IH, IW) > 0:
+            y, st, mt = K.stem_conv(images, self.stem_w2, B, IH, IW, training)
+        else:
+            y, st, mt = K.igemm(images, self.stem_w, M, 64, self.stem_kp, sgeom, dtype=T, loader=K.LOADER_STEM, want_stats=training)
+        coef = self._bn_coef("image_encoder.stem.1", st, mt, 64, M, training)
+        x = torch.empty((B * Hp * Wp, 64), device=dev, dtype=T)
+        idx = torch.empty((B * Hp * Wp, 64), device=dev, dtype=torch.uint8)
+        call("vqa_stem_pool_fwd", dt(T), ptr(y), ptr(coef), ptr(x), ptr(idx), B, H1, W1, 64)
+        return x, Hp, Wp, (dict(images=images, y=y, coef=coef, idx=idx, geom=sgeom, H1=H1, W1=W1) if keep else None)
+
+    def _stages_fwd(self, x, B, H, W, training, keep, record=None, after_stage=None):
+        """Residual stages with their SE / spatial attention, A2-A5, from the pooled stem output x [B*H*W][64].  Eval without kept
+        activations (not training, not keep, fold_eval) runs the Conv+BN-folded blocks, bf16 or MXFP8 (infer_precision; `record`
+        as in forward()); everything else the training blocks with their BatchNorm routes.  keep: the stage records are returned
+        for the tape (otherwise a stage's activations are freed as the next stage runs).  after_stage(s): called when stage s has
+        been issued (forward() issues the text encoder behind stage 1 there).
+        Returns (features [B*H*W][C], H, W, C, stage records)."""
+        T, dev, C = self.dtype, x.device, 64
+        if self.infer_precision not in ("bf16", "mxfp8"):
+            raise ValueError(f"unknown infer_precision {self.infer_precision!r}")
+        folded = self._fold_bn() if (self.fold_eval and not training and not keep) else None
         foldmx, xq = None, None                   # MXFP8 folded weights; MXFP8 copy of the current block input (if one exists)
         if folded is not None and self.infer_precision == "mxfp8":
             if T != torch.bfloat16:
                 raise RuntimeError("infer_precision 'mxfp8' needs the bf16 compute dtype")
             foldmx = self._fold_mxfp8()
-        elif self.infer_precision not in ("bf16", "mxfp8"):
-            raise ValueError(f"unknown infer_precision {self.infer_precision!r}")
-        tape["stages"] = []
+        srecs = []
         for s, Cout in enumerate(LY.STAGE_CHANNELS, start=1):
             srec = {"blocks": []}
             for b in range(2):
@@ -712,7 +752,7 @@ class HipEngine:
                 facc = training and self.fuse_bn_finalize and T == torch.bfloat16
                 y1, st1, mt1, g1, Ho, Wo = self._conv(x, B, H, W, Cin, p + ".conv1.weight", Cout, 3, stride, 1, training, acc=facc)
                 M = B * Ho * Wo
-                fuse12 = (mt1 < 0 and self.fuse_bn_conv and cnn_tape and self._c64p_ok(B, Ho, Wo, Cout, Cout, 3, 1)
+                fuse12 = (mt1 < 0 and self.fuse_bn_conv and keep and self._c64p_ok(B, Ho, Wo, Cout, Cout, 3, 1)
                           and K.c64w_bn_ok(B, Ho, Wo))
                 if fuse12:                                   # conv2 normalises conv1's raw output in its LDS patch: a1 never exists
                     a1 = None
@@ -780,62 +820,118 @@ class HipEngine:
                      ptr(amap), ptr(out), B, H, W, C)
                 srec["spatial"] = dict(x=x, pooled2=pooled2, amax=amax, amap=amap, H=H, W=W, C=C)
                 x = out
-            if cnn_tape:                          # (without a tape the stage's activations are freed as the next stage runs)
-                tape["stages"].append(srec)
-            if s == 1:
-                issue_text()
-            if self.mark: self.mark(f"forward: stage{s}")
-        feat = x                                  # [B*Hf*Wf, 512] == tokens of the projector (NHWC makes the permute free)
-        Hf, Wf, Cf = H, W, C
-        ntok = Hf * Wf
-        tape["feat"] = dict(Hf=Hf, Wf=Wf, Cf=Cf)
+            if keep:
+                srecs.append(srec)
+            if after_stage is not None:
+                after_stage(s)
+        return x, H, W, C, srecs
 
-        # ---- fusion, A9-A11
-        enc, ev_txt = text["enc"], text["ev"]
-        if use_side:
-            main.wait_event(ev_txt)
+    def _pos_enc(self, L):
+        pe = self.buf["text_encoder.positional_encoding.pe"]
+        if L > pe.shape[1]:
+            raise RuntimeError(f"sequence length {L} exceeds max_question_length {pe.shape[1]}")
+        return pe
+
+    def _text_fwd(self, token_ids, maskf, p, tape=None, hoist_q=False):
+        """Text encoder, A6-A8, on the current stream: embedding, transformer layers, final_norm, with dropout p; their records go
+        into `tape` when one is given.  hoist_q: also norm_query + W_q of the first cross-attention layer, which need the text
+        features only.  Returns (encoded text [Bt*L][d], that layer's _cross_q_path result | None)."""
+        cfg, T = self.cfg, self.dtype
+        d, heads = cfg["embed_dim"], cfg["num_attention_heads"]
+        Bt, L = token_ids.shape
+        rows = Bt * L
+        pe = self._pos_enc(L)
+        emb_e = self.E["text_encoder.token_embedding.weight"]
+        sd0 = self._seed()
+        xt = torch.empty((rows, d), device=token_ids.device, dtype=T)
+        call("vqa_embed_fwd", dt(T), ptr(token_ids), ptr(self.P(emb_e.name)), ptr(pe), ptr(xt), rows, L, d, emb_e.shape[0],
+             math.sqrt(d), float(p), sd0)
+        if tape is not None:
+            tape["embed"] = dict(ids=token_ids, seed=sd0, p=p)
+            tape["tlayers"] = []
+        for l in range(cfg["num_transformer_layers"]):
+            pl = f"text_encoder.layers.{l}"
+            rec = self._attn_block_fwd(xt, xt, pl + ".norm1", None, pl + ".self_attention", maskf, Bt, L, L, heads, d // heads, p,
+                                       pl + ".norm2", pl + ".ffn.fc1", pl + ".ffn.fc2", self_attn=True)
+            if tape is not None:
+                tape["tlayers"].append(rec)
+            xt = rec["out"]
+        enc, enc_st = self._ln(xt, "text_encoder.final_norm")
+        if tape is not None:
+            tape["final_norm"] = dict(x=xt, st=enc_st)
+        q0 = None
+        if hoist_q:
+            p0 = "fusion.cross_attention.layers.0"
+            q0 = self._cross_q_path(enc, p0 + ".norm_query", p0 + ".cross_attention")
+        return enc, q0
+
+    def _projector_fwd(self, feat, ntok, p):
+        """Image projector, A9: Linear, then LayerNorm over (projection + position embedding) with dropout p.  feat: NHWC features
+        [B*ntok][512].  Returns (image tokens [B*ntok][d], tape record)."""
+        d = self.cfg["embed_dim"]
         pj = "fusion.image_projector.projection"
         pz = self._lin(feat, pj + ".0.weight", pj + ".0.bias")
         sdp = self._seed()
         posemb = self.P("fusion.image_projector.position_embedding")
         if ntok * d > posemb.numel():            # the reference fails the same way (broadcast error at models/fusion.py:110)
             raise RuntimeError(f"{ntok} image tokens but position_embedding holds {posemb.numel() // d} (num_image_tokens)")
-        img, img_st = self._ln(pz, pj + ".1", p=pfus, seed=sdp, addrow=posemb, period=ntok)
-        tape["proj"] = dict(feat=feat, pz=pz, st=img_st, seed=sdp, p=pfus, ntok=ntok)
-        q = enc
-        tape["clayers"] = []
+        img, img_st = self._ln(pz, pj + ".1", p=p, seed=sdp, addrow=posemb, period=ntok)
+        return img, dict(feat=feat, pz=pz, st=img_st, seed=sdp, p=p, ntok=ntok)
+
+    def _cross_q_path(self, q_in, norm_q, attn):
+        """norm_query + W_q of a cross-attention layer (cross_attention.py:286 and the query projection inside CrossAttention): needs
+        the query stream only."""
+        nq, stq = self._ln(q_in, norm_q)
+        return nq, stq, self._lin(nq, attn + ".W_q.weight")
+
+    def _cross_kv_path(self, kv_in, norm_kv, attn, d, out=None):
+        """norm_kv + W_k | W_v of a cross-attention layer (cross_attention.py:287): needs the image tokens only -- the same tensor for
+        every layer of StackedCrossAttention (cross_attention.py:357-361), so layers >= 1 do not sit on the query chain.
+        out: a [rows][2d] destination that receives K | V (encode_images: this layer's slot of the context)."""
+        nkv, stkv = self._ln(kv_in, norm_kv)
+        wk, wv = attn + ".W_k.weight", attn + ".W_v.weight"
+        if self._adjacent([wk, wv]):
+            kv = self._lin_multi(nkv, [wk, wv], out=out)
+            return nkv, stkv, kv, kv[:, d:], 2 * d, True
+        if out is None:
+            return nkv, stkv, self._lin(nkv, wk), self._lin(nkv, wv), d, False
+        out[:, :d].copy_(self._lin(nkv, wk))
+        out[:, d:].copy_(self._lin(nkv, wv))
+        return nkv, stkv, out, out[:, d:], 2 * d, True
+
+    def _cross_layers_fwd(self, q, img, Bt, L, ntok, p, want_aux, q0=None, kv_of=None, kv_index=None, n_kv=0, csr=None, tape=None):
+        """Cross-attention layers, A10, over the query rows q [Bt*L][d] with dropout p; their records go into `tape` when one is
+        given.  img: the image tokens every layer projects its K | V from, unless kv_of(l) returns layer l's _cross_kv_path result
+        (issued earlier, or cached by encode_images).  q0: layer 0's _cross_q_path result when it was hoisted.  kv_index / n_kv and
+        csr: as in _attn_block_fwd.  want_aux: every layer's probabilities are views of ONE [ncl][Bt][H][L][ntok] buffer (the drop-in
+        hands it out as one graph output).  Returns (attended rows, per-layer probabilities, that buffer | None)."""
+        cfg = self.cfg
+        d, heads, ncl = cfg["embed_dim"], cfg["num_attention_heads"], cfg["num_cross_layers"]
+        caw = torch.empty((ncl, Bt, heads, L, ntok), device=q.device, dtype=torch.float32) if (want_aux and ncl) else None
         probs_all = []
-        ncl = cfg["num_cross_layers"]
-        # aux: every layer's probabilities are views of ONE [ncl][B][H][L][ntok] buffer (the drop-in hands it out as one graph output)
-        caw = torch.empty((ncl, Bt, heads, L, ntok), device=dev, dtype=torch.float32) if (want_aux and ncl) else None
-        pre_kv = [None] * ncl
-        if self.hoist_cross and use_side and ncl > 1:
-            # every layer's K / V come from the SAME image tokens: layers >= 1 are projected on the (now idle) text stream while
-            # layer 0 runs here.  img lives on this stream and is read there; the results live there and are read here: both are
-            # ordered by the events below and kept alive by the tape (forward-only: freed after the last wait, see DESIGN section 3)
-            ev_img = torch.cuda.Event(); ev_img.record(main)
-            self.side.wait_event(ev_img)
-            with torch.cuda.stream(self.side):
-                for l in range(1, ncl):
-                    p = f"fusion.cross_attention.layers.{l}"
-                    pre_kv[l] = (self._cross_kv_path(img, p + ".norm_kv", p + ".cross_attention", d), torch.cuda.Event())
-                    pre_kv[l][1].record()
+        if tape is not None:
+            tape["clayers"] = []
         for l in range(ncl):
-            p = f"fusion.cross_attention.layers.{l}"
-            pkv = None
-            if pre_kv[l] is not None:
-                pkv, ev_kv = pre_kv[l]
-                main.wait_event(ev_kv)
-            rec = self._attn_block_fwd(q, img, None, p + ".norm_query", p + ".norm_kv", p + ".cross_attention", None, Bt, L, ntok,
-                                       heads, hd, pfus, p + ".norm_ffn", p + ".ffn.0", p + ".ffn.3", self_attn=False,
-                                       pre_q=text.get("q0") if l == 0 else None, pre_kv=pkv, probs=None if caw is None else caw[l],
-                                       csr=csr)
-            tape["clayers"].append(rec)
+            pl = f"fusion.cross_attention.layers.{l}"
+            rec = self._attn_block_fwd(q, img, pl + ".norm_query", pl + ".norm_kv", pl + ".cross_attention", None, Bt, L, ntok,
+                                       heads, d // heads, p, pl + ".norm_ffn", pl + ".ffn.0", pl + ".ffn.3", self_attn=False,
+                                       pre_q=q0 if l == 0 else None, pre_kv=None if kv_of is None else kv_of(l),
+                                       probs=None if caw is None else caw[l], kv_index=kv_index, n_kv=n_kv, csr=csr)
+            if tape is not None:
+                tape["clayers"].append(rec)
             probs_all.append(rec["probs"])
             q = rec["out"]
-        cat = torch.empty((Bt, 2 * d), device=dev, dtype=T)
-        call("vqa_masked_pool_pair_fwd", dt(T), ptr(q), ptr(enc), ptr(maskf), ptr(cat), Bt, L, d)      # [attended | text] means, one launch
-        fused_pre = torch.empty((Bt, d), device=dev, dtype=T)
+        return q, probs_all, caw
+
+    def _tail_fwd(self, q, enc, maskf, Bt, L, phead, lowp_logits):
+        """Fusion tail and answer head, A11-A12: the [attended | text] masked means of q and enc ([Bt*L][d]) in one launch, gate (or
+        sum), output_norm, then the classifier's three Linears with dropout phead.  lowp_logits: the logits stay in the compute
+        dtype (no fp32 copy).  Returns (logits, cat [Bt][2d], fused [Bt][d], tape record of the pools, tape record of the head)."""
+        cfg, T = self.cfg, self.dtype
+        d = cfg["embed_dim"]
+        cat = torch.empty((Bt, 2 * d), device=q.device, dtype=T)
+        call("vqa_masked_pool_pair_fwd", dt(T), ptr(q), ptr(enc), ptr(maskf), ptr(cat), Bt, L, d)
+        fused_pre = torch.empty((Bt, d), device=q.device, dtype=T)
         z = None
         if cfg["use_gating"]:
             z = self._lin(cat, "fusion.gate.gate.0.weight", "fusion.gate.gate.0.bias")
@@ -844,54 +940,35 @@ class HipEngine:
             att = cat[:, :d].contiguous(); txt = cat[:, d:].contiguous()
             call("vqa_add", dt(T), ptr(att), ptr(txt), ptr(fused_pre), Bt * d)
         fused, fst = self._ln(fused_pre, "fusion.output_norm")
-        tape["pool"] = dict(q=q, enc=enc, cat=cat, z=z, fused_pre=fused_pre, fst=fst, maskf=maskf, L=L, d=d)
+        pool_rec = dict(q=q, enc=enc, cat=cat, z=z, fused_pre=fused_pre, fst=fst, maskf=maskf, L=L, d=d)
         if self.mark: self.mark("forward: fusion")
-
-        # ---- answer head, A12
         c = "answer_head.classifier"
         s1, s2 = self._seed(), self._seed()
         h1 = self._lin(fused, c + ".0.weight", c + ".0.bias", relu=1, p=phead, seed=s1)
         h2 = self._lin(h1, c + ".3.weight", c + ".3.bias", relu=1, p=phead, seed=s2)
         logits = self._lin(h2, c + ".6.weight", c + ".6.bias")
-        tape["head"] = dict(fused=fused, h1=h1, h2=h2, s1=s1, s2=s2, p=phead)
-        logits_f = logits.float() if (T != torch.float32 and not lowp_logits) else logits
+        head_rec = dict(fused=fused, h1=h1, h2=h2, s1=s1, s2=s2, p=phead)
+        if T != torch.float32 and not lowp_logits:
+            logits = logits.float()
+        return logits, cat, fused, pool_rec, head_rec
 
-        aux = None
-        if caw is not None:
-            tape["caw"] = caw
-        if want_aux:
-            feat_nchw = torch.empty((B, Cf, Hf, Wf), device=dev, dtype=torch.float32)
-            call("vqa_nhwc_to_nchw", dt(T), ptr(feat), ptr(feat_nchw), B, Hf * Wf, Cf)
-            aux = {
-                "image_features": feat_nchw,
-                "text_features": enc.float().view(Bt, L, d),
-                "text_pooled": cat[:, d:].float(),          # fusion's entry overrides the encoder's (vqa_model.py:303-309)
-                "fused": fused.float(),
-                "cross_attention_weights": probs_all,
-                "image_projected": img.float().view(B, ntok, d),
-                "attended_pooled": cat[:, :d].float(),
-            }
-        if not need_tape:
-            tape = None
-        return logits_f, aux, tape
+    def _aux_of(self, feat, n_img, Hf, Wf, Cf, img, enc, cat, fused, probs_all):
+        """The aux dictionary of VQAModel.forward(return_aux=True) (vqa_model.py:303-309), fp32.  feat (NHWC [n_img*Hf*Wf][Cf]) and
+        img (projected tokens) have one row block per IMAGE, enc / cat / fused / probs_all one per question."""
+        Bt, d = fused.shape
+        feat_nchw = torch.empty((n_img, Cf, Hf, Wf), device=feat.device, dtype=torch.float32)
+        call("vqa_nhwc_to_nchw", dt(self.dtype), ptr(feat), ptr(feat_nchw), n_img, Hf * Wf, Cf)
+        return {
+            "image_features": feat_nchw,
+            "text_features": enc.float().view(Bt, -1, d),
+            "text_pooled": cat[:, d:].float(),          # fusion's entry overrides the encoder's (vqa_model.py:303-309)
+            "fused": fused.float(),
+            "cross_attention_weights": probs_all,
+            "image_projected": img.float().view(n_img, Hf * Wf, d),
+            "attended_pooled": cat[:, :d].float(),
+        }
 
-    def _cross_q_path(self, q_in, norm_q, attn):
-        """norm_query + W_q of a cross-attention layer (cross_attention.py:286 and the query projection inside CrossAttention): needs
-        the query stream only."""
-        nq, stq = self._ln(q_in, norm_q)
-        return nq, stq, self._lin(nq, attn + ".W_q.weight")
-
-    def _cross_kv_path(self, kv_in, norm_kv, attn, d):
-        """norm_kv + W_k | W_v of a cross-attention layer (cross_attention.py:287): needs the image tokens only -- the same tensor for
-        every layer of StackedCrossAttention (cross_attention.py:357-361), so layers >= 1 do not sit on the query chain."""
-        nkv, stkv = self._ln(kv_in, norm_kv)
-        wk, wv = attn + ".W_k.weight", attn + ".W_v.weight"
-        if self._adjacent([wk, wv]):
-            kv = self._lin_multi(nkv, [wk, wv])
-            return nkv, stkv, kv, kv[:, d:], 2 * d, True
-        return nkv, stkv, self._lin(nkv, wk), self._lin(nkv, wv), d, False
-
-    def _attn_block_fwd(self, q_in, kv_in, _unused, norm_q, norm_kv, attn, kmask, B, Lq, Lk, heads, hd, p, norm_f, fc1, fc2, self_attn,
+    def _attn_block_fwd(self, q_in, kv_in, norm_q, norm_kv, attn, kmask, B, Lq, Lk, heads, hd, p, norm_f, fc1, fc2, self_attn,
                         pre_q=None, pre_kv=None, probs=None, kv_index=None, n_kv=0, csr=None):
         """pre-norm attention + FFN block (TransformerEncoderLayer.forward text_encoder.py:373-399 and
         MultiHeadCrossAttention.forward cross_attention.py:285-299).  pre_q / pre_kv: the results of _cross_q_path / _cross_kv_path when
@@ -919,28 +996,18 @@ class HipEngine:
             probs = torch.empty((B, heads, Lq, Lk), device=Q.device, dtype=torch.float32)
         ctx = torch.empty((B * Lq, d), device=Q.device, dtype=T)
         sa = self._seed()
+        mfma = T == torch.bfloat16 and Lq <= 32 and Lk <= 160 and hd in (32, 64)
+        lead = () if mfma else (dt(T),)           # the MFMA kernels are bf16 only; the generic ones take the dtype first
+        qkv_args = (ptr(Q), ptr(Kt), ptr(V), ldq, ldkv, ldkv)
+        out_args = (ptr(kmask), ptr(probs), ptr(ctx), d, B, heads, Lq, Lk, hd)
         if csr is not None:
-            kv_index, n_kv = csr[0], csr[3]
-            if T == torch.bfloat16 and Lq <= 32 and Lk <= 160 and hd in (32, 64):
-                call("vqa_attention_fwd_mfma_idx_train", ptr(Q), ptr(Kt), ptr(V), ldq, ldkv, ldkv, ptr(kv_index), n_kv, ptr(kmask), ptr(probs),
-                     ptr(ctx), d, B, heads, Lq, Lk, hd, float(p), sa)
-            else:
-                call("vqa_attention_fwd_idx_train", dt(T), ptr(Q), ptr(Kt), ptr(V), ldq, ldkv, ldkv, ptr(kv_index), n_kv, ptr(kmask),
-                     ptr(probs), ptr(ctx), d, B, heads, Lq, Lk, hd, float(p), sa)
+            call("vqa_attention_fwd_mfma_idx_train" if mfma else "vqa_attention_fwd_idx_train", *lead, *qkv_args, ptr(csr[0]), csr[3],
+                 *out_args, float(p), sa)
         elif kv_index is not None:
             assert p == 0.0, "indexed attention is inference only"
-            if T == torch.bfloat16 and Lq <= 32 and Lk <= 160 and hd in (32, 64):
-                call("vqa_attention_fwd_mfma_idx", ptr(Q), ptr(Kt), ptr(V), ldq, ldkv, ldkv, ptr(kv_index), n_kv, ptr(kmask), ptr(probs), ptr(ctx),
-                     d, B, heads, Lq, Lk, hd)
-            else:
-                call("vqa_attention_fwd_idx", dt(T), ptr(Q), ptr(Kt), ptr(V), ldq, ldkv, ldkv, ptr(kv_index), n_kv, ptr(kmask), ptr(probs),
-                     ptr(ctx), d, B, heads, Lq, Lk, hd)
-        elif T == torch.bfloat16 and Lq <= 32 and Lk <= 160 and hd in (32, 64):
-            call("vqa_attention_fwd_mfma", ptr(Q), ptr(Kt), ptr(V), ldq, ldkv, ldkv, ptr(kmask), ptr(probs), ptr(ctx), d, B, heads, Lq, Lk, hd,
-                 float(p), sa)
+            call("vqa_attention_fwd_mfma_idx" if mfma else "vqa_attention_fwd_idx", *lead, *qkv_args, ptr(kv_index), n_kv, *out_args)
         else:
-            call("vqa_attention_fwd", dt(T), ptr(Q), ptr(Kt), ptr(V), ldq, ldkv, ldkv, ptr(kmask), ptr(probs), ptr(ctx), d, B, heads, Lq, Lk, hd,
-                 float(p), sa)
+            call("vqa_attention_fwd_mfma" if mfma else "vqa_attention_fwd", *lead, *qkv_args, *out_args, float(p), sa)
         so = self._seed()
         x1 = self._lin(ctx, attn + ".W_o.weight", p=p, seed=so, addend=q_in)
         nf, stf = self._ln(x1, norm_f)
@@ -954,110 +1021,26 @@ class HipEngine:
 
     # ------------------------------------------------------------------ many questions per image (inference only)
     def encode_images(self, images: torch.Tensor, want_aux: bool = False) -> dict:
-        """The image half of the eval forward, once per image: the one-launch stem, the Conv+BN-folded stages (bf16 or MXFP8,
-        infer_precision), SE / spatial attention, the projector (Linear + position embedding + LayerNorm) and norm_kv + W_k | W_v of
-        EVERY cross-attention layer.  Same launches and bits as forward(training=False, need_tape=False) issues for these tensors.
+        """The image half of the eval forward, once per image: the forward parts forward(training=False, need_tape=False) runs for
+        these tensors -- _stem_fwd, _stages_fwd (Conv+BN folded, bf16 or MXFP8: infer_precision), _projector_fwd -- and then
+        _cross_kv_path (norm_kv + W_k | W_v) of EVERY cross-attention layer, written into that layer's slot of one buffer.
         Returns the context answer() reads: {"kv": [ncl][U*ntok][2d] compute dtype (K | V per image token), "U", "ntok"} and, with
         want_aux, "feat" (NHWC features [U*ntok][512]) and "img" (projected image tokens [U*ntok][d])."""
-        cfg, T = self.cfg, self.dtype
+        cfg = self.cfg
         if not self.fold_eval:
             raise RuntimeError("encode_images runs the Conv+BN-folded eval path (fold_eval = True)")
-        if self.infer_precision not in ("bf16", "mxfp8"):
-            raise ValueError(f"unknown infer_precision {self.infer_precision!r}")
         self._site = 0
         self.begin_step(for_backward=False)
-        U, _, IH, IW = images.shape
-        dev = images.device
-        # ---- stem (forward's inference form)
-        H1, W1 = (IH + 6 - 7) // 2 + 1, (IW + 6 - 7) // 2 + 1
-        M = U * H1 * W1
-        Hp, Wp = (H1 + 2 - 3) // 2 + 1, (W1 + 2 - 3) // 2 + 1
-        x = None
-        if self.fuse_stem_eval and self.stem_w2 is not None:
-            x = K.stem_conv_pool(images, self.stem_w2, self._bn_coef("image_encoder.stem.1", None, 0, 64, M, False), U, IH, IW)
-        if x is None:
-            if self.stem_w2 is not None and K.stem_conv_blocks(U, IH, IW) > 0:
-                y, st, mt = K.stem_conv(images, self.stem_w2, U, IH, IW, False)
-            else:
-                y, st, mt = K.igemm(images, self.stem_w, M, 64, self.stem_kp, (U, IH, IW, 3, H1, W1, 7, 7, 2, 3), dtype=T,
-                                    loader=K.LOADER_STEM, want_stats=False)
-            coef = self._bn_coef("image_encoder.stem.1", st, mt, 64, M, False)
-            x = torch.empty((U * Hp * Wp, 64), device=dev, dtype=T)
-            idx = torch.empty((U * Hp * Wp, 64), device=dev, dtype=torch.uint8)
-            call("vqa_stem_pool_fwd", dt(T), ptr(y), ptr(coef), ptr(x), ptr(idx), U, H1, W1, 64)
-        H, W, C = Hp, Wp, 64
-        # ---- residual stages (Conv+BN folded), SE, spatial attention
-        folded = self._fold_bn()
-        foldmx, xq = None, None
-        if self.infer_precision == "mxfp8":
-            if T != torch.bfloat16:
-                raise RuntimeError("infer_precision 'mxfp8' needs the bf16 compute dtype")
-            foldmx = self._fold_mxfp8()
-        for s, Cout in enumerate(LY.STAGE_CHANNELS, start=1):
-            for b in range(2):
-                p = f"image_encoder.stage{s}.blocks.{b}"
-                stride = 2 if (b == 0 and s > 1) else 1
-                Cin = C
-                Ho, Wo = (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1
-                M = U * Ho * Wo
-                if foldmx is not None:
-                    if xq is None:
-                        xq = K.mx_quant(x)
-                    (w1, b1), (w2, b2) = foldmx[p + ".conv1.weight"], foldmx[p + ".conv2.weight"]
-                    _, a1q = K.conv_mxfp8(xq, w1, M, Cout, (U, H, W, Cin, Ho, Wo, 3, 3, stride, 1), bias=b1, relu=1, want_bf16=False, want_mx=True)
-                else:
-                    w1, b1 = folded[p + ".conv1.weight"]
-                    w2, b2 = folded[p + ".conv2.weight"]
-                    a1, _, _ = K.igemm(x, w1, M, Cout, 9 * Cin, (U, H, W, Cin, Ho, Wo, 3, 3, stride, 1), dtype=T, bias=b1, relu=1)
-                res = x
-                if (p + ".downsample.0.weight") in self.E:
-                    wd, bd = folded[p + ".downsample.0.weight"]
-                    res, _, _ = K.igemm(x, wd, M, Cout, Cin, (U, H, W, Cin, Ho, Wo, 1, 1, stride, 0), dtype=T, bias=bd)
-                if foldmx is not None:
-                    out, xq = K.conv_mxfp8(a1q, w2, M, Cout, (U, Ho, Wo, Cout, Ho, Wo, 3, 3, 1, 1), bias=b2, addend=res, relu=2, want_mx=(b == 0))
-                else:
-                    out, _, _ = K.igemm(a1, w2, M, Cout, 9 * Cout, (U, Ho, Wo, Cout, Ho, Wo, 3, 3, 1, 1), dtype=T, bias=b2, addend=res, relu=2)
-                x, H, W, C = out, Ho, Wo, Cout
-            ap = f"image_encoder.stage{s}.attention"
-            if (ap + ".se.fc1.weight") in self.E:
-                Cr = self.E[ap + ".se.fc1.weight"].shape[0]
-                pooled = torch.empty((U, C), device=dev, dtype=torch.float32)
-                hidden = torch.empty((U, Cr), device=dev, dtype=torch.float32)
-                scale = torch.empty((U, C), device=dev, dtype=torch.float32)
-                out = torch.empty_like(x)
-                call("vqa_se_fwd", dt(T), ptr(x), ptr(self.P(ap + ".se.fc1.weight")), ptr(self.P(ap + ".se.fc2.weight")),
-                     ptr(pooled), ptr(hidden), ptr(scale), ptr(out), U, H * W, C, Cr, None, 0)
-                x = out
-            if (ap + ".spatial.conv.weight") in self.E:
-                pooled2 = torch.empty((U * H * W, 2), device=dev, dtype=torch.float32)
-                amax = torch.empty((U * H * W,), device=dev, dtype=torch.int32)
-                amap = torch.empty((U * H * W,), device=dev, dtype=torch.float32)
-                out = torch.empty_like(x)
-                call("vqa_spatial_fwd", dt(T), ptr(x), ptr(self.P(ap + ".spatial.conv.weight")), ptr(pooled2), ptr(amax),
-                     ptr(amap), ptr(out), U, H, W, C)
-                x = out
-        feat, ntok, d = x, H * W, cfg["embed_dim"]
-        # ---- projector, then norm_kv + W_k | W_v of every cross layer (all read the same image tokens, cross_attention.py:357-361)
-        pj = "fusion.image_projector.projection"
-        pz = self._lin(feat, pj + ".0.weight", pj + ".0.bias")
-        sdp = self._seed()
-        posemb = self.P("fusion.image_projector.position_embedding")
-        if ntok * d > posemb.numel():
-            raise RuntimeError(f"{ntok} image tokens but position_embedding holds {posemb.numel() // d} (num_image_tokens)")
-        img, _ = self._ln(pz, pj + ".1", p=0.0, seed=sdp, addrow=posemb, period=ntok)
-        ncl = cfg["num_cross_layers"]
-        kv = torch.empty((ncl, U * ntok, 2 * d), device=dev, dtype=T)
+        U = images.shape[0]
+        x, H, W, _ = self._stem_fwd(images, False, False)
+        feat, H, W, C, _ = self._stages_fwd(x, U, H, W, False, False)
+        ntok, d, ncl = H * W, cfg["embed_dim"], cfg["num_cross_layers"]
+        img, _ = self._projector_fwd(feat, ntok, 0.0)
+        # every layer reads the same image tokens (cross_attention.py:357-361)
+        kv = torch.empty((ncl, U * ntok, 2 * d), device=images.device, dtype=self.dtype)
         for l in range(ncl):
-            a = f"fusion.cross_attention.layers.{l}"
-            nkv, _ = self._ln(img, a + ".norm_kv")
-            wk, wv = a + ".cross_attention.W_k.weight", a + ".cross_attention.W_v.weight"
-            if self._adjacent([wk, wv]):                 # the one [2d][d] GEMM _cross_kv_path issues, written into this layer's slot
-                e0 = self.E[wk]
-                w = self.wsrc[e0.offset: e0.offset + 2 * d * d].view(2 * d, d)
-                K.igemm(nkv, w, U * ntok, 2 * d, d, K.linear_geom(U * ntok, d), dtype=T, out=kv[l])
-            else:
-                kv[l, :, :d].copy_(self._lin(nkv, wk))
-                kv[l, :, d:].copy_(self._lin(nkv, wv))
+            p = f"fusion.cross_attention.layers.{l}"
+            self._cross_kv_path(img, p + ".norm_kv", p + ".cross_attention", d, out=kv[l])
         ctx = {"kv": kv, "U": U, "ntok": ntok}
         if want_aux:
             ctx.update(feat=feat, img=img, Hf=H, Wf=W, Cf=C)
@@ -1065,80 +1048,27 @@ class HipEngine:
 
     def answer(self, ctx: dict, token_ids: torch.Tensor, maskf: Optional[torch.Tensor], kv_index: torch.Tensor, want_aux: bool = False,
                lowp_logits: bool = False):
-        """The question half of the eval forward over a context of encode_images(): text encoder, every cross layer's query path with
-        vqa_attention_fwd(_mfma)_idx over the cached K / V (question i attends to image kv_index[i]), the masked pools, the gate,
-        output_norm and the head.  kv_index: int32 [N] on the device, every entry in [0, ctx["U"]) (the caller checks).  All on the
-        current stream, no tape, no weight cast: the compute-dtype weights are those encode_images() cast (the drop-in refuses a context
+        """The question half of the eval forward over a context of encode_images(): forward()'s parts with dropout 0 and no tape --
+        _text_fwd, _cross_layers_fwd over the cached K | V (vqa_attention_fwd(_mfma)_idx: question i attends to image kv_index[i]),
+        _tail_fwd.  kv_index: int32 [N] on the device, every entry in [0, ctx["U"]) (the caller checks).  All on the
+        current stream, no weight cast: the compute-dtype weights are those encode_images() cast (the drop-in refuses a context
         once the parameters changed).  Returns (fp32 logits [N][num_answers], aux | None); lowp_logits: the logits stay in the compute
-        dtype and the cast launch is skipped (forward's keyword; vqa_softmax_topk reads bf16 and leaves the fp32 copy itself)."""
-        cfg, T = self.cfg, self.dtype
+        dtype and the cast launch is skipped (forward's keyword; vqa_softmax_topk reads bf16 and leaves the fp32 copy itself).
+        aux has one image_features / image_projected row per unique image, every other entry one row per question."""
         self._site = 0
-        d, heads = cfg["embed_dim"], cfg["num_attention_heads"]
-        hd = d // heads
+        d = self.cfg["embed_dim"]
         N, L = token_ids.shape
         U, ntok, kvs = ctx["U"], ctx["ntok"], ctx["kv"]
-        dev = token_ids.device
-        pe = self.buf["text_encoder.positional_encoding.pe"]
-        if L > pe.shape[1]:
-            raise RuntimeError(f"sequence length {L} exceeds max_question_length {pe.shape[1]}")
-        # ---- text encoder (forward's issue_text, dropout off)
-        emb_e = self.E["text_encoder.token_embedding.weight"]
-        sd0 = self._seed()
-        xt = torch.empty((N * L, d), device=dev, dtype=T)
-        call("vqa_embed_fwd", dt(T), ptr(token_ids), ptr(self.P(emb_e.name)), ptr(pe), ptr(xt), N * L, L, d, emb_e.shape[0], math.sqrt(d), 0.0, sd0)
-        for l in range(cfg["num_transformer_layers"]):
-            p = f"text_encoder.layers.{l}"
-            rec = self._attn_block_fwd(xt, xt, None, p + ".norm1", None, p + ".self_attention", maskf, N, L, L, heads, hd, 0.0,
-                                       p + ".norm2", p + ".ffn.fc1", p + ".ffn.fc2", self_attn=True)
-            xt = rec["out"]
-        enc, _ = self._ln(xt, "text_encoder.final_norm")
-        # ---- cross layers over the cached K / V
-        q = enc
-        ncl = cfg["num_cross_layers"]
-        caw = torch.empty((ncl, N, heads, L, ntok), device=dev, dtype=torch.float32) if (want_aux and ncl) else None
-        probs_all = []
-        for l in range(ncl):
-            p = f"fusion.cross_attention.layers.{l}"
-            pkv = (None, None, kvs[l], kvs[l][:, d:], 2 * d, True)
-            rec = self._attn_block_fwd(q, None, None, p + ".norm_query", p + ".norm_kv", p + ".cross_attention", None, N, L, ntok,
-                                       heads, hd, 0.0, p + ".norm_ffn", p + ".ffn.0", p + ".ffn.3", self_attn=False,
-                                       pre_kv=pkv, probs=None if caw is None else caw[l], kv_index=kv_index, n_kv=U)
-            probs_all.append(rec["probs"])
-            q = rec["out"]
-        # ---- pools, gate, output_norm, head (forward's tail, dropout off)
-        cat = torch.empty((N, 2 * d), device=dev, dtype=T)
-        call("vqa_masked_pool_pair_fwd", dt(T), ptr(q), ptr(enc), ptr(maskf), ptr(cat), N, L, d)
-        fused_pre = torch.empty((N, d), device=dev, dtype=T)
-        if cfg["use_gating"]:
-            z = self._lin(cat, "fusion.gate.gate.0.weight", "fusion.gate.gate.0.bias")
-            call("vqa_gate_fwd", dt(T), ptr(z), ptr(cat), ptr(fused_pre), N, d)
-        else:
-            att = cat[:, :d].contiguous(); txt = cat[:, d:].contiguous()
-            call("vqa_add", dt(T), ptr(att), ptr(txt), ptr(fused_pre), N * d)
-        fused, _ = self._ln(fused_pre, "fusion.output_norm")
-        c = "answer_head.classifier"
-        s1, s2 = self._seed(), self._seed()
-        h1 = self._lin(fused, c + ".0.weight", c + ".0.bias", relu=1, p=0.0, seed=s1)
-        h2 = self._lin(h1, c + ".3.weight", c + ".3.bias", relu=1, p=0.0, seed=s2)
-        logits = self._lin(h2, c + ".6.weight", c + ".6.bias")
-        logits_f = logits.float() if (T != torch.float32 and not lowp_logits) else logits
+        enc, _ = self._text_fwd(token_ids, maskf, 0.0)
+        q, probs_all, _ = self._cross_layers_fwd(enc, None, N, L, ntok, 0.0, want_aux, kv_index=kv_index, n_kv=U,
+                                                 kv_of=lambda l: (None, None, kvs[l], kvs[l][:, d:], 2 * d, True))
+        logits, cat, fused, _, _ = self._tail_fwd(q, enc, maskf, N, L, 0.0, lowp_logits)
         aux = None
         if want_aux:
             if "feat" not in ctx:
                 raise RuntimeError("aux outputs need a context made with want_aux=True")
-            Hf, Wf, Cf = ctx["Hf"], ctx["Wf"], ctx["Cf"]
-            feat_nchw = torch.empty((U, Cf, Hf, Wf), device=dev, dtype=torch.float32)
-            call("vqa_nhwc_to_nchw", dt(T), ptr(ctx["feat"]), ptr(feat_nchw), U, Hf * Wf, Cf)
-            aux = {
-                "image_features": feat_nchw,                               # one row per unique image
-                "text_features": enc.float().view(N, L, d),
-                "text_pooled": cat[:, d:].float(),
-                "fused": fused.float(),
-                "cross_attention_weights": probs_all,                      # per question
-                "image_projected": ctx["img"].float().view(U, ntok, d),    # one row per unique image
-                "attended_pooled": cat[:, :d].float(),
-            }
-        return logits_f, aux
+            aux = self._aux_of(ctx["feat"], U, ctx["Hf"], ctx["Wf"], ctx["Cf"], ctx["img"], enc, cat, fused, probs_all)
+        return logits, aux
 
     def _attn_block_bwd(self, rec, dout, G, dkv_addend=None, kv_side=False, addend_event=None, dprobs=None):
         """Returns (d q_in, d kv_in, event) ; for self-attention d kv_in is folded into d q_in.
