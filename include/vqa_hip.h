@@ -442,6 +442,29 @@ int vqa_adamw_ranges(float* p, const float* g, float* m, float* v, const long lo
                      float beta2, float eps, float weight_decay, long long calls, const float* sumsq, float max_norm, float gscale,
                      const int* skip, int* skipped, int* lag, const int* frozen, int nf, void* p_bf16, hipStream_t stream);
 
+/* Exponential moving average of the weights, kept by the optimizer launch itself.
+   vqa_adamw_ema = vqa_adamw (p, m, v and the bf16 copy get the same bits) and, for every element it updated,
+       ema[i] = d * ema[i] + (1 - d) * p_new[i]          (fp32: 1 - d and (1 - d) * p_new rounded once each, then one fma)
+   from the p_new still in a register: the average costs one read and one write of `ema`, no launch and no second read of p.
+   d = ema_decay when ema_warmup == 0, else min(ema_decay, (1 + t) / (10 + t)) in fp32 with Adam's step number t = calls - skipped[2]
+   formed on the device.  A skipped launch (skip[0] != 0) leaves `ema` untouched bit for bit and advances no warm-up.
+   vqa_adamw_ranges_ema = vqa_adamw_ranges with the same addition: `ema` is neither read nor written outside the trainable ranges,
+   and the warm-up of a range uses that range's OWN step number calls - skipped[2] - lag[its lag index] -- the average of a parameter
+   advances only while the parameter trains, exactly as its Adam step does (a part thawed late starts its warm-up when it thaws).
+   vqa_ema_update: the same update as a pass of its own over a flat buffer, ema[i] = d * ema[i] + (1 - d) * p[i] with the EFFECTIVE d
+   given by the caller (torch.optim loops); the same p and ema give the bits the fused launches give.  Any alignment (16-byte
+   accesses when both pointers allow them).
+   Status 1000 without a launch: ema NULL (vqa_ema_update: or p), ema_decay / d outside [0, 1] or NaN, n < 0, and whatever the entry
+   they extend refuses. */
+int vqa_adamw_ema(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
+                  float weight_decay, long long calls, const float* sumsq, float max_norm, float gscale,
+                  const int* skip, int* skipped, void* p_bf16, float* ema, float ema_decay, int ema_warmup, hipStream_t stream);
+int vqa_adamw_ranges_ema(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n, float lr, float beta1,
+                         float beta2, float eps, float weight_decay, long long calls, const float* sumsq, float max_norm, float gscale,
+                         const int* skip, int* skipped, int* lag, const int* frozen, int nf, void* p_bf16,
+                         float* ema, float ema_decay, int ema_warmup, hipStream_t stream);
+int vqa_ema_update(float* ema, const float* p, long long n, float d, hipStream_t stream);
+
 /* ---- input pipeline on the GPU -----------------------------------------------------------------
  * vqa_image_normalize: torchvision ToTensor + Normalize of data/preprocess.py:34-35,117-121 -- uint8 HWC [B][H][W][3] ->
  * float32 NCHW, (u/255 - mean[c]) / std[c] in torch's operation order (bit-identical), optional per-sample horizontal flip

@@ -4,7 +4,7 @@ Import with importlib (the directory name is not a Python identifier):
     pkg = importlib.import_module("visual-question-answering-vqa-system_amd")
 """
 from . import _lib, kernels  # noqa: F401
-from . import layout, engine, trainer, flops, finetune  # noqa: F401,E402
+from . import layout, engine, ema, trainer, flops, finetune  # noqa: F401,E402
 
 
 def dropin_path() -> str:
@@ -32,6 +32,11 @@ def load_dropin_soft_targets():
 def load_dropin_losses():
     """The drop-in `utils.losses` (CrossEntropyLoss with weight / ignore_index / label_smoothing as one fused launch)."""
     return _load_dropin_file("vqa_hip_dropin_utils_losses", "utils", "losses.py")
+
+
+def load_dropin_ema():
+    """The drop-in `utils.ema` (ParameterEMA: a weight average for torch.optim loops, one launch per update)."""
+    return _load_dropin_file("vqa_hip_dropin_utils_ema", "utils", "ema.py")
 
 
 def _load_dropin_file(name, *rel):

@@ -928,6 +928,130 @@ __global__ void adamw_lag_kernel(int* __restrict__ lag, const int* __restrict__ 
   for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < nf; k += gridDim.x * blockDim.x) lag[frozen[k]] += 1;
 }
 
+// Exponential moving average of the weights: ema = d * ema + (1 - d) * p_new, fp32.  ONE expression for the fused AdamW variants and
+// the stand-alone pass (the same p_new and ema give the same bits whichever launch computes them): 1 - d and its product with p are
+// each rounded once, the sum is one fma; contraction is off so that no surrounding code can change that.
+__device__ __forceinline__ float ema_blend(float e, float p, float d) {
+#pragma clang fp contract(off)
+  const float q = (1.f - d) * p;
+  return __builtin_fmaf(d, e, q);
+}
+// decay of the update at Adam step t: the caller's decay, or with warm-up min(decay, (1 + t) / (10 + t)) -- 2/11 at the first
+// applied step, within 1 % of 0.999 from t = 8981 on: the average forgets the initial weights quickly and settles at the decay
+__device__ __forceinline__ float ema_decay_at(float decay, int warmup, long long t) {
+  if (!warmup) return decay;
+  return fminf(decay, (float)(1 + t) / (float)(10 + t));
+}
+// adamw_kernel (same statements, same order: p, m, v and the bf16 copy get the bits adamw_kernel gives them) + the average of the
+// updated parameter, taken from the register that still holds it: 8 B per element on top of the 28 B, no second read of p.
+// A skipped launch returns before `ema` is touched; t does not advance then, so neither does the warm-up.
+__global__ void adamw_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n,
+                                 float lr, float b1, float b2, float eps, float wd, long long calls, const float* __restrict__ sumsq,
+                                 float max_norm, float gscale, const int* __restrict__ skip, int* __restrict__ skipped, bf16_t* __restrict__ p_bf16,
+                                 float* __restrict__ ema, float ema_decay, int ema_warmup) {
+  if (skip && *skip != 0) {
+    if (skipped && blockIdx.x == 0 && threadIdx.x == 0) { skipped[0] += *skip; skipped[1] += 1; skipped[2] += 1; }
+    return;
+  }
+  const long long t = calls - (skipped ? (long long)skipped[2] : 0ll);
+  const float bc1 = (float)(1.0 - pow((double)b1, (double)t)), bc2 = (float)(1.0 - pow((double)b2, (double)t));
+  float coef = gscale;
+  if (sumsq && max_norm > 0.f) {
+    const float norm = sqrtf(*sumsq) * gscale;
+    const float c = max_norm / (norm + 1e-6f);
+    if (c < 1.f) coef *= c;
+  }
+  const float step = lr / bc1, rbc2 = 1.f / sqrtf(bc2);
+  const float d = ema_decay_at(ema_decay, ema_warmup, t);
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    const float gr = g[i] * coef;
+    float pi = p[i] * (1.f - lr * wd);
+    const float mi = b1 * m[i] + (1.f - b1) * gr;
+    const float vi = b2 * v[i] + (1.f - b2) * gr * gr;
+    m[i] = mi; v[i] = vi;
+    pi -= step * mi / (sqrtf(vi) * rbc2 + eps);
+    p[i] = pi;
+    if (p_bf16) p_bf16[i] = f2bf(pi);
+    ema[i] = ema_blend(ema[i], pi, d);
+  }
+}
+// adamw_ranges_kernel + the average, over the same table: `ema` is neither read nor written outside the trainable ranges, and the
+// warm-up of range r runs on that range's OWN Adam step number t0 - lag[...] (a parameter's average advances only while it trains).
+__global__ __launch_bounds__(256) void adamw_ranges_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                               float* __restrict__ v, const long long* __restrict__ table, int R, long long n,
+                                                               float lr, float b1, float b2, float eps, float wd, long long calls,
+                                                               const float* __restrict__ sumsq, float max_norm, float gscale,
+                                                               const int* __restrict__ skip, int* __restrict__ skipped, const int* __restrict__ lag,
+                                                               bf16_t* __restrict__ p_bf16, float* __restrict__ ema, float ema_decay, int ema_warmup) {
+  if (skip && *skip != 0) {
+    if (skipped && blockIdx.x == 0 && threadIdx.x == 0) { skipped[0] += *skip; skipped[1] += 1; skipped[2] += 1; }
+    return;
+  }
+  __shared__ long long s_lo[VQA_RANGES_MAX], s_pos[VQA_RANGES_MAX];
+  __shared__ float s_step[VQA_RANGES_MAX], s_rbc2[VQA_RANGES_MAX], s_d[VQA_RANGES_MAX];
+  const long long t0 = calls - (skipped ? (long long)skipped[2] : 0ll);
+  for (int r = threadIdx.x; r < R; r += blockDim.x) {
+    s_lo[r] = table[4 * r]; s_pos[r] = table[4 * r + 2];
+    const long long t = t0 - (lag ? (long long)lag[table[4 * r + 3]] : 0ll);
+    const float bc1 = (float)(1.0 - pow((double)b1, (double)t)), bc2 = (float)(1.0 - pow((double)b2, (double)t));
+    s_step[r] = lr / bc1; s_rbc2[r] = 1.f / sqrtf(bc2);
+    s_d[r] = ema_decay_at(ema_decay, ema_warmup, t);
+  }
+  __syncthreads();
+  float coef = gscale;
+  if (sumsq && max_norm > 0.f) {
+    const float norm = sqrtf(*sumsq) * gscale;
+    const float c = max_norm / (norm + 1e-6f);
+    if (c < 1.f) coef *= c;
+  }
+  const long long nv = n / 4;
+  for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nv; q += (long long)gridDim.x * blockDim.x) {
+    const long long e = 4 * q;
+    const int r = range_of(s_pos, R, e);
+    const long long i = s_lo[r] + (e - s_pos[r]);
+    const float step = s_step[r], rbc2 = s_rbc2[r], d = s_d[r];
+    const float4 g4 = *reinterpret_cast<const float4*>(g + i);
+    float4 p4 = *reinterpret_cast<const float4*>(p + i);
+    float4 m4 = *reinterpret_cast<const float4*>(m + i);
+    float4 v4 = *reinterpret_cast<const float4*>(v + i);
+    float4 e4 = *reinterpret_cast<const float4*>(ema + i);
+    float* pp = &p4.x; float* mm = &m4.x; float* vv = &v4.x; const float* gg = &g4.x; float* ee = &e4.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float gr = gg[k] * coef;
+      float pi = pp[k] * (1.f - lr * wd);
+      const float mi = b1 * mm[k] + (1.f - b1) * gr;
+      const float vi = b2 * vv[k] + (1.f - b2) * gr * gr;
+      mm[k] = mi; vv[k] = vi;
+      pi -= step * mi / (sqrtf(vi) * rbc2 + eps);
+      pp[k] = pi;
+      ee[k] = ema_blend(ee[k], pi, d);
+    }
+    *reinterpret_cast<float4*>(p + i) = p4;
+    *reinterpret_cast<float4*>(m + i) = m4;
+    *reinterpret_cast<float4*>(v + i) = v4;
+    *reinterpret_cast<float4*>(ema + i) = e4;
+    if (p_bf16) {
+      uint2 w;
+      w.x = (uint32_t)f2bf(p4.x) | ((uint32_t)f2bf(p4.y) << 16);
+      w.y = (uint32_t)f2bf(p4.z) | ((uint32_t)f2bf(p4.w) << 16);
+      *reinterpret_cast<uint2*>(p_bf16 + i) = w;
+    }
+  }
+}
+// The update as a pass of its own over a flat buffer (torch.optim loops: dropin/utils/ema.py): 12 B per element.  nv float4 groups
+// (0 when a pointer is not 16-byte aligned), then the scalar rest.
+__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ p, long long n, long long nv, float d) {
+  const long long stride = (long long)gridDim.x * blockDim.x, i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (long long q = i0; q < nv; q += stride) {
+    const float4 p4 = reinterpret_cast<const float4*>(p)[q];
+    float4 e4 = reinterpret_cast<float4*>(ema)[q];
+    e4.x = ema_blend(e4.x, p4.x, d); e4.y = ema_blend(e4.y, p4.y, d); e4.z = ema_blend(e4.z, p4.z, d); e4.w = ema_blend(e4.w, p4.w, d);
+    reinterpret_cast<float4*>(ema)[q] = e4;
+  }
+  for (long long i = 4 * nv + i0; i < n; i += stride) ema[i] = ema_blend(ema[i], p[i], d);
+}
+
 // ---------------------------------------------------------------------------------------------
 #define DT(call_f, call_b) do { if (dtype) { call_b; } else { call_f; } } while (0)
 static inline unsigned g1(size_t n) { return (unsigned)((n + 255) / 256); }
@@ -1247,6 +1371,36 @@ int vqa_adamw_ranges(float* p, const float* g, float* m, float* v, const long lo
   hipLaunchKernelGGL(adamw_ranges_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, table, R, n, lr, b1, b2, eps, wd, calls, sumsq,
                      max_norm, gscale, skip, skipped, (const int*)lag, (bf16_t*)p_bf16);
   if (nf > 0) hipLaunchKernelGGL(adamw_lag_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, lag, frozen, nf, skip);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+
+// vqa_adamw / vqa_adamw_ranges + the weight average in the same launch (same grids); vqa_ema_update: the average alone.
+static inline bool ema_decay_ok(float d) { return d >= 0.f && d <= 1.f; }        // (NaN fails both comparisons)
+int vqa_adamw_ema(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float wd,
+                  long long calls, const float* sumsq, float max_norm, float gscale, const int* skip, int* skipped, void* p_bf16,
+                  float* ema, float ema_decay, int ema_warmup, hipStream_t st) {
+  if (calls < 1 || n < 0 || !ema || !ema_decay_ok(ema_decay)) return VQA_EARG;
+  size_t blocks = ((size_t)n + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(adamw_ema_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, (size_t)n, lr, b1, b2, eps, wd, calls, sumsq, max_norm,
+                     gscale, skip, skipped, (bf16_t*)p_bf16, ema, ema_decay, ema_warmup);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+int vqa_adamw_ranges_ema(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n, float lr, float b1, float b2,
+                         float eps, float wd, long long calls, const float* sumsq, float max_norm, float gscale, const int* skip, int* skipped,
+                         int* lag, const int* frozen, int nf, void* p_bf16, float* ema, float ema_decay, int ema_warmup, hipStream_t st) {
+  if (calls < 1 || R < 0 || R > VQA_RANGES_MAX || n < 0 || n % 4 || (R == 0 && n != 0) || nf < 0 || (nf > 0 && (!lag || !frozen))) return VQA_EARG;
+  if (!ema || !ema_decay_ok(ema_decay)) return VQA_EARG;
+  size_t blocks = ((size_t)n / 4 + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(adamw_ranges_ema_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, table, R, n, lr, b1, b2, eps, wd, calls, sumsq,
+                     max_norm, gscale, skip, skipped, (const int*)lag, (bf16_t*)p_bf16, ema, ema_decay, ema_warmup);
+  if (nf > 0) hipLaunchKernelGGL(adamw_lag_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, lag, frozen, nf, skip);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+int vqa_ema_update(float* ema, const float* p, long long n, float d, hipStream_t st) {
+  if (!ema || !p || n < 0 || !ema_decay_ok(d)) return VQA_EARG;
+  const long long nv = (((uintptr_t)ema | (uintptr_t)p) & 15) ? 0 : n / 4;
+  size_t blocks = ((size_t)(nv ? nv : n) + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(ema_update_kernel, dim3((unsigned)blocks), dim3(256), 0, st, ema, p, n, nv, d);
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
 

@@ -99,6 +99,10 @@ HBM_BYTES = {
     "vqa_adamw": ("optimizer", lambda a: a[4] * 4 * 7),
     "vqa_sumsq_ranges": ("optimizer", lambda a: a[3] * 4),
     "vqa_adamw_ranges": ("optimizer", lambda a: a[6] * 4 * 7),
+    # + the weight average: read and write `ema` (8 B per element); alone: read p, read and write ema
+    "vqa_adamw_ema": ("optimizer", lambda a: a[4] * 4 * 9),
+    "vqa_adamw_ranges_ema": ("optimizer", lambda a: a[6] * 4 * 9),
+    "vqa_ema_update": ("optimizer", lambda a: a[2] * 4 * 3),
 }
 
 

@@ -9,11 +9,13 @@ or "gloo" in the CPU rehearsal tests) and divided by world size inside the optim
 """
 from __future__ import annotations
 
+import contextlib
 from typing import List, Optional
 
 import torch
 import torch.distributed as dist
 
+from . import ema as EMA
 from . import finetune as FT
 from . import layout as LY
 from ._lib import call, dt, ptr
@@ -160,14 +162,30 @@ def _is_soft(targets) -> bool:
 
 class HipTrainer:
     def __init__(self, model, lr=1e-4, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
-                 process_group=None, overlap=True, force_reducer=False, label_smoothing=0.0, class_weight=None, ignore_index=None):
+                 process_group=None, overlap=True, force_reducer=False, label_smoothing=0.0, class_weight=None, ignore_index=None,
+                 ema_decay=None, ema_warmup=False):
+        """ema_decay (None, or a float in [0, 1]): keep an exponential moving average of the weights, self.ema (a flat fp32 buffer laid out
+        like model._flat, started at the initial weights): ema = d * ema + (1 - d) * p after every applied update, computed by the AdamW
+        launch itself (vqa_adamw_ema / vqa_adamw_ranges_ema) from the updated parameter it still holds -- no extra launch.  ema_warmup:
+        d = min(ema_decay, (1 + t) / (10 + t)) with Adam's step number t (per parameter when parts are frozen: the average of a
+        parameter advances only while it trains).  A skipped step leaves the average untouched.  `ema_decay` stays a plain attribute that
+        may be changed between steps, like `lr`.  None (default): no buffer, and the step issues exactly the launches it issues without
+        this feature.  Data parallel: every rank applies the same update to identical parameters, so the averages stay identical and
+        nothing is communicated.  ema_weights() / ema_state_dict() / load_ema_state_dict() evaluate on, export and restore the average."""
         self.model = model
+        # validated on the host before anything is allocated or launched
+        self.ema_decay = None if ema_decay is None else EMA.check_decay(ema_decay, "HipTrainer: ema_decay")
+        self.ema_warmup = bool(ema_warmup)
+        self.ema = None
+        self._ema_swapped = False
         self.engine = model._ensure_engine()
         # nn.CrossEntropyLoss's constructor options for hard labels (all at their defaults: the plain loss launch, unchanged)
         self.label_smoothing, self.ignore_index, self.class_weight = self._check_loss_opts(label_smoothing, class_weight, ignore_index)
         self._loss_opts = self.label_smoothing != 0.0 or self.class_weight is not None or self.ignore_index is not None
         self.lr, self.wd, self.betas, self.eps, self.max_norm = lr, weight_decay, betas, eps, max_grad_norm
         flat = model._flat
+        if self.ema_decay is not None:
+            self.ema = flat.detach().clone()
         self.G = torch.zeros_like(flat)
         self.m = torch.zeros_like(flat)
         self.v = torch.zeros_like(flat)
@@ -258,8 +276,13 @@ class HipTrainer:
         loss and a ZERO gradient: the step still runs AdamW on it (weight decay and the moments' decay apply), which is what the
         reference loop does with torch when every target is ignored; torch's NaN gradient in the weighted case is not reproduced.
         Such steps are counted on the device and check() raises ValueError for them."""
+        if self._ema_swapped:
+            raise RuntimeError("HipTrainer.step inside ema_weights(): the model holds the averaged weights; leave the block first")
         eng, T = self.engine, self.engine.dtype
         dev = self.G.device
+        ema_args = ()
+        if self.ema is not None:                           # (ema_decay may have been changed since the constructor checked it)
+            ema_args = (ptr(self.ema), EMA.check_decay(self.ema_decay, "HipTrainer: ema_decay"), int(bool(self.ema_warmup)))
         soft = _is_soft(targets)
         if soft and self._loss_opts:
             raise TypeError("HipTrainer.step: label_smoothing / class_weight / ignore_index apply to hard labels; "
@@ -328,14 +351,15 @@ class HipTrainer:
         b1, b2 = self.betas
         if self._ranges is None:
             call("vqa_sumsq", ptr(self.G), self.G.numel(), ptr(self.sumsq))
-            call("vqa_adamw", ptr(self.model._flat), ptr(self.G), ptr(self.m), ptr(self.v), self.G.numel(), self.lr, b1, b2, self.eps,
-                 self.wd, self.calls, ptr(self.sumsq), float(self.max_norm), gscale, ptr(self.bad_step), ptr(self._bad), ptr(eng.adamw_copy_target()))
+            call("vqa_adamw_ema" if ema_args else "vqa_adamw", ptr(self.model._flat), ptr(self.G), ptr(self.m), ptr(self.v), self.G.numel(),
+                 self.lr, b1, b2, self.eps, self.wd, self.calls, ptr(self.sumsq), float(self.max_norm), gscale, ptr(self.bad_step), ptr(self._bad),
+                 ptr(eng.adamw_copy_target()), *ema_args)
         else:                                      # frozen parameters: only the trainable ranges are read and written
             table, R, n, fidx, nf = self._ranges
             call("vqa_sumsq_ranges", ptr(self.G), ptr(table), R, n, ptr(self.sumsq))
-            call("vqa_adamw_ranges", ptr(self.model._flat), ptr(self.G), ptr(self.m), ptr(self.v), ptr(table), R, n, self.lr, b1, b2,
-                 self.eps, self.wd, self.calls, ptr(self.sumsq), float(self.max_norm), gscale, ptr(self.bad_step), ptr(self._bad),
-                 ptr(self._lag), ptr(fidx), nf, ptr(eng.adamw_copy_target()))
+            call("vqa_adamw_ranges_ema" if ema_args else "vqa_adamw_ranges", ptr(self.model._flat), ptr(self.G), ptr(self.m), ptr(self.v),
+                 ptr(table), R, n, self.lr, b1, b2, self.eps, self.wd, self.calls, ptr(self.sumsq), float(self.max_norm), gscale,
+                 ptr(self.bad_step), ptr(self._bad), ptr(self._lag), ptr(fidx), nf, ptr(eng.adamw_copy_target()), *ema_args)
         # the kernel wrote the bf16 operand copy too: the next step() skips the cast launch if nothing touched the parameters in between
         self._copy_sig = self._param_sig() if eng.adamw_copy_target() is not None else None
         return self.loss, logits_f
@@ -349,6 +373,40 @@ class HipTrainer:
         if not on_dev:                                     # checked on the host: a pinned copy goes out without a sync
             idx = idx.pin_memory().to(dev, non_blocking=True)
         return idx
+
+    # ---- the weight average (ema_decay is not None)
+    def _need_ema(self, what):
+        if self.ema is None:
+            raise RuntimeError(f"HipTrainer.{what} needs the weight average: construct the trainer with ema_decay=<float in [0, 1]>")
+        return self.ema
+
+    def ema_state_dict(self):
+        """model.state_dict() with every parameter replaced by a clone of its slice of the average (same keys, shapes and dtypes: it loads
+        with strict=True into this VQAModel and into the reference's).  Buffers -- the BatchNorm running statistics among them -- are the
+        live model's: they are running averages already."""
+        return EMA.state_dict(self.model, self._need_ema("ema_state_dict"))
+
+    def load_ema_state_dict(self, sd):
+        """The inverse of ema_state_dict(), for resuming: the parameter entries of `sd` become the average; buffer keys are ignored.
+        KeyError for a missing parameter, ValueError for a shape mismatch (nothing is written then)."""
+        EMA.load_state_dict(self.model, self._need_ema("load_ema_state_dict"), sd)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """`with trainer.ema_weights():` -- the model holds the averaged weights inside the block (validation with the same model object:
+        eager eval forward, forward_graphed, predict, predict_topk, encode_images + answer, graphs captured earlier included) and its
+        own weights again afterwards, also when the block raises.  The contents of model._flat and self.ema are exchanged through torch
+        ops and exchanged back: parameters, average and both moments have their earlier bits after the block, an ImageContext from one
+        side is refused on the other, and the next step() re-casts the bf16 operand copy.  step() inside the block raises RuntimeError."""
+        ema = self._need_ema("ema_weights")
+        if self._ema_swapped:
+            raise RuntimeError("HipTrainer.ema_weights() is not re-entrant")
+        with EMA.swapped(self.model, ema):
+            self._ema_swapped = True
+            try:
+                yield self.model
+            finally:
+                self._ema_swapped = False
 
     def params_changed(self):
         """Tell the trainer that the parameters were written behind torch's back (through `.data`, a raw pointer, another C-ABI call):
