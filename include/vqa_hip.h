@@ -465,6 +465,13 @@ int vqa_adamw_ranges_ema(float* p, const float* g, float* m, float* v, const lon
                          float* ema, float ema_decay, int ema_warmup, hipStream_t stream);
 int vqa_ema_update(float* ema, const float* p, long long n, float d, hipStream_t stream);
 
+/* Row gather for cached image features (VQAModel.encode_features, ImageFeatures.select): dst[i] = src[index[i]] for i < n, rows of
+   row_bytes bytes of any element type.  src holds n_src rows; index is device int32 [n] with every entry in [0, n_src) -- the caller
+   checks the range; an entry outside it leaves its destination row unwritten and reads nothing.  16-byte vector loads and stores, one
+   workgroup per 16 KB chunk of a row.  Status 1000 without a launch: row_bytes <= 0 or no multiple of 16, n or n_src negative, and
+   for n > 0 a NULL or not 16-byte-aligned src / dst, a NULL index, n_src == 0, or 2^24 or more chunks (n * ceil(row_bytes / 16384)).  n == 0 launches nothing. */
+int vqa_gather_rows(const void* src, const int* index, void* dst, int n, long long row_bytes, int n_src, hipStream_t stream);
+
 /* ---- input pipeline on the GPU -----------------------------------------------------------------
  * vqa_image_normalize: torchvision ToTensor + Normalize of data/preprocess.py:34-35,117-121 -- uint8 HWC [B][H][W][3] ->
  * float32 NCHW, (u/255 - mean[c]) / std[c] in torch's operation order (bit-identical), optional per-sample horizontal flip

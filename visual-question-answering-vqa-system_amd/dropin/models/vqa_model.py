@@ -168,6 +168,42 @@ def _grouped_backward(ctx, dlogits):
 torch.library.register_autograd("vqa_hip::vqa_forward_grouped", _grouped_backward, setup_context=_grouped_setup_ctx)
 
 
+# training from cached image features (ImageFeatures; the image encoder is frozen, in eval mode and never runs):
+#   torch.ops.vqa_hip.vqa_forward_features(features [U][Hf][Wf][Cf], token_ids [N], mask, image_index int32 [N] | None, params, handle,
+#                                          training) -> logits [N]
+# The backward is vqa_backward itself: the tape's plan has no CNN part, and the features get no gradient.
+@torch.library.custom_op("vqa_hip::vqa_forward_features", mutates_args=(), device_types="cuda")
+def _vqa_forward_features_op(features: torch.Tensor, token_ids: torch.Tensor, mask: Optional[torch.Tensor],
+                             image_index: Optional[torch.Tensor], flat_params: torch.Tensor, handle: int, training: bool) -> torch.Tensor:
+    model = _MODELS[handle]
+    plan, model._pending_plan = model._pending_plan, None
+    logits, _, tape = model._engine.forward_features(features, token_ids, mask, training, False, need_tape=True, kv_index=image_index,
+                                                     plan=plan)
+    model._tape_seq += 1
+    model._tapes[model._tape_seq] = tape
+    while len(model._tapes) > model.max_live_tapes:
+        model._tapes.pop(next(iter(model._tapes)))
+    return logits
+
+
+@_vqa_forward_features_op.register_fake
+def _(features, token_ids, mask, image_index, flat_params, handle, training):
+    return features.new_empty((token_ids.shape[0], _MODELS[handle].num_answers), dtype=torch.float32)
+
+
+def _features_setup_ctx(ctx, inputs, output):
+    ctx.handle = inputs[5]
+    ctx.tape_id = _MODELS[inputs[5]]._tape_seq
+
+
+def _features_backward(ctx, dlogits):
+    G = torch.ops.vqa_hip.vqa_backward(dlogits, ctx.handle, ctx.tape_id)
+    return None, None, None, None, G, None, None
+
+
+torch.library.register_autograd("vqa_hip::vqa_forward_features", _features_backward, setup_context=_features_setup_ctx)
+
+
 def _setup_ctx(ctx, inputs, output):
     handle = inputs[4]
     ctx.handle = handle
@@ -417,12 +453,36 @@ class _FlatParams(torch.autograd.Function):
 # torch.optim steps counted process-wide: an optimizer may write the parameters without bumping their version counters (its foreach
 # kernels work on aliases), so any step makes every ImageContext stale (a server that trains nothing in-process never pays for it)
 _OPT_STEPS = [0]
+_OPT_PRE: Dict[int, Dict[int, int]] = {}      # id(optimizer) -> {model handle: _feat_version()} while that optimizer's step() runs
+
+
+def _before_optimizer_step(optimizer, args, kwargs):
+    # only models that ever handed out an ImageFeatures are looked at: a process that caches no features pays one dict scan per step.
+    # (A step that raises leaves its entry behind until that optimizer's next step overwrites it: one small dict per optimizer.)
+    pre = {h: m._feat_version() for h, m in _MODELS.items() if m._feat_live}
+    if pre:
+        _OPT_PRE[id(optimizer)] = pre
+    else:
+        _OPT_PRE.pop(id(optimizer), None)
 
 
 def _count_optimizer_step(optimizer, args, kwargs):
     _OPT_STEPS[0] += 1
+    # cached image features (VQAModel._feat_stamp): a step that wrote an image_encoder parameter (the optimizer writes exactly the
+    # parameters that hold a gradient) makes them stale; what any other step did to the version counters _feat_version reads is excused
+    before = _OPT_PRE.pop(id(optimizer), None)
+    live = [(h, m) for h, m in _MODELS.items() if m._feat_live]
+    if not live:
+        return
+    written = {id(p) for g in optimizer.param_groups for p in g["params"] if p.grad is not None}
+    for h, m in live:
+        if before is None or h not in before or any(id(p) in written for p in m._cnn_params()):
+            m._feat_epoch += 1                  # (no reading from before the step -- the features were made inside it: nothing to excuse by)
+        else:
+            m._feat_excused += m._feat_version() - before[h]
 
 
+_optim_hooks.register_optimizer_step_pre_hook(_before_optimizer_step)
 _optim_hooks.register_optimizer_step_post_hook(_count_optimizer_step)
 
 
@@ -456,6 +516,72 @@ class ImageContext:
 
     def __repr__(self):
         return f"ImageContext(num_images={self.num_images})"
+
+
+def _checked_index(index, U: int, what: str) -> torch.Tensor:
+    """A 1-D integer index with every entry in [0, U), as given (any integer dtype, CPU or device): ValueError for another shape or
+    dtype, IndexError for an entry out of range.  The range check is free for a CPU index and one device-to-host read for a device
+    index (VQAModel._image_index's rule)."""
+    if not isinstance(index, torch.Tensor):
+        index = torch.as_tensor(index)
+    if index.dim() != 1:
+        raise ValueError(f"{what} must be 1-D; got shape {tuple(index.shape)}")
+    if index.dtype.is_floating_point or index.dtype.is_complex or index.dtype == torch.bool:
+        raise ValueError(f"{what} must hold integers, got {index.dtype}")
+    if index.shape[0]:
+        lo, hi = (int(v) for v in torch.stack(torch.aminmax(index)).tolist())
+        if lo < 0 or hi >= U:
+            raise IndexError(f"{what} holds {lo if lo < 0 else hi}, outside [0, {U}) for {U} images")
+    return index
+
+
+class ImageFeatures:
+    """The image encoder's output for U images (VQAModel.encode_features): NHWC features [U, Hf, Wf, Cf] in the compute dtype on the
+    device -- 50 KB per image at the default shape in bf16, so a dataset-sized bank stays resident.  Everything that takes images for a
+    frozen, eval-mode image encoder takes one of these instead and skips the CNN: model(...), forward_grouped, encode_images,
+    HipTrainer.step.  Valid while the image encoder's parameters and BatchNorm buffers are what they were when it was made (writes to
+    the text encoder, fusion and answer head do not matter); refused with RuntimeError afterwards (VQAModel._feat_stamp)."""
+    __slots__ = ("_t", "_stamp", "_handle")
+
+    def __init__(self, t: torch.Tensor, stamp: tuple, handle: int):
+        self._t = t
+        self._stamp = stamp
+        self._handle = handle
+
+    @property
+    def num_images(self) -> int:
+        return self._t.shape[0]
+
+    def tensor(self) -> torch.Tensor:
+        """The device tensor [U, Hf, Wf, Cf] itself (not a copy): for torch.save; VQAModel.features_from_tensor wraps it again."""
+        return self._t
+
+    def select(self, index) -> "ImageFeatures":
+        """The features of the images index[i], in that order (repeats allowed), as a new [len(index), Hf, Wf, Cf] block: one
+        vqa_gather_rows launch.  index: 1-D, any integer dtype, CPU or device; the range check is free for a CPU index (which then
+        goes to the device without a sync) and costs one device-to-host read for a device index.  ValueError for a wrong shape or
+        dtype, IndexError for an entry outside [0, num_images), both before any launch."""
+        model = _MODELS[self._handle]
+        index = _checked_index(index, self.num_images, "ImageFeatures.select: index")
+        dev = self._t.device
+        if index.device != dev:
+            index = index.to(torch.int32).pin_memory().to(dev, non_blocking=True) if dev.type == "cuda" else index.to(dev, torch.int32)
+        else:
+            index = index.to(torch.int32)
+        return ImageFeatures(model._pkg.kernels.gather_rows(self._t, index.contiguous()), self._stamp, self._handle)
+
+    @staticmethod
+    def cat(parts) -> "ImageFeatures":
+        """The features of several encode_features() calls as one block, in order.  All parts must come from one model in one state."""
+        parts = list(parts)
+        if not parts or any(not isinstance(p, ImageFeatures) for p in parts):
+            raise ValueError("ImageFeatures.cat needs a non-empty sequence of ImageFeatures")
+        if any(p._handle != parts[0]._handle or p._stamp != parts[0]._stamp for p in parts):
+            raise RuntimeError("ImageFeatures.cat: the parts were made by different models, or the image encoder changed between them")
+        return ImageFeatures(torch.cat([p._t for p in parts], dim=0), parts[0]._stamp, parts[0]._handle)
+
+    def __repr__(self):
+        return f"ImageFeatures(num_images={self.num_images}, shape={tuple(self._t.shape[1:])}, dtype={self._t.dtype})"
 
 
 class VQAModel(nn.Module):
@@ -516,6 +642,9 @@ class VQAModel(nn.Module):
         self._graphs: Dict[Any, Any] = {}           # captured inference graphs, one per input shape (forward_graphed)
         self._tape_seq = 0
         self._ctx_epoch = 0                         # bumped by whatever invalidates an ImageContext torch cannot see (_ctx_stamp)
+        self._feat_epoch = 0                        # bumped by whatever changes the image encoder (_feat_stamp)
+        self._feat_excused = 0                      # flat-buffer version bumps known to have left the image encoder alone (_feat_stamp)
+        self._feat_live = False                     # an ImageFeatures was handed out: the optimizer step hooks look at this model
         self._handle = _NEXT_HANDLE[0]
         _NEXT_HANDLE[0] += 1
         _MODELS[self._handle] = self
@@ -587,6 +716,7 @@ class VQAModel(nn.Module):
         self._flat = flat
         self._engine = None
         self._ctx_epoch += 1
+        self._feat_epoch += 1
         self.__dict__.pop("_params_cache", None)
         if self._graphs:                             # captured graphs hold the OLD flat buffer's pointers
             torch.cuda.synchronize()
@@ -624,6 +754,7 @@ class VQAModel(nn.Module):
             raise ValueError("inference precision 'mxfp8' needs compute_dtype='bf16' (this model computes in fp32)")
         self._infer_precision = precision
         self._ctx_epoch += 1
+        self._feat_epoch += 1
         if self._engine is not None:
             self._engine.infer_precision = precision
         return self
@@ -633,13 +764,19 @@ class VQAModel(nn.Module):
             return super().load_state_dict(state_dict, strict=strict, assign=assign)
         finally:
             self._ctx_epoch += 1                     # BatchNorm buffers are not views of the flat buffer: its version misses them
+            self._feat_epoch += 1
 
     # ---- reference API
     def forward(self, images: torch.Tensor, token_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 return_aux: bool = False, image_index: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, Optional[Dict]]:
         """image_index (extension, inference only): images is [U, 3, H, W], token_ids [N, L] and question i is asked of image
         image_index[i]; the result equals forward(images[image_index], token_ids, attention_mask) while the image half runs once per
-        image (see answer())."""
+        image (see answer()).
+        images may be an ImageFeatures (extension; encode_features): the image encoder, frozen and in eval mode, does not run, and
+        everything after it is this forward -- eval, or training under autograd with gradients to the other three parts (then
+        image_index is forward_grouped's, and return_aux raises NotImplementedError)."""
+        if isinstance(images, ImageFeatures):
+            return self._forward_features(images, token_ids, attention_mask, return_aux, image_index)
         if not images.is_cuda:
             raise RuntimeError("VQAModel (HIP) got CPU inputs; this implementation only runs on an MI355X (no CPU fallback)")
         if image_index is not None:
@@ -724,6 +861,136 @@ class VQAModel(nn.Module):
         # running statistics, and HipTrainer's AdamW writes the parameters through a raw pointer) and the model epoch
         # (load_state_dict, .to(), set_inference_precision).  Four integers: answer() at N = 1 is a latency path
         return (self._ctx_epoch, self._flat._version, _OPT_STEPS[0], eng.step_id)
+
+    # ---- cached image features (extension)
+    def _feat_stamp(self, eng):
+        # What an ImageFeatures must still match.  Unlike an ImageContext it depends on the image encoder ALONE, and every AdamW step
+        # of a fine-tuning run writes the other three parts, so _ctx_stamp's terms (whole-buffer version, every optimizer step, every
+        # training forward) would refuse a bank after its first step.  Three host integers, nothing read from the device:
+        #   _feat_epoch              bumped by load_state_dict, .to() (_reflatten), set_inference_precision, a HipTrainer step whose plan
+        #                            trains an image_encoder parameter (trainer.py), a torch.optim step that wrote one (the step hooks
+        #                            above: the optimizer writes the parameters that hold a gradient), ema_weights() unless the trainer
+        #                            knows the average's image encoder equals the model's, and invalidate_features();
+        #   eng.cnn_train_forwards   forwards that ran the CNN in train mode: BatchNorm running statistics moved;
+        #   _feat_version - excused  torch's version counters of the flat buffer and of the image_encoder parameters: an in-place torch
+        #                            write to one of those parameters (or to the flat buffer they are views of) moves them.  After
+        #                            .to() every Parameter has a counter of its own, so writes to the other parts are not seen at all;
+        #                            a model whose parameters still share the flat buffer's counter sees every write.  Bumps by writers
+        #                            known to leave the image encoder alone are excused (_feat_excused: torch.optim steps that wrote no
+        #                            image_encoder parameter, the ema_weights() exchange while the average still has this image encoder); any
+        #                            other bump makes the features stale.  HipTrainer's AdamW writes through a raw pointer and moves
+        #                            no counter.
+        # Not seen (as HipTrainer.params_changed documents for the operand copy): writes through `.data` or a raw pointer, which
+        # bypass torch's version counters; after one, call invalidate_features().
+        self._feat_live = True
+        return (self._feat_epoch, eng.cnn_train_forwards, self._feat_version() - self._feat_excused)
+
+    def _feat_version(self):
+        return self._flat._version + sum(p._version for p in self._cnn_params())
+
+    def _cnn_params(self):
+        pl = self._param_list()
+        idx = self.__dict__.get("_cnn_param_idx")
+        if idx is None:
+            idx = [j for j, e in enumerate(self._param_entries) if e.name.startswith("image_encoder.")]
+            self.__dict__["_cnn_param_idx"] = idx
+        return [pl[j] for j in idx]
+
+    def invalidate_features(self):
+        """Declare every ImageFeatures made so far stale: for writes to the image encoder that torch's version counters do not see
+        (through `.data`, a raw pointer or another C-ABI call)."""
+        self._feat_epoch += 1
+
+    def _check_features(self, features: "ImageFeatures", what: str):
+        """The engine, after checking that `features` may stand in for this model's frozen, eval-mode image encoder: RuntimeError for
+        another model's features, stale ones, a trainable image_encoder parameter while autograd records, or a train-mode image encoder
+        -- all host logic, before any launch."""
+        if features._handle != self._handle:
+            raise RuntimeError(f"{what}: these ImageFeatures were made by another model")
+        eng = self._ensure_engine()
+        if features._stamp != self._feat_stamp(eng):
+            raise RuntimeError(f"{what}: stale ImageFeatures: the image encoder's parameters, BatchNorm buffers or inference precision "
+                               "changed since encode_features() made them; encode the images again")
+        if self._part_modes()[0]:
+            raise RuntimeError(f"{what}: ImageFeatures stand in for an eval-mode image encoder: call model.image_encoder.eval()")
+        t = features._t
+        if t.dim() != 4 or t.dtype != self.compute_dtype or t.device != self._flat.device or not t.is_contiguous():
+            raise RuntimeError(f"{what}: the features must be a contiguous [U, Hf, Wf, Cf] {self.compute_dtype} tensor on {self._flat.device}")
+        return eng
+
+    def encode_features(self, images: torch.Tensor, out: Optional["ImageFeatures"] = None, at: int = 0) -> "ImageFeatures":
+        """Run the image encoder alone, once per image, and keep its output: exactly the launches forward() issues for a frozen,
+        eval-mode image encoder (stem and residual stages on the Conv+BN-folded path, set_inference_precision honoured), nothing after
+        them.  Inference only, under encode_images' rules (eval mode, no autograd).  out / at: write the U results into rows
+        [at, at + U) of an existing ImageFeatures (features_from_tensor(torch.empty(...)) makes an empty bank) and return it, so a
+        dataset-sized bank is filled batch by batch; ImageFeatures.cat joins separate results instead."""
+        if not images.is_cuda:
+            raise RuntimeError("VQAModel (HIP) got CPU inputs; this implementation only runs on an MI355X (no CPU fallback)")
+        self._inference_only("encode_features", images)
+        eng = self._ensure_engine()
+        if out is not None:
+            if not isinstance(out, ImageFeatures):
+                raise TypeError("encode_features: `out` must be an ImageFeatures")
+            self._check_features(out, "encode_features(out=)")
+            if isinstance(at, bool) or int(at) != at or at < 0 or at + images.shape[0] > out.num_images:
+                raise IndexError(f"encode_features: rows [{at}, {at + images.shape[0]}) do not fit a bank of {out.num_images} images")
+        feat = eng.encode_features(images.contiguous().float())
+        if out is None:
+            return ImageFeatures(feat, self._feat_stamp(eng), self._handle)
+        if tuple(feat.shape[1:]) != tuple(out._t.shape[1:]):
+            raise RuntimeError(f"encode_features: these images give {tuple(feat.shape[1:])} features, the bank holds {tuple(out._t.shape[1:])}")
+        out._t[int(at): int(at) + feat.shape[0]].copy_(feat)
+        return out
+
+    def features_from_tensor(self, t: torch.Tensor) -> "ImageFeatures":
+        """Wrap a [U, Hf, Wf, 512] tensor in the compute dtype on the model's device (ImageFeatures.tensor() saved earlier, or an empty
+        bank to fill with encode_features(out=)) as features of the image encoder AS IT IS NOW.  Shape, dtype and device are checked;
+        that the values came from these weights is the caller's word."""
+        if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.shape[3] != self.image_encoder.output_channels:
+            raise ValueError(f"features_from_tensor: expected a [U, Hf, Wf, {self.image_encoder.output_channels}] tensor, got "
+                             + (f"shape {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__))
+        if t.dtype != self.compute_dtype:
+            raise ValueError(f"features_from_tensor: this model computes in {self.compute_dtype}, the tensor holds {t.dtype}")
+        if t.device != self._flat.device:
+            raise ValueError(f"features_from_tensor: the tensor is on {t.device}, the model on {self._flat.device}")
+        if t.requires_grad:
+            raise ValueError("features_from_tensor: cached features carry no gradient; pass t.detach()")
+        return ImageFeatures(t.contiguous(), self._feat_stamp(self._ensure_engine()), self._handle)
+
+    def _forward_features(self, features, token_ids, attention_mask, return_aux, image_index, grouped=False):
+        """forward / forward_grouped over ImageFeatures: autograd through vqa_forward_features (gradients to the parameters outside
+        the image encoder), otherwise the engine's no-tape routes."""
+        eng = self._check_features(features, "forward")
+        if not token_ids.is_cuda:
+            raise RuntimeError("VQAModel (HIP) got CPU inputs; this implementation only runs on an MI355X (no CPU fallback)")
+        feat = features._t
+        dev = feat.device
+        U, N = feat.shape[0], token_ids.shape[0]
+        idx = self._image_index(image_index, U, N, dev)
+        params = self._param_list()
+        recording = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+        if recording and any(p.requires_grad for p in self._cnn_params()):
+            raise RuntimeError("forward: ImageFeatures stand in for a frozen image encoder: call model.image_encoder.requires_grad_(False)")
+        if return_aux and recording:
+            raise NotImplementedError("forward(ImageFeatures, return_aux=True) under autograd: gradients through aux outputs are not "
+                                      "supported from cached features (run it under torch.no_grad())")
+        token_ids = token_ids.contiguous().long()
+        maskf = None if attention_mask is None else attention_mask.contiguous().float()
+        grouped = grouped or image_index is not None
+        if idx is None and (grouped or U != N):
+            idx = self._implied_index(U, N, dev)
+        if recording:
+            flat = _FlatParams.apply(self._flat, self._handle, *params)
+            self._pending_plan = self._finetune_plan(params, False, self.training)
+            logits = torch.ops.vqa_hip.vqa_forward_features(feat, token_ids, maskf, idx, flat, self._handle, self.training)
+            return logits, None
+        if grouped and not self.training:
+            # eval with an image index: the images route is answer(encode_images(images)); so is this one, from the features
+            logits, aux = eng.answer(eng.context_from_features(feat, want_aux=return_aux), token_ids, maskf, idx, want_aux=return_aux)
+            return (logits, aux) if return_aux else (logits, None)
+        logits, aux, _ = eng.forward_features(feat, token_ids, maskf, self.training, return_aux, need_tape=False, kv_index=idx,
+                                              plan=self._modes_plan())
+        return (logits, aux) if return_aux else (logits, None)
 
     def _inference_only(self, what, images=None):
         if self.training:
@@ -818,7 +1085,10 @@ class VQAModel(nn.Module):
         a zero feature gradient.  With U = N and image_index = arange(N) every value (dropout included) is bit-equal to forward().
         Eval mode without autograd delegates to forward(image_index=...).  return_aux=True raises NotImplementedError while autograd
         records (no gradients through aux under grouping); otherwise aux has U image rows and N question rows.
-        Raises IndexError for an index outside [0, U), ValueError for a wrong shape or dtype."""
+        Raises IndexError for an index outside [0, U), ValueError for a wrong shape or dtype.
+        images may be an ImageFeatures of the U images (encode_features; frozen, eval-mode image encoder): the CNN pass is skipped."""
+        if isinstance(images, ImageFeatures):
+            return self._forward_features(images, token_ids, attention_mask, return_aux, image_index, grouped=True)
         if not images.is_cuda:
             raise RuntimeError("VQAModel (HIP) got CPU inputs; this implementation only runs on an MI355X (no CPU fallback)")
         U, N = images.shape[0], token_ids.shape[0]
@@ -849,7 +1119,12 @@ class VQAModel(nn.Module):
         """Run the image half of the eval forward once per image (stem, residual stages, SE / spatial attention, projector and the
         K / V projections of every cross-attention layer) and keep it for answer().  Inference only (eval mode, no autograd).  The
         context keeps about 100 KB per image at the default configuration (49 tokens x 2 layers x K | V in bf16), and the NHWC features
-        plus projected tokens for return_aux (another ~75 KB)."""
+        plus projected tokens for return_aux (another ~75 KB).
+        images may be an ImageFeatures (encode_features): only the projector and the K / V projections run."""
+        if isinstance(images, ImageFeatures):
+            self._inference_only("encode_images")
+            eng = self._check_features(images, "encode_images")
+            return ImageContext(images.num_images, eng.context_from_features(images._t, want_aux=True), self._ctx_stamp(eng), self._handle)
         if not images.is_cuda:
             raise RuntimeError("VQAModel (HIP) got CPU inputs; this implementation only runs on an MI355X (no CPU fallback)")
         self._inference_only("encode_images", images)

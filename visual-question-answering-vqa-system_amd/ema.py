@@ -71,7 +71,7 @@ def load_state_dict(model, ema: torch.Tensor, sd):
 
 
 @contextlib.contextmanager
-def swapped(model, ema: torch.Tensor):
+def swapped(model, ema: torch.Tensor, keeps_cnn: bool = False):
     """Exchange the CONTENTS of model._flat and the average for the duration of the block, and exchange them back on exit (also when
     the block raises): validation on the averaged weights with the same model object.
 
@@ -79,17 +79,24 @@ def swapped(model, ema: torch.Tensor):
     side is refused on the other (VQAModel._ctx_stamp), and HipTrainer re-casts the bf16 operand copy at its next step (_param_sig).
     Captured inference graphs stay valid: they hold the flat buffer's POINTER and re-derive every working copy (the bf16 cast, the
     Conv+BN fold, the stem operands) from it on each replay, so a graph captured outside runs on the averaged weights inside.  The
-    model epoch is bumped all the same, for whatever caches on it."""
+    model epoch is bumped all the same, for whatever caches on it.  keeps_cnn: the caller knows that the average's image encoder
+    equals the model's (HipTrainer: nothing wrote it since the average was made): cached ImageFeatures then stay valid on both sides (VQAModel._feat_stamp:
+    the exchange's version bumps are excused); otherwise they are refused like the contexts."""
     flat = model._flat
     if ema.shape != flat.shape or ema.device != flat.device or ema.dtype != flat.dtype:
         raise RuntimeError("the average no longer matches model._flat (the model was moved with .to() after the average was made)")
 
     def exchange():
+        v0 = model._feat_version() if keeps_cnn else 0
         with torch.no_grad():
             tmp = flat.clone()
             flat.copy_(ema)
             ema.copy_(tmp)
         model._ctx_epoch += 1
+        if keeps_cnn:
+            model._feat_excused += model._feat_version() - v0
+        else:
+            model._feat_epoch += 1
 
     exchange()
     try:

@@ -90,6 +90,8 @@ class HipEngine:
         self.seed_base = 0x5EED
         self.seed_rank = None
         self.step_id = 0
+        self.cnn_train_forwards = 0               # forwards that ran the CNN in train mode (BatchNorm running statistics moved): cached
+                                                  # image features are stale after one (VQAModel._feat_stamp)
         self.wsrc = flat
         self._wsrc_fresh = False                  # one-shot: the bf16 copy wsrc was written by the last fused AdamW launch (trainer.py)
         self._wt: Dict[str, torch.Tensor] = {}
@@ -247,11 +249,14 @@ class HipEngine:
     def _make_stem_fcoef(self):
         return stem_fcoef(self.P("image_encoder.stem.1.weight"), self.P("image_encoder.stem.1.bias"))
 
-    def begin_step(self, for_backward: bool = True):
-        """Refresh the working copies of the weights (one cast of the whole flat buffer in bf16 mode)."""
+    def begin_step(self, for_backward: bool = True, stem: bool = True):
+        """Refresh the working copies of the weights (one cast of the whole flat buffer in bf16 mode).
+        stem=False (the routes that start from cached image features: forward_features, context_from_features): the stem runs
+        neither forward nor backward, so its operands (the packed conv weight, the BatchNorm-backward helper) are not built."""
         self._wt = {}
         self._stem_fcoef = None
         self._pack_ev = None
+        make_fcoef = self._make_stem_fcoef if stem else (lambda: None)
         if for_backward:                          # inference (no tape) needs neither the transposed weights nor the stem helper
             # Both are BACKWARD operands: on the weight-gradient stream (idle until the backward starts) they no longer sit in front of
             # the stem on the main stream (one 43 us pack launch + five small torch launches per step); backward() waits for the event
@@ -260,11 +265,11 @@ class HipEngine:
                 ev = torch.cuda.Event(); ev.record(torch.cuda.current_stream())     # the parameters are final (optimizer step) on this stream
                 s2.wait_event(ev)
                 with torch.cuda.stream(s2):
-                    self._stem_fcoef = self._make_stem_fcoef()
+                    self._stem_fcoef = make_fcoef()
                     self._pack_planned()
                     self._pack_ev = torch.cuda.Event(); self._pack_ev.record(s2)
             else:
-                self._stem_fcoef = self._make_stem_fcoef() if self._wt_plan else None    # only once a backward has been seen
+                self._stem_fcoef = make_fcoef() if self._wt_plan else None    # only once a backward has been seen
                 self._pack_planned()
         if self.dtype == torch.bfloat16:
             if self.wsrc is self.flat or self.wsrc.numel() != self.flat.numel():
@@ -277,6 +282,8 @@ class HipEngine:
             self._wsrc_fresh = False
         else:
             self.wsrc = self.flat
+        if not stem:                              # (every route that runs _stem_fwd packs the stem operands in its own begin_step)
+            return
         bk = 64 if self.dtype == torch.bfloat16 else 32
         kp = (147 + bk - 1) // bk * bk
         self.stem_kp = kp
@@ -577,6 +584,8 @@ class HipEngine:
             cnn_tape = need_tape
         if ctrain or ttrain or ftrain or htrain:
             self.step_id += 1
+        if ctrain:
+            self.cnn_train_forwards += 1
         self.begin_step(for_backward=need_tape)
         if ctrain and self.fuse_bn_finalize and self.dtype == torch.bfloat16:
             self._acc_reset()                     # one memset for every BatchNorm accumulator of this forward
@@ -662,6 +671,87 @@ class HipEngine:
             return pkv
 
         q, probs_all, caw = self._cross_layers_fwd(enc, img, Bt, L, ntok, pfus, want_aux, q0=text["q0"], kv_of=kv_of, csr=csr, tape=tape)
+        logits, cat, fused, tape["pool"], tape["head"] = self._tail_fwd(q, enc, maskf, Bt, L, phead, lowp_logits)
+        if caw is not None:
+            tape["caw"] = caw
+        aux = self._aux_of(feat, B, Hf, Wf, Cf, img, enc, cat, fused, probs_all) if want_aux else None
+        return logits, aux, (tape if need_tape else None)
+
+    def forward_features(self, feat: torch.Tensor, token_ids: torch.Tensor, maskf: Optional[torch.Tensor], training: bool,
+                         want_aux: bool = False, need_tape: bool = True, lowp_logits: bool = False,
+                         kv_index: Optional[torch.Tensor] = None, plan=None):
+        """forward() from cached image features: feat is what encode_features() returned for the U images (NHWC [U][Hf][Wf][Cf],
+        compute dtype, contiguous), the image encoder is frozen and in eval mode, and _stem_fwd / _stages_fwd do not run.  Everything
+        else is forward(): the same step_id rule, _site reset and weight cast, the parts issued in forward()'s order (text encoder
+        on the side stream, projector, hoisted K | V, cross-attention layers, tail), so dropout sites and seeds are numbered as there
+        and every launch after the CNN gets the bits the images route gives it.  training / plan / kv_index / want_aux /
+        lowp_logits as in forward(); a taped call needs a plan without a CNN backward (no image_encoder parameter trains), and the
+        plan's CNN mode must be eval.  The tape carries no stem or stage records: backward() never reads them under such a plan."""
+        cfg, T = self.cfg, self.dtype
+        if feat.dim() != 4 or feat.dtype != T or not feat.is_contiguous():
+            raise RuntimeError(f"forward_features: features must be a contiguous [U, Hf, Wf, Cf] tensor in {T}")
+        if plan is not None:
+            ctrain, ttrain, ftrain, htrain = plan.modes
+            if ctrain or (need_tape and plan.cnn_low is not None):
+                raise RuntimeError("forward_features: cached image features need a frozen image encoder in eval mode")
+        else:
+            if need_tape:
+                raise RuntimeError("forward_features: a taped forward needs a fine-tuning plan with the image encoder frozen")
+            ttrain = ftrain = htrain = training
+        self._site = 0
+        if ttrain or ftrain or htrain:
+            self.step_id += 1
+        self.begin_step(for_backward=need_tape, stem=False)
+        B, Hf, Wf, Cf = feat.shape
+        ntok = Hf * Wf
+        feat = feat.view(B * ntok, Cf)
+        tape: dict = {"training": False, "B": B, "Bq": token_ids.shape[0]}
+        if need_tape:
+            tape["plan"] = plan
+        pdrop = cfg["dropout"] if ttrain else 0.0
+        pfus = cfg["dropout"] if ftrain else 0.0
+        phead = cfg["answer_dropout"] if htrain else 0.0
+        main = torch.cuda.current_stream()
+        use_side = self.two_streams and self.side is not None
+        Bt, L = token_ids.shape
+        self._pos_enc(L)
+        ncl = cfg["num_cross_layers"]
+        if use_side:
+            ev0 = torch.cuda.Event(); ev0.record(main)
+        csr = None
+        if kv_index is not None:                  # (issued where forward() issues it: ahead of the text encoder)
+            offsets = torch.empty((B + 1,), device=feat.device, dtype=torch.int32)
+            order = torch.empty((Bt,), device=feat.device, dtype=torch.int32)
+            call("vqa_index_csr", ptr(kv_index), Bt, B, ptr(offsets), ptr(order))
+            csr = (kv_index, offsets, order, B)
+            tape["csr"] = csr
+        if use_side:
+            self.side.wait_event(ev0)             # weights cast + everything earlier on main is visible to the side stream
+        with torch.cuda.stream(self.side if use_side else main):
+            enc, q0 = self._text_fwd(token_ids, maskf, pdrop, tape, hoist_q=self.hoist_cross and ncl >= 1)
+            ev_text = torch.cuda.Event(); ev_text.record()
+        tape["feat"] = dict(Hf=Hf, Wf=Wf, Cf=Cf)
+        if use_side:
+            main.wait_event(ev_text)
+        img, tape["proj"] = self._projector_fwd(feat, ntok, pfus)
+        pre_kv = [None] * ncl
+        if self.hoist_cross and use_side and ncl > 1:                    # (as in forward(): layers >= 1 project K | V on the text stream)
+            ev_img = torch.cuda.Event(); ev_img.record(main)
+            self.side.wait_event(ev_img)
+            with torch.cuda.stream(self.side):
+                for l in range(1, ncl):
+                    p = f"fusion.cross_attention.layers.{l}"
+                    pre_kv[l] = (self._cross_kv_path(img, p + ".norm_kv", p + ".cross_attention", cfg["embed_dim"]), torch.cuda.Event())
+                    pre_kv[l][1].record()
+
+        def kv_of(l):
+            if pre_kv[l] is None:
+                return None
+            pkv, ev_kv = pre_kv[l]
+            main.wait_event(ev_kv)
+            return pkv
+
+        q, probs_all, caw = self._cross_layers_fwd(enc, img, Bt, L, ntok, pfus, want_aux, q0=q0, kv_of=kv_of, csr=csr, tape=tape)
         logits, cat, fused, tape["pool"], tape["head"] = self._tail_fwd(q, enc, maskf, Bt, L, phead, lowp_logits)
         if caw is not None:
             tape["caw"] = caw
@@ -1026,7 +1116,6 @@ class HipEngine:
         _cross_kv_path (norm_kv + W_k | W_v) of EVERY cross-attention layer, written into that layer's slot of one buffer.
         Returns the context answer() reads: {"kv": [ncl][U*ntok][2d] compute dtype (K | V per image token), "U", "ntok"} and, with
         want_aux, "feat" (NHWC features [U*ntok][512]) and "img" (projected image tokens [U*ntok][d])."""
-        cfg = self.cfg
         if not self.fold_eval:
             raise RuntimeError("encode_images runs the Conv+BN-folded eval path (fold_eval = True)")
         self._site = 0
@@ -1034,10 +1123,35 @@ class HipEngine:
         U = images.shape[0]
         x, H, W, _ = self._stem_fwd(images, False, False)
         feat, H, W, C, _ = self._stages_fwd(x, U, H, W, False, False)
+        return self._context_of(feat, U, H, W, C, want_aux)
+
+    def encode_features(self, images: torch.Tensor) -> torch.Tensor:
+        """The image encoder alone, as forward() runs it for a frozen, eval-mode, untaped CNN: _stem_fwd and _stages_fwd on the
+        Conv+BN-folded eval path (bf16 or MXFP8: infer_precision), nothing after them.  Returns the NHWC features [U][Hf][Wf][Cf] in
+        the compute dtype -- what forward_features() and context_from_features() start from."""
+        self._site = 0
+        self.begin_step(for_backward=False)
+        U = images.shape[0]
+        x, H, W, _ = self._stem_fwd(images, False, False)
+        feat, H, W, C, _ = self._stages_fwd(x, U, H, W, False, False)
+        return feat.view(U, H, W, C)
+
+    def context_from_features(self, feat: torch.Tensor, want_aux: bool = False) -> dict:
+        """encode_images() from cached features (encode_features): only the projector and every layer's K | V run."""
+        if feat.dim() != 4 or feat.dtype != self.dtype or not feat.is_contiguous():
+            raise RuntimeError(f"context_from_features: features must be a contiguous [U, Hf, Wf, Cf] tensor in {self.dtype}")
+        self._site = 0
+        self.begin_step(for_backward=False, stem=False)
+        U, H, W, C = feat.shape
+        return self._context_of(feat.view(U * H * W, C), U, H, W, C, want_aux)
+
+    def _context_of(self, feat, U, H, W, C, want_aux):
+        """The context of encode_images() from the NHWC features [U*H*W][C]: _projector_fwd, then _cross_kv_path of every layer."""
+        cfg = self.cfg
         ntok, d, ncl = H * W, cfg["embed_dim"], cfg["num_cross_layers"]
         img, _ = self._projector_fwd(feat, ntok, 0.0)
         # every layer reads the same image tokens (cross_attention.py:357-361)
-        kv = torch.empty((ncl, U * ntok, 2 * d), device=images.device, dtype=self.dtype)
+        kv = torch.empty((ncl, U * ntok, 2 * d), device=feat.device, dtype=self.dtype)
         for l in range(ncl):
             p = f"fusion.cross_attention.layers.{l}"
             self._cross_kv_path(img, p + ".norm_kv", p + ".cross_attention", d, out=kv[l])

@@ -74,6 +74,7 @@ class Plan:
     """What a taped forward / its backward do for one trainable set and one set of part modes.
 
     modes        (cnn, text, fusion, head) training flags
+    cnn_trains   some image_encoder parameter trains (cached image features do not survive such a step)
     cnn_tape     the CNN keeps its activations (some image_encoder parameter trains, or the images require grad)
     cnn_low      lowest CNN level the data-gradient chain reaches: None (no CNN backward), 4 ... 1 (stage), 0 (stem)
     text         the text encoder's backward runs (some text_encoder parameter trains)
@@ -93,7 +94,8 @@ class Plan:
         def any_of(prefix):
             return any(t for n, t in tr.items() if n.startswith(prefix))
 
-        self.cnn_tape = any_of("image_encoder.") or self.images_grad
+        self.cnn_trains = any_of("image_encoder.")        # an optimizer step under this plan writes the image encoder
+        self.cnn_tape = self.cnn_trains or self.images_grad
         if self.images_grad or any_of("image_encoder.stem."):
             self.cnn_low: Optional[int] = 0
         else:

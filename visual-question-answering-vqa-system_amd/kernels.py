@@ -691,6 +691,28 @@ def layernorm_bwd(dout, x, gamma, stats, dgamma, dbeta, *, addend=None, drop_p=0
     return dx
 
 
+def gather_rows(src, index, out=None):
+    """out[i] = src[index[i]] along the first dimension, one launch (vqa_gather_rows).  src: contiguous [n_src, ...] of any dtype whose
+    rows are a multiple of 16 bytes; index: contiguous int32 [n] on src's device with every entry in [0, n_src) -- the CALLER checks the
+    range (ImageFeatures.select does), the kernel only refuses to read outside src.  Returns [n, ...] in src's dtype."""
+    if src.dim() < 1 or not src.is_contiguous():
+        raise ValueError("gather_rows: src must be contiguous with at least one dimension")
+    if index.dtype != torch.int32 or index.dim() != 1 or index.device != src.device or not index.is_contiguous():
+        raise ValueError(f"gather_rows: index must be a contiguous int32 vector on {src.device}")
+    n, n_src = index.shape[0], src.shape[0]
+    row_bytes = (src.numel() // n_src if n_src else 0) * src.element_size()
+    if n and (row_bytes <= 0 or row_bytes % 16):
+        raise ValueError(f"gather_rows: rows of {row_bytes} bytes; a positive multiple of 16 is needed")
+    shape = (n,) + tuple(src.shape[1:])
+    if out is None:
+        out = torch.empty(shape, device=src.device, dtype=src.dtype)
+    elif tuple(out.shape) != shape or out.dtype != src.dtype or out.device != src.device or not out.is_contiguous():
+        raise ValueError(f"gather_rows: out must be a contiguous {src.dtype} tensor of shape {shape} on {src.device}")
+    if n:
+        call("vqa_gather_rows", ptr(src), ptr(index), ptr(out), n, row_bytes, n_src)
+    return out
+
+
 def softmax_topk(logits, k, allowed=None, scale=1.0, want_logits=False):
     """The k best columns of every row of logits [B][N] (fp32 or bf16, unit column stride, any row stride >= N) with their softmax
     probabilities, one launch (vqa_softmax_topk).  allowed: bool / uint8 [N] (shared) or [B][N], non-zero = the column may be picked

@@ -160,6 +160,11 @@ def _is_soft(targets) -> bool:
     return isinstance(targets, tuple) and hasattr(targets, "ids") and hasattr(targets, "weights") and hasattr(targets, "counts")
 
 
+def _is_features(images) -> bool:
+    """An ImageFeatures of the drop-in models.vqa_model, recognised by its fields (as _is_soft: the module has several import names)."""
+    return hasattr(images, "_stamp") and hasattr(images, "_handle") and hasattr(images, "tensor") and hasattr(images, "select")
+
+
 class HipTrainer:
     def __init__(self, model, lr=1e-4, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
                  process_group=None, overlap=True, force_reducer=False, label_smoothing=0.0, class_weight=None, ignore_index=None,
@@ -178,6 +183,10 @@ class HipTrainer:
         self.ema_warmup = bool(ema_warmup)
         self.ema = None
         self._ema_swapped = False
+        # what VQAModel._feat_stamp read of the image encoder when the average was cloned from the weights: while it reads the same, no
+        # one wrote the image encoder since (this trainer, another one, torch.optim, load_state_dict), so the average's image-encoder
+        # slice still equals the model's and ema_weights() leaves cached ImageFeatures valid.  None: unknown (an average was loaded)
+        self._ema_cnn_stamp = None
         self.engine = model._ensure_engine()
         # nn.CrossEntropyLoss's constructor options for hard labels (all at their defaults: the plain loss launch, unchanged)
         self.label_smoothing, self.ignore_index, self.class_weight = self._check_loss_opts(label_smoothing, class_weight, ignore_index)
@@ -186,6 +195,7 @@ class HipTrainer:
         flat = model._flat
         if self.ema_decay is not None:
             self.ema = flat.detach().clone()
+            self._ema_cnn_stamp = self._cnn_stamp()
         self.G = torch.zeros_like(flat)
         self.m = torch.zeros_like(flat)
         self.v = torch.zeros_like(flat)
@@ -275,7 +285,11 @@ class HipTrainer:
         then raise TypeError.  A batch of zero total weight (every target ignored, or every kept target of class weight 0) has a NaN
         loss and a ZERO gradient: the step still runs AdamW on it (weight decay and the moments' decay apply), which is what the
         reference loop does with torch when every target is ignored; torch's NaN gradient in the weighted case is not reproduced.
-        Such steps are counted on the device and check() raises ValueError for them."""
+        Such steps are counted on the device and check() raises ValueError for them.
+        images may be an ImageFeatures (VQAModel.encode_features; with image_index: of the U images): the image encoder, which must be
+        frozen and in eval mode, does not run, and everything after it is the same step -- the launches of the images step without the
+        CNN forward, bit for bit.  RuntimeError before any launch when an image_encoder parameter requires grad, the image encoder is
+        in train mode, or the features are stale."""
         if self._ema_swapped:
             raise RuntimeError("HipTrainer.step inside ema_weights(): the model holds the averaged weights; leave the block first")
         eng, T = self.engine, self.engine.dtype
@@ -284,6 +298,9 @@ class HipTrainer:
         if self.ema is not None:                           # (ema_decay may have been changed since the constructor checked it)
             ema_args = (ptr(self.ema), EMA.check_decay(self.ema_decay, "HipTrainer: ema_decay"), int(bool(self.ema_warmup)))
         soft = _is_soft(targets)
+        feats = images if _is_features(images) else None
+        if feats is not None:
+            images = feats.tensor()
         if soft and self._loss_opts:
             raise TypeError("HipTrainer.step: label_smoothing / class_weight / ignore_index apply to hard labels; "
                             "SoftTargets cannot be combined with them")
@@ -298,17 +315,27 @@ class HipTrainer:
         Bq = token_ids.shape[0] if (image_index is not None and token_ids.dim() == 2) else images.shape[0]
         if soft:
             targets.validate(Bq, dev)
-        if images.dim() != 4 or images.shape[1] != 3 or token_ids.dim() != 2 or token_ids.shape[0] != Bq or (not soft and targets.shape != (Bq,)):
+        if images.dim() != 4 or (feats is None and images.shape[1] != 3) or token_ids.dim() != 2 or token_ids.shape[0] != Bq or (not soft and targets.shape != (Bq,)):
             raise RuntimeError("HipTrainer.step: expected images [B,3,H,W], token_ids [B,L], targets [B]"
                                + ("" if image_index is None else " with B questions"))
+        # fine-tuning: requires_grad and the parts' modes, resolved on every step (finetune.Plan; None: the plain step)
+        plan = self.model._finetune_plan(self.model._param_list(), False, True)
+        if feats is not None:                              # host checks, ahead of the image index's copy / range read: nothing has gone out yet
+            if plan is None or plan.cnn_trains:
+                raise RuntimeError("HipTrainer.step: ImageFeatures stand in for a frozen image encoder: call "
+                                   "model.image_encoder.requires_grad_(False)")
+            self.model._check_features(feats, "HipTrainer.step")
         kv_index = None
         if image_index is not None:
             kv_index = self._device_index(image_index, images.shape[0], Bq, dev)
         if attention_mask is not None and not (isinstance(attention_mask, torch.Tensor) and attention_mask.device == dev
                                                and attention_mask.shape == token_ids.shape):
             raise RuntimeError(f"HipTrainer.step: `attention_mask` must be a [B,L] tensor on {dev} (or None)")
+        if feats is None and (plan is None or plan.cnn_trains):      # this step's AdamW writes the image encoder: cached features go stale
+            self.model._feat_epoch += 1
         # the kernels read raw pointers: enforce the dtypes / contiguity VQAModel.forward enforces (vqa_model.py drop-in)
-        images = images.contiguous().float()
+        if feats is None:
+            images = images.contiguous().float()
         token_ids = token_ids.contiguous().long()
         if not soft:
             targets = targets.contiguous().long()
@@ -317,10 +344,12 @@ class HipTrainer:
         if self._copy_sig is not None and eng.adamw_copy_target() is not None and self._copy_sig == self._param_sig():
             eng._wsrc_fresh = True                 # (one-shot, consumed by the begin_step of the forward below)
         maskf = None if attention_mask is None else attention_mask.contiguous().float()
-        # fine-tuning: requires_grad and the parts' modes, resolved on every step (finetune.Plan; None: the plain step)
-        plan = self.model._finetune_plan(self.model._param_list(), False, True)
         self._set_mask(None if plan is None else plan.trainable)
-        logits, _, tape = eng.forward(images, token_ids, maskf, True, False, need_tape=True, lowp_logits=True, kv_index=kv_index, plan=plan)
+        if feats is not None:
+            logits, _, tape = eng.forward_features(images, token_ids, maskf, True, False, need_tape=True, lowp_logits=True, kv_index=kv_index,
+                                                   plan=plan)
+        else:
+            logits, _, tape = eng.forward(images, token_ids, maskf, True, False, need_tape=True, lowp_logits=True, kv_index=kv_index, plan=plan)
         B, N = logits.shape
         # the loss kernel reads the logits in the compute dtype, writes d logits in it and leaves the fp32 logits the caller gets:
         # the same values as logits.float() -> loss -> d logits.to(bf16), two elementwise launches less between forward and backward
@@ -390,6 +419,7 @@ class HipTrainer:
         """The inverse of ema_state_dict(), for resuming: the parameter entries of `sd` become the average; buffer keys are ignored.
         KeyError for a missing parameter, ValueError for a shape mismatch (nothing is written then)."""
         EMA.load_state_dict(self.model, self._need_ema("load_ema_state_dict"), sd)
+        self._ema_cnn_stamp = None
 
     @contextlib.contextmanager
     def ema_weights(self):
@@ -397,16 +427,24 @@ class HipTrainer:
         eager eval forward, forward_graphed, predict, predict_topk, encode_images + answer, graphs captured earlier included) and its
         own weights again afterwards, also when the block raises.  The contents of model._flat and self.ema are exchanged through torch
         ops and exchanged back: parameters, average and both moments have their earlier bits after the block, an ImageContext from one
-        side is refused on the other, and the next step() re-casts the bf16 operand copy.  step() inside the block raises RuntimeError."""
+        side is refused on the other, and the next step() re-casts the bf16 operand copy.  step() inside the block raises RuntimeError.
+        ImageFeatures stay valid across the block as long as nothing wrote the image encoder since the average was made (the average
+        of a frozen parameter is the parameter); otherwise they are refused like the contexts."""
         ema = self._need_ema("ema_weights")
         if self._ema_swapped:
             raise RuntimeError("HipTrainer.ema_weights() is not re-entrant")
-        with EMA.swapped(self.model, ema):
+        # (getattr: tests/test_ema_ref_cpu.py makes its trainer with __new__, without the constructor's attributes)
+        made = getattr(self, "_ema_cnn_stamp", None)
+        with EMA.swapped(self.model, ema, keeps_cnn=made is not None and made == self._cnn_stamp()):
             self._ema_swapped = True
             try:
                 yield self.model
             finally:
                 self._ema_swapped = False
+
+    def _cnn_stamp(self):
+        m = self.model
+        return (m._feat_epoch, m._feat_version() - m._feat_excused)
 
     def params_changed(self):
         """Tell the trainer that the parameters were written behind torch's back (through `.data`, a raw pointer, another C-ABI call):
