@@ -369,6 +369,23 @@ int vqa_cross_entropy_soft(int dtype, const void* logits, const int* ids, const 
                            unsigned long long* acc, hipStream_t stream);
 int vqa_challenge_accuracy_update(const float* logits, const int* ids, const int* counts, int K, unsigned long long* acc, int B, int N,
                                   hipStream_t stream);
+/* Sigmoid + binary cross-entropy against the soft answer scores (the VQA v2 recipe): vqa_cross_entropy_soft's arguments and the same
+ * t[b][c] = sum of weights[b][k] over ids[b][k] == c (duplicates add up, -1 slots are skipped, nothing is clamped).
+ *   loss += (1/B) * sum_b sum_c [ max(x,0) + log1p(exp(-|x|)) - x*t ]  = F.binary_cross_entropy_with_logits(x, t, reduction="sum") / B:
+ *   summed over answers, averaged over questions; the stable form (x = +-90 gives finite values); the x*t part is taken from the K
+ *   slots in slot order.  dlogits = (sigmoid(x) - t) * gscale / B in the compute dtype (may be NULL: the loss alone).
+ *   A row without an in-vocabulary answer (t all zero) is NOT a zero row here: it gets sigmoid(x) * gscale / B, every logit is pushed
+ *   down.  Under vqa_cross_entropy_soft that row is a zero row; the difference is intended.
+ *   logits_f32 (optional) receives the raw logits, bit for bit.  An id < -1 or >= N is never read: the row adds NaN to the loss, gets
+ *   a NaN gradient row and counts one in *err (may be NULL), as in vqa_cross_entropy_soft.
+ *   ws (B floats, or NULL): per-row terms go to ws and are folded in row order -- no float atomic on *loss, two launches give the same
+ *   bits; NULL: float atomics on *loss.  counts + acc (both optional): the challenge accuracy in integer thirds in the same pass,
+ *   acc[0] += min(3, votes for the row's arg-max), acc[1] += 1; the arg-max is the lowest index that holds the row maximum.
+ * Status 1000 without a launch: NULL logits / ids / weights; K < 1 or K > 64; B < 1 or N < 1; acc without counts; dtype other than
+ * 0 (fp32) / 1 (bf16); gscale not finite. */
+int vqa_bce_soft(int dtype, const void* logits, const int* ids, const float* weights, int K, float* loss, void* dlogits,
+                 float* logits_f32, int B, int N, float gscale, int* err, float* ws, const int* counts, unsigned long long* acc,
+                 hipStream_t stream);
 /* masked mean over tokens (models/fusion.py:303-313, models/text_encoder.py:522-527) */
 /* both masked means of the fusion tail in one launch (round 4): out[B][2D] = [mean_m(x0) | mean_m(x1)] with the same mask, and the
  * matching backward dx{0,1}[b][l][:] = dcat[b][{0,D}:] * m[b][l] / cnt (models/fusion.py:281-296); per-element arithmetic of

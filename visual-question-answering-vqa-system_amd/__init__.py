@@ -25,7 +25,8 @@ def load_dropin_metrics():
 
 
 def load_dropin_soft_targets():
-    """The drop-in `utils.soft_targets` (sparse soft answer scores: SoftTargets, answer_scores, SoftTargetCrossEntropy)."""
+    """The drop-in `utils.soft_targets` (sparse soft answer scores: SoftTargets, answer_scores, SoftTargetCrossEntropy,
+    SoftTargetBCEWithLogits)."""
     return _load_dropin_file("vqa_hip_dropin_utils_soft_targets", "utils", "soft_targets.py")
 
 

@@ -122,6 +122,7 @@ SIGNATURES = {
     "vqa_answer_scores": [P, P, P, P, I, I, I, I, P, P],
     "vqa_cross_entropy_soft": [I, P, P, P, I, P, P, P, I, I, F, P, P, P, P, P],
     "vqa_challenge_accuracy_update": [P, P, P, I, P, I, I, P],
+    "vqa_bce_soft": [I, P, P, P, I, P, P, P, I, I, F, P, P, P, P, P],
     "vqa_convert": [I, I, P, P, LL, P],
     "vqa_sumsq": [P, LL, P, P],
     "vqa_image_normalize": [P, P, P, I, I, I, F, F, F, F, F, F, P],

@@ -2097,6 +2097,94 @@ extern "C" int vqa_challenge_accuracy_update(const float* logits, const int* ids
 }
 
 // ---------------------------------------------------------------------------------------------
+// Sigmoid + binary cross-entropy against the soft answer scores (the VQA v2 recipe: every answer is its own yes/no problem, so
+// several annotator answers can be right at once and a question without an in-vocabulary answer still pushes every logit down).
+//   loss    += (1/B) * sum_b sum_c [ max(x,0) + log1p(exp(-|x|)) - x*t ]      (F.binary_cross_entropy_with_logits, "sum", / B)
+//   dlogits  = (sigmoid(x) - t) * gscale / B
+// with cross_entropy_soft_kernel's sparse t, its layout (one wave per question, lane k holds slot k), its bad-target rule, its
+// ws / fold and its fused challenge accuracy.  The softplus sum runs over the whole row (lane c takes c, c + 64, ... in ascending
+// order, then the butterfly); the x*t part comes from the K slots in slot order, as the soft kernel forms `dot`.  Both forms are
+// the stable ones: exp only ever sees -|x|, so x = +-90 stays finite, and sigmoid(x) = {1, e} / (1 + e) with e = exp(-|x|).
+// A row with t == 0 everywhere is NOT a zero row here (under cross-entropy it is): it gets sigmoid(x) * gscale / B.
+// The column loops run a wave-uniform trip count (c0 uniform, c = c0 + lane masked by c < N), so the readlanes inside them are
+// executed by every lane.
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void bce_soft_kernel(const T* __restrict__ logits, const int* __restrict__ ids, const float* __restrict__ weights,
+                                                       int K, float* loss, T* __restrict__ dlogits, float* __restrict__ logits_f32, int B, int N,
+                                                       float gscale, int* err, float* part, const int* __restrict__ counts, unsigned long long* acc) {
+  const int lane = threadIdx.x & 63;
+  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  int thirds = -1;
+  if (row < B) {                                                         // (wave-uniform: a wave owns one row)
+    const T* lr = logits + (size_t)row * N;
+    float m = -INFINITY;
+    if (acc) {
+      for (int c = lane; c < N; c += 64) m = fmaxf(m, to_f<T>(lr[c]));
+      m = wave_max(m);
+    }
+    float sp = 0.f;
+    int best = N;
+    for (int c = lane; c < N; c += 64) {
+      const float x = to_f<T>(lr[c]);
+      sp += fmaxf(x, 0.f) + log1pf(expf(-fabsf(x)));
+      if (acc && x == m) best = min(best, c);                            // arg-max, ties -> lowest index (c ascends per lane)
+    }
+    sp = wave_sum(sp);
+    // the slots, exactly as in cross_entropy_soft_kernel: -1 is empty, an id < -1 or >= N is never read and rejects the row
+    const int id = lane < K ? ids[(size_t)row * K + lane] : -1;
+    const bool used = id >= 0 && id < N;
+    const bool bad = __ballot(id < -1 || id >= N) != 0ull;
+    const float w = used ? weights[(size_t)row * K + lane] : 0.f;
+    const float xk = used ? to_f<T>(lr[id]) : 0.f;
+    float dot = 0.f;
+    for (int k = 0; k < K; ++k) dot += lane_f(w, k) * lane_f(xk, k);     // slot order: sum_k w_k * x[id_k] = sum_c x[c] * t[c]
+    if (lane == 0) {
+      const float term = bad ? __builtin_nanf("") : (sp - dot) / (float)B;
+      if (part) part[row] = term;
+      else if (loss) atomicAdd(loss, term);
+      if (bad && err) atomicAdd(err, 1);
+    }
+    if (dlogits || logits_f32) {
+      for (int c0 = 0; c0 < N; c0 += 64) {                               // uniform trip count: every lane runs the readlanes below
+        const int c = c0 + lane;
+        const bool in = c < N;
+        const float x = in ? to_f<T>(lr[c]) : 0.f;
+        if (in && logits_f32) logits_f32[(size_t)row * N + c] = x;
+        if (dlogits) {
+          float t = 0.f;
+          for (int k = 0; k < K; ++k) {                                  // duplicates add up
+            const int idk = lane_i(id, k);
+            const float wk = lane_f(w, k);
+            t += idk == c ? wk : 0.f;
+          }
+          const float e = expf(-fabsf(x));
+          const float sg = (x >= 0.f ? 1.f : e) / (1.f + e);
+          if (in) dlogits[(size_t)row * N + c] = from_f<T>(bad ? __builtin_nanf("") : (sg - t) * gscale / (float)B);
+        }
+      }
+    }
+    if (acc) thirds = row_thirds(wave_min_i(best), id, lane < K ? counts[(size_t)row * K + lane] : 0, K, lane);
+  }
+  if (acc) block_add_thirds(acc, thirds);                                // (holds a barrier: reached by every thread, row or not)
+}
+
+// vqa_cross_entropy_soft's arguments; nothing is launched on an argument error
+extern "C" int vqa_bce_soft(int dtype, const void* logits, const int* ids, const float* weights, int K, float* loss, void* dlogits,
+                            float* logits_f32, int B, int N, float gscale, int* err, float* ws, const int* counts, unsigned long long* acc,
+                            hipStream_t st) {
+  if (!logits || !ids || !weights || K < 1 || K > 64 || B < 1 || N < 1 || (acc && !counts) || (dtype != 0 && dtype != 1)) return VQA_EARG;
+  if (!(fabsf(gscale) <= 3.402823466e38f)) return VQA_EARG;              // (NaN fails the comparison too)
+  dim3 grid((B + 3) / 4);
+  DT(hipLaunchKernelGGL(bce_soft_kernel<float>, grid, dim3(256), 0, st, (const float*)logits, ids, weights, K, loss, (float*)dlogits, logits_f32,
+                        B, N, gscale, err, ws, counts, acc),
+     hipLaunchKernelGGL(bce_soft_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)logits, ids, weights, K, loss, (bf16_t*)dlogits, logits_f32,
+                        B, N, gscale, err, ws, counts, acc));
+  if (ws && loss) launch_fold(ws, B, 1, 1, loss, 1, nullptr, st);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Cross entropy with nn.CrossEntropyLoss's constructor options (training/train.py:120): class weights w[N], ignore_index and label
 // smoothing eps, reduction "mean".  keep[b] = target b is not ignore_index, wy[b] = keep[b] * w[t_b], W = sum_b wy[b],
 // Sw = sum_c w[c], lp = log_softmax(x):

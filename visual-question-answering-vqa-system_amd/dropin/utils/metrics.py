@@ -119,7 +119,7 @@ class VQAChallengeAccuracy:
         self._host = [0, 0]                                    # the string call form: {thirds, questions} counted on the host
 
     def _fused_acc(self, device) -> torch.Tensor:
-        """The device counters (HipTrainer.step hands them to the loss launch: `vqa_cross_entropy_soft` counts/acc)."""
+        """The device counters (HipTrainer.step hands them to the loss launch: `vqa_cross_entropy_soft` / `vqa_bce_soft` counts/acc)."""
         if self._counters is None or self._counters.device != device:
             if self._counters is not None:
                 self._host = [h + int(v) for h, v in zip(self._host, self._counters.cpu())]

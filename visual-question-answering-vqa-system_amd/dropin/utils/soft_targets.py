@@ -9,6 +9,9 @@ carries at most A (id, weight, count) triples:
     loss, logits = trainer.step(images, ids, mask, soft, metrics=VQAChallengeAccuracy())      # fused path, or
     loss = SoftTargetCrossEntropy()(model(images, ids, mask)[0], soft)                        # any torch.optim loop
 
+The VQA v2 recipe itself trains a sigmoid per answer with binary cross-entropy against the same scores: HipTrainer(model, loss="bce")
+for the fused step, SoftTargetBCEWithLogits() in the place of SoftTargetCrossEntropy() for a torch.optim loop.
+
 There is no CPU path: host tensors raise.
 """
 from __future__ import annotations
@@ -134,3 +137,53 @@ class SoftTargetCrossEntropy(nn.Module):
         soft.validate(logits.shape[0], logits.device)
         need = torch.is_grad_enabled() and logits.requires_grad
         return torch.ops.vqa_hip.soft_cross_entropy(logits, soft.ids, soft.weights, need)[0]
+
+
+# torch.ops.vqa_hip.soft_bce(logits, ids, weights, need_grad) -> (loss scalar, d loss / d logits or an empty tensor)
+@torch.library.custom_op("vqa_hip::soft_bce", mutates_args=(), device_types="cuda")
+def _soft_bce_op(logits: torch.Tensor, ids: torch.Tensor, weights: torch.Tensor, need_grad: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+    L = _pkg()._lib
+    lg = logits.detach().contiguous()
+    B, N = lg.shape
+    loss = torch.zeros((), device=lg.device, dtype=torch.float32)
+    err = torch.zeros(1, device=lg.device, dtype=torch.int32)
+    ws = torch.empty((B,), device=lg.device, dtype=torch.float32)
+    dlogits = torch.empty_like(lg) if need_grad else lg.new_empty((0,))
+    L.call("vqa_bce_soft", L.dt(lg), lg.data_ptr(), ids.data_ptr(), weights.data_ptr(), ids.shape[1], loss.data_ptr(),
+           dlogits.data_ptr() if need_grad else None, None, B, N, 1.0, err.data_ptr(), ws.data_ptr(), None, None)
+    bad = int(err.item())                                      # the one sync of this (slow) path
+    if bad:
+        raise IndexError(f"{bad} row(s) with an answer id out of range [-1, {N})")
+    return loss, dlogits
+
+
+@_soft_bce_op.register_fake
+def _(logits, ids, weights, need_grad):
+    return logits.new_empty((), dtype=torch.float32), (torch.empty_like(logits) if need_grad else logits.new_empty((0,)))
+
+
+def _sbce_setup(ctx, inputs, output):
+    ctx.save_for_backward(output[1])
+
+
+def _sbce_backward(ctx, gloss, _gdl):
+    (dlogits,) = ctx.saved_tensors
+    if dlogits.numel() == 0:
+        raise RuntimeError("soft_bce was called with need_grad=False: there is no gradient to return")
+    return dlogits * gloss.to(dlogits.dtype), None, None, None
+
+
+torch.library.register_autograd("vqa_hip::soft_bce", _sbce_backward, setup_context=_sbce_setup)
+
+
+class SoftTargetBCEWithLogits(nn.Module):
+    """F.binary_cross_entropy_with_logits(logits, t, reduction="sum") / B (summed over the answers, averaged over the questions) for
+    the sparse t of a SoftTargets: one fused HIP launch for the loss and its gradient (`vqa_bce_soft`), reached through autograd.
+    A question without an in-vocabulary answer contributes sigmoid(x) / B to the gradient (under SoftTargetCrossEntropy: nothing)."""
+
+    def forward(self, logits: torch.Tensor, soft: SoftTargets) -> torch.Tensor:
+        if not (isinstance(logits, torch.Tensor) and logits.is_cuda and logits.dim() == 2):
+            raise RuntimeError("SoftTargetBCEWithLogits (HIP): logits must be a [B, N] GPU tensor; there is no CPU path")
+        soft.validate(logits.shape[0], logits.device)
+        need = torch.is_grad_enabled() and logits.requires_grad
+        return torch.ops.vqa_hip.soft_bce(logits, soft.ids, soft.weights, need)[0]

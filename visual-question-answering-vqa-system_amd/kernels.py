@@ -89,6 +89,8 @@ HBM_BYTES = {
     "vqa_cross_entropy": ("token", lambda a: a[6] * a[7] * (_ES(a[0]) + 4)),
     # soft targets: the logits traffic of the hard kernel + ids, weights, counts [B][K]; the annotator ids are 8 bytes in, 12 out
     "vqa_cross_entropy_soft": ("token", lambda a: a[8] * a[9] * (_ES(a[0]) + 4) + a[8] * a[4] * (8 + 4 * _P(a[13]))),
+    # sigmoid BCE on the same targets: the same tensors in and out
+    "vqa_bce_soft": ("token", lambda a: a[8] * a[9] * (_ES(a[0]) + 4) + a[8] * a[4] * (8 + 4 * _P(a[13]))),
     # options: the hard kernel's logits traffic + the targets and the class weights once (every wave re-reads them from cache)
     "vqa_cross_entropy_opts": ("token", lambda a: a[6] * a[7] * (_ES(a[0]) + 4) + a[6] * 8 + a[7] * 4 * _P(a[11])),
     "vqa_challenge_accuracy_update": ("token", lambda a: a[5] * a[6] * 4 + a[5] * a[3] * 8),

@@ -168,8 +168,10 @@ def _is_features(images) -> bool:
 class HipTrainer:
     def __init__(self, model, lr=1e-4, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
                  process_group=None, overlap=True, force_reducer=False, label_smoothing=0.0, class_weight=None, ignore_index=None,
-                 ema_decay=None, ema_warmup=False):
-        """ema_decay (None, or a float in [0, 1]): keep an exponential moving average of the weights, self.ema (a flat fp32 buffer laid out
+                 ema_decay=None, ema_warmup=False, loss="ce"):
+        """loss: "ce" (default: softmax cross-entropy, exactly the step without this option) or "bce" (sigmoid + binary cross-entropy on
+        SoftTargets, see step()); readable afterwards as `loss_kind` (`loss` is the device scalar).
+        ema_decay (None, or a float in [0, 1]): keep an exponential moving average of the weights, self.ema (a flat fp32 buffer laid out
         like model._flat, started at the initial weights): ema = d * ema + (1 - d) * p after every applied update, computed by the AdamW
         launch itself (vqa_adamw_ema / vqa_adamw_ranges_ema) from the updated parameter it still holds -- no extra launch.  ema_warmup:
         d = min(ema_decay, (1 + t) / (10 + t)) with Adam's step number t (per parameter when parts are frozen: the average of a
@@ -179,6 +181,12 @@ class HipTrainer:
         nothing is communicated.  ema_weights() / ema_state_dict() / load_ema_state_dict() evaluate on, export and restore the average."""
         self.model = model
         # validated on the host before anything is allocated or launched
+        if not (isinstance(loss, str) and loss in ("ce", "bce")):
+            raise ValueError(f'HipTrainer: loss must be "ce" or "bce", got {loss!r}')
+        if loss == "bce" and not (label_smoothing == 0.0 and class_weight is None and ignore_index is None):
+            raise ValueError('HipTrainer: label_smoothing / class_weight / ignore_index belong to the cross-entropy loss; '
+                             'loss="bce" takes none of them')
+        self.loss_kind = loss
         self.ema_decay = None if ema_decay is None else EMA.check_decay(ema_decay, "HipTrainer: ema_decay")
         self.ema_warmup = bool(ema_warmup)
         self.ema = None
@@ -282,7 +290,14 @@ class HipTrainer:
         `metrics` must then be a VQAChallengeAccuracy (and the targets carry `counts`): it is counted inside the loss launch.
         With label_smoothing / class_weight / ignore_index given to the constructor the loss is F.cross_entropy with those options
         (`vqa_cross_entropy_opts`) and a VQAAccuracy is counted inside that launch over the rows that are not ignored; SoftTargets
-        then raise TypeError.  A batch of zero total weight (every target ignored, or every kept target of class weight 0) has a NaN
+        then raise TypeError.
+        With loss="bce" given to the constructor (`trainer.loss_kind`) the targets must be SoftTargets and the loss is sigmoid + binary
+        cross-entropy against the soft scores, F.binary_cross_entropy_with_logits(logits, t, reduction="sum") / B: summed over the
+        answers, averaged over the questions (`vqa_bce_soft`, in the place of `vqa_cross_entropy_soft`, with the challenge accuracy
+        riding in it the same way).  A question without an in-vocabulary answer then still pushes every logit down (under
+        cross-entropy its gradient row is zero).  A label tensor raises TypeError: wrap hard labels as
+        SoftTargets(labels.int()[:, None], ones).
+        A batch of zero total weight (every target ignored, or every kept target of class weight 0) has a NaN
         loss and a ZERO gradient: the step still runs AdamW on it (weight decay and the moments' decay apply), which is what the
         reference loop does with torch when every target is ignored; torch's NaN gradient in the weighted case is not reproduced.
         Such steps are counted on the device and check() raises ValueError for them.
@@ -298,6 +313,10 @@ class HipTrainer:
         if self.ema is not None:                           # (ema_decay may have been changed since the constructor checked it)
             ema_args = (ptr(self.ema), EMA.check_decay(self.ema_decay, "HipTrainer: ema_decay"), int(bool(self.ema_warmup)))
         soft = _is_soft(targets)
+        bce = self.loss_kind == "bce"
+        if bce and not soft:
+            raise TypeError('HipTrainer.step: loss="bce" trains on SoftTargets; wrap hard labels as '
+                            "SoftTargets(labels.int()[:, None], ones) with ones = torch.ones(B, 1) on the device")
         feats = images if _is_features(images) else None
         if feats is not None:
             images = feats.tensor()
@@ -359,8 +378,8 @@ class HipTrainer:
         ce_ws = torch.empty((B,), device=images.device, dtype=torch.float32)
         if soft:                                           # the challenge accuracy rides in the same launch (counts + acc)
             acc = None if metrics is None else metrics._fused_acc(dev)
-            call("vqa_cross_entropy_soft", dt(logits), ptr(logits), ptr(targets.ids), ptr(targets.weights), targets.ids.shape[1], ptr(self.loss),
-                 ptr(dlogits), ptr(logits_f) if lowp else None, B, N, 1.0, ptr(self.bad_step), ptr(ce_ws),
+            call("vqa_bce_soft" if bce else "vqa_cross_entropy_soft", dt(logits), ptr(logits), ptr(targets.ids), ptr(targets.weights),
+                 targets.ids.shape[1], ptr(self.loss), ptr(dlogits), ptr(logits_f) if lowp else None, B, N, 1.0, ptr(self.bad_step), ptr(ce_ws),
                  None if acc is None else ptr(targets.counts), ptr(acc))
         elif self._loss_opts:                              # VQAAccuracy's counters ride in the same launch (kept rows only)
             fused = metrics is not None and hasattr(metrics, "_buf")
