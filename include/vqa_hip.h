@@ -210,7 +210,7 @@ int vqa_bn_apply_acc(int dtype, const void* y, const unsigned long long* acc, co
                      float momentum, float eps, float* pool_part, hipStream_t stream);
 int vqa_bn_bwd_blocks(long long rows);
 int vqa_bn_bwd_reduce(int dtype, const void* dout, const void* outact, const void* y, const float* coef, const void* y2,
-                      const float* coef2, float* slab /* [blocks][3][C], or the u64 accumulator [3*C + 1] when acc_mode = 1 */, long long rows,
+                      const float* coef2, float* slab /* [blocks][3][C], or the u64 accumulator [vqa_bn_acc_words(3, C)] (replicas x two planes + flag) when acc_mode = 1 */, long long rows,
                       int C, int self_mask /* mask = relu(bn(y))>0 from y */, int acc_mode, hipStream_t stream);
 int vqa_bn_bwd_apply_acc(int dtype, const void* dout, const void* outact, const void* y, const unsigned long long* facc, const float* gamma,
                          const float* coef, float* dgamma, float* dbeta, void* dy, const void* y2, const float* gamma2, const float* coef2,

@@ -341,7 +341,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__
   }
 }
 
-// The same map with the finalize folded into the prologue: the column sums arrive as fixed-point accumulators facc[3][C] (+ flag),
+// The same map with the finalize folded into the prologue: the column sums arrive as a fixed-point accumulator facc[vqa_bn_acc_words(3, C)]
+// (R replicas x [3][C] in a hi and a lo plane, the flag word between the planes: common.h),
 // every thread derives A | B | C of its channels (formulas of bn_bwd_finalize_kernel, training mode), the first workgroup adds
 // d gamma / d beta (and the shortcut BatchNorm's, DUAL) into the gradient buffer.
 template <typename T, bool SELF, bool DUAL>
@@ -1208,7 +1209,7 @@ int vqa_bn_apply_pool(int dtype, const void* y, const float* coef, const void* r
 #undef BN_APPLYP
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
-// Train-mode BatchNorm apply whose statistics are fixed-point accumulators acc[2*C + 1] (filled by the producing conv launched
+// Train-mode BatchNorm apply whose statistics are fixed-point accumulators acc[vqa_bn_acc_words(2, C)] (filled by the producing conv launched
 // with stats_mode = 1): finalize + running-statistics update + apply (+ residual | + BatchNorm(res) from racc, + ReLU) in ONE launch;
 // coef_out / rcoef_out [4][C] are published for the backward.  pool_part != NULL: the SE-pooling variant (vqa_bn_apply_pool).
 // 64-bit words of a fixed-point accumulator for K sums of C channels (replicas + flag, even): what the caller zeroes and passes
@@ -1253,7 +1254,8 @@ int vqa_bn_apply_acc(int dtype, const void* y, const unsigned long long* acc, co
 }
 int vqa_bn_bwd_blocks(long long rows) { long long g = (rows + 63) / 64; const int cap = vqa_env_int("VQA_BNR_GRID", rows < 65536 ? 256 : 512); return (int)(g > cap ? cap : (g < 1 ? 1 : g)); }
 // slab: [vqa_bn_bwd_blocks(rows)][3][C] floats
-// acc_mode = 1: `slab` is a fixed-point accumulator unsigned long long [3*C + 1] (zeroed by the caller) instead of a float slab
+// acc_mode = 1: `slab` is a fixed-point accumulator unsigned long long [vqa_bn_acc_words(3, C)] (replicas x two planes + flag, common.h; zeroed by the
+// caller) instead of a float slab
 int vqa_bn_bwd_reduce(int dtype, const void* dout, const void* outact, const void* y, const float* coef, const void* y2, const float* coef2,
                       float* slab, long long rows, int C, int self_mask, int acc_mode, hipStream_t st) {
   const int VEC = dtype ? 8 : 4;
@@ -1273,7 +1275,7 @@ int vqa_bn_bwd_finalize(const float* slab, int nblk, int C, int which, double co
   hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 63) / 64), dim3(1024), 0, st, slab, nblk, C, which, count, gamma, coef, training, dgamma, dbeta, bcoef);
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
-// BatchNorm backward apply with the finalize folded in (training mode): facc[3*C + 1] fixed-point sums from vqa_bn_bwd_reduce /
+// BatchNorm backward apply with the finalize folded in (training mode): facc[vqa_bn_acc_words(3, C)] fixed-point sums from vqa_bn_bwd_reduce /
 // vqa_se_bwd in accumulate mode; d gamma / d beta (+=) are written by the first workgroup.  y2 / gamma2 / coef2 / dgamma2 / dbeta2 / dy2:
 // the 1x1 shortcut's BatchNorm sharing g (all or none).  self_mask: ReLU mask recomputed from y (coef scale | shift), outact unused.
 int vqa_bn_bwd_apply_acc(int dtype, const void* dout, const void* outact, const void* y, const unsigned long long* facc, const float* gamma,
