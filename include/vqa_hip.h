@@ -482,6 +482,37 @@ int vqa_adamw_ranges_ema(float* p, const float* g, float* m, float* v, const lon
                          float* ema, float ema_decay, int ema_warmup, hipStream_t stream);
 int vqa_ema_update(float* ema, const float* p, long long n, float d, hipStream_t stream);
 
+/* ---- step state on the device (HipTrainer.step_graphed: the train step replayed from a captured HIP graph) ---------------------
+   A captured launch freezes every by-value argument at its capture-time value.  What changes from step to step therefore lives in
+   one device block, written by vqa_step_state_set -- a one-thread kernel, launched eagerly right before a replay; its arguments are
+   copied at launch, so there is no staging buffer, no host-to-device copy and no host synchronisation -- and read by:
+     * vqa_adamw_dev / vqa_adamw_ema_dev / vqa_adamw_ranges_dev / vqa_adamw_ranges_ema_dev: the four entries above with lr, beta1, beta2,
+       eps, weight_decay, calls, max_norm, gscale (and ema_decay, ema_warmup) taken from the block instead of by value; the kernels load
+       the block into locals and run the by-value kernels' body, so p, m, v, the bf16 copy, ema and skipped get the same bits.  The
+       range checks the by-value entries make on calls and ema_decay are the caller's (the host cannot see the block);
+     * every kernel that takes a dropout seed.  A seed word is self-describing: with bit 63 clear it is the seed itself, as before
+       (rank << 44 | step << 12 | site never reaches bit 63); with bit 63 set, bits 0-47 are the device address of
+       vqa_step_state::seed_step and bits 48-59 the site (< 4096), and the kernel uses *address | site.  seed_step holds
+       rank << 44 | (step & 0xFFFFFFFF) << 12 of the step being run.  No signature changes: `unsigned long long seed` carries either form. */
+typedef struct __attribute__((aligned(16))) vqa_step_state {
+  long long calls;
+  unsigned long long seed_step;
+  float lr, b1, b2, eps, wd, max_norm, gscale, ema_decay;
+  int ema_warmup;
+} vqa_step_state;
+int vqa_step_state_set(vqa_step_state* state, long long calls, unsigned long long seed_step, float lr, float beta1, float beta2, float eps,
+                       float weight_decay, float max_norm, float gscale, float ema_decay, int ema_warmup, hipStream_t stream);
+int vqa_adamw_dev(float* p, const float* g, float* m, float* v, long long n, const vqa_step_state* state, const float* sumsq,
+                  const int* skip, int* skipped, void* p_bf16, hipStream_t stream);
+int vqa_adamw_ema_dev(float* p, const float* g, float* m, float* v, long long n, const vqa_step_state* state, const float* sumsq,
+                      const int* skip, int* skipped, void* p_bf16, float* ema, hipStream_t stream);
+int vqa_adamw_ranges_dev(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n,
+                         const vqa_step_state* state, const float* sumsq, const int* skip, int* skipped, int* lag, const int* frozen, int nf,
+                         void* p_bf16, hipStream_t stream);
+int vqa_adamw_ranges_ema_dev(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n,
+                             const vqa_step_state* state, const float* sumsq, const int* skip, int* skipped, int* lag, const int* frozen,
+                             int nf, void* p_bf16, float* ema, hipStream_t stream);
+
 /* Row gather for cached image features (VQAModel.encode_features, ImageFeatures.select): dst[i] = src[index[i]] for i < n, rows of
    row_bytes bytes of any element type.  src holds n_src rows; index is device int32 [n] with every entry in [0, n_src) -- the caller
    checks the range; an entry outside it leaves its destination row unwritten and reads nothing.  16-byte vector loads and stores, one

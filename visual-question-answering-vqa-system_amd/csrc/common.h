@@ -1,6 +1,7 @@
 // Shared device helpers for the gfx950 (MI355X, CDNA4) VQA kernels.  Wave = 64 lanes.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <stdlib.h>
@@ -91,6 +92,17 @@ __device__ __forceinline__ bool drop_keep32(uint32_t key, uint32_t idx, float p)
   const uint32_t h = mix32(idx ^ key);
   return (float)(h >> 8) * (1.0f / 16777216.0f) >= p;
 }
+// A seed word is self-describing.  Bit 63 clear: the seed itself (rank << 44 | step << 12 | site: the rank sits at bit 44, so a plain
+// seed never reaches bit 63).  Bit 63 set: bits 0-47 hold the device address of vqa_step_state::seed_step (rank << 44 | step << 12 of
+// the step being run, written by vqa_step_state_set) and bits 48-59 the site; the seed is that word | site.  A captured train step
+// carries such words, so every replay draws the masks of ITS step.  One uniform 8-byte read: call it once at the top of a kernel,
+// never per element (drop_key / drop_keep take the resolved value).
+#define VQA_SEED_INDIRECT (1ull << 63)
+__device__ __forceinline__ uint64_t drop_resolve(uint64_t seed) {
+  if (!(seed & VQA_SEED_INDIRECT)) return seed;
+  const unsigned long long* word = reinterpret_cast<const unsigned long long*>((uintptr_t)(seed & 0xFFFFFFFFFFFFull));
+  return (uint64_t)*word | ((seed >> 48) & 0xFFFull);
+}
 __device__ __forceinline__ bool drop_keep(uint64_t seed, uint64_t idx, float p) {
   uint32_t h = mix32((uint32_t)idx ^ mix32((uint32_t)(idx >> 32) + (uint32_t)seed) ^ (uint32_t)(seed >> 32) * 0x9E3779B9u);
   return (float)(h >> 8) * (1.0f / 16777216.0f) >= p;
@@ -175,6 +187,21 @@ __device__ __forceinline__ void bn_acc_coef(const BnAcc& f, int C, int c, double
     }
   }
 }
+
+// The device step-state block of include/vqa_hip.h (the sources do not include the public header: the definition is repeated here and
+// pinned by the assertions below and by tests/test_step_graph_cpu.py, which reads the header's).
+#ifndef VQA_STEP_STATE_DEFINED
+#define VQA_STEP_STATE_DEFINED
+typedef struct __attribute__((aligned(16))) vqa_step_state {
+  long long calls;
+  unsigned long long seed_step;
+  float lr, b1, b2, eps, wd, max_norm, gscale, ema_decay;
+  int ema_warmup;
+} vqa_step_state;
+#endif
+static_assert(sizeof(vqa_step_state) == 64 && alignof(vqa_step_state) == 16, "vqa_step_state: 52 bytes of fields in a 16-byte aligned block");
+static_assert(offsetof(vqa_step_state, seed_step) == 8 && offsetof(vqa_step_state, lr) == 16 && offsetof(vqa_step_state, ema_warmup) == 48,
+              "vqa_step_state: field order of include/vqa_hip.h");
 
 #define VQA_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 

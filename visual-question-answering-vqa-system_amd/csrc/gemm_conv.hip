@@ -504,7 +504,7 @@ __global__ __launch_bounds__(NW * 64, OCC) void igemm_kernel(IGemmParams p) {   
   }
   if (p.drop_p > 0.f) {
     const float ks = 1.f / (1.f - p.drop_p);
-    const uint32_t dkey = drop_key(p.drop_seed);          // M*N < 2^32 (checked by the host entry)
+    const uint32_t dkey = drop_key(drop_resolve(p.drop_seed));   // M*N < 2^32 (checked by the host entry); resolved once per kernel, only when dropout is on
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll

@@ -14,6 +14,7 @@
 template <typename T>
 __global__ void embed_fwd_kernel(const long long* __restrict__ ids, const float* __restrict__ emb, const float* __restrict__ pe,
                                  T* __restrict__ out, int rows, int L, int D, int V, float scale, float p, uint64_t seed) {
+  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (size_t)rows * D) return;
   const int d = (int)(i % D), row = (int)(i / D), l = row % L;
@@ -109,6 +110,7 @@ constexpr int EMB_VB = 16;
 template <typename T>
 __global__ __launch_bounds__(256) void embed_bwd_kernel(const long long* __restrict__ ids, const T* __restrict__ dout, float* demb,
                                                         int rows, int D, int V, float scale, float p, uint64_t seed) {
+  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
   extern __shared__ float eacc[];                             // [EMB_VB][D]
   __shared__ int list[1024];                                  // (row << 4) | (id - v0), in row order
   __shared__ int wcnt[4];
@@ -186,6 +188,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const T* __restrict__ x, const float* __restrict__ gamma, const float* __restrict__ beta,
                                                             T* __restrict__ out, float* __restrict__ stats, int rows, int D, float eps,
                                                             float p, uint64_t seed, const float* __restrict__ addrow, int period) {
+  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
   const int lane = threadIdx.x & 63;
   const int wid = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
   for (int row = wid; row < rows; row += nw) {
@@ -212,6 +215,7 @@ template <int LPR>
 __global__ __launch_bounds__(256) void layernorm_fwd_bf16v_kernel(const bf16_t* __restrict__ x, const float* __restrict__ gamma,
                                                                   const float* __restrict__ beta, bf16_t* __restrict__ out, float* __restrict__ stats,
                                                                   int rows, float eps, float p, uint64_t seed, const float* __restrict__ addrow, int period) {
+  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
   constexpr int D = LPR * 8, RPW = 64 / LPR;
   const int lane = threadIdx.x & 63, sub = lane / LPR, sl = lane % LPR;
   const int wid = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nw = (gridDim.x * blockDim.x) >> 6;
@@ -256,6 +260,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const T* __restrict_
                                                             const float* __restrict__ stats, const T* __restrict__ addend, T* __restrict__ dx,
                                                             float* dgamma, float* dbeta, int rows, int D, float p, uint64_t seed,
                                                             float* dadd, int period, float* part) {
+  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wid = blockIdx.x * 4 + wave, nw = gridDim.x * 4;
   float ag[8], ab[8];
@@ -348,6 +353,7 @@ __global__ __launch_bounds__(512) void layernorm_bwd_bf16v_kernel(const bf16_t* 
                                                                   const bf16_t* __restrict__ addend, bf16_t* __restrict__ dx, float* dgamma,
                                                                   float* dbeta, int rows, int D, float p, uint64_t seed, float* dadd, int period,
                                                                   float* part) {
+  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wid = blockIdx.x * 8 + wave, nw = gridDim.x * 8;
   const int c0 = lane * 8;
@@ -408,6 +414,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ q, 
                                                       int ldq, int ldk, int ldv, const float* __restrict__ kmask, float* __restrict__ probs,
                                                       T* __restrict__ ctx, int ldc, int H, int Lq, int Lk, int hd, float scale, float p, uint64_t seed,
                                                       const int* __restrict__ kv_index, int n_kv) {
+  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
   extern __shared__ float sm[];
   const int b = blockIdx.x / H, h = blockIdx.x - b * H, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ldh = hd + 1, ldp = Lk + 1;
   int kb = b;                                                        // batch of the K / V / kmask rows
@@ -468,6 +475,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const T* __restrict__ dct
                                                       T* __restrict__ dq, T* __restrict__ dk, T* __restrict__ dv, int lddq, int lddk, int lddv,
                                                       int H, int Lq, int Lk, int hd, float scale, float p, uint64_t seed,
                                                       const float* __restrict__ dprobs) {
+  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
   extern __shared__ float sm[];
   const int b = blockIdx.x / H, h = blockIdx.x - b * H, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ldh = hd + 1, ldp = Lk + 1;
   float* Qs = sm; float* Os = Qs + Lq * ldh; float* Ks = Os + Lq * ldh; float* Vs = Ks + Lk * ldh;
@@ -648,6 +656,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void bias_act_bwd_kernel(const T* __restrict__ dout, const T* __restrict__ outact, T* __restrict__ dz,
                                                            float* dbias, int M, int N, int relu_drop, float p, uint64_t seed,
                                                            float* part) {
+  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
   // block handles a strip of 64 columns x rows_per_block rows; thread (r = tid/64, c = tid%64)
   const int c = blockIdx.x * 64 + (threadIdx.x & 63), rl = threadIdx.x >> 6;
   const int rows_per = (M + gridDim.y - 1) / gridDim.y;
@@ -679,6 +688,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void bias_act_bwd_vec_kernel(const T* __restrict__ dout, const T* __restrict__ outact, T* __restrict__ dz,
                                                                float* dbias, int M, int N, float p, uint64_t seed, int rows_per,
                                                                float* part) {
+  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
   constexpr int VEC = Vec16<T>::N;
   const int cvs = N / VEC;                                   // column groups per row
   const int gpb = cvs < 256 ? cvs : 256;                     // column groups handled by one block (per blockIdx.x)
@@ -791,9 +801,21 @@ __global__ __launch_bounds__(256) void sumsq_final_kernel(float* out, int nparts
   if (threadIdx.x == 0) out[0] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 // clip_grad_norm_(max_norm) + AdamW (decoupled weight decay), torch semantics (training/train.py:204-208,127-132)
-__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n,
-                             float lr, float b1, float b2, float eps, float wd, long long calls, const float* __restrict__ sumsq,
-                             float max_norm, float gscale, const int* __restrict__ skip, int* __restrict__ skipped, bf16_t* __restrict__ p_bf16) {
+// The by-value hyper-parameters of one AdamW launch, in one struct: the by-value kernels fill it from their arguments, the _dev kernels
+// from the device step-state block (vqa_step_state, written by vqa_step_state_set right before a captured step is replayed).  Both then
+// run the SAME __device__ body below, which copies the fields into locals first: same statements, same order, same bits.
+struct AdamHyper { float lr, b1, b2, eps, wd; long long calls; float max_norm, gscale, ema_decay; int ema_warmup; };
+__device__ __forceinline__ AdamHyper adam_hyper_of(const vqa_step_state* __restrict__ st) {
+  AdamHyper h;
+  h.lr = st->lr; h.b1 = st->b1; h.b2 = st->b2; h.eps = st->eps; h.wd = st->wd; h.calls = st->calls;
+  h.max_norm = st->max_norm; h.gscale = st->gscale; h.ema_decay = st->ema_decay; h.ema_warmup = st->ema_warmup;
+  return h;
+}
+__device__ __forceinline__ void adamw_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n,
+                                           const AdamHyper& hy, const float* __restrict__ sumsq, const int* __restrict__ skip,
+                                           int* __restrict__ skipped, bf16_t* __restrict__ p_bf16) {
+  const float lr = hy.lr, b1 = hy.b1, b2 = hy.b2, eps = hy.eps, wd = hy.wd, max_norm = hy.max_norm, gscale = hy.gscale;
+  const long long calls = hy.calls;
   // p_bf16 != nullptr: the bf16 working copy of the parameters (what the next forward's GEMMs read) is written here as well -- the
   // separate cast launch over the flat buffer (116 MB of traffic, 34 us at the head of every step) is gone.  A skipped launch leaves
   // both the parameters and the copy as they were.
@@ -827,6 +849,18 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     p[i] = pi;
     if (p_bf16) p_bf16[i] = f2bf(pi);
   }
+}
+__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n,
+                             float lr, float b1, float b2, float eps, float wd, long long calls, const float* __restrict__ sumsq,
+                             float max_norm, float gscale, const int* __restrict__ skip, int* __restrict__ skipped, bf16_t* __restrict__ p_bf16) {
+  const AdamHyper hy{lr, b1, b2, eps, wd, calls, max_norm, gscale, 0.f, 0};
+  adamw_body(p, g, m, v, n, hy, sumsq, skip, skipped, p_bf16);
+}
+__global__ void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n,
+                                 const vqa_step_state* __restrict__ state, const float* __restrict__ sumsq, const int* __restrict__ skip,
+                                 int* __restrict__ skipped, bf16_t* __restrict__ p_bf16) {
+  const AdamHyper hy = adam_hyper_of(state);
+  adamw_body(p, g, m, v, n, hy, sumsq, skip, skipped, p_bf16);
 }
 
 // The same two kernels over a table of TRAINABLE ranges (fine-tuning with frozen parameters, trainer.py): elements outside every
@@ -864,12 +898,13 @@ __global__ __launch_bounds__(256) void sumsq_ranges_kernel(const float* __restri
 // clip + AdamW of adamw_kernel, per range: Adam's step number of range r is calls - skipped[2] - lag[table[r].lag index], where lag[j]
 // counts the applied steps during which parameter j was frozen (torch.optim.AdamW advances a parameter's `step` only when it has a
 // gradient).  Every parameter inside one range shares its lag (the caller merges only such neighbours).
-__global__ __launch_bounds__(256) void adamw_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                           float* __restrict__ v, const long long* __restrict__ table, int R, long long n,
-                                                           float lr, float b1, float b2, float eps, float wd, long long calls,
-                                                           const float* __restrict__ sumsq, float max_norm, float gscale,
-                                                           const int* __restrict__ skip, int* __restrict__ skipped, const int* __restrict__ lag,
-                                                           bf16_t* __restrict__ p_bf16) {
+__device__ __forceinline__ void adamw_ranges_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                  float* __restrict__ v, const long long* __restrict__ table, int R, long long n,
+                                                  const AdamHyper& hy, const float* __restrict__ sumsq,
+                                                  const int* __restrict__ skip, int* __restrict__ skipped, const int* __restrict__ lag,
+                                                  bf16_t* __restrict__ p_bf16) {
+  const float lr = hy.lr, b1 = hy.b1, b2 = hy.b2, eps = hy.eps, wd = hy.wd, max_norm = hy.max_norm, gscale = hy.gscale;
+  const long long calls = hy.calls;
   if (skip && *skip != 0) {
     if (skipped && blockIdx.x == 0 && threadIdx.x == 0) { skipped[0] += *skip; skipped[1] += 1; skipped[2] += 1; }
     return;
@@ -922,6 +957,23 @@ __global__ __launch_bounds__(256) void adamw_ranges_kernel(float* __restrict__ p
     }
   }
 }
+__global__ __launch_bounds__(256) void adamw_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                           float* __restrict__ v, const long long* __restrict__ table, int R, long long n,
+                                                           float lr, float b1, float b2, float eps, float wd, long long calls,
+                                                           const float* __restrict__ sumsq, float max_norm, float gscale,
+                                                           const int* __restrict__ skip, int* __restrict__ skipped, const int* __restrict__ lag,
+                                                           bf16_t* __restrict__ p_bf16) {
+  const AdamHyper hy{lr, b1, b2, eps, wd, calls, max_norm, gscale, 0.f, 0};
+  adamw_ranges_body(p, g, m, v, table, R, n, hy, sumsq, skip, skipped, lag, p_bf16);
+}
+__global__ __launch_bounds__(256) void adamw_ranges_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                               float* __restrict__ v, const long long* __restrict__ table, int R, long long n,
+                                                               const vqa_step_state* __restrict__ state, const float* __restrict__ sumsq,
+                                                               const int* __restrict__ skip, int* __restrict__ skipped,
+                                                               const int* __restrict__ lag, bf16_t* __restrict__ p_bf16) {
+  const AdamHyper hy = adam_hyper_of(state);
+  adamw_ranges_body(p, g, m, v, table, R, n, hy, sumsq, skip, skipped, lag, p_bf16);
+}
 // after an applied step: lag[frozen[k]] += 1 (one thread per frozen parameter; runs behind adamw_ranges_kernel on the same stream)
 __global__ void adamw_lag_kernel(int* __restrict__ lag, const int* __restrict__ frozen, int nf, const int* __restrict__ skip) {
   if (skip && *skip != 0) return;
@@ -945,10 +997,13 @@ __device__ __forceinline__ float ema_decay_at(float decay, int warmup, long long
 // adamw_kernel (same statements, same order: p, m, v and the bf16 copy get the bits adamw_kernel gives them) + the average of the
 // updated parameter, taken from the register that still holds it: 8 B per element on top of the 28 B, no second read of p.
 // A skipped launch returns before `ema` is touched; t does not advance then, so neither does the warm-up.
-__global__ void adamw_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n,
-                                 float lr, float b1, float b2, float eps, float wd, long long calls, const float* __restrict__ sumsq,
-                                 float max_norm, float gscale, const int* __restrict__ skip, int* __restrict__ skipped, bf16_t* __restrict__ p_bf16,
-                                 float* __restrict__ ema, float ema_decay, int ema_warmup) {
+__device__ __forceinline__ void adamw_ema_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                               size_t n, const AdamHyper& hy, const float* __restrict__ sumsq, const int* __restrict__ skip,
+                                               int* __restrict__ skipped, bf16_t* __restrict__ p_bf16, float* __restrict__ ema) {
+  const float lr = hy.lr, b1 = hy.b1, b2 = hy.b2, eps = hy.eps, wd = hy.wd, max_norm = hy.max_norm, gscale = hy.gscale;
+  const long long calls = hy.calls;
+  const float ema_decay = hy.ema_decay;
+  const int ema_warmup = hy.ema_warmup;
   if (skip && *skip != 0) {
     if (skipped && blockIdx.x == 0 && threadIdx.x == 0) { skipped[0] += *skip; skipped[1] += 1; skipped[2] += 1; }
     return;
@@ -975,14 +1030,30 @@ __global__ void adamw_ema_kernel(float* __restrict__ p, const float* __restrict_
     ema[i] = ema_blend(ema[i], pi, d);
   }
 }
+__global__ void adamw_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n,
+                                 float lr, float b1, float b2, float eps, float wd, long long calls, const float* __restrict__ sumsq,
+                                 float max_norm, float gscale, const int* __restrict__ skip, int* __restrict__ skipped, bf16_t* __restrict__ p_bf16,
+                                 float* __restrict__ ema, float ema_decay, int ema_warmup) {
+  const AdamHyper hy{lr, b1, b2, eps, wd, calls, max_norm, gscale, ema_decay, ema_warmup};
+  adamw_ema_body(p, g, m, v, n, hy, sumsq, skip, skipped, p_bf16, ema);
+}
+__global__ void adamw_ema_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n,
+                                     const vqa_step_state* __restrict__ state, const float* __restrict__ sumsq, const int* __restrict__ skip,
+                                     int* __restrict__ skipped, bf16_t* __restrict__ p_bf16, float* __restrict__ ema) {
+  const AdamHyper hy = adam_hyper_of(state);
+  adamw_ema_body(p, g, m, v, n, hy, sumsq, skip, skipped, p_bf16, ema);
+}
 // adamw_ranges_kernel + the average, over the same table: `ema` is neither read nor written outside the trainable ranges, and the
 // warm-up of range r runs on that range's OWN Adam step number t0 - lag[...] (a parameter's average advances only while it trains).
-__global__ __launch_bounds__(256) void adamw_ranges_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                               float* __restrict__ v, const long long* __restrict__ table, int R, long long n,
-                                                               float lr, float b1, float b2, float eps, float wd, long long calls,
-                                                               const float* __restrict__ sumsq, float max_norm, float gscale,
-                                                               const int* __restrict__ skip, int* __restrict__ skipped, const int* __restrict__ lag,
-                                                               bf16_t* __restrict__ p_bf16, float* __restrict__ ema, float ema_decay, int ema_warmup) {
+__device__ __forceinline__ void adamw_ranges_ema_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                      float* __restrict__ v, const long long* __restrict__ table, int R, long long n,
+                                                      const AdamHyper& hy, const float* __restrict__ sumsq,
+                                                      const int* __restrict__ skip, int* __restrict__ skipped, const int* __restrict__ lag,
+                                                      bf16_t* __restrict__ p_bf16, float* __restrict__ ema) {
+  const float lr = hy.lr, b1 = hy.b1, b2 = hy.b2, eps = hy.eps, wd = hy.wd, max_norm = hy.max_norm, gscale = hy.gscale;
+  const long long calls = hy.calls;
+  const float ema_decay = hy.ema_decay;
+  const int ema_warmup = hy.ema_warmup;
   if (skip && *skip != 0) {
     if (skipped && blockIdx.x == 0 && threadIdx.x == 0) { skipped[0] += *skip; skipped[1] += 1; skipped[2] += 1; }
     return;
@@ -1037,6 +1108,34 @@ __global__ __launch_bounds__(256) void adamw_ranges_ema_kernel(float* __restrict
       w.y = (uint32_t)f2bf(p4.z) | ((uint32_t)f2bf(p4.w) << 16);
       *reinterpret_cast<uint2*>(p_bf16 + i) = w;
     }
+  }
+}
+__global__ __launch_bounds__(256) void adamw_ranges_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                               float* __restrict__ v, const long long* __restrict__ table, int R, long long n,
+                                                               float lr, float b1, float b2, float eps, float wd, long long calls,
+                                                               const float* __restrict__ sumsq, float max_norm, float gscale,
+                                                               const int* __restrict__ skip, int* __restrict__ skipped, const int* __restrict__ lag,
+                                                               bf16_t* __restrict__ p_bf16, float* __restrict__ ema, float ema_decay, int ema_warmup) {
+  const AdamHyper hy{lr, b1, b2, eps, wd, calls, max_norm, gscale, ema_decay, ema_warmup};
+  adamw_ranges_ema_body(p, g, m, v, table, R, n, hy, sumsq, skip, skipped, lag, p_bf16, ema);
+}
+__global__ __launch_bounds__(256) void adamw_ranges_ema_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                   float* __restrict__ v, const long long* __restrict__ table, int R, long long n,
+                                                                   const vqa_step_state* __restrict__ state, const float* __restrict__ sumsq,
+                                                                   const int* __restrict__ skip, int* __restrict__ skipped,
+                                                                   const int* __restrict__ lag, bf16_t* __restrict__ p_bf16,
+                                                                   float* __restrict__ ema) {
+  const AdamHyper hy = adam_hyper_of(state);
+  adamw_ranges_ema_body(p, g, m, v, table, R, n, hy, sumsq, skip, skipped, lag, p_bf16, ema);
+}
+// One thread writes the step-state block (plain stores): launched eagerly on the stream right before a captured step is replayed; the
+// values travel as kernel arguments, which the runtime copies at launch.
+__global__ void step_state_set_kernel(vqa_step_state* state, long long calls, unsigned long long seed_step, float lr, float b1, float b2,
+                                      float eps, float wd, float max_norm, float gscale, float ema_decay, int ema_warmup) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    state->calls = calls; state->seed_step = seed_step;
+    state->lr = lr; state->b1 = b1; state->b2 = b2; state->eps = eps; state->wd = wd;
+    state->max_norm = max_norm; state->gscale = gscale; state->ema_decay = ema_decay; state->ema_warmup = ema_warmup;
   }
 }
 // The update as a pass of its own over a flat buffer (torch.optim loops: dropin/utils/ema.py): 12 B per element.  nv float4 groups
@@ -1396,6 +1495,51 @@ int vqa_adamw_ranges_ema(float* p, const float* g, float* m, float* v, const lon
   if (nf > 0) hipLaunchKernelGGL(adamw_lag_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, lag, frozen, nf, skip);
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
+// The four AdamW entries with their by-value hyper-parameters read from the device step-state block (same grids, same bodies).
+static inline bool state_ok(const void* state) { return state && !((uintptr_t)state & 15); }
+int vqa_step_state_set(vqa_step_state* state, long long calls, unsigned long long seed_step, float lr, float b1, float b2, float eps,
+                       float wd, float max_norm, float gscale, float ema_decay, int ema_warmup, hipStream_t st) {
+  if (!state_ok(state) || calls < 1 || (seed_step & (VQA_SEED_INDIRECT | 0xFFFull))) return VQA_EARG;
+  hipLaunchKernelGGL(step_state_set_kernel, dim3(1), dim3(1), 0, st, state, calls, seed_step, lr, b1, b2, eps, wd, max_norm, gscale, ema_decay,
+                     ema_warmup);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+int vqa_adamw_dev(float* p, const float* g, float* m, float* v, long long n, const vqa_step_state* state, const float* sumsq,
+                  const int* skip, int* skipped, void* p_bf16, hipStream_t st) {
+  if (!state_ok(state) || n < 0) return VQA_EARG;
+  size_t blocks = ((size_t)n + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(adamw_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, (size_t)n, state, sumsq, skip, skipped, (bf16_t*)p_bf16);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+int vqa_adamw_ema_dev(float* p, const float* g, float* m, float* v, long long n, const vqa_step_state* state, const float* sumsq,
+                      const int* skip, int* skipped, void* p_bf16, float* ema, hipStream_t st) {
+  if (!state_ok(state) || n < 0 || !ema) return VQA_EARG;
+  size_t blocks = ((size_t)n + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(adamw_ema_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, (size_t)n, state, sumsq, skip, skipped,
+                     (bf16_t*)p_bf16, ema);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+int vqa_adamw_ranges_dev(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n,
+                         const vqa_step_state* state, const float* sumsq, const int* skip, int* skipped, int* lag, const int* frozen, int nf,
+                         void* p_bf16, hipStream_t st) {
+  if (!state_ok(state) || R < 0 || R > VQA_RANGES_MAX || n < 0 || n % 4 || (R == 0 && n != 0) || nf < 0 || (nf > 0 && (!lag || !frozen))) return VQA_EARG;
+  size_t blocks = ((size_t)n / 4 + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(adamw_ranges_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, table, R, n, state, sumsq, skip, skipped,
+                     (const int*)lag, (bf16_t*)p_bf16);
+  if (nf > 0) hipLaunchKernelGGL(adamw_lag_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, lag, frozen, nf, skip);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+int vqa_adamw_ranges_ema_dev(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n,
+                             const vqa_step_state* state, const float* sumsq, const int* skip, int* skipped, int* lag, const int* frozen,
+                             int nf, void* p_bf16, float* ema, hipStream_t st) {
+  if (!state_ok(state) || R < 0 || R > VQA_RANGES_MAX || n < 0 || n % 4 || (R == 0 && n != 0) || nf < 0 || (nf > 0 && (!lag || !frozen))) return VQA_EARG;
+  if (!ema) return VQA_EARG;
+  size_t blocks = ((size_t)n / 4 + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(adamw_ranges_ema_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, table, R, n, state, sumsq, skip, skipped,
+                     (const int*)lag, (bf16_t*)p_bf16, ema);
+  if (nf > 0) hipLaunchKernelGGL(adamw_lag_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, lag, frozen, nf, skip);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
 int vqa_ema_update(float* ema, const float* p, long long n, float d, hipStream_t st) {
   if (!ema || !p || n < 0 || !ema_decay_ok(d)) return VQA_EARG;
   const long long nv = (((uintptr_t)ema | (uintptr_t)p) & 15) ? 0 : n / 4;
@@ -1425,6 +1569,7 @@ __global__ __launch_bounds__(WPB * 64, 1) void attn_fwd_mfma_kernel(const bf16_t
                                                             int ldq, int ldk, int ldv, const float* __restrict__ kmask, float* __restrict__ probs,
                                                             bf16_t* __restrict__ ctx, int ldc, int BH, int H, int Lq, int Lk, float p, uint64_t seed,
                                                             const int* __restrict__ kv_index, int n_kv) {
+  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
   constexpr int LDV = HD;                       // V tile row stride (elements): 64 / 128 bytes, 8-byte aligned for the transposed reads
   constexpr int KR = NKT * 32;                  // key rows of the tiles
   constexpr int LDP = KR + 1;                   // probability staging row stride (floats)
@@ -1596,6 +1741,7 @@ __global__ __launch_bounds__(WPB * 64, 1) void attn_bwd_mfma_kernel(const bf16_t
                                                             const float* __restrict__ probs, bf16_t* __restrict__ dq, bf16_t* __restrict__ dk,
                                                             bf16_t* __restrict__ dv, int lddq, int lddk, int lddv, int BH, int H, int Lq, int Lk,
                                                             float p, uint64_t seed, const float* __restrict__ dprobs) {
+  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
   constexpr int KR = NKT * 32;
   constexpr int LDP = KR + 1;
   constexpr int WAVE_BYTES = (KR + 32 + 32) * HD * 2 + 32 * LDP * 4 + 32 * 4 + (DPR ? 32 * LDP * 4 : 0);
@@ -2395,6 +2541,7 @@ __global__ __launch_bounds__(256) void attn_bwd_idx_kernel(const T* __restrict__
                                                           T* __restrict__ dq, T* __restrict__ dk, T* __restrict__ dv, int lddq, int lddk, int lddv,
                                                           int H, int Lq, int Lk, int hd, float scale, float p, uint64_t seed,
                                                           const int* __restrict__ offsets, const int* __restrict__ order, int N) {
+  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
   extern __shared__ float sm[];
   const int u = blockIdx.x / H, h = blockIdx.x - u * H, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ldh = hd + 1, ldp = Lk + 1;
   float* Qs = sm; float* Os = Qs + Lq * ldh; float* Ks = Os + Lq * ldh; float* Vs = Ks + Lk * ldh;
@@ -2483,6 +2630,7 @@ __global__ __launch_bounds__(WPB * 64, 1) void attn_bwd_mfma_idx_kernel(const bf
                                                                 bf16_t* __restrict__ dv, int lddq, int lddk, int lddv, int UH, int H, int Lq, int Lk,
                                                                 float p, uint64_t seed, const int* __restrict__ offsets,
                                                                 const int* __restrict__ order, int N) {
+  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
   constexpr int KR = NKT * 32;
   constexpr int LDP = KR + 1;
   constexpr int NACC = NKT * (HD / 32) * 16;    // accumulator registers per lane and tensor

@@ -16,6 +16,7 @@ import torch
 
 from . import kernels as K
 from . import layout as LY
+from . import stepgraph as SG
 from ._lib import call, dt, ptr
 
 
@@ -90,6 +91,10 @@ class HipEngine:
         self.seed_base = 0x5EED
         self.seed_rank = None
         self.step_id = 0
+        # device address of a vqa_step_state's seed_step word, or None.  While it is set (HipTrainer.step_graphed, around the capture
+        # of a train step) _seed() hands out the flagged form of the seed word (stepgraph.seed_word): the kernels read the step's
+        # rank << 44 | step << 12 from that address, so a replay draws the masks of ITS step instead of the capture's
+        self._seed_src = None
         self.cnn_train_forwards = 0               # forwards that ran the CNN in train mode (BatchNorm running statistics moved): cached
                                                   # image features are stale after one (VQAModel._feat_stamp)
         self.wsrc = flat
@@ -98,6 +103,7 @@ class HipEngine:
         self._wt_plan: Dict[str, tuple] = {}      # operands packed by begin_step (filled by _packT on first use)
         self._wt_table = None
         self._wt_buf = None
+        self._wt_gen = 0                          # how often the packed-operand buffer was laid out anew (a captured step holds its address)
         # schedule switches: plain attributes (tools/ flip them for A/B measurements); the product never reads the environment
         self._deferred = []
         self._keep = []
@@ -194,9 +200,11 @@ class HipEngine:
                 dst += (rows * ld + 7) // 8 * 8
             self._wt_table = (torch.tensor(rowsd, dtype=torch.int64).to(self.flat.device), views, dst, blk, len(rowsd))
             self._wt_buf = torch.empty(dst, device=self.flat.device, dtype=self.dtype)
+            self._wt_gen += 1
         table, views, total, blk, nd = self._wt_table
         if self._wt_buf.dtype != self.dtype or self._wt_buf.device != self.flat.device:
             self._wt_buf = torch.empty(total, device=self.flat.device, dtype=self.dtype)
+            self._wt_gen += 1
         call("vqa_pack_transpose_batch", K.dt(self.dtype), ptr(self.flat), ptr(self._wt_buf), ptr(table), nd, blk)
         for key, dst, rows, ld in views:
             self._wt[key] = self._wt_buf[dst: dst + rows * ld].view(rows, ld)
@@ -272,9 +280,7 @@ class HipEngine:
                 self._stem_fcoef = make_fcoef() if self._wt_plan else None    # only once a backward has been seen
                 self._pack_planned()
         if self.dtype == torch.bfloat16:
-            if self.wsrc is self.flat or self.wsrc.numel() != self.flat.numel():
-                self.wsrc = torch.empty(self.flat.numel(), device=self.flat.device, dtype=torch.bfloat16)
-                self._wsrc_fresh = False
+            self.ensure_operand_copy()
             # HipTrainer's AdamW launch writes this copy itself (adamw_copy_target) and vouches for it for exactly ONE begin_step, after
             # checking that nothing touched the parameters through torch in between (trainer._param_sig); every other caller casts
             if not self._wsrc_fresh:
@@ -293,6 +299,34 @@ class HipEngine:
             self.stem_w2 = torch.empty((64, 192), device=self.flat.device, dtype=torch.bfloat16)
             call("vqa_stem_pack", ptr(self.P("image_encoder.stem.0.weight")), ptr(self.stem_w2))
 
+    def ensure_operand_copy(self):
+        """bf16 mode: allocate the operand copy of the parameters if it does not exist yet (begin_step's first act; also called by
+        HipTrainer.step_graphed ahead of its first step, so that the buffer's address is the same in every call's graph key)."""
+        if self.dtype == torch.bfloat16 and (self.wsrc is self.flat or self.wsrc.numel() != self.flat.numel()):
+            self.wsrc = torch.empty(self.flat.numel(), device=self.flat.device, dtype=torch.bfloat16)
+            self._wsrc_fresh = False
+
+    def refresh_operand_copy(self):
+        """Cast the fp32 parameters into the bf16 operand copy now (what begin_step does when nobody vouches for the copy); nothing
+        in fp32 mode or before the copy exists."""
+        if self.adamw_copy_target() is not None:
+            call("vqa_convert", 0, 1, ptr(self.flat), ptr(self.wsrc), self.flat.numel())
+
+    def count_step(self, modes, runs_cnn=True):
+        """The bookkeeping of one training forward with part modes `modes` (cnn, text, fusion, head): forward() and
+        forward_features() call it themselves unless their caller did (counted=True: HipTrainer's step prologue, which also runs
+        ahead of a replayed step that never enters forward())."""
+        if any(modes[0 if runs_cnn else 1:]):
+            self.step_id += 1
+        if runs_cnn and modes[0]:
+            self.cnn_train_forwards += 1
+
+    def operands_settled(self) -> bool:
+        """True when the next begin_step packs the planned backward operands into the buffer it already has: a step may be captured.
+        False right after a backward that needed a new operand (it packed on demand): the next begin_step lays the buffer out anew,
+        with a table copied from the host, which no capture may contain."""
+        return not self._wt_plan or self._wt_table is not None
+
     def adamw_copy_target(self):
         """bf16 operand buffer the fused AdamW kernel may write next to the fp32 parameters (None: fp32 schedule / not allocated yet)."""
         if self.dtype != torch.bfloat16 or self.wsrc is self.flat or self.wsrc.numel() != self.flat.numel():
@@ -304,6 +338,8 @@ class HipEngine:
         self._site += 1
         if self.seed_rank is None:
             self.seed_rank = torch.distributed.get_rank() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 0
+        if self._seed_src is not None:            # (the tape stores what this returns: the backward regenerates the same masks)
+            return SG.seed_word(self._seed_src, self._site)
         return (self.seed_rank << 44) | (((self.seed_base + self.step_id) & 0xFFFFFFFF) << 12) | self._site
 
     # ------------------------------------------------------------------ small op helpers
@@ -560,7 +596,7 @@ class HipEngine:
     # ------------------------------------------------------------------ forward
     def forward(self, images: torch.Tensor, token_ids: torch.Tensor, maskf: Optional[torch.Tensor], training: bool,
                 want_aux: bool = False, need_tape: bool = True, lowp_logits: bool = False, record: Optional[dict] = None,
-                kv_index: Optional[torch.Tensor] = None, plan=None):
+                kv_index: Optional[torch.Tensor] = None, plan=None, counted: bool = False):
         """plan (fine-tuning with frozen parts, finetune.Plan; None: every part in mode `training`, everything taped): BatchNorm
         and dropout follow each part's own mode, and a CNN with nothing to train and no image gradient runs without a tape -- the
         Conv+BN-folded eval route in eval mode, the training forward (running statistics updated) without kept activations in train
@@ -582,10 +618,8 @@ class HipEngine:
         else:
             ctrain = ttrain = ftrain = htrain = training
             cnn_tape = need_tape
-        if ctrain or ttrain or ftrain or htrain:
-            self.step_id += 1
-        if ctrain:
-            self.cnn_train_forwards += 1
+        if not counted:                           # (see count_step)
+            self.count_step((ctrain, ttrain, ftrain, htrain))
         self.begin_step(for_backward=need_tape)
         if ctrain and self.fuse_bn_finalize and self.dtype == torch.bfloat16:
             self._acc_reset()                     # one memset for every BatchNorm accumulator of this forward
@@ -679,7 +713,7 @@ class HipEngine:
 
     def forward_features(self, feat: torch.Tensor, token_ids: torch.Tensor, maskf: Optional[torch.Tensor], training: bool,
                          want_aux: bool = False, need_tape: bool = True, lowp_logits: bool = False,
-                         kv_index: Optional[torch.Tensor] = None, plan=None):
+                         kv_index: Optional[torch.Tensor] = None, plan=None, counted: bool = False):
         """forward() from cached image features: feat is what encode_features() returned for the U images (NHWC [U][Hf][Wf][Cf],
         compute dtype, contiguous), the image encoder is frozen and in eval mode, and _stem_fwd / _stages_fwd do not run.  Everything
         else is forward(): the same step_id rule, _site reset and weight cast, the parts issued in forward()'s order (text encoder
@@ -699,8 +733,8 @@ class HipEngine:
                 raise RuntimeError("forward_features: a taped forward needs a fine-tuning plan with the image encoder frozen")
             ttrain = ftrain = htrain = training
         self._site = 0
-        if ttrain or ftrain or htrain:
-            self.step_id += 1
+        if not counted:
+            self.count_step((False, ttrain, ftrain, htrain), runs_cnn=False)
         self.begin_step(for_backward=need_tape, stem=False)
         B, Hf, Wf, Cf = feat.shape
         ntok = Hf * Wf

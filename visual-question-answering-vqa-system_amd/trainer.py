@@ -18,6 +18,7 @@ import torch.distributed as dist
 from . import ema as EMA
 from . import finetune as FT
 from . import layout as LY
+from . import stepgraph as SG
 from ._lib import call, dt, ptr
 
 
@@ -232,7 +233,14 @@ class HipTrainer:
         self._ever_frozen = False                  # some parameter was frozen at some step: the plain kernels' global step is off
         self._lag_class = [0] * len(model._param_entries)
         self._ranges = None                        # (table, R, n, frozen indices, nf) on the device
+        self._ranges_gen = 0                       # how often that table was rebuilt (a captured step holds its address and sizes)
         self._lag = torch.zeros(len(model._param_entries), device=flat.device, dtype=torch.int32)
+        # step_graphed: captured train steps (LRU, capped by model.graph_max_shapes like model._graphs), how often each key was seen
+        # (the first two calls of a key run eagerly), and the device step-state block the captured launches read (stepgraph.py)
+        self._graphs = {}
+        self._graph_seen = {}
+        self._state = None
+        self.graph_captures = 0
 
     def _check_loss_opts(self, label_smoothing, class_weight, ignore_index):
         """Validated (label_smoothing float, ignore_index int | None, class_weight fp32 [num_answers] on the device | None); host
@@ -276,6 +284,7 @@ class HipTrainer:
         frozen = [j for j, t in enumerate(tr) if not t]
         fidx = torch.tensor(frozen if frozen else [0], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
         self._ranges = (table, len(rows), n, fidx, len(frozen))
+        self._ranges_gen += 1
         self.reducer.set_trainable(ranges)
 
     def step(self, images, token_ids, attention_mask, targets, metrics=None, image_index=None):
@@ -305,70 +314,99 @@ class HipTrainer:
         frozen and in eval mode, does not run, and everything after it is the same step -- the launches of the images step without the
         CNN forward, bit for bit.  RuntimeError before any launch when an image_encoder parameter requires grad, the image encoder is
         in train mode, or the features are stale."""
+        return self._enqueue(self._prologue("step", images, token_ids, attention_mask, targets, metrics, image_index))
+
+    def _prologue(self, who, images, token_ids, attention_mask, targets, metrics, image_index):
+        """The host half of a step: validation, the fine-tuning plan, the image index's device copy, the optimizer's range table and
+        -- last, once nothing can be refused any more -- the bookkeeping (calls, the engine's step_id and cnn_train_forwards, the
+        model's _feat_epoch).  Launches nothing through the C ABI.  Returns what _enqueue needs."""
         if self._ema_swapped:
-            raise RuntimeError("HipTrainer.step inside ema_weights(): the model holds the averaged weights; leave the block first")
-        eng, T = self.engine, self.engine.dtype
+            raise RuntimeError(f"HipTrainer.{who} inside ema_weights(): the model holds the averaged weights; leave the block first")
+        eng = self.engine
         dev = self.G.device
-        ema_args = ()
         if self.ema is not None:                           # (ema_decay may have been changed since the constructor checked it)
-            ema_args = (ptr(self.ema), EMA.check_decay(self.ema_decay, "HipTrainer: ema_decay"), int(bool(self.ema_warmup)))
+            EMA.check_decay(self.ema_decay, "HipTrainer: ema_decay")
         soft = _is_soft(targets)
         bce = self.loss_kind == "bce"
         if bce and not soft:
-            raise TypeError('HipTrainer.step: loss="bce" trains on SoftTargets; wrap hard labels as '
+            raise TypeError(f'HipTrainer.{who}: loss="bce" trains on SoftTargets; wrap hard labels as '
                             "SoftTargets(labels.int()[:, None], ones) with ones = torch.ones(B, 1) on the device")
         feats = images if _is_features(images) else None
         if feats is not None:
             images = feats.tensor()
         if soft and self._loss_opts:
-            raise TypeError("HipTrainer.step: label_smoothing / class_weight / ignore_index apply to hard labels; "
+            raise TypeError(f"HipTrainer.{who}: label_smoothing / class_weight / ignore_index apply to hard labels; "
                             "SoftTargets cannot be combined with them")
         if metrics is not None and soft != hasattr(metrics, "_fused_acc"):
-            raise TypeError("HipTrainer.step: soft targets are scored by VQAChallengeAccuracy, hard labels by VQAAccuracy "
+            raise TypeError(f"HipTrainer.{who}: soft targets are scored by VQAChallengeAccuracy, hard labels by VQAAccuracy "
                             f"(got {type(metrics).__name__} with {'SoftTargets' if soft else 'a label tensor'})")
         if metrics is not None and soft and targets.counts is None:
-            raise TypeError("HipTrainer.step: VQAChallengeAccuracy needs SoftTargets that carry `counts`")
+            raise TypeError(f"HipTrainer.{who}: VQAChallengeAccuracy needs SoftTargets that carry `counts`")
         for name, t in (("images", images), ("token_ids", token_ids)) + ((("targets", targets),) if not soft else ()):
             if not (isinstance(t, torch.Tensor) and t.device == dev):
-                raise RuntimeError(f"HipTrainer.step: `{name}` must be a tensor on {dev} (there is no CPU path)")
+                raise RuntimeError(f"HipTrainer.{who}: `{name}` must be a tensor on {dev} (there is no CPU path)")
         Bq = token_ids.shape[0] if (image_index is not None and token_ids.dim() == 2) else images.shape[0]
         if soft:
             targets.validate(Bq, dev)
         if images.dim() != 4 or (feats is None and images.shape[1] != 3) or token_ids.dim() != 2 or token_ids.shape[0] != Bq or (not soft and targets.shape != (Bq,)):
-            raise RuntimeError("HipTrainer.step: expected images [B,3,H,W], token_ids [B,L], targets [B]"
+            raise RuntimeError(f"HipTrainer.{who}: expected images [B,3,H,W], token_ids [B,L], targets [B]"
                                + ("" if image_index is None else " with B questions"))
         # fine-tuning: requires_grad and the parts' modes, resolved on every step (finetune.Plan; None: the plain step)
         plan = self.model._finetune_plan(self.model._param_list(), False, True)
         if feats is not None:                              # host checks, ahead of the image index's copy / range read: nothing has gone out yet
             if plan is None or plan.cnn_trains:
-                raise RuntimeError("HipTrainer.step: ImageFeatures stand in for a frozen image encoder: call "
+                raise RuntimeError(f"HipTrainer.{who}: ImageFeatures stand in for a frozen image encoder: call "
                                    "model.image_encoder.requires_grad_(False)")
-            self.model._check_features(feats, "HipTrainer.step")
+            self.model._check_features(feats, f"HipTrainer.{who}")
         kv_index = None
         if image_index is not None:
             kv_index = self._device_index(image_index, images.shape[0], Bq, dev)
         if attention_mask is not None and not (isinstance(attention_mask, torch.Tensor) and attention_mask.device == dev
                                                and attention_mask.shape == token_ids.shape):
-            raise RuntimeError(f"HipTrainer.step: `attention_mask` must be a [B,L] tensor on {dev} (or None)")
-        if feats is None and (plan is None or plan.cnn_trains):      # this step's AdamW writes the image encoder: cached features go stale
-            self.model._feat_epoch += 1
+            raise RuntimeError(f"HipTrainer.{who}: `attention_mask` must be a [B,L] tensor on {dev} (or None)")
+        eng._pos_enc(token_ids.shape[1])                   # (a question that is too long is refused here, before anything is counted)
         # the kernels read raw pointers: enforce the dtypes / contiguity VQAModel.forward enforces (vqa_model.py drop-in)
         if feats is None:
             images = images.contiguous().float()
         token_ids = token_ids.contiguous().long()
         if not soft:
             targets = targets.contiguous().long()
-        self.G.zero_()
-        self._scal.zero_()
-        if self._copy_sig is not None and eng.adamw_copy_target() is not None and self._copy_sig == self._param_sig():
-            eng._wsrc_fresh = True                 # (one-shot, consumed by the begin_step of the forward below)
         maskf = None if attention_mask is None else attention_mask.contiguous().float()
         self._set_mask(None if plan is None else plan.trainable)
-        if feats is not None:
-            logits, _, tape = eng.forward_features(images, token_ids, maskf, True, False, need_tape=True, lowp_logits=True, kv_index=kv_index,
-                                                   plan=plan)
-        else:
-            logits, _, tape = eng.forward(images, token_ids, maskf, True, False, need_tape=True, lowp_logits=True, kv_index=kv_index, plan=plan)
+        # ---- bookkeeping: from here on the step counts
+        if feats is None and (plan is None or plan.cnn_trains):      # this step's AdamW writes the image encoder: cached features go stale
+            self.model._feat_epoch += 1
+        eng.count_step(plan.modes if plan is not None else (True, True, True, True), runs_cnn=feats is None)
+        self.calls += 1
+        return dict(features=feats is not None, images=images, token_ids=token_ids, maskf=maskf, targets=targets, soft=soft, bce=bce,
+                    metrics=metrics, kv_index=kv_index, plan=plan)
+
+    def _enqueue(self, c, state=None):
+        """The device half of a step: every launch, in the order the step has always issued them; returns (loss, logits fp32).
+        state (step_graphed, while the step is being captured): the device step-state block.  The dropout seeds are then the flagged
+        words that point into it, AdamW is the _dev entry that reads its hyper-parameters from it, and the bf16 operand copy the
+        previous AdamW launch wrote is trusted (step_graphed re-casts it eagerly before a replay when the host check fails)."""
+        eng = self.engine
+        images, token_ids, maskf, targets, metrics, kv_index, plan = (c[k] for k in ("images", "token_ids", "maskf", "targets", "metrics",
+                                                                                      "kv_index", "plan"))
+        soft, bce = c["soft"], c["bce"]
+        dev = self.G.device
+        self.G.zero_()
+        self._scal.zero_()
+        if state is not None:
+            eng._wsrc_fresh = eng.adamw_copy_target() is not None
+        elif self._copy_sig is not None and eng.adamw_copy_target() is not None and self._copy_sig == self._param_sig():
+            eng._wsrc_fresh = True                 # (one-shot, consumed by the begin_step of the forward below)
+        eng._seed_src = None if state is None else state.data_ptr() + SG.SEED_STEP_OFFSET
+        try:
+            if c["features"]:
+                logits, _, tape = eng.forward_features(images, token_ids, maskf, True, False, need_tape=True, lowp_logits=True, kv_index=kv_index,
+                                                       plan=plan, counted=True)
+            else:
+                logits, _, tape = eng.forward(images, token_ids, maskf, True, False, need_tape=True, lowp_logits=True, kv_index=kv_index, plan=plan,
+                                              counted=True)
+        finally:
+            eng._seed_src = None
         B, N = logits.shape
         # the loss kernel reads the logits in the compute dtype, writes d logits in it and leaves the fp32 logits the caller gets:
         # the same values as logits.float() -> loss -> d logits.to(bf16), two elementwise launches less between forward and backward
@@ -395,22 +433,138 @@ class HipTrainer:
             metrics.update(logits_f, targets)
         eng.backward(tape, dlogits, self.G, on_segment=self.reducer.on_segment if self.reducer.active else None)
         gscale = self.reducer.finish()
-        self.calls += 1
         b1, b2 = self.betas
+        if state is not None:                      # the captured form: hyper-parameters, step number and gscale come from the block
+            hyper, ema_args, sfx = (ptr(state),), (() if self.ema is None else (ptr(self.ema),)), "_dev"
+        else:
+            hyper, sfx = (self.lr, b1, b2, self.eps, self.wd, self.calls), ""
+            ema_args = () if self.ema is None else (ptr(self.ema), float(self.ema_decay), int(bool(self.ema_warmup)))
+        tail = () if state is not None else (float(self.max_norm), gscale)
         if self._ranges is None:
             call("vqa_sumsq", ptr(self.G), self.G.numel(), ptr(self.sumsq))
-            call("vqa_adamw_ema" if ema_args else "vqa_adamw", ptr(self.model._flat), ptr(self.G), ptr(self.m), ptr(self.v), self.G.numel(),
-                 self.lr, b1, b2, self.eps, self.wd, self.calls, ptr(self.sumsq), float(self.max_norm), gscale, ptr(self.bad_step), ptr(self._bad),
-                 ptr(eng.adamw_copy_target()), *ema_args)
+            call(("vqa_adamw_ema" if ema_args else "vqa_adamw") + sfx, ptr(self.model._flat), ptr(self.G), ptr(self.m), ptr(self.v), self.G.numel(),
+                 *hyper, ptr(self.sumsq), *tail, ptr(self.bad_step), ptr(self._bad), ptr(eng.adamw_copy_target()), *ema_args)
         else:                                      # frozen parameters: only the trainable ranges are read and written
             table, R, n, fidx, nf = self._ranges
             call("vqa_sumsq_ranges", ptr(self.G), ptr(table), R, n, ptr(self.sumsq))
-            call("vqa_adamw_ranges_ema" if ema_args else "vqa_adamw_ranges", ptr(self.model._flat), ptr(self.G), ptr(self.m), ptr(self.v),
-                 ptr(table), R, n, self.lr, b1, b2, self.eps, self.wd, self.calls, ptr(self.sumsq), float(self.max_norm), gscale,
-                 ptr(self.bad_step), ptr(self._bad), ptr(self._lag), ptr(fidx), nf, ptr(eng.adamw_copy_target()), *ema_args)
+            call(("vqa_adamw_ranges_ema" if ema_args else "vqa_adamw_ranges") + sfx, ptr(self.model._flat), ptr(self.G), ptr(self.m), ptr(self.v),
+                 ptr(table), R, n, *hyper, ptr(self.sumsq), *tail, ptr(self.bad_step), ptr(self._bad), ptr(self._lag), ptr(fidx), nf,
+                 ptr(eng.adamw_copy_target()), *ema_args)
         # the kernel wrote the bf16 operand copy too: the next step() skips the cast launch if nothing touched the parameters in between
         self._copy_sig = self._param_sig() if eng.adamw_copy_target() is not None else None
         return self.loss, logits_f
+
+    # ---- the captured step
+    def step_graphed(self, images, token_ids, attention_mask, targets, metrics=None, image_index=None):
+        """step() replayed from a captured HIP graph: same arguments, checks, errors and return value, bit-equal results, and the
+        host enqueues three things per step instead of every launch.  The first two calls for a key (stepgraph.step_key: shapes and
+        dtypes of the inputs, mask / index present, K of SoftTargets, features or images, the fine-tuning plan, the loss and its
+        options, EMA on or off, the `metrics` object, the parameter / operand-copy / packed-operand / range-table buffers) are eager steps; the third
+        captures the launches of _enqueue on static copies of the inputs and replays them; later calls copy the inputs in, write the
+        device step-state block (vqa_step_state_set: this step's seed word and Adam step number, and lr / betas / eps / wd /
+        max_norm / ema_decay / ema_warmup as they read NOW -- changing them never re-captures) and replay.  A torch-side write to
+        the parameters since the last AdamW launch (load_state_dict, a torch optimizer, ema_weights(), an eager step() in between
+        leaves the copy fresh) is answered by an eager vqa_convert ahead of the replay, as step() would cast.
+        The returned logits (and the loss, as with step()) are the graph's static buffers: valid until the next call with the same
+        key.  check(), t, grad_norm(), ema_*, params_changed() and `metrics` work as with step().
+        RuntimeError before any launch: more than one rank or force_reducer=True (no collectives inside a graph), a current stream
+        that is capturing, a call inside ema_weights()."""
+        if self.reducer.active:
+            raise RuntimeError("HipTrainer.step_graphed: a captured step holds no collectives -- it runs in a world of one rank "
+                               "without force_reducer; use step()")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("HipTrainer.step_graphed: the current stream is capturing; a graph is not captured inside another")
+        c = self._prologue("step_graphed", images, token_ids, attention_mask, targets, metrics, image_index)
+        eng = self.engine
+        eng.ensure_operand_copy()                          # (its address is part of the key from the first call on)
+        key = SG.step_key(features=c["features"], images=c["images"], token_ids=c["token_ids"], attention_mask=c["maskf"],
+                          image_index=c["kv_index"], targets=c["targets"], plan=c["plan"], loss_kind=self.loss_kind,
+                          loss_opts=(self.label_smoothing, self.ignore_index, None if self.class_weight is None else self.class_weight.data_ptr()),
+                          ema=self.ema is not None, metrics=metrics, flat_ptr=self.model._flat.data_ptr(), wsrc_ptr=eng.wsrc.data_ptr(),
+                          table_id=None if self._ranges is None else self._ranges_gen)
+        g = self._graphs.pop(key, None)
+        if g is not None and g[4] != eng._wt_gen:
+            # the engine laid its packed backward operands out anew since the capture (another trainable set needed more of them):
+            # the graph holds the old buffer's address.  Dropped like an evicted one, and captured again as soon as the engine allows
+            torch.cuda.synchronize()
+            g = None
+            self._graph_seen[key] = 2
+        if g is None:
+            seen = self._graph_seen.get(key, 0)
+            if seen < 2 or not eng.operands_settled():                                   # a real step and the warm-up: _wt_plan, wsrc, one-time kernel attributes, caches
+                if len(self._graph_seen) > 4 * max(1, self.model.graph_max_shapes):
+                    self._graph_seen.clear()
+                self._graph_seen[key] = seen + 1
+                return self._enqueue(c)
+        if self._state is None:
+            self._state = torch.zeros(SG.STATE_BYTES // 4, device=self.G.device, dtype=torch.int32)
+        # the operand copy: the graph trusts the one the previous AdamW launch wrote; when the host cannot vouch for it, cast now
+        if eng.adamw_copy_target() is not None and not (self._copy_sig is not None and self._copy_sig == self._param_sig()):
+            eng.refresh_operand_copy()
+        b1, b2 = self.betas
+        ema_on = self.ema is not None
+        call("vqa_step_state_set", ptr(self._state), self.calls, SG.seed_step(self._seed_rank(), eng.seed_base, eng.step_id),
+             float(self.lr), float(b1), float(b2), float(self.eps), float(self.wd), float(self.max_norm), 1.0,
+             float(self.ema_decay) if ema_on else 0.0, int(bool(self.ema_warmup)) if ema_on else 0)
+        if g is None:
+            g = self._capture_step(c)
+            self._graph_seen.pop(key, None)
+        self._graph_put(key, g)                            # (re)inserted at the young end of the LRU order
+        graph, static, out = g[:3]
+        for name, dst in static.items():
+            src = c[name]
+            for d_, s_ in zip(dst, self._tensors_of(src)):
+                d_.copy_(s_)
+        graph.replay()
+        # the captured AdamW wrote the operand copy: vouch for it as step() does
+        self._copy_sig = self._param_sig() if eng.adamw_copy_target() is not None else None
+        return out
+
+    def _seed_rank(self):
+        eng = self.engine
+        if eng.seed_rank is None:
+            eng.seed_rank = dist.get_rank() if (dist.is_available() and dist.is_initialized()) else 0
+        return eng.seed_rank
+
+    @staticmethod
+    def _tensors_of(x):
+        """The tensors of one step input, in a fixed order: a tensor itself, the fields of SoftTargets that are present."""
+        if _is_soft(x):
+            return [t for t in (x.ids, x.weights, x.counts) if t is not None]
+        return [x]
+
+    def _capture_step(self, c):
+        """Capture _enqueue on static copies of the inputs; returns (graph, {input name: static tensors}, (loss, logits), held,
+        generation of the engine's packed operands)."""
+        static, cc = {}, dict(c)
+        for name in ("images", "token_ids", "maskf", "kv_index", "targets"):
+            if c[name] is None:
+                continue
+            copies = [t.detach().clone() for t in self._tensors_of(c[name])]
+            static[name] = copies
+            if _is_soft(c[name]):
+                it = iter(copies)
+                cc[name] = type(c[name])(*(None if f is None else next(it) for f in (c[name].ids, c[name].weights, c[name].counts)))
+            else:
+                cc[name] = copies[0]
+        sig = self._copy_sig
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out = self._enqueue(cc, state=self._state)
+        self._copy_sig = sig                               # (nothing ran yet: the replay below sets it)
+        eng = self.engine                                  # per-step operands the capture left behind live in the graph's pool: an
+        eng._wt, eng._accbuf = {}, None                    # eager step must not pick them up (begin_step / _acc rebuild their own)
+        self.graph_captures += 1
+        # held: the static inputs' owners, the tracker whose counters the graph writes, the range table it reads
+        return graph, static, out, (cc, c["metrics"], self._ranges), self.engine._wt_gen
+
+    def _graph_put(self, key, g):
+        cap = max(1, int(self.model.graph_max_shapes))
+        if len(self._graphs) >= cap:
+            torch.cuda.synchronize()                       # an evicted graph's private pool must outlive its last replay in flight
+            while len(self._graphs) >= cap:
+                self._graphs.pop(next(iter(self._graphs)))
+        self._graphs[key] = g
 
     def _device_index(self, image_index, U, N, dev):
         """int32 [N] device copy of a checked image index (VQAModel._image_index rules; None -> the implied index)."""
