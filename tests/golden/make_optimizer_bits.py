@@ -1,0 +1,48 @@
+"""Record tests/golden/optimizer_bits.json: SHA-256 of every output buffer of the optimizer-tail entries (vqa_sumsq*, vqa_adamw,
+vqa_adamw_ema, vqa_adamw_ranges, vqa_adamw_ranges_ema, vqa_ema_update, vqa_step_state_set) over the cases of tests/_optbits.py.
+
+Run on an MI355X with the library whose bits are to be pinned -- for a refactor, the PARENT commit's build (the C ABI is unchanged, so
+it loads through the binding's LIB_PATH, as in tools/ab_lib.py):
+
+    python tests/golden/make_optimizer_bits.py [--lib tools/_build/libvqa_hip_parent.so] [--out tests/golden/optimizer_bits.json]
+
+Every case runs twice on fresh inputs; a digest that differs between the two passes refuses the recording.  Stored with the digests:
+the `hipcc --version` line and the device name of the recording.  tests/test_gpu_optimizer_bits.py recomputes the digests with the
+product library and compares every one."""
+import argparse
+import json
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))                          # tests/: _pkg, _optbits
+
+import torch  # noqa: E402
+
+import _optbits as OB  # noqa: E402
+from _pkg import sub  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lib", default=None, help="another build of libvqa_hip.so (default: the product library)")
+    ap.add_argument("--out", default=os.path.join(HERE, "optimizer_bits.json"))
+    a = ap.parse_args()
+    L = sub("_lib")
+    if a.lib:
+        L.LIB_PATH, L._lib = os.path.abspath(a.lib), None
+    first = {k: fn() for k, fn in OB.cases().items()}
+    second = {k: fn() for k, fn in OB.cases().items()}
+    bad = [k for k in first if first[k] != second[k]]
+    if bad:
+        sys.exit("not reproducible, nothing written: " + ", ".join(bad))
+    rec = {"library": os.path.basename(L.LIB_PATH) if a.lib else "product", "hipcc": OB.toolchain(),
+           "device": torch.cuda.get_device_name(0), "cases": first}
+    with open(a.out, "w") as f:
+        json.dump(rec, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(f"{a.out}: {len(first)} cases, {sum(len(v) for v in first.values())} digests")
+
+
+if __name__ == "__main__":
+    main()

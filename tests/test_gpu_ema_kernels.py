@@ -1,5 +1,5 @@
 """GPU: the weight average inside the optimizer launches (vqa_adamw_ema, vqa_adamw_ranges_ema) and alone (vqa_ema_update),
-csrc/token_ops.hip.
+csrc/optim_ops.hip.
 
 Per case: the parameters, both moments and the bf16 operand copy are BIT-equal to what vqa_adamw / vqa_adamw_ranges give on a twin state
 (adding the average must not reorder or contract the optimizer arithmetic); the average follows the float64 reference (tests/_emaref.py)

@@ -1,4 +1,4 @@
-"""GPU: the frozen-parameter optimizer tail (vqa_sumsq_ranges + vqa_adamw_ranges, csrc/token_ops.hip) against float64.
+"""GPU: the frozen-parameter optimizer tail (vqa_sumsq_ranges + vqa_adamw_ranges, csrc/optim_ops.hip) against float64.
 
 The two entries run clip_grad_norm_ + AdamW over a table of trainable ranges {lo, hi, pos, lag index} of a flat buffer
 (finetune.range_table_rows builds it).  Checked here, per table shape: elements outside every range are never read (the gradient is NaN

@@ -1,6 +1,6 @@
 """The weight average (EMA) of the fused step, measured (bf16, default configuration, B = 512, HipTrainer):
 
-    python tools/bench_ema.py [--out profiles/ema_bench.json] [--reps 5] [--steps 10]
+    python tools/bench_ema.py [--out profiles/ema_bench.json] [--reps 5] [--steps 10] [--lib PATH] [--kernels-only]
 
 Train steps of six set-ups, each on its own trainer, warmed up, then timed alternately in one process with device events around
 `--steps` back-to-back steps (reps alternations, median per step):
@@ -12,7 +12,8 @@ Train steps of six set-ups, each on its own trainer, warmed up, then timed alter
 Then the kernels alone over flat buffers of the model's size, alternated the same way over `--kernel-iters` back-to-back launches:
 vqa_adamw, vqa_adamw_ema, vqa_adamw_ranges, vqa_adamw_ranges_ema (one range over the whole buffer), vqa_ema_update,
 torch._foreach_lerp_ over the 164 views and Tensor.lerp_ over the flat buffer, with the bytes each moves by the byte model of
-kernels.HBM_BYTES (the torch ops: 12 B per element) and the rate that follows from the measured time."""
+kernels.HBM_BYTES (the torch ops: 12 B per element) and the rate that follows from the measured time.
+--lib PATH measures another build of libvqa_hip.so (the binding's LIB_PATH, as tools/ab_lib.py); --kernels-only leaves the train steps out."""
 import argparse
 import importlib
 import json
@@ -116,10 +117,18 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--kernel-iters", type=int, default=50)
+    ap.add_argument("--lib", default=None)
+    ap.add_argument("--kernels-only", action="store_true")
     a = ap.parse_args()
+    if a.lib:
+        pkg._lib.LIB_PATH, pkg._lib._lib = os.path.abspath(a.lib), None
+    res = {"batch": B, "dtype": "bf16", "ema_decay": DECAY, "steps_per_rep": a.steps, "reps": a.reps, "device": torch.cuda.get_device_name(0),
+           "library": os.path.basename(pkg._lib.LIB_PATH)}
+    if a.kernels_only:
+        res["flat_elements"], res["kernel_us"] = kernels_alone(make_model(False), a.reps, a.kernel_iters)
+        return report(res, a.out)
     images, ids, mask, answers = (t.to(DEV) for t in O.synthetic_batch(B, seed=7))
     mask[:, 0] = 1
-    res = {"batch": B, "dtype": "bf16", "ema_decay": DECAY, "steps_per_rep": a.steps, "reps": a.reps, "device": torch.cuda.get_device_name(0)}
 
     models = {k: make_model(k.startswith("frozen")) for k in SETUPS}
     trainers = {k: pkg.trainer.HipTrainer(models[k], ema_decay=DECAY if k.endswith("ema") else None) for k in SETUPS}
@@ -146,11 +155,16 @@ def main():
     torch.cuda.empty_cache()
 
     res["flat_elements"], res["kernel_us"] = kernels_alone(m, a.reps, a.kernel_iters)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
+    report(res, a.out)
+
+
+def report(res, out):
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
         json.dump(res, f, indent=1)
     short = lambda d: {k: [round(v["median"], 4), round(v["min"], 4), round(v["max"], 4)] for k, v in d.items()}
-    print("train_step_ms [median, min, max]", json.dumps(short(res["train_step_ms"])))
+    if "train_step_ms" in res:
+        print("train_step_ms [median, min, max]", json.dumps(short(res["train_step_ms"])))
     print("kernel_us [median, min, max]", json.dumps(short(res["kernel_us"])))
     print("kernel GB/s by the byte model", json.dumps({k: round(v["model_bytes_over_median_GBps"], 1) for k, v in res["kernel_us"].items()}))
 

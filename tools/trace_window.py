@@ -13,7 +13,7 @@ for r in rows:
         wgs *= max(1, int(r["Grid_Size_" + ax]) // max(1, int(r["Workgroup_Size_" + ax])))
     K.append((s, e, r["Kernel_Name"], wgs))
 K.sort()
-ad = [i for i, k in enumerate(K) if k[2].startswith("adamw_kernel")]
+ad = [i for i, k in enumerate(K) if "adamw_kernel" in k[2]]
 step = K[ad[-4] + 1: ad[-3] + 1]
 t0 = step[0][0]
 print(f"step span {(step[-1][1] - t0) / 1e3:.1f} us, {len(step)} kernels")

@@ -1,11 +1,11 @@
 // Token-side kernels for gfx950: embedding+positional encoding, LayerNorm, multi-head attention
 // (self: keys masked with -inf, cross: unmasked), masked mean-pool, sigmoid gate, bias/ReLU/dropout
-// backward, cross-entropy, and the fused optimizer tail (global L2 norm, clip, AdamW).
+// backward, the losses, the metrics and the dtype casts.  (The optimizer tail -- L2 norm, clip, AdamW, weight EMA -- is optim_ops.hip.)
 //   embedding*sqrt(d)+pe      models/text_encoder.py:504-510, :112-114
 //   LayerNorm                 models/text_encoder.py:390,395,519 ; cross_attention.py:286-287,295 ; fusion.py:326
 //   attention                 models/text_encoder.py:237-258 ; models/cross_attention.py:176-198
 //   masked mean / gate        models/fusion.py:303-320, :160-166
-//   CE / clip / AdamW         training/train.py:120, :204-208, :127-132
+//   CE                        training/train.py:120
 // Rows are tokens ([B*L][D], D contiguous).  One 64-lane wave owns one row / one (batch, head).
 #include <cstdlib>
 #include "common.h"
@@ -773,385 +773,6 @@ __global__ void convert_kernel(const TI* __restrict__ in, TO* __restrict__ out, 
 }
 
 // ---------------------------------------------------------------------------------------------
-// optimizer tail over flat fp32 buffers
-// ---------------------------------------------------------------------------------------------
-// Deterministic two-stage sum of squares (replicas must compute bit-identical clip factors): per-block partials in a fixed
-// slot each, then one block folds them in a fixed order.  out[0] = result, out[1 .. 1+blocks) = partials.
-__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, size_t n, float* out) {
-  float s = 0.f;
-  const size_t nv = n / 4;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (size_t)gridDim.x * blockDim.x) {
-    const float4 v = reinterpret_cast<const float4*>(g)[i];
-    s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-  }
-  if (blockIdx.x == 0) for (size_t i = nv * 4 + threadIdx.x; i < n; i += blockDim.x) s += g[i] * g[i];
-  __shared__ float sh[4];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) out[1 + blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-__global__ __launch_bounds__(256) void sumsq_final_kernel(float* out, int nparts) {
-  float s = 0.f;
-  for (int i = threadIdx.x; i < nparts; i += 256) s += out[1 + i];
-  __shared__ float sh[4];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) out[0] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-// clip_grad_norm_(max_norm) + AdamW (decoupled weight decay), torch semantics (training/train.py:204-208,127-132)
-// The by-value hyper-parameters of one AdamW launch, in one struct: the by-value kernels fill it from their arguments, the _dev kernels
-// from the device step-state block (vqa_step_state, written by vqa_step_state_set right before a captured step is replayed).  Both then
-// run the SAME __device__ body below, which copies the fields into locals first: same statements, same order, same bits.
-struct AdamHyper { float lr, b1, b2, eps, wd; long long calls; float max_norm, gscale, ema_decay; int ema_warmup; };
-__device__ __forceinline__ AdamHyper adam_hyper_of(const vqa_step_state* __restrict__ st) {
-  AdamHyper h;
-  h.lr = st->lr; h.b1 = st->b1; h.b2 = st->b2; h.eps = st->eps; h.wd = st->wd; h.calls = st->calls;
-  h.max_norm = st->max_norm; h.gscale = st->gscale; h.ema_decay = st->ema_decay; h.ema_warmup = st->ema_warmup;
-  return h;
-}
-__device__ __forceinline__ void adamw_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n,
-                                           const AdamHyper& hy, const float* __restrict__ sumsq, const int* __restrict__ skip,
-                                           int* __restrict__ skipped, bf16_t* __restrict__ p_bf16) {
-  const float lr = hy.lr, b1 = hy.b1, b2 = hy.b2, eps = hy.eps, wd = hy.wd, max_norm = hy.max_norm, gscale = hy.gscale;
-  const long long calls = hy.calls;
-  // p_bf16 != nullptr: the bf16 working copy of the parameters (what the next forward's GEMMs read) is written here as well -- the
-  // separate cast launch over the flat buffer (116 MB of traffic, 34 us at the head of every step) is gone.  A skipped launch leaves
-  // both the parameters and the copy as they were.
-  // skip[0] != 0 (rows with an out-of-range target in THIS step, summed over ranks): the reference raises before
-  // optimizer.step() (nn.CrossEntropyLoss, training/train.py:120,182-208) and leaves the model intact -- so does this kernel:
-  // parameters and both moments stay untouched; skipped[0] += rows, skipped[1] += 1 (read by the host at its logging interval),
-  // skipped[2] += 1 (never reset: the device-side record of how many launches did NOT count as an optimizer step).
-  if (skip && *skip != 0) {
-    if (skipped && blockIdx.x == 0 && threadIdx.x == 0) { skipped[0] += *skip; skipped[1] += 1; skipped[2] += 1; }
-    return;
-  }
-  // Adam's step number lives on the DEVICE: calls (the host's launch count, this one included) minus the launches skipped so far.
-  // skipped[2] is only written by a launch that skips, and such a launch reads it nowhere else: no race.  (Round 3 derived the bias
-  // corrections from a host counter that was repaired only at the caller's next check(): every step in between ran one step ahead.)
-  const long long t = calls - (skipped ? (long long)skipped[2] : 0ll);
-  const float bc1 = (float)(1.0 - pow((double)b1, (double)t)), bc2 = (float)(1.0 - pow((double)b2, (double)t));
-  float coef = gscale;
-  if (sumsq && max_norm > 0.f) {
-    const float norm = sqrtf(*sumsq) * gscale;
-    const float c = max_norm / (norm + 1e-6f);
-    if (c < 1.f) coef *= c;
-  }
-  const float step = lr / bc1, rbc2 = 1.f / sqrtf(bc2);
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float gr = g[i] * coef;
-    float pi = p[i] * (1.f - lr * wd);
-    const float mi = b1 * m[i] + (1.f - b1) * gr;
-    const float vi = b2 * v[i] + (1.f - b2) * gr * gr;
-    m[i] = mi; v[i] = vi;
-    pi -= step * mi / (sqrtf(vi) * rbc2 + eps);
-    p[i] = pi;
-    if (p_bf16) p_bf16[i] = f2bf(pi);
-  }
-}
-__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n,
-                             float lr, float b1, float b2, float eps, float wd, long long calls, const float* __restrict__ sumsq,
-                             float max_norm, float gscale, const int* __restrict__ skip, int* __restrict__ skipped, bf16_t* __restrict__ p_bf16) {
-  const AdamHyper hy{lr, b1, b2, eps, wd, calls, max_norm, gscale, 0.f, 0};
-  adamw_body(p, g, m, v, n, hy, sumsq, skip, skipped, p_bf16);
-}
-__global__ void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n,
-                                 const vqa_step_state* __restrict__ state, const float* __restrict__ sumsq, const int* __restrict__ skip,
-                                 int* __restrict__ skipped, bf16_t* __restrict__ p_bf16) {
-  const AdamHyper hy = adam_hyper_of(state);
-  adamw_body(p, g, m, v, n, hy, sumsq, skip, skipped, p_bf16);
-}
-
-// The same two kernels over a table of TRAINABLE ranges (fine-tuning with frozen parameters, trainer.py): elements outside every
-// range are never read or written.  table: int64 rows {lo, hi, pos, lag index} -- [lo, hi) of the flat buffer, pos = where the range
-// starts in the concatenation of all ranges (ascending); lo, hi, pos multiples of 4 (the layout's 8-element slots), so every float4
-// lies inside one range.  Threads stride over that concatenation: the grid is sized to the trainable count, not to the buffer.
-#define VQA_RANGES_MAX 512
-__device__ __forceinline__ int range_of(const long long* __restrict__ pos, int R, long long e) {
-  int lo = 0, hi = R - 1;                   // the last range whose pos <= e
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (pos[mid] <= e) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-__global__ __launch_bounds__(256) void sumsq_ranges_kernel(const float* __restrict__ g, const long long* __restrict__ table, int R, long long n,
-                                                           float* out) {
-  __shared__ long long s_lo[VQA_RANGES_MAX], s_pos[VQA_RANGES_MAX];
-  for (int r = threadIdx.x; r < R; r += blockDim.x) { s_lo[r] = table[4 * r]; s_pos[r] = table[4 * r + 2]; }
-  __syncthreads();
-  float s = 0.f;
-  const long long nv = n / 4;
-  for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nv; q += (long long)gridDim.x * blockDim.x) {
-    const long long e = 4 * q;
-    const int r = range_of(s_pos, R, e);
-    const float4 v = *reinterpret_cast<const float4*>(g + s_lo[r] + (e - s_pos[r]));
-    s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
-  }
-  __shared__ float sh[4];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) out[1 + blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-// clip + AdamW of adamw_kernel, per range: Adam's step number of range r is calls - skipped[2] - lag[table[r].lag index], where lag[j]
-// counts the applied steps during which parameter j was frozen (torch.optim.AdamW advances a parameter's `step` only when it has a
-// gradient).  Every parameter inside one range shares its lag (the caller merges only such neighbours).
-__device__ __forceinline__ void adamw_ranges_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                  float* __restrict__ v, const long long* __restrict__ table, int R, long long n,
-                                                  const AdamHyper& hy, const float* __restrict__ sumsq,
-                                                  const int* __restrict__ skip, int* __restrict__ skipped, const int* __restrict__ lag,
-                                                  bf16_t* __restrict__ p_bf16) {
-  const float lr = hy.lr, b1 = hy.b1, b2 = hy.b2, eps = hy.eps, wd = hy.wd, max_norm = hy.max_norm, gscale = hy.gscale;
-  const long long calls = hy.calls;
-  if (skip && *skip != 0) {
-    if (skipped && blockIdx.x == 0 && threadIdx.x == 0) { skipped[0] += *skip; skipped[1] += 1; skipped[2] += 1; }
-    return;
-  }
-  __shared__ long long s_lo[VQA_RANGES_MAX], s_pos[VQA_RANGES_MAX];
-  __shared__ float s_step[VQA_RANGES_MAX], s_rbc2[VQA_RANGES_MAX];
-  const long long t0 = calls - (skipped ? (long long)skipped[2] : 0ll);
-  for (int r = threadIdx.x; r < R; r += blockDim.x) {
-    s_lo[r] = table[4 * r]; s_pos[r] = table[4 * r + 2];
-    const long long t = t0 - (lag ? (long long)lag[table[4 * r + 3]] : 0ll);
-    const float bc1 = (float)(1.0 - pow((double)b1, (double)t)), bc2 = (float)(1.0 - pow((double)b2, (double)t));
-    s_step[r] = lr / bc1; s_rbc2[r] = 1.f / sqrtf(bc2);
-  }
-  __syncthreads();
-  float coef = gscale;
-  if (sumsq && max_norm > 0.f) {
-    const float norm = sqrtf(*sumsq) * gscale;
-    const float c = max_norm / (norm + 1e-6f);
-    if (c < 1.f) coef *= c;
-  }
-  const long long nv = n / 4;
-  for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nv; q += (long long)gridDim.x * blockDim.x) {
-    const long long e = 4 * q;
-    const int r = range_of(s_pos, R, e);
-    const long long i = s_lo[r] + (e - s_pos[r]);
-    const float step = s_step[r], rbc2 = s_rbc2[r];
-    const float4 g4 = *reinterpret_cast<const float4*>(g + i);
-    float4 p4 = *reinterpret_cast<const float4*>(p + i);
-    float4 m4 = *reinterpret_cast<const float4*>(m + i);
-    float4 v4 = *reinterpret_cast<const float4*>(v + i);
-    float* pp = &p4.x; float* mm = &m4.x; float* vv = &v4.x; const float* gg = &g4.x;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float gr = gg[k] * coef;
-      float pi = pp[k] * (1.f - lr * wd);
-      const float mi = b1 * mm[k] + (1.f - b1) * gr;
-      const float vi = b2 * vv[k] + (1.f - b2) * gr * gr;
-      mm[k] = mi; vv[k] = vi;
-      pi -= step * mi / (sqrtf(vi) * rbc2 + eps);
-      pp[k] = pi;
-    }
-    *reinterpret_cast<float4*>(p + i) = p4;
-    *reinterpret_cast<float4*>(m + i) = m4;
-    *reinterpret_cast<float4*>(v + i) = v4;
-    if (p_bf16) {
-      uint2 w;
-      w.x = (uint32_t)f2bf(p4.x) | ((uint32_t)f2bf(p4.y) << 16);
-      w.y = (uint32_t)f2bf(p4.z) | ((uint32_t)f2bf(p4.w) << 16);
-      *reinterpret_cast<uint2*>(p_bf16 + i) = w;
-    }
-  }
-}
-__global__ __launch_bounds__(256) void adamw_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                           float* __restrict__ v, const long long* __restrict__ table, int R, long long n,
-                                                           float lr, float b1, float b2, float eps, float wd, long long calls,
-                                                           const float* __restrict__ sumsq, float max_norm, float gscale,
-                                                           const int* __restrict__ skip, int* __restrict__ skipped, const int* __restrict__ lag,
-                                                           bf16_t* __restrict__ p_bf16) {
-  const AdamHyper hy{lr, b1, b2, eps, wd, calls, max_norm, gscale, 0.f, 0};
-  adamw_ranges_body(p, g, m, v, table, R, n, hy, sumsq, skip, skipped, lag, p_bf16);
-}
-__global__ __launch_bounds__(256) void adamw_ranges_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                               float* __restrict__ v, const long long* __restrict__ table, int R, long long n,
-                                                               const vqa_step_state* __restrict__ state, const float* __restrict__ sumsq,
-                                                               const int* __restrict__ skip, int* __restrict__ skipped,
-                                                               const int* __restrict__ lag, bf16_t* __restrict__ p_bf16) {
-  const AdamHyper hy = adam_hyper_of(state);
-  adamw_ranges_body(p, g, m, v, table, R, n, hy, sumsq, skip, skipped, lag, p_bf16);
-}
-// after an applied step: lag[frozen[k]] += 1 (one thread per frozen parameter; runs behind adamw_ranges_kernel on the same stream)
-__global__ void adamw_lag_kernel(int* __restrict__ lag, const int* __restrict__ frozen, int nf, const int* __restrict__ skip) {
-  if (skip && *skip != 0) return;
-  for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < nf; k += gridDim.x * blockDim.x) lag[frozen[k]] += 1;
-}
-
-// Exponential moving average of the weights: ema = d * ema + (1 - d) * p_new, fp32.  ONE expression for the fused AdamW variants and
-// the stand-alone pass (the same p_new and ema give the same bits whichever launch computes them): 1 - d and its product with p are
-// each rounded once, the sum is one fma; contraction is off so that no surrounding code can change that.
-__device__ __forceinline__ float ema_blend(float e, float p, float d) {
-#pragma clang fp contract(off)
-  const float q = (1.f - d) * p;
-  return __builtin_fmaf(d, e, q);
-}
-// decay of the update at Adam step t: the caller's decay, or with warm-up min(decay, (1 + t) / (10 + t)) -- 2/11 at the first
-// applied step, within 1 % of 0.999 from t = 8981 on: the average forgets the initial weights quickly and settles at the decay
-__device__ __forceinline__ float ema_decay_at(float decay, int warmup, long long t) {
-  if (!warmup) return decay;
-  return fminf(decay, (float)(1 + t) / (float)(10 + t));
-}
-// adamw_kernel (same statements, same order: p, m, v and the bf16 copy get the bits adamw_kernel gives them) + the average of the
-// updated parameter, taken from the register that still holds it: 8 B per element on top of the 28 B, no second read of p.
-// A skipped launch returns before `ema` is touched; t does not advance then, so neither does the warm-up.
-__device__ __forceinline__ void adamw_ema_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                               size_t n, const AdamHyper& hy, const float* __restrict__ sumsq, const int* __restrict__ skip,
-                                               int* __restrict__ skipped, bf16_t* __restrict__ p_bf16, float* __restrict__ ema) {
-  const float lr = hy.lr, b1 = hy.b1, b2 = hy.b2, eps = hy.eps, wd = hy.wd, max_norm = hy.max_norm, gscale = hy.gscale;
-  const long long calls = hy.calls;
-  const float ema_decay = hy.ema_decay;
-  const int ema_warmup = hy.ema_warmup;
-  if (skip && *skip != 0) {
-    if (skipped && blockIdx.x == 0 && threadIdx.x == 0) { skipped[0] += *skip; skipped[1] += 1; skipped[2] += 1; }
-    return;
-  }
-  const long long t = calls - (skipped ? (long long)skipped[2] : 0ll);
-  const float bc1 = (float)(1.0 - pow((double)b1, (double)t)), bc2 = (float)(1.0 - pow((double)b2, (double)t));
-  float coef = gscale;
-  if (sumsq && max_norm > 0.f) {
-    const float norm = sqrtf(*sumsq) * gscale;
-    const float c = max_norm / (norm + 1e-6f);
-    if (c < 1.f) coef *= c;
-  }
-  const float step = lr / bc1, rbc2 = 1.f / sqrtf(bc2);
-  const float d = ema_decay_at(ema_decay, ema_warmup, t);
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float gr = g[i] * coef;
-    float pi = p[i] * (1.f - lr * wd);
-    const float mi = b1 * m[i] + (1.f - b1) * gr;
-    const float vi = b2 * v[i] + (1.f - b2) * gr * gr;
-    m[i] = mi; v[i] = vi;
-    pi -= step * mi / (sqrtf(vi) * rbc2 + eps);
-    p[i] = pi;
-    if (p_bf16) p_bf16[i] = f2bf(pi);
-    ema[i] = ema_blend(ema[i], pi, d);
-  }
-}
-__global__ void adamw_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n,
-                                 float lr, float b1, float b2, float eps, float wd, long long calls, const float* __restrict__ sumsq,
-                                 float max_norm, float gscale, const int* __restrict__ skip, int* __restrict__ skipped, bf16_t* __restrict__ p_bf16,
-                                 float* __restrict__ ema, float ema_decay, int ema_warmup) {
-  const AdamHyper hy{lr, b1, b2, eps, wd, calls, max_norm, gscale, ema_decay, ema_warmup};
-  adamw_ema_body(p, g, m, v, n, hy, sumsq, skip, skipped, p_bf16, ema);
-}
-__global__ void adamw_ema_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n,
-                                     const vqa_step_state* __restrict__ state, const float* __restrict__ sumsq, const int* __restrict__ skip,
-                                     int* __restrict__ skipped, bf16_t* __restrict__ p_bf16, float* __restrict__ ema) {
-  const AdamHyper hy = adam_hyper_of(state);
-  adamw_ema_body(p, g, m, v, n, hy, sumsq, skip, skipped, p_bf16, ema);
-}
-// adamw_ranges_kernel + the average, over the same table: `ema` is neither read nor written outside the trainable ranges, and the
-// warm-up of range r runs on that range's OWN Adam step number t0 - lag[...] (a parameter's average advances only while it trains).
-__device__ __forceinline__ void adamw_ranges_ema_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                      float* __restrict__ v, const long long* __restrict__ table, int R, long long n,
-                                                      const AdamHyper& hy, const float* __restrict__ sumsq,
-                                                      const int* __restrict__ skip, int* __restrict__ skipped, const int* __restrict__ lag,
-                                                      bf16_t* __restrict__ p_bf16, float* __restrict__ ema) {
-  const float lr = hy.lr, b1 = hy.b1, b2 = hy.b2, eps = hy.eps, wd = hy.wd, max_norm = hy.max_norm, gscale = hy.gscale;
-  const long long calls = hy.calls;
-  const float ema_decay = hy.ema_decay;
-  const int ema_warmup = hy.ema_warmup;
-  if (skip && *skip != 0) {
-    if (skipped && blockIdx.x == 0 && threadIdx.x == 0) { skipped[0] += *skip; skipped[1] += 1; skipped[2] += 1; }
-    return;
-  }
-  __shared__ long long s_lo[VQA_RANGES_MAX], s_pos[VQA_RANGES_MAX];
-  __shared__ float s_step[VQA_RANGES_MAX], s_rbc2[VQA_RANGES_MAX], s_d[VQA_RANGES_MAX];
-  const long long t0 = calls - (skipped ? (long long)skipped[2] : 0ll);
-  for (int r = threadIdx.x; r < R; r += blockDim.x) {
-    s_lo[r] = table[4 * r]; s_pos[r] = table[4 * r + 2];
-    const long long t = t0 - (lag ? (long long)lag[table[4 * r + 3]] : 0ll);
-    const float bc1 = (float)(1.0 - pow((double)b1, (double)t)), bc2 = (float)(1.0 - pow((double)b2, (double)t));
-    s_step[r] = lr / bc1; s_rbc2[r] = 1.f / sqrtf(bc2);
-    s_d[r] = ema_decay_at(ema_decay, ema_warmup, t);
-  }
-  __syncthreads();
-  float coef = gscale;
-  if (sumsq && max_norm > 0.f) {
-    const float norm = sqrtf(*sumsq) * gscale;
-    const float c = max_norm / (norm + 1e-6f);
-    if (c < 1.f) coef *= c;
-  }
-  const long long nv = n / 4;
-  for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nv; q += (long long)gridDim.x * blockDim.x) {
-    const long long e = 4 * q;
-    const int r = range_of(s_pos, R, e);
-    const long long i = s_lo[r] + (e - s_pos[r]);
-    const float step = s_step[r], rbc2 = s_rbc2[r], d = s_d[r];
-    const float4 g4 = *reinterpret_cast<const float4*>(g + i);
-    float4 p4 = *reinterpret_cast<const float4*>(p + i);
-    float4 m4 = *reinterpret_cast<const float4*>(m + i);
-    float4 v4 = *reinterpret_cast<const float4*>(v + i);
-    float4 e4 = *reinterpret_cast<const float4*>(ema + i);
-    float* pp = &p4.x; float* mm = &m4.x; float* vv = &v4.x; const float* gg = &g4.x; float* ee = &e4.x;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const float gr = gg[k] * coef;
-      float pi = pp[k] * (1.f - lr * wd);
-      const float mi = b1 * mm[k] + (1.f - b1) * gr;
-      const float vi = b2 * vv[k] + (1.f - b2) * gr * gr;
-      mm[k] = mi; vv[k] = vi;
-      pi -= step * mi / (sqrtf(vi) * rbc2 + eps);
-      pp[k] = pi;
-      ee[k] = ema_blend(ee[k], pi, d);
-    }
-    *reinterpret_cast<float4*>(p + i) = p4;
-    *reinterpret_cast<float4*>(m + i) = m4;
-    *reinterpret_cast<float4*>(v + i) = v4;
-    *reinterpret_cast<float4*>(ema + i) = e4;
-    if (p_bf16) {
-      uint2 w;
-      w.x = (uint32_t)f2bf(p4.x) | ((uint32_t)f2bf(p4.y) << 16);
-      w.y = (uint32_t)f2bf(p4.z) | ((uint32_t)f2bf(p4.w) << 16);
-      *reinterpret_cast<uint2*>(p_bf16 + i) = w;
-    }
-  }
-}
-__global__ __launch_bounds__(256) void adamw_ranges_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                               float* __restrict__ v, const long long* __restrict__ table, int R, long long n,
-                                                               float lr, float b1, float b2, float eps, float wd, long long calls,
-                                                               const float* __restrict__ sumsq, float max_norm, float gscale,
-                                                               const int* __restrict__ skip, int* __restrict__ skipped, const int* __restrict__ lag,
-                                                               bf16_t* __restrict__ p_bf16, float* __restrict__ ema, float ema_decay, int ema_warmup) {
-  const AdamHyper hy{lr, b1, b2, eps, wd, calls, max_norm, gscale, ema_decay, ema_warmup};
-  adamw_ranges_ema_body(p, g, m, v, table, R, n, hy, sumsq, skip, skipped, lag, p_bf16, ema);
-}
-__global__ __launch_bounds__(256) void adamw_ranges_ema_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                                   float* __restrict__ v, const long long* __restrict__ table, int R, long long n,
-                                                                   const vqa_step_state* __restrict__ state, const float* __restrict__ sumsq,
-                                                                   const int* __restrict__ skip, int* __restrict__ skipped,
-                                                                   const int* __restrict__ lag, bf16_t* __restrict__ p_bf16,
-                                                                   float* __restrict__ ema) {
-  const AdamHyper hy = adam_hyper_of(state);
-  adamw_ranges_ema_body(p, g, m, v, table, R, n, hy, sumsq, skip, skipped, lag, p_bf16, ema);
-}
-// One thread writes the step-state block (plain stores): launched eagerly on the stream right before a captured step is replayed; the
-// values travel as kernel arguments, which the runtime copies at launch.
-__global__ void step_state_set_kernel(vqa_step_state* state, long long calls, unsigned long long seed_step, float lr, float b1, float b2,
-                                      float eps, float wd, float max_norm, float gscale, float ema_decay, int ema_warmup) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    state->calls = calls; state->seed_step = seed_step;
-    state->lr = lr; state->b1 = b1; state->b2 = b2; state->eps = eps; state->wd = wd;
-    state->max_norm = max_norm; state->gscale = gscale; state->ema_decay = ema_decay; state->ema_warmup = ema_warmup;
-  }
-}
-// The update as a pass of its own over a flat buffer (torch.optim loops: dropin/utils/ema.py): 12 B per element.  nv float4 groups
-// (0 when a pointer is not 16-byte aligned), then the scalar rest.
-__global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ p, long long n, long long nv, float d) {
-  const long long stride = (long long)gridDim.x * blockDim.x, i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  for (long long q = i0; q < nv; q += stride) {
-    const float4 p4 = reinterpret_cast<const float4*>(p)[q];
-    float4 e4 = reinterpret_cast<float4*>(ema)[q];
-    e4.x = ema_blend(e4.x, p4.x, d); e4.y = ema_blend(e4.y, p4.y, d); e4.z = ema_blend(e4.z, p4.z, d); e4.w = ema_blend(e4.w, p4.w, d);
-    reinterpret_cast<float4*>(ema)[q] = e4;
-  }
-  for (long long i = 4 * nv + i0; i < n; i += stride) ema[i] = ema_blend(ema[i], p[i], d);
-}
-
-// ---------------------------------------------------------------------------------------------
 #define DT(call_f, call_b) do { if (dtype) { call_b; } else { call_f; } } while (0)
 static inline unsigned g1(size_t n) { return (unsigned)((n + 255) / 256); }
 
@@ -1438,113 +1059,6 @@ int vqa_convert(int dtype_in, int dtype_out, const void* in, void* out, long lon
   else if (dtype_in && !dtype_out) hipLaunchKernelGGL((convert_kernel<bf16_t, float>), dim3(g), dim3(256), 0, st, (const bf16_t*)in, (float*)out, (size_t)n);
   else if (!dtype_in) hipLaunchKernelGGL((convert_kernel<float, float>), dim3(g), dim3(256), 0, st, (const float*)in, (float*)out, (size_t)n);
   else hipLaunchKernelGGL((convert_kernel<bf16_t, bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)in, (bf16_t*)out, (size_t)n);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-int vqa_sumsq(const float* g, long long n, float* out, hipStream_t st) {
-  size_t blocks = ((size_t)n / 4 + 255) / 256; if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(sumsq_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g, (size_t)n, out);
-  hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, st, out, (int)blocks);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-int vqa_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float wd,
-              long long calls, const float* sumsq, float max_norm, float gscale, const int* skip, int* skipped, void* p_bf16, hipStream_t st) {
-  if (calls < 1) return VQA_EARG;
-  size_t blocks = ((size_t)n + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, (size_t)n, lr, b1, b2, eps, wd, calls, sumsq, max_norm, gscale,
-                     skip, skipped, (bf16_t*)p_bf16);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-
-int vqa_sumsq_ranges(const float* g, const long long* table, int R, long long n, float* out, hipStream_t st) {
-  if (R < 0 || R > VQA_RANGES_MAX || n < 0 || n % 4 || (R == 0 && n != 0)) return VQA_EARG;
-  size_t blocks = ((size_t)n / 4 + 255) / 256; if (blocks > 2048) blocks = 2048; if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(sumsq_ranges_kernel, dim3((unsigned)blocks), dim3(256), 0, st, g, table, R, n, out);
-  hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, st, out, (int)blocks);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-int vqa_adamw_ranges(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n, float lr, float b1, float b2,
-                     float eps, float wd, long long calls, const float* sumsq, float max_norm, float gscale, const int* skip, int* skipped,
-                     int* lag, const int* frozen, int nf, void* p_bf16, hipStream_t st) {
-  if (calls < 1 || R < 0 || R > VQA_RANGES_MAX || n < 0 || n % 4 || (R == 0 && n != 0) || nf < 0 || (nf > 0 && (!lag || !frozen))) return VQA_EARG;
-  size_t blocks = ((size_t)n / 4 + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adamw_ranges_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, table, R, n, lr, b1, b2, eps, wd, calls, sumsq,
-                     max_norm, gscale, skip, skipped, (const int*)lag, (bf16_t*)p_bf16);
-  if (nf > 0) hipLaunchKernelGGL(adamw_lag_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, lag, frozen, nf, skip);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-
-// vqa_adamw / vqa_adamw_ranges + the weight average in the same launch (same grids); vqa_ema_update: the average alone.
-static inline bool ema_decay_ok(float d) { return d >= 0.f && d <= 1.f; }        // (NaN fails both comparisons)
-int vqa_adamw_ema(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2, float eps, float wd,
-                  long long calls, const float* sumsq, float max_norm, float gscale, const int* skip, int* skipped, void* p_bf16,
-                  float* ema, float ema_decay, int ema_warmup, hipStream_t st) {
-  if (calls < 1 || n < 0 || !ema || !ema_decay_ok(ema_decay)) return VQA_EARG;
-  size_t blocks = ((size_t)n + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adamw_ema_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, (size_t)n, lr, b1, b2, eps, wd, calls, sumsq, max_norm,
-                     gscale, skip, skipped, (bf16_t*)p_bf16, ema, ema_decay, ema_warmup);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-int vqa_adamw_ranges_ema(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n, float lr, float b1, float b2,
-                         float eps, float wd, long long calls, const float* sumsq, float max_norm, float gscale, const int* skip, int* skipped,
-                         int* lag, const int* frozen, int nf, void* p_bf16, float* ema, float ema_decay, int ema_warmup, hipStream_t st) {
-  if (calls < 1 || R < 0 || R > VQA_RANGES_MAX || n < 0 || n % 4 || (R == 0 && n != 0) || nf < 0 || (nf > 0 && (!lag || !frozen))) return VQA_EARG;
-  if (!ema || !ema_decay_ok(ema_decay)) return VQA_EARG;
-  size_t blocks = ((size_t)n / 4 + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adamw_ranges_ema_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, table, R, n, lr, b1, b2, eps, wd, calls, sumsq,
-                     max_norm, gscale, skip, skipped, (const int*)lag, (bf16_t*)p_bf16, ema, ema_decay, ema_warmup);
-  if (nf > 0) hipLaunchKernelGGL(adamw_lag_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, lag, frozen, nf, skip);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-// The four AdamW entries with their by-value hyper-parameters read from the device step-state block (same grids, same bodies).
-static inline bool state_ok(const void* state) { return state && !((uintptr_t)state & 15); }
-int vqa_step_state_set(vqa_step_state* state, long long calls, unsigned long long seed_step, float lr, float b1, float b2, float eps,
-                       float wd, float max_norm, float gscale, float ema_decay, int ema_warmup, hipStream_t st) {
-  if (!state_ok(state) || calls < 1 || (seed_step & (VQA_SEED_INDIRECT | 0xFFFull))) return VQA_EARG;
-  hipLaunchKernelGGL(step_state_set_kernel, dim3(1), dim3(1), 0, st, state, calls, seed_step, lr, b1, b2, eps, wd, max_norm, gscale, ema_decay,
-                     ema_warmup);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-int vqa_adamw_dev(float* p, const float* g, float* m, float* v, long long n, const vqa_step_state* state, const float* sumsq,
-                  const int* skip, int* skipped, void* p_bf16, hipStream_t st) {
-  if (!state_ok(state) || n < 0) return VQA_EARG;
-  size_t blocks = ((size_t)n + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adamw_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, (size_t)n, state, sumsq, skip, skipped, (bf16_t*)p_bf16);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-int vqa_adamw_ema_dev(float* p, const float* g, float* m, float* v, long long n, const vqa_step_state* state, const float* sumsq,
-                      const int* skip, int* skipped, void* p_bf16, float* ema, hipStream_t st) {
-  if (!state_ok(state) || n < 0 || !ema) return VQA_EARG;
-  size_t blocks = ((size_t)n + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adamw_ema_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, (size_t)n, state, sumsq, skip, skipped,
-                     (bf16_t*)p_bf16, ema);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-int vqa_adamw_ranges_dev(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n,
-                         const vqa_step_state* state, const float* sumsq, const int* skip, int* skipped, int* lag, const int* frozen, int nf,
-                         void* p_bf16, hipStream_t st) {
-  if (!state_ok(state) || R < 0 || R > VQA_RANGES_MAX || n < 0 || n % 4 || (R == 0 && n != 0) || nf < 0 || (nf > 0 && (!lag || !frozen))) return VQA_EARG;
-  size_t blocks = ((size_t)n / 4 + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adamw_ranges_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, table, R, n, state, sumsq, skip, skipped,
-                     (const int*)lag, (bf16_t*)p_bf16);
-  if (nf > 0) hipLaunchKernelGGL(adamw_lag_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, lag, frozen, nf, skip);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-int vqa_adamw_ranges_ema_dev(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n,
-                             const vqa_step_state* state, const float* sumsq, const int* skip, int* skipped, int* lag, const int* frozen,
-                             int nf, void* p_bf16, float* ema, hipStream_t st) {
-  if (!state_ok(state) || R < 0 || R > VQA_RANGES_MAX || n < 0 || n % 4 || (R == 0 && n != 0) || nf < 0 || (nf > 0 && (!lag || !frozen))) return VQA_EARG;
-  if (!ema) return VQA_EARG;
-  size_t blocks = ((size_t)n / 4 + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(adamw_ranges_ema_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p, g, m, v, table, R, n, state, sumsq, skip, skipped,
-                     (const int*)lag, (bf16_t*)p_bf16, ema);
-  if (nf > 0) hipLaunchKernelGGL(adamw_lag_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, lag, frozen, nf, skip);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-int vqa_ema_update(float* ema, const float* p, long long n, float d, hipStream_t st) {
-  if (!ema || !p || n < 0 || !ema_decay_ok(d)) return VQA_EARG;
-  const long long nv = (((uintptr_t)ema | (uintptr_t)p) & 15) ? 0 : n / 4;
-  size_t blocks = ((size_t)(nv ? nv : n) + 255) / 256; if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(ema_update_kernel, dim3((unsigned)blocks), dim3(256), 0, st, ema, p, n, nv, d);
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
 
