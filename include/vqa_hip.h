@@ -513,6 +513,44 @@ int vqa_adamw_ranges_ema_dev(float* p, const float* g, float* m, float* v, const
                              const vqa_step_state* state, const float* sumsq, const int* skip, int* skipped, int* lag, const int* frozen,
                              int nf, void* p_bf16, float* ema, hipStream_t stream);
 
+/* ---- parameter groups (HipTrainer(param_groups=...)): a learning-rate scale and a weight decay per group of parameters ----------
+   Every range of the table belongs to one of at most 16 groups: group_of_range is a device int32 array of R entries in 0 ... 15 (the
+   caller's to keep there; the kernels take an entry modulo 16, so none reads outside the block).  A range of group g is updated as
+   vqa_adamw_ranges updates it, with  lr * groups->lr_scale[g]  in the place of lr and  groups->wd[g]  in the place of weight_decay
+   (the launch's own weight_decay is not used): torch.optim.AdamW with one param group per group.  The norm and its clip stay global
+   (vqa_sumsq_ranges over the same table).  lr_scale[g] == 0 is not freezing: both moments, the step number and the average advance,
+   the parameter keeps its value and the bf16 copy is written from it.  With every lr_scale 1 and every wd the launch's weight_decay
+   the four entries give the bits of the vqa_adamw_ranges entries they extend: they are the same kernel body.
+   The block lives on the device and is read there when a kernel runs -- by the by-value entries and the _dev entries alike, so an
+   eager and a captured step share one mechanism.  vqa_group_hyper_set writes it with a one-thread kernel: lr_scale and wd are HOST
+   arrays of G entries, read at call time and handed to the kernel by value (no staging buffer, no copy, no host synchronisation);
+   entries G ... 15 of the block are set to 0.  wd is the effective value per group.
+   Status 1000 without a launch: vqa_group_hyper_set -- G outside 1 ... 16, a NULL or not 16-byte-aligned block, a NULL array, a value
+   that is negative or not finite; the four entries -- a NULL group_of_range, a NULL or misaligned groups, and whatever the
+   vqa_adamw_ranges entry they extend refuses. */
+#define VQA_GROUPS_MAX 16
+typedef struct __attribute__((aligned(16))) vqa_group_hyper {
+  float lr_scale[VQA_GROUPS_MAX];
+  float wd[VQA_GROUPS_MAX];
+} vqa_group_hyper;
+int vqa_group_hyper_set(vqa_group_hyper* block, int G, const float* lr_scale, const float* wd, hipStream_t stream);
+int vqa_adamw_groups(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n, float lr, float beta1,
+                     float beta2, float eps, float weight_decay, long long calls, const float* sumsq, float max_norm, float gscale,
+                     const int* skip, int* skipped, int* lag, const int* frozen, int nf, void* p_bf16, const int* group_of_range,
+                     const vqa_group_hyper* groups, hipStream_t stream);
+int vqa_adamw_groups_ema(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n, float lr, float beta1,
+                         float beta2, float eps, float weight_decay, long long calls, const float* sumsq, float max_norm, float gscale,
+                         const int* skip, int* skipped, int* lag, const int* frozen, int nf, void* p_bf16,
+                         float* ema, float ema_decay, int ema_warmup, const int* group_of_range, const vqa_group_hyper* groups,
+                         hipStream_t stream);
+int vqa_adamw_groups_dev(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n,
+                         const vqa_step_state* state, const float* sumsq, const int* skip, int* skipped, int* lag, const int* frozen, int nf,
+                         void* p_bf16, const int* group_of_range, const vqa_group_hyper* groups, hipStream_t stream);
+int vqa_adamw_groups_ema_dev(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n,
+                             const vqa_step_state* state, const float* sumsq, const int* skip, int* skipped, int* lag, const int* frozen,
+                             int nf, void* p_bf16, float* ema, const int* group_of_range, const vqa_group_hyper* groups,
+                             hipStream_t stream);
+
 /* Row gather for cached image features (VQAModel.encode_features, ImageFeatures.select): dst[i] = src[index[i]] for i < n, rows of
    row_bytes bytes of any element type.  src holds n_src rows; index is device int32 [n] with every entry in [0, n_src) -- the caller
    checks the range; an entry outside it leaves its destination row unwritten and reads nothing.  16-byte vector loads and stores, one

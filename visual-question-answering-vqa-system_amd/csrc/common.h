@@ -203,6 +203,18 @@ static_assert(sizeof(vqa_step_state) == 64 && alignof(vqa_step_state) == 16, "vq
 static_assert(offsetof(vqa_step_state, seed_step) == 8 && offsetof(vqa_step_state, lr) == 16 && offsetof(vqa_step_state, ema_warmup) == 48,
               "vqa_step_state: field order of include/vqa_hip.h");
 
+// The parameter groups' block of include/vqa_hip.h (HipTrainer(param_groups=...)), repeated here in the same way.
+#define VQA_GROUPS_MAX 16
+#ifndef VQA_GROUP_HYPER_DEFINED
+#define VQA_GROUP_HYPER_DEFINED
+typedef struct __attribute__((aligned(16))) vqa_group_hyper {
+  float lr_scale[VQA_GROUPS_MAX];
+  float wd[VQA_GROUPS_MAX];
+} vqa_group_hyper;
+#endif
+static_assert(sizeof(vqa_group_hyper) == 128 && alignof(vqa_group_hyper) == 16 && offsetof(vqa_group_hyper, wd) == 64,
+              "vqa_group_hyper: two arrays of 16 floats in a 16-byte aligned block");
+
 #define VQA_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
 // ------------------------------------------------------------------------------------------------------------------

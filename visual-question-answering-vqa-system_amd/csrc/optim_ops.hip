@@ -5,6 +5,8 @@
 // flat (every element of the buffer) and ranges (a table of trainable ranges) -- each compiled with and without the weight average
 // (EMA) and with its hyper-parameters from the kernel arguments (HyperArgs) or from the device step-state block (HyperState).  The
 // eight entries that result give the same bits for the same inputs because they run the same statements, not because copies agree.
+// Parameter groups (GROUPS) are a third flag of the ranges loop: each range then takes its learning rate and weight decay from a
+// device block of per-group values (vqa_group_hyper) instead of the launch's; four more entries, the same statements again.
 #include "common.h"
 
 // Sum of a 256-thread block's values in a fixed order (wave sums, then (w0 + w1) + (w2 + w3)); thread 0 stores it to *dst.
@@ -122,17 +124,18 @@ __device__ __forceinline__ float clip_coef(const float* __restrict__ sumsq, floa
 // the scalars that depend on the step number t: lr / bias correction 1, 1 / sqrt(bias correction 2), the average's decay
 struct AdamStep { float step, rbc2, d; };
 template <bool EMA>
-__device__ __forceinline__ AdamStep adam_step_at(const AdamHyper& hy, long long t) {
+__device__ __forceinline__ AdamStep adam_step_at(const AdamHyper& hy, float lr, long long t) {
   const float bc1 = (float)(1.0 - pow((double)hy.b1, (double)t)), bc2 = (float)(1.0 - pow((double)hy.b2, (double)t));
   AdamStep s;
-  s.step = hy.lr / bc1; s.rbc2 = 1.f / sqrtf(bc2);
+  s.step = lr / bc1; s.rbc2 = 1.f / sqrtf(bc2);
   s.d = 0.f;
   if constexpr (EMA) s.d = ema_decay_at(hy.ema_decay, hy.ema_warmup, t);
   return s;
 }
-// one element: p, m, v in, p, m, v out
-__device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g, const AdamHyper& hy, float coef, float step, float rbc2) {
-  const float lr = hy.lr, b1 = hy.b1, b2 = hy.b2, eps = hy.eps, wd = hy.wd;
+// one element: p, m, v in, p, m, v out; lr and wd are the element's own (the launch's, or its parameter group's)
+__device__ __forceinline__ void adam_elem(float& p, float& m, float& v, float g, const AdamHyper& hy, float lr, float wd, float coef,
+                                          float step, float rbc2) {
+  const float b1 = hy.b1, b2 = hy.b2, eps = hy.eps;
   const float gr = g * coef;
   float pi = p * (1.f - lr * wd);
   const float mi = b1 * m + (1.f - b1) * gr;
@@ -152,12 +155,12 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
                              bf16_t* __restrict__ p_bf16, float* __restrict__ ema) {
   const AdamHyper hy = src.get();
   if (adam_skipped(skip, skipped)) return;
-  const AdamStep s = adam_step_at<EMA>(hy, adam_t0(hy.calls, skipped));
+  const AdamStep s = adam_step_at<EMA>(hy, hy.lr, adam_t0(hy.calls, skipped));
   const float coef = clip_coef(sumsq, hy.max_norm, hy.gscale);
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
     const float gi = g[i];
     float pi = p[i], mi = m[i], vi = v[i];
-    adam_elem(pi, mi, vi, gi, hy, coef, s.step, s.rbc2);
+    adam_elem(pi, mi, vi, gi, hy, hy.lr, hy.wd, coef, s.step, s.rbc2);
     m[i] = mi; v[i] = vi; p[i] = pi;
     if (p_bf16) p_bf16[i] = f2bf(pi);
     if constexpr (EMA) ema[i] = ema_blend(ema[i], pi, s.d);
@@ -169,21 +172,34 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 // (torch.optim.AdamW advances a parameter's `step` only when it has a gradient); every parameter inside one range shares its lag (the
 // caller merges only such neighbours).  The average's warm-up of range r runs on that range's OWN step number (a parameter's average
 // advances only while it trains), and `ema` is neither read nor written outside the ranges.
-template <bool EMA, class Hyper>
+// GROUPS (parameter groups): range r belongs to group g = group_of_range[r] and is updated with lr * groups->lr_scale[g] and
+// groups->wd[g] in the place of lr and wd -- two more per-range scalars next to the step's (4 KB of LDS on top of 12 - 14: still
+// eight workgroups per CU).  The block is read on the device when the kernel runs, so a captured launch follows vqa_group_hyper_set.
+// g is the caller's to keep in 0 ... 15; it is taken modulo 16, so no index reads outside the block.
+template <bool EMA, class Hyper, bool GROUPS>
 __global__ __launch_bounds__(256) void adamw_ranges_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                            float* __restrict__ v, const long long* __restrict__ table, int R, long long n,
                                                            Hyper src, const float* __restrict__ sumsq, const int* __restrict__ skip,
                                                            int* __restrict__ skipped, const int* __restrict__ lag,
-                                                           bf16_t* __restrict__ p_bf16, float* __restrict__ ema) {
+                                                           bf16_t* __restrict__ p_bf16, float* __restrict__ ema,
+                                                           const int* __restrict__ group_of_range,
+                                                           const vqa_group_hyper* __restrict__ groups) {
   const AdamHyper hy = src.get();
   if (adam_skipped(skip, skipped)) return;
   __shared__ long long s_lo[VQA_RANGES_MAX], s_pos[VQA_RANGES_MAX];
   __shared__ float s_step[VQA_RANGES_MAX], s_rbc2[VQA_RANGES_MAX];
   __shared__ float s_d[EMA ? VQA_RANGES_MAX : 1];          // (never referenced without EMA: takes no LDS then)
+  __shared__ float s_lr[GROUPS ? VQA_RANGES_MAX : 1], s_wd[GROUPS ? VQA_RANGES_MAX : 1];     // (nor these without GROUPS)
   const long long t0 = adam_t0(hy.calls, skipped);
   for (int r = threadIdx.x; r < R; r += blockDim.x) {
     s_lo[r] = table[4 * r]; s_pos[r] = table[4 * r + 2];
-    const AdamStep s = adam_step_at<EMA>(hy, t0 - (lag ? (long long)lag[table[4 * r + 3]] : 0ll));
+    float lr_r = hy.lr;
+    if constexpr (GROUPS) {
+      const int gi = group_of_range[r] & (VQA_GROUPS_MAX - 1);
+      lr_r = hy.lr * groups->lr_scale[gi];
+      s_lr[r] = lr_r; s_wd[r] = groups->wd[gi];
+    }
+    const AdamStep s = adam_step_at<EMA>(hy, lr_r, t0 - (lag ? (long long)lag[table[4 * r + 3]] : 0ll));
     s_step[r] = s.step; s_rbc2[r] = s.rbc2;
     if constexpr (EMA) s_d[r] = s.d;
   }
@@ -194,6 +210,8 @@ __global__ __launch_bounds__(256) void adamw_ranges_kernel(float* __restrict__ p
     int r;
     const long long i = range_index(s_lo, s_pos, R, 4 * q, r);
     const float step = s_step[r], rbc2 = s_rbc2[r];
+    float lr = hy.lr, wd = hy.wd;
+    if constexpr (GROUPS) { lr = s_lr[r]; wd = s_wd[r]; }
     const float4 g4 = *reinterpret_cast<const float4*>(g + i);
     float4 p4 = *reinterpret_cast<const float4*>(p + i);
     float4 m4 = *reinterpret_cast<const float4*>(m + i);
@@ -204,7 +222,7 @@ __global__ __launch_bounds__(256) void adamw_ranges_kernel(float* __restrict__ p
     float* pp = &p4.x; float* mm = &m4.x; float* vv = &v4.x; const float* gg = &g4.x; float* ee = &e4.x;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      adam_elem(pp[k], mm[k], vv[k], gg[k], hy, coef, step, rbc2);
+      adam_elem(pp[k], mm[k], vv[k], gg[k], hy, lr, wd, coef, step, rbc2);
       if constexpr (EMA) ee[k] = ema_blend(ee[k], pp[k], d);
     }
     *reinterpret_cast<float4*>(p + i) = p4;
@@ -235,6 +253,14 @@ __global__ void step_state_set_kernel(vqa_step_state* state, long long calls, un
     state->max_norm = max_norm; state->gscale = gscale; state->ema_decay = ema_decay; state->ema_warmup = ema_warmup;
   }
 }
+// One thread writes the parameter groups' block, the same way: the 32 floats travel by value in the launch's arguments.
+struct GroupHyperArg { float4 q[8]; };
+__global__ void group_hyper_set_kernel(vqa_group_hyper* block, GroupHyperArg a) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) reinterpret_cast<float4*>(block)[k] = a.q[k];
+  }
+}
 // The average as a pass of its own over a flat buffer (torch.optim loops: dropin/utils/ema.py): 12 B per element.  nv float4 groups
 // (0 when a pointer is not 16-byte aligned), then the scalar rest.
 __global__ __launch_bounds__(256) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ p, long long n, long long nv, float d) {
@@ -259,6 +285,8 @@ static inline bool ranges_args_ok(int R, long long n, int nf, const int* lag, co
 }
 static inline bool ema_decay_ok(float d) { return d >= 0.f && d <= 1.f; }        // (NaN fails both comparisons)
 static inline bool state_ok(const void* state) { return state && !((uintptr_t)state & 15); }
+static inline bool group_value_ok(float x) { return x >= 0.f && x <= 3.402823466e38f; }   // finite and not negative (NaN fails both)
+static inline bool groups_ok(const int* group_of_range, const vqa_group_hyper* groups) { return group_of_range && state_ok(groups); }
 static inline HyperArgs hyper_args(float lr, float b1, float b2, float eps, float wd, long long calls, float max_norm, float gscale,
                                    float ema_decay = 0.f, int ema_warmup = 0) {
   return HyperArgs{AdamHyper{lr, b1, b2, eps, wd, calls, max_norm, gscale, ema_decay, ema_warmup}};
@@ -272,12 +300,12 @@ static int launch_adamw(float* p, const float* g, float* m, float* v, long long 
                      skipped, (bf16_t*)p_bf16, ema);
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
-template <bool EMA, class Hyper>
+template <bool EMA, bool GROUPS = false, class Hyper>
 static int launch_adamw_ranges(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n, Hyper src,
                                const float* sumsq, const int* skip, int* skipped, int* lag, const int* frozen, int nf, void* p_bf16,
-                               float* ema, hipStream_t st) {
-  hipLaunchKernelGGL((adamw_ranges_kernel<EMA, Hyper>), dim3(blocks_of((size_t)n / 4, 4096)), dim3(256), 0, st, p, g, m, v, table, R, n, src,
-                     sumsq, skip, skipped, (const int*)lag, (bf16_t*)p_bf16, ema);
+                               float* ema, hipStream_t st, const int* group_of_range = nullptr, const vqa_group_hyper* groups = nullptr) {
+  hipLaunchKernelGGL((adamw_ranges_kernel<EMA, Hyper, GROUPS>), dim3(blocks_of((size_t)n / 4, 4096)), dim3(256), 0, st, p, g, m, v, table, R,
+                     n, src, sumsq, skip, skipped, (const int*)lag, (bf16_t*)p_bf16, ema, group_of_range, groups);
   if (nf > 0) hipLaunchKernelGGL(adamw_lag_kernel, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, lag, frozen, nf, skip);
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
@@ -357,6 +385,51 @@ int vqa_adamw_ranges_ema_dev(float* p, const float* g, float* m, float* v, const
   if (!state_ok(state) || !ranges_args_ok(R, n, nf, lag, frozen)) return VQA_EARG;
   if (!ema) return VQA_EARG;
   return launch_adamw_ranges<true>(p, g, m, v, table, R, n, HyperState{state}, sumsq, skip, skipped, lag, frozen, nf, p_bf16, ema, st);
+}
+
+// Parameter groups: the block of per-group values, and the four range entries that read it on the device (the same launcher, GROUPS on).
+int vqa_group_hyper_set(vqa_group_hyper* block, int G, const float* lr_scale, const float* wd, hipStream_t st) {
+  if (!state_ok(block) || G < 1 || G > VQA_GROUPS_MAX || !lr_scale || !wd) return VQA_EARG;
+  GroupHyperArg a = {};
+  float* f = &a.q[0].x;
+  for (int k = 0; k < G; ++k) {
+    if (!group_value_ok(lr_scale[k]) || !group_value_ok(wd[k])) return VQA_EARG;
+    f[k] = lr_scale[k]; f[VQA_GROUPS_MAX + k] = wd[k];
+  }
+  hipLaunchKernelGGL(group_hyper_set_kernel, dim3(1), dim3(1), 0, st, block, a);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+int vqa_adamw_groups(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n, float lr, float b1, float b2,
+                     float eps, float wd, long long calls, const float* sumsq, float max_norm, float gscale, const int* skip, int* skipped,
+                     int* lag, const int* frozen, int nf, void* p_bf16, const int* group_of_range, const vqa_group_hyper* groups,
+                     hipStream_t st) {
+  if (calls < 1 || !ranges_args_ok(R, n, nf, lag, frozen) || !groups_ok(group_of_range, groups)) return VQA_EARG;
+  return launch_adamw_ranges<false, true>(p, g, m, v, table, R, n, hyper_args(lr, b1, b2, eps, wd, calls, max_norm, gscale), sumsq, skip,
+                                          skipped, lag, frozen, nf, p_bf16, nullptr, st, group_of_range, groups);
+}
+int vqa_adamw_groups_ema(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n, float lr, float b1, float b2,
+                         float eps, float wd, long long calls, const float* sumsq, float max_norm, float gscale, const int* skip, int* skipped,
+                         int* lag, const int* frozen, int nf, void* p_bf16, float* ema, float ema_decay, int ema_warmup,
+                         const int* group_of_range, const vqa_group_hyper* groups, hipStream_t st) {
+  if (calls < 1 || !ranges_args_ok(R, n, nf, lag, frozen) || !groups_ok(group_of_range, groups)) return VQA_EARG;
+  if (!ema || !ema_decay_ok(ema_decay)) return VQA_EARG;
+  return launch_adamw_ranges<true, true>(p, g, m, v, table, R, n, hyper_args(lr, b1, b2, eps, wd, calls, max_norm, gscale, ema_decay, ema_warmup),
+                                         sumsq, skip, skipped, lag, frozen, nf, p_bf16, ema, st, group_of_range, groups);
+}
+int vqa_adamw_groups_dev(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n,
+                         const vqa_step_state* state, const float* sumsq, const int* skip, int* skipped, int* lag, const int* frozen, int nf,
+                         void* p_bf16, const int* group_of_range, const vqa_group_hyper* groups, hipStream_t st) {
+  if (!state_ok(state) || !ranges_args_ok(R, n, nf, lag, frozen) || !groups_ok(group_of_range, groups)) return VQA_EARG;
+  return launch_adamw_ranges<false, true>(p, g, m, v, table, R, n, HyperState{state}, sumsq, skip, skipped, lag, frozen, nf, p_bf16, nullptr,
+                                          st, group_of_range, groups);
+}
+int vqa_adamw_groups_ema_dev(float* p, const float* g, float* m, float* v, const long long* table, int R, long long n,
+                             const vqa_step_state* state, const float* sumsq, const int* skip, int* skipped, int* lag, const int* frozen,
+                             int nf, void* p_bf16, float* ema, const int* group_of_range, const vqa_group_hyper* groups, hipStream_t st) {
+  if (!state_ok(state) || !ranges_args_ok(R, n, nf, lag, frozen) || !groups_ok(group_of_range, groups)) return VQA_EARG;
+  if (!ema) return VQA_EARG;
+  return launch_adamw_ranges<true, true>(p, g, m, v, table, R, n, HyperState{state}, sumsq, skip, skipped, lag, frozen, nf, p_bf16, ema, st,
+                                         group_of_range, groups);
 }
 
 int vqa_ema_update(float* ema, const float* p, long long n, float d, hipStream_t st) {

@@ -105,6 +105,9 @@ HBM_BYTES = {
     "vqa_adamw_ema": ("optimizer", lambda a: a[4] * 4 * 9),
     "vqa_adamw_ranges_ema": ("optimizer", lambda a: a[6] * 4 * 9),
     "vqa_ema_update": ("optimizer", lambda a: a[2] * 4 * 3),
+    # parameter groups: the range kernels' traffic (the groups' block is 128 bytes)
+    "vqa_adamw_groups": ("optimizer", lambda a: a[6] * 4 * 7),
+    "vqa_adamw_groups_ema": ("optimizer", lambda a: a[6] * 4 * 9),
 }
 
 

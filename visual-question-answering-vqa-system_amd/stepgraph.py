@@ -67,8 +67,27 @@ class StepState(C.Structure):
                 ("_pad", C.c_int * 3)]
 
 
+GROUPS_MAX = 16
+
+
+class GroupHyper(C.Structure):
+    """vqa_group_hyper of include/vqa_hip.h (16-byte aligned, 128 bytes): the parameter groups' lr scales and weight decays."""
+    _fields_ = [("lr_scale", C.c_float * GROUPS_MAX), ("wd", C.c_float * GROUPS_MAX)]
+
+
+GROUP_HYPER_BYTES = 128
+
+
 STATE_BYTES = 64
 SEED_STEP_OFFSET = 8
+
+
+def table_id(generation, groups=None):
+    """step_key's table_id: the generation of the optimizer's range table (None: the plain kernels), and with parameter groups their
+    STRUCTURE beside it (finetune.ParamGroups.key(): the group of every parameter) -- a grouped step issues other launches, and the
+    per-range group array is rebuilt with the table.  The groups' VALUES (lr_scale, weight_decay) live in a device block and never
+    enter: changing them captures nothing anew."""
+    return generation if groups is None else (generation, tuple(groups))
 
 
 def _sig(t):
@@ -88,7 +107,8 @@ def step_key(*, features: bool, images, token_ids, attention_mask, image_index, 
     flat_ptr / wsrc_ptr: addresses of the parameter buffer and of the bf16 operand copy; table_id: generation of the optimizer's range
     table (None: the plain kernels) -- a generation, not an address: a rebuilt table may land on the address of the one it replaced,
     with other sizes, and a graph captured on the old one must never be found again.  (The engine's buffer of packed backward
-    operands is re-laid when a new trainable set needs more of them; step_graphed checks its generation when it finds a graph.)"""
+    operands is re-laid when a new trainable set needs more of them; step_graphed checks its generation when it finds a graph.)
+    With parameter groups table_id is what table_id() below makes of the generation and the groups' structure."""
     if hasattr(targets, "ids") and hasattr(targets, "weights"):
         tsig = ("soft", _sig(targets.ids), _sig(targets.weights), _sig(getattr(targets, "counts", None)))
     else:

@@ -10,6 +10,7 @@ or "gloo" in the CPU rehearsal tests) and divided by world size inside the optim
 from __future__ import annotations
 
 import contextlib
+import ctypes
 from typing import List, Optional
 
 import torch
@@ -169,7 +170,7 @@ def _is_features(images) -> bool:
 class HipTrainer:
     def __init__(self, model, lr=1e-4, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
                  process_group=None, overlap=True, force_reducer=False, label_smoothing=0.0, class_weight=None, ignore_index=None,
-                 ema_decay=None, ema_warmup=False, loss="ce"):
+                 ema_decay=None, ema_warmup=False, loss="ce", param_groups=None):
         """loss: "ce" (default: softmax cross-entropy, exactly the step without this option) or "bce" (sigmoid + binary cross-entropy on
         SoftTargets, see step()); readable afterwards as `loss_kind` (`loss` is the device scalar).
         ema_decay (None, or a float in [0, 1]): keep an exponential moving average of the weights, self.ema (a flat fp32 buffer laid out
@@ -179,7 +180,21 @@ class HipTrainer:
         parameter advances only while it trains).  A skipped step leaves the average untouched.  `ema_decay` stays a plain attribute that
         may be changed between steps, like `lr`.  None (default): no buffer, and the step issues exactly the launches it issues without
         this feature.  Data parallel: every rank applies the same update to identical parameters, so the averages stay identical and
-        nothing is communicated.  ema_weights() / ema_state_dict() / load_ema_state_dict() evaluate on, export and restore the average."""
+        nothing is communicated.  ema_weights() / ema_state_dict() / load_ema_state_dict() evaluate on, export and restore the average.
+        param_groups (None, or a list of dicts {"params": selector, "lr_scale": 1.0, "weight_decay": None}): a learning-rate scale and a
+        weight decay per group of parameters.  A selector is an iterable of parameter names (state_dict names), name prefixes (strings
+        that end in ".", e.g. "image_encoder.") and Parameter objects of this model; what no group selects forms an implicit last
+        group (lr_scale 1, weight_decay None); weight_decay None follows the live `wd` of the trainer.  A parameter of group g is
+        updated as torch.optim.AdamW([{"params": ..., "lr": lr * lr_scale_g, "weight_decay": wd_g}, ...], betas, eps) updates it, after
+        clip_grad_norm_ over ALL trainable parameters (the norm stays global).  lr_scale 0 is not freezing: the moments, Adam's step
+        number and the average advance, the parameter keeps its bits.  `param_groups` (attribute) is then the list of live dicts
+        {"names", "lr_scale", "weight_decay"}: the two values may be changed between steps, like `lr`, and reach the kernels through a
+        device block (vqa_group_hyper_set, launched only when a value changed) -- also those of a captured step, which is never
+        re-captured for them.  finetune.no_weight_decay_groups(model) builds the usual two groups.  KeyError for an unknown name or a
+        prefix that matches nothing; ValueError for a parameter in two groups, a parameter of another model, an empty group, more than
+        16 groups, a value that is negative or not finite, or groups that need more than 512 ranges -- all before anything is
+        allocated.  None (default): exactly the step without this feature, launch for launch.  Data parallel: the same groups on
+        every rank give the same update; nothing is communicated and the reducer's trainable set does not change."""
         self.model = model
         # validated on the host before anything is allocated or launched
         if not (isinstance(loss, str) and loss in ("ce", "bce")):
@@ -188,6 +203,8 @@ class HipTrainer:
             raise ValueError('HipTrainer: label_smoothing / class_weight / ignore_index belong to the cross-entropy loss; '
                              'loss="bce" takes none of them')
         self.loss_kind = loss
+        self._pg = None if param_groups is None else FT.ParamGroups(model._param_entries, model._param_list(), param_groups)
+        self.param_groups = None if self._pg is None else self._pg.groups
         self.ema_decay = None if ema_decay is None else EMA.check_decay(ema_decay, "HipTrainer: ema_decay")
         self.ema_warmup = bool(ema_warmup)
         self.ema = None
@@ -235,6 +252,11 @@ class HipTrainer:
         self._ranges = None                        # (table, R, n, frozen indices, nf) on the device
         self._ranges_gen = 0                       # how often that table was rebuilt (a captured step holds its address and sizes)
         self._lag = torch.zeros(len(model._param_entries), device=flat.device, dtype=torch.int32)
+        # parameter groups: the device block of their values (vqa_group_hyper) and the values it holds (None: never written).  With
+        # groups the optimizer always runs over the range table, whose ranges then also end at group boundaries; the group of every
+        # range travels in an int32 array of its own, rebuilt with the table (_ranges[5])
+        self._group_block = None if self._pg is None else torch.zeros(SG.GROUP_HYPER_BYTES // 4, device=flat.device, dtype=torch.int32)
+        self._group_written = None
         # step_graphed: captured train steps (LRU, capped by model.graph_max_shapes like model._graphs), how often each key was seen
         # (the first two calls of a key run eagerly), and the device step-state block the captured launches read (stepgraph.py)
         self._graphs = {}
@@ -266,26 +288,39 @@ class HipTrainer:
         """Trainable set of this step (tuple of bools in layout order, or None for all): rebuild the range table when it changed."""
         if trainable is not None and all(trainable):
             trainable = None
-        if trainable == self._mask and (self._ranges is not None or not self._ever_frozen):
-            return
-        self._mask = trainable
+        grouped = self._pg is not None                 # (the table route even when nothing was ever frozen: all lags zero)
+        if trainable == self._mask and (self._ranges is not None or not (self._ever_frozen or grouped)):
+            return                                     # (a change of the groups' VALUES never comes here: the table stays)
         tr = trainable if trainable is not None else (True,) * len(self._lag_class)
-        self._lag_class = FT.refine_classes(self._lag_class, tr)
+        lag_class = FT.refine_classes(self._lag_class, tr)
+        ranges = None
+        if grouped:                                    # refused before anything of this trainer changes
+            ranges = FT.trainable_ranges(self.model._param_entries, tr, lag_class, self._pg.group_of)
+            if len(ranges) > FT.RANGES_MAX:
+                raise ValueError(f"HipTrainer: this trainable set and these parameter groups need {len(ranges)} ranges; the optimizer's "
+                                 f"table holds {FT.RANGES_MAX}")
+        self._mask = trainable
+        self._lag_class = lag_class
         self._ever_frozen = self._ever_frozen or trainable is not None
-        if not self._ever_frozen:
+        if not self._ever_frozen and not grouped:
             self._ranges = None
             self.reducer.set_trainable(None)
             return
-        ranges = FT.trainable_ranges(self.model._param_entries, tr, self._lag_class)
+        if ranges is None:
+            ranges = FT.trainable_ranges(self.model._param_entries, tr, self._lag_class)
         rows = FT.range_table_rows(ranges)
         n = sum(hi - lo for lo, hi, _ in ranges)
         dev = self.G.device
         table = torch.tensor(rows if rows else [[0, 0, 0, 0]], dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
         frozen = [j for j, t in enumerate(tr) if not t]
         fidx = torch.tensor(frozen if frozen else [0], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
-        self._ranges = (table, len(rows), n, fidx, len(frozen))
+        garr = None
+        if grouped:
+            gof = [self._pg.group_of[j] for _, _, j in ranges]
+            garr = torch.tensor(gof if gof else [0], dtype=torch.int32).pin_memory().to(dev, non_blocking=True)
+        self._ranges = (table, len(rows), n, fidx, len(frozen), garr)
         self._ranges_gen += 1
-        self.reducer.set_trainable(ranges)
+        self.reducer.set_trainable(ranges if trainable is not None or not grouped else None)
 
     def step(self, images, token_ids, attention_mask, targets, metrics=None, image_index=None):
         """One full train step; returns (loss device scalar, logits fp32).  `metrics`: optional device-side accuracy tracker
@@ -326,6 +361,7 @@ class HipTrainer:
         dev = self.G.device
         if self.ema is not None:                           # (ema_decay may have been changed since the constructor checked it)
             EMA.check_decay(self.ema_decay, "HipTrainer: ema_decay")
+        group_values = None if self._pg is None else self._pg.effective(self.wd)      # (ValueError: a bad live value)
         soft = _is_soft(targets)
         bce = self.loss_kind == "bce"
         if bce and not soft:
@@ -379,7 +415,17 @@ class HipTrainer:
         eng.count_step(plan.modes if plan is not None else (True, True, True, True), runs_cnn=feats is None)
         self.calls += 1
         return dict(features=feats is not None, images=images, token_ids=token_ids, maskf=maskf, targets=targets, soft=soft, bce=bce,
-                    metrics=metrics, kv_index=kv_index, plan=plan)
+                    metrics=metrics, kv_index=kv_index, plan=plan, group_values=group_values)
+
+    def _write_groups(self, values):
+        """The parameter groups' effective values go to their device block when they differ from what it holds: an eager one-thread
+        launch on the current stream, ahead of the AdamW launch (or the replay) that reads the block."""
+        if values is None or values == self._group_written:
+            return
+        scales, wds = values
+        F = ctypes.c_float * len(scales)
+        call("vqa_group_hyper_set", ptr(self._group_block), len(scales), F(*scales), F(*wds))
+        self._group_written = values
 
     def _enqueue(self, c, state=None):
         """The device half of a step: every launch, in the order the step has always issued them; returns (loss, logits fp32).
@@ -391,6 +437,8 @@ class HipTrainer:
                                                                                       "kv_index", "plan"))
         soft, bce = c["soft"], c["bce"]
         dev = self.G.device
+        if state is None:                          # (a captured step: step_graphed wrote the block eagerly, beside the step state)
+            self._write_groups(c["group_values"])
         self.G.zero_()
         self._scal.zero_()
         if state is not None:
@@ -445,11 +493,13 @@ class HipTrainer:
             call(("vqa_adamw_ema" if ema_args else "vqa_adamw") + sfx, ptr(self.model._flat), ptr(self.G), ptr(self.m), ptr(self.v), self.G.numel(),
                  *hyper, ptr(self.sumsq), *tail, ptr(self.bad_step), ptr(self._bad), ptr(eng.adamw_copy_target()), *ema_args)
         else:                                      # frozen parameters: only the trainable ranges are read and written
-            table, R, n, fidx, nf = self._ranges
+            table, R, n, fidx, nf, garr = self._ranges
+            # parameter groups: the same launch with every range's group and the block of the groups' values behind its arguments
+            entry, gargs = ("vqa_adamw_ranges", ()) if garr is None else ("vqa_adamw_groups", (ptr(garr), ptr(self._group_block)))
             call("vqa_sumsq_ranges", ptr(self.G), ptr(table), R, n, ptr(self.sumsq))
-            call(("vqa_adamw_ranges_ema" if ema_args else "vqa_adamw_ranges") + sfx, ptr(self.model._flat), ptr(self.G), ptr(self.m), ptr(self.v),
+            call(entry + ("_ema" if ema_args else "") + sfx, ptr(self.model._flat), ptr(self.G), ptr(self.m), ptr(self.v),
                  ptr(table), R, n, *hyper, ptr(self.sumsq), *tail, ptr(self.bad_step), ptr(self._bad), ptr(self._lag), ptr(fidx), nf,
-                 ptr(eng.adamw_copy_target()), *ema_args)
+                 ptr(eng.adamw_copy_target()), *ema_args, *gargs)
         # the kernel wrote the bf16 operand copy too: the next step() skips the cast launch if nothing touched the parameters in between
         self._copy_sig = self._param_sig() if eng.adamw_copy_target() is not None else None
         return self.loss, logits_f
@@ -462,7 +512,8 @@ class HipTrainer:
         options, EMA on or off, the `metrics` object, the parameter / operand-copy / packed-operand / range-table buffers) are eager steps; the third
         captures the launches of _enqueue on static copies of the inputs and replays them; later calls copy the inputs in, write the
         device step-state block (vqa_step_state_set: this step's seed word and Adam step number, and lr / betas / eps / wd /
-        max_norm / ema_decay / ema_warmup as they read NOW -- changing them never re-captures) and replay.  A torch-side write to
+        max_norm / ema_decay / ema_warmup as they read NOW -- changing them never re-captures; the parameter groups' lr_scale and
+        weight_decay likewise, through vqa_group_hyper_set when one of them changed) and replay.  A torch-side write to
         the parameters since the last AdamW launch (load_state_dict, a torch optimizer, ema_weights(), an eager step() in between
         leaves the copy fresh) is answered by an eager vqa_convert ahead of the replay, as step() would cast.
         The returned logits (and the loss, as with step()) are the graph's static buffers: valid until the next call with the same
@@ -481,7 +532,7 @@ class HipTrainer:
                           image_index=c["kv_index"], targets=c["targets"], plan=c["plan"], loss_kind=self.loss_kind,
                           loss_opts=(self.label_smoothing, self.ignore_index, None if self.class_weight is None else self.class_weight.data_ptr()),
                           ema=self.ema is not None, metrics=metrics, flat_ptr=self.model._flat.data_ptr(), wsrc_ptr=eng.wsrc.data_ptr(),
-                          table_id=None if self._ranges is None else self._ranges_gen)
+                          table_id=SG.table_id(None if self._ranges is None else self._ranges_gen, None if self._pg is None else self._pg.key()))
         g = self._graphs.pop(key, None)
         if g is not None and g[4] != eng._wt_gen:
             # the engine laid its packed backward operands out anew since the capture (another trainable set needed more of them):
@@ -506,6 +557,7 @@ class HipTrainer:
         call("vqa_step_state_set", ptr(self._state), self.calls, SG.seed_step(self._seed_rank(), eng.seed_base, eng.step_id),
              float(self.lr), float(b1), float(b2), float(self.eps), float(self.wd), float(self.max_norm), 1.0,
              float(self.ema_decay) if ema_on else 0.0, int(bool(self.ema_warmup)) if ema_on else 0)
+        self._write_groups(c["group_values"])
         if g is None:
             g = self._capture_step(c)
             self._graph_seen.pop(key, None)
