@@ -1,6 +1,6 @@
 """Loss options of the fused step, measured (bf16, default configuration, B = 512, HipTrainer):
 
-    python tools/bench_loss_opts.py [--out profiles/loss_opts_bench.json] [--reps 5] [--steps 10]
+    python tools/bench_loss_opts.py [--out profiles/loss_opts_bench.json] [--reps 5] [--steps 10] [--lib PATH] [--kernels-only]
 
 Train steps of four set-ups, each on its own trainer, warmed up, then timed alternately in one process with device events around
 `--steps` back-to-back steps (reps alternations, median per step):
@@ -9,8 +9,11 @@ Train steps of four set-ups, each on its own trainer, warmed up, then timed alte
     opts          HipTrainer(model, label_smoothing=0.1, class_weight=w, ignore_index=-100), ~5 % of the targets ignored
     opts_metric   ... with metrics=VQAAccuracy() (counted inside the loss launch)
 Then the kernels alone at [512, 1000] and [256, 2000] bf16 logits, alternated the same way over `--kernel-iters` back-to-back
-launches, each with its fold launch: vqa_cross_entropy, vqa_cross_entropy_soft (K = 10), vqa_cross_entropy_opts with all three
-options, with and without the fused counters, the same entry with its options at their defaults, and vqa_accuracy_update."""
+launches, each with its fold launch: vqa_cross_entropy, vqa_cross_entropy_soft and vqa_bce_soft (K = 10) with and without the fused
+challenge accuracy, vqa_cross_entropy_opts with all three options, with and without the fused counters, the same entry with its
+options at their defaults, vqa_accuracy_update, vqa_challenge_accuracy_update, vqa_answer_scores and vqa_softmax_topk (K = 5) --
+every entry of csrc/loss_ops.hip.
+--lib PATH measures another build of libvqa_hip.so (the binding's LIB_PATH, as tools/ab_lib.py); --kernels-only leaves the train steps out."""
 import argparse
 import importlib
 import json
@@ -74,23 +77,36 @@ def kernels_alone(L, ST, rows, n, reps, iters):
     ti = t.clone()
     ti[torch.rand(rows, generator=g).to(DEV) < 0.05] = -100
     w = class_weights(n).to(DEV)
-    soft = ST.answer_scores(torch.randint(0, n, (rows, A), generator=g).to(DEV), n)
+    answers = torch.randint(0, n, (rows, A), generator=g).to(DEV)
+    soft = ST.answer_scores(answers, n)
+    ids, wts, cnts = torch.empty_like(soft.ids), torch.empty_like(soft.weights), torch.empty_like(soft.counts)
     loss, ws = torch.zeros(1, device=DEV), torch.empty(rows, device=DEV)
     dl, lfo = torch.empty_like(logits), torch.empty_like(lf)
     acc3, empty = torch.zeros(3, device=DEV, dtype=torch.int64), torch.zeros(1, device=DEV, dtype=torch.int32)
+    acc2 = torch.zeros(2, device=DEV, dtype=torch.int64)
+    tidx, tprob = torch.empty(rows, 5, device=DEV, dtype=torch.int64), torch.empty(rows, 5, device=DEV)
     p = L.ptr
 
     def opts(tt, cw, has, eps, acc):
         return lambda: L.call("vqa_cross_entropy_opts", 1, p(logits), p(tt), p(loss), p(dl), p(lfo), rows, n, 1.0, None, p(ws), p(cw), -100, has, eps,
                               p(acc), p(empty))
+
+    def soft_loss(entry, acc):
+        return lambda: L.call(entry, 1, p(logits), p(soft.ids), p(soft.weights), A, p(loss), p(dl), p(lfo), rows, n, 1.0, None, p(ws),
+                              p(soft.counts) if acc else None, p(acc2) if acc else None)
     kern = {
         "cross_entropy": lambda: L.call("vqa_cross_entropy", 1, p(logits), p(t), p(loss), p(dl), p(lfo), rows, n, 1.0, None, p(ws)),
-        "cross_entropy_soft": lambda: L.call("vqa_cross_entropy_soft", 1, p(logits), p(soft.ids), p(soft.weights), A, p(loss), p(dl), p(lfo), rows, n,
-                                             1.0, None, p(ws), None, None),
+        "cross_entropy_soft": soft_loss("vqa_cross_entropy_soft", False),
+        "cross_entropy_soft_acc": soft_loss("vqa_cross_entropy_soft", True),
+        "bce_soft": soft_loss("vqa_bce_soft", False),
+        "bce_soft_acc": soft_loss("vqa_bce_soft", True),
         "cross_entropy_opts_defaults": opts(t, None, 0, 0.0, None),
         "cross_entropy_opts": opts(ti, w, 1, 0.1, None),
         "cross_entropy_opts_acc": opts(ti, w, 1, 0.1, acc3),
         "accuracy_update": lambda: L.call("vqa_accuracy_update", p(lf), p(t), p(acc3), rows, n),
+        "challenge_accuracy_update": lambda: L.call("vqa_challenge_accuracy_update", p(lf), p(soft.ids), p(soft.counts), A, p(acc2), rows, n),
+        "answer_scores": lambda: L.call("vqa_answer_scores", p(answers), p(ids), p(wts), p(cnts), rows, A, n, 0, None),
+        "softmax_topk": lambda: L.call("vqa_softmax_topk", 1, p(logits), n, None, 0, 1.0, p(tidx), p(tprob), None, rows, n, 5),
     }
     k = alternate(kern, reps, iters)
     return {name: {s: (v * 1e3 if not isinstance(v, list) else [x * 1e3 for x in v]) for s, v in d.items()} for name, d in k.items()}
@@ -102,15 +118,22 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--kernel-iters", type=int, default=200)
+    ap.add_argument("--lib", default=None)
+    ap.add_argument("--kernels-only", action="store_true")
     a = ap.parse_args()
     L, M, ST = pkg._lib, pkg.load_dropin_metrics(), pkg.load_dropin_soft_targets()
+    if a.lib:
+        L.LIB_PATH, L._lib = os.path.abspath(a.lib), None
+    if a.kernels_only:
+        res = {"dtype": "bf16", "reps": a.reps, "device": torch.cuda.get_device_name(0), "library": os.path.basename(L.LIB_PATH)}
+        return report(res, a.out, L, ST, a)
     images, ids, mask, answers = (t.to(DEV) for t in O.synthetic_batch(B, seed=7))
     mask[:, 0] = 1
     N = 1000
     ignored = answers.clone()
     ignored[torch.rand(B, generator=torch.Generator().manual_seed(3)).to(DEV) < 0.05] = -100
     res = {"batch": B, "dtype": "bf16", "steps_per_rep": a.steps, "reps": a.reps, "device": torch.cuda.get_device_name(0),
-           "options": {"label_smoothing": 0.1, "class_weight": "rsqrt(rank), mean 1", "ignore_index": -100, "ignored_rows": int((ignored == -100).sum())}}
+           "library": os.path.basename(L.LIB_PATH), "options": {"label_smoothing": 0.1, "class_weight": "rsqrt(rank), mean 1", "ignore_index": -100, "ignored_rows": int((ignored == -100).sum())}}
 
     okw = dict(label_smoothing=0.1, class_weight=class_weights(N), ignore_index=-100)
     trainers = {k: pkg.trainer.HipTrainer(make_model(), **(okw if k.startswith("opts") else {})) for k in SETUPS}
@@ -122,13 +145,18 @@ def main():
     del trainers, step
     torch.cuda.empty_cache()
 
+    report(res, a.out, L, ST, a)
+
+
+def report(res, out, L, ST, a):
     # the kernels alone (bf16 logits, as the step hands them over)
     res["kernel_us"] = {f"{rows}x{n}": kernels_alone(L, ST, rows, n, a.reps, a.kernel_iters) for rows, n in ((512, 1000), (256, 2000))}
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
         json.dump(res, f, indent=1)
     short = lambda d: {k: [round(v["median"], 4), round(v["min"], 4), round(v["max"], 4)] for k, v in d.items()}
-    print("train_step_ms", json.dumps(short(res["train_step_ms"])))
+    if "train_step_ms" in res:
+        print("train_step_ms", json.dumps(short(res["train_step_ms"])))
     for shape, d in res["kernel_us"].items():
         print("kernel_us", shape, json.dumps(short(d)))
 

@@ -217,6 +217,10 @@ static_assert(sizeof(vqa_group_hyper) == 128 && alignof(vqa_group_hyper) == 16 &
 
 #define VQA_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
 
+// dst0[c] (c < n0) / dst1[c - n0] += sum over rows r < nrows of part[r * stride + c], rows in index order (fold_rows_kernel).  Defined in
+// token_ops.hip, where the kernel lives: other translation units launch it through this, so its device code exists once.
+void vqa_launch_fold(const float* part, int nrows, size_t stride, int ncols, float* dst0, int n0, float* dst1, hipStream_t st);
+
 // ------------------------------------------------------------------------------------------------------------------
 // Dynamic LDS above the default limit: every launch site calls vqa_ensure_lds(kernel, bytes) before its launch.  The largest size
 // set so far is remembered per (kernel, device) in a fixed lock-free table, so the common case is one hipGetDevice and a few atomic

@@ -1,11 +1,11 @@
 // Token-side kernels for gfx950: embedding+positional encoding, LayerNorm, multi-head attention
 // (self: keys masked with -inf, cross: unmasked), masked mean-pool, sigmoid gate, bias/ReLU/dropout
-// backward, the losses, the metrics and the dtype casts.  (The optimizer tail -- L2 norm, clip, AdamW, weight EMA -- is optim_ops.hip.)
+// backward, the fixed-order folds and the dtype casts.  (The optimizer tail -- L2 norm, clip, AdamW, weight EMA -- is optim_ops.hip;
+// everything that reads the answer logits -- losses, metrics, answer scores, top-k -- is loss_ops.hip.)
 //   embedding*sqrt(d)+pe      models/text_encoder.py:504-510, :112-114
 //   LayerNorm                 models/text_encoder.py:390,395,519 ; cross_attention.py:286-287,295 ; fusion.py:326
 //   attention                 models/text_encoder.py:237-258 ; models/cross_attention.py:176-198
 //   masked mean / gate        models/fusion.py:303-320, :160-166
-//   CE                        training/train.py:120
 // Rows are tokens ([B*L][D], D contiguous).  One 64-lane wave owns one row / one (batch, head).
 #include <cstdlib>
 #include "common.h"
@@ -61,7 +61,8 @@ __global__ __launch_bounds__(1024) void fold_rows_kernel(const float* __restrict
     if (c < n0) dst0[c] += a; else dst1[c - n0] += a;
   }
 }
-static inline void launch_fold(const float* part, int nrows, size_t stride, int ncols, float* dst0, int n0, float* dst1, hipStream_t st) {
+// (declared in common.h: loss_ops.hip folds its row terms through it, so the kernel's device code exists once)
+void vqa_launch_fold(const float* part, int nrows, size_t stride, int ncols, float* dst0, int n0, float* dst1, hipStream_t st) {
   hipLaunchKernelGGL(fold_rows_kernel, dim3((ncols + 63) / 64), dim3(64, 16), 0, st, part, nrows, stride, ncols, dst0, n0, dst1);
 }
 // Many folds in one launch: the parameter gradients they produce are only read by the optimizer at the end of the step, so the engine
@@ -731,41 +732,6 @@ __global__ __launch_bounds__(256) void bias_act_bwd_vec_kernel(const T* __restri
   }
 }
 
-// cross entropy (mean) forward+backward in one pass: wave per row
-template <typename T>
-__global__ __launch_bounds__(256) void cross_entropy_kernel(const T* __restrict__ logits, const long long* __restrict__ targets, float* loss,
-                                                            T* __restrict__ dlogits, float* __restrict__ logits_f32, int B, int N, float gscale,
-                                                            int* err, float* part) {
-  const int lane = threadIdx.x & 63;
-  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (row < B) {
-    const T* lr = logits + (size_t)row * N;
-    float m = -INFINITY;
-    for (int c = lane; c < N; c += 64) m = fmaxf(m, to_f<T>(lr[c]));
-    m = wave_max(m);
-    float s = 0.f;
-    for (int c = lane; c < N; c += 64) s += expf(to_f<T>(lr[c]) - m);
-    s = wave_sum(s);
-    const long long t64 = targets[row];
-    // a target outside [0, N) raises in the reference (nn.CrossEntropyLoss, training/train.py:120): never read out of bounds,
-    // count the row in *err (the host mirror raises from it) and poison its loss term and gradient row with NaN
-    const bool bad = t64 < 0 || t64 >= (long long)N;
-    const int t = bad ? 0 : (int)t64;
-    const float lse = m + logf(s);
-    if (lane == 0) {
-      const float term = bad ? __builtin_nanf("") : (lse - to_f<T>(lr[t])) / (float)B;
-      if (part) part[row] = term;
-      else if (loss) atomicAdd(loss, term);
-      if (bad && err) atomicAdd(err, 1);
-    }
-    for (int c = lane; c < N; c += 64) {
-      const float x = to_f<T>(lr[c]);
-      if (logits_f32) logits_f32[(size_t)row * N + c] = x;
-      if (dlogits) dlogits[(size_t)row * N + c] = from_f<T>(bad ? __builtin_nanf("") : (expf(x - lse) - (c == t ? 1.f : 0.f)) * gscale / (float)B);
-    }
-  }
-}
-
 template <typename TI, typename TO>
 __global__ void convert_kernel(const TI* __restrict__ in, TO* __restrict__ out, size_t n) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -873,7 +839,7 @@ int vqa_layernorm_bwd(int dtype, const void* dout, const void* x, const float* g
     dim3 grid(g.gx, g.gy);
     DT(hipLaunchKernelGGL(colsum_rows_kernel<float>, grid, dim3(256), 0, st, (const float*)dout, dadd, Bb, g.N, part_cs),
        hipLaunchKernelGGL(colsum_rows_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)dout, dadd, Bb, g.N, part_cs));
-    if (part_cs && !defer_fold) launch_fold(part_cs, (int)g.gy, g.N, (int)g.N, dadd, (int)g.N, nullptr, st);
+    if (part_cs && !defer_fold) vqa_launch_fold(part_cs, (int)g.gy, g.N, (int)g.N, dadd, (int)g.N, nullptr, st);
     dadd = nullptr;
   }
   if (dtype && D % 8 == 0) {                               // vectorised bf16 path, >= 4 rows per wave, at most one workgroup per CU
@@ -883,7 +849,7 @@ int vqa_layernorm_bwd(int dtype, const void* dout, const void* x, const float* g
     DT(hipLaunchKernelGGL(layernorm_bwd_kernel<float>, dim3(g.nb), dim3(256), 0, st, (const float*)dout, (const float*)x, gamma, stats, (const float*)addend, (float*)dx, dgamma, dbeta, rows, D, p, seed, dadd, period, part_ln),
        hipLaunchKernelGGL(layernorm_bwd_kernel<bf16_t>, dim3(g.nb), dim3(256), 0, st, (const bf16_t*)dout, (const bf16_t*)x, gamma, stats, (const bf16_t*)addend, (bf16_t*)dx, dgamma, dbeta, rows, D, p, seed, dadd, period, part_ln));
   }
-  if (part_ln && !defer_fold) launch_fold(part_ln, g.nb, (size_t)2 * D, 2 * D, dgamma, D, dbeta, st);
+  if (part_ln && !defer_fold) vqa_launch_fold(part_ln, g.nb, (size_t)2 * D, 2 * D, dgamma, D, dbeta, st);
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
 int vqa_attention_fwd(int dtype, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const float* kmask, float* probs,
@@ -1018,7 +984,7 @@ int vqa_bias_act_bwd(int dtype, const void* dout, const void* outact, void* dz, 
     DT(hipLaunchKernelGGL(bias_act_bwd_kernel<float>, g.grid, dim3(256), 0, st, (const float*)dout, (const float*)outact, (float*)dz, dbias, M, N, 0, p, seed, ws),
        hipLaunchKernelGGL(bias_act_bwd_kernel<bf16_t>, g.grid, dim3(256), 0, st, (const bf16_t*)dout, (const bf16_t*)outact, (bf16_t*)dz, dbias, M, N, 0, p, seed, ws));
   }
-  if (ws && dbias && !defer_fold) launch_fold(ws, (int)g.grid.y, (size_t)N, N, dbias, N, nullptr, st);
+  if (ws && dbias && !defer_fold) vqa_launch_fold(ws, (int)g.grid.y, (size_t)N, N, dbias, N, nullptr, st);
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
 // dst0_j[c] (c < n0_j) / dst1_j[c - n0_j] += sum over rows r < nrows_j of part_j[r * stride_j + c], rows in index order -- the deferred folds of
@@ -1039,17 +1005,6 @@ int vqa_fold_group(int njobs, const float* const* part, const int* nrows, const 
     }
     hipLaunchKernelGGL(fold_group_kernel, dim3(g.blk0[g.n]), dim3(64, 16), 0, st, g);
   }
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-// ws (B floats or nullptr): the per-row loss terms are summed in row order by a second launch (bit-reproducible); nullptr -> one
-// float atomic per row.  *loss is accumulated into (+=): zero it first.
-int vqa_cross_entropy(int dtype, const void* logits, const long long* targets, float* loss, void* dlogits, float* logits_f32, int B, int N,
-                      float gscale, int* err, float* ws, hipStream_t st) {
-  if (!logits || !targets || B <= 0 || N <= 0) return VQA_EARG;
-  dim3 grid((B + 3) / 4);
-  DT(hipLaunchKernelGGL(cross_entropy_kernel<float>, grid, dim3(256), 0, st, (const float*)logits, targets, loss, (float*)dlogits, logits_f32, B, N, gscale, err, ws),
-     hipLaunchKernelGGL(cross_entropy_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)logits, targets, loss, (bf16_t*)dlogits, logits_f32, B, N, gscale, err, ws));
-  if (ws && loss) launch_fold(ws, B, 1, 1, loss, 1, nullptr, st);        // B "rows" of one column
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
 // dtype_in / dtype_out: 0 = f32, 1 = bf16
@@ -1444,537 +1399,6 @@ extern "C" int vqa_attention_bwd_mfma_dp(const void* dctx, int ldc, const void* 
                                          const float* probs, const float* dprobs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv,
                                          int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t st) {
   return attention_bwd_mfma<true>(dctx, ldc, q, k, v, ldq, ldk, ldv, probs, dprobs, dq, dk, dv, lddq, lddk, lddv, B, H, Lq, Lk, hd, p, seed, st);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Device-side accuracy counters (utils/metrics.py:55-94 VQAAccuracy.update without its .cpu()/.item() syncs).
-// One wave per sample: rank of the target = #{j : x[j] > x[t]} + #{j < t : x[j] == x[t]} (ties resolve to the lowest index,
-// like argmax); top-1 correct <=> rank == 0, top-5 correct <=> rank < 5.  counters = {correct, correct_top5, total} (u64, +=).
-// A target outside [0, N) counts as wrong (the reference's comparison can never match it either).
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void accuracy_kernel(const float* __restrict__ logits, const long long* __restrict__ targets,
-                                                       unsigned long long* counters, int B, int N) {
-  const int lane = threadIdx.x & 63;
-  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (row >= B) return;
-  const long long t = targets[row];
-  const float* x = logits + (size_t)row * N;
-  float cnt = 0.f;
-  const bool valid = t >= 0 && t < N;
-  if (valid) {
-    const float xt = x[t];
-    for (int j = lane; j < N; j += 64) {
-      const float v = x[j];
-      cnt += (v > xt || (v == xt && j < (int)t)) ? 1.f : 0.f;
-    }
-  }
-  cnt = wave_sum(cnt);
-  if (lane == 0) {
-    if (valid && cnt < 0.5f) atomicAdd(counters + 0, 1ull);
-    if (valid && cnt < 4.5f) atomicAdd(counters + 1, 1ull);
-    atomicAdd(counters + 2, 1ull);
-  }
-}
-
-extern "C" int vqa_accuracy_update(const float* logits, const long long* targets, unsigned long long* counters, int B, int N, hipStream_t st) {
-  if (!logits || !targets || !counters || B <= 0 || N <= 0) return VQA_EARG;
-  hipLaunchKernelGGL(accuracy_kernel, dim3((B + 3) / 4), dim3(256), 0, st, logits, targets, counters, B, N);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Top-k answers with their softmax probabilities (the tail of VQAModel.predict / api/inference.py:228-246: softmax + topk), one
-// launch, one wave per row.  y[j] = logits[j] where allowed (or without a mask), else -inf.  Index a ranks before b when
-// y[a] > y[b], or y[a] == y[b] and a < b (accuracy_kernel's lowest-index tie rule); NaN ranks above every number, NaNs among
-// themselves by index: torch.sort(y, descending=True, stable=True).  The order is decided on y alone, through an order-preserving
-// 32-bit key (NaN -> all ones, -0 == +0) joined with the reversed index into one 64-bit word, so a pick is an integer maximum.
-// probs = exp(scale * y - m) / sum_j exp(scale * y[j] - m), m = max_j scale * y[j] (NaNs skipped by the max, so a row that holds a
-// NaN, or nothing but -inf, gives NaN for every probability as torch.softmax does).  K rounds, each the best word strictly below the
-// previous pick: no per-row state, no atomics, no LDS.
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t topk_key(float y) {
-  if (y != y) return 0xffffffffu;
-  uint32_t b = __float_as_uint(y);
-  if (b == 0x80000000u) b = 0u;
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float topk_val(uint32_t k) {          // inverse of topk_key (the all-ones key gives a NaN)
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-__device__ __forceinline__ unsigned long long topk_word(uint32_t key, int j) {
-  return ((unsigned long long)key << 32) | (unsigned long long)(0x7fffffffu - (uint32_t)j);
-}
-__device__ __forceinline__ float topk_arg(float scale, float y, float m) {      // scale * y - m with both roundings (never one fma)
-#pragma clang fp contract(off)
-  const float s = scale * y;
-  return s - m;
-}
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint32_t hi = __shfl_xor((uint32_t)(v >> 32), o, 64), lo = __shfl_xor((uint32_t)v, o, 64);
-    const unsigned long long w = ((unsigned long long)hi << 32) | lo;
-    v = w > v ? w : v;
-  }
-  return v;
-}
-
-// The row is read again in each of the K + 2 passes (L2-resident: 4 KB at N = 1000).
-template <typename T>
-__global__ __launch_bounds__(256) void softmax_topk_kernel(const T* __restrict__ logits, long long ld, const unsigned char* __restrict__ allowed,
-                                                           long long allowed_ld, float scale, long long* __restrict__ idx,
-                                                           float* __restrict__ probs, float* __restrict__ logits_f, int B, int N, int K) {
-  const int lane = threadIdx.x & 63;
-  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (row >= B) return;
-  const T* x = logits + (size_t)row * ld;
-  const unsigned char* al = allowed ? allowed + (size_t)row * allowed_ld : nullptr;
-  float* xf = logits_f ? logits_f + (size_t)row * N : nullptr;
-  auto y_at = [&](int j) -> float {
-    const float v = to_f<T>(x[j]);
-    return (al && !al[j]) ? -INFINITY : v;
-  };
-  // pass 1: raw fp32 copy, row maximum of scale * y
-  float m = -INFINITY;
-  for (int j = lane; j < N; j += 64) {
-    if (xf) xf[j] = to_f<T>(x[j]);
-    m = fmaxf(m, scale * y_at(j));
-  }
-  m = wave_max(m);
-  // pass 2: denominator, per lane in index order, then the butterfly (a fixed order: bit-reproducible)
-  float sum = 0.f;
-  for (int j = lane; j < N; j += 64) sum += expf(topk_arg(scale, y_at(j), m));
-  sum = wave_sum(sum);
-  // K rounds of selection; lane r keeps pick r
-  unsigned long long prev = ~0ull, mine = 0ull;
-  for (int r = 0; r < K; ++r) {
-    unsigned long long best = 0ull;
-    for (int j = lane; j < N; j += 64) {
-      const unsigned long long c = topk_word(topk_key(y_at(j)), j);
-      if (c < prev && c > best) best = c;
-    }
-    best = wave_max_u64(best);
-    prev = best;
-    if (lane == r) mine = best;
-  }
-  if (lane < K) {
-    const float y = topk_val((uint32_t)(mine >> 32));
-    idx[(size_t)row * K + lane] = (long long)(0x7fffffffu - (uint32_t)mine);
-    probs[(size_t)row * K + lane] = expf(topk_arg(scale, y, m)) / sum;
-  }
-}
-
-template <typename T>
-static void launch_softmax_topk(const void* logits, long long ld, const unsigned char* allowed, long long allowed_ld, float scale, long long* idx,
-                                float* probs, float* logits_f, int B, int N, int K, hipStream_t st) {
-  hipLaunchKernelGGL(softmax_topk_kernel<T>, dim3((B + 3) / 4), dim3(256), 0, st, (const T*)logits, ld, allowed, allowed_ld, scale, idx, probs,
-                     logits_f, B, N, K);
-}
-
-extern "C" int vqa_softmax_topk(int dtype, const void* logits, long long ld, const unsigned char* allowed, long long allowed_ld, float scale,
-                                long long* idx, float* probs, float* logits_f, int B, int N, int K, hipStream_t st) {
-  if (!logits || !idx || !probs || B < 1 || N < 1 || K < 1 || K > 64 || K > N || ld < N || (allowed_ld != 0 && allowed_ld < N)
-      || !(scale > 0.f) || !(scale <= 3.402823466e38f) || (dtype != 0 && dtype != 1)) return VQA_EARG;
-  DT(launch_softmax_topk<float>(logits, ld, allowed, allowed_ld, scale, idx, probs, logits_f, B, N, K, st),
-     launch_softmax_topk<bf16_t>(logits, ld, allowed, allowed_ld, scale, idx, probs, logits_f, B, N, K, st));
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Soft answer scores (VQA v2: ten annotator answers per question, acc(ans) = min(1, #agreeing annotators / 3),
-// utils/metrics.py:12-19, :136-184 VQAChallengeAccuracy).
-//   vqa_answer_scores              annotator ids [B][A] -> sparse soft targets {ids, counts, weights} [B][A], one wave per question
-//   vqa_cross_entropy_soft         cross_entropy_kernel with sum_k w_k * onehot(id_k) in place of the one-hot target; the challenge
-//                                  accuracy of the same rows rides along (the arg-max is the lowest index that holds the row maximum
-//                                  the softmax needs anyway)
-//   vqa_challenge_accuracy_update  the metric alone (evaluation)
-// The metric is counted in integer THIRDS: acc[0] += min(3, votes for the arg-max), acc[1] += 1 per question -- exact and
-// independent of the order the rows arrive in.  The four rows of a workgroup are added up in LDS first: one atomic pair per
-// workgroup instead of one per row (atomics on one address are serialised).
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int lane_i(int v, int k) { return __builtin_amdgcn_readlane(v, k); }                    // k wave-uniform
-__device__ __forceinline__ float lane_f(float v, int k) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), k)); }
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-// votes for class `best` among the row's slots (lane k < K holds slot k), capped at 3; the same value in every lane
-__device__ __forceinline__ int row_thirds(int best, int id, int cnt, int K, int lane) {
-  int votes = (lane < K && id == best) ? cnt : 0;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) votes += __shfl_xor(votes, o, 64);
-  return min(3, max(0, votes));
-}
-// every thread of the workgroup calls this (it holds a barrier); `thirds` < 0: this wave has no row
-__device__ __forceinline__ void block_add_thirds(unsigned long long* acc, int thirds) {
-  __shared__ int sh[4];
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = thirds;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t = 0ull, n = 0ull;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) if (sh[w] >= 0) { t += (unsigned long long)sh[w]; n += 1ull; }
-    if (n) { atomicAdd(acc + 0, t); atomicAdd(acc + 1, n); }
-  }
-}
-
-__global__ __launch_bounds__(256) void answer_scores_kernel(const long long* __restrict__ answers, int* __restrict__ ids, float* __restrict__ weights,
-                                                            int* __restrict__ counts, int B, int A, int N, int mode, int* err) {
-  const int lane = threadIdx.x & 63;
-  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (row >= B) return;
-  const long long a = lane < A ? answers[(size_t)row * A + lane] : -1ll;
-  const bool valid = a >= 0 && a < (long long)N;                       // -1: the annotator's answer is not in the vocabulary
-  const bool rowbad = __ballot(a < -1ll || a >= (long long)N) != 0ull;
-  const int ai = valid ? (int)a : -1;                                  // (a valid id is below N: it fits)
-  int cnt = 0, earlier = 0;
-  for (int j = 0; j < A; ++j) {
-    const int aj = lane_i(ai, j);                                      // read by EVERY lane: never under a divergent condition
-    const int same = (valid && aj == ai) ? 1 : 0;
-    cnt += same;
-    earlier += j < lane ? same : 0;
-  }
-  const bool first = valid && earlier == 0;
-  const unsigned long long firsts = __ballot(first);                  // distinct ids, in order of first occurrence
-  const int slot = __popcll(firsts & ((1ull << lane) - 1ull)), nslots = __popcll(firsts);
-  float w = first ? fminf(1.f, (float)cnt / 3.f) : 0.f;
-  if (mode == 1) {                                                     // rows sum to one: the sum is taken in slot order
-    float s = 0.f;
-    for (unsigned long long m = firsts; m; m &= m - 1ull) s += __shfl(w, __ffsll((long long)m) - 1, 64);
-    if (first && s > 0.f) w = w / s;
-  }
-  const size_t o = (size_t)row * A;
-  if (rowbad) {                                                        // slot 0 carries the id N: the loss kernel rejects the row
-    if (lane < A) { ids[o + lane] = lane == 0 ? N : -1; weights[o + lane] = 0.f; counts[o + lane] = 0; }
-    if (lane == 0 && err) atomicAdd(err, 1);
-    return;
-  }
-  if (first) { ids[o + slot] = (int)a; weights[o + slot] = w; counts[o + slot] = cnt; }
-  if (lane >= nslots && lane < A) { ids[o + lane] = -1; weights[o + lane] = 0.f; counts[o + lane] = 0; }
-}
-
-// cross_entropy_kernel's operation order (max, sum of exp, lse, the store loop); with K = 1 and weight 1 every value is the same bits
-template <typename T>
-__global__ __launch_bounds__(256) void cross_entropy_soft_kernel(const T* __restrict__ logits, const int* __restrict__ ids, const float* __restrict__ weights,
-                                                                 int K, float* loss, T* __restrict__ dlogits, float* __restrict__ logits_f32, int B, int N,
-                                                                 float gscale, int* err, float* part, const int* __restrict__ counts, unsigned long long* acc) {
-  const int lane = threadIdx.x & 63;
-  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  int thirds = -1;
-  if (row < B) {
-    const T* lr = logits + (size_t)row * N;
-    float m = -INFINITY;
-    for (int c = lane; c < N; c += 64) m = fmaxf(m, to_f<T>(lr[c]));
-    m = wave_max(m);
-    float s = 0.f;
-    int best = N;
-    for (int c = lane; c < N; c += 64) {
-      const float x = to_f<T>(lr[c]);
-      s += expf(x - m);
-      if (x == m) best = min(best, c);                                 // arg-max, ties -> lowest index (c ascends per lane)
-    }
-    s = wave_sum(s);
-    // lane k holds slot k: id -1 is an empty slot; an id < -1 or >= N is handled like a bad hard target (never read out of bounds,
-    // the row is counted in *err, its loss term and gradient row are NaN)
-    const int id = lane < K ? ids[(size_t)row * K + lane] : -1;
-    const bool used = id >= 0 && id < N;
-    const bool bad = __ballot(id < -1 || id >= N) != 0ull;
-    const float w = used ? weights[(size_t)row * K + lane] : 0.f;
-    const float xk = used ? to_f<T>(lr[id]) : 0.f;
-    float W = 0.f, dot = 0.f;
-    for (int k = 0; k < K; ++k) {                                      // slot order: W = sum_k w_k, dot = sum_k w_k * x[id_k]
-      const float wk = lane_f(w, k);
-      W += wk;
-      dot += wk * lane_f(xk, k);
-    }
-    const float lse = m + logf(s);
-    if (lane == 0) {
-      const float term = bad ? __builtin_nanf("") : (W * lse - dot) / (float)B;
-      if (part) part[row] = term;
-      else if (loss) atomicAdd(loss, term);
-      if (bad && err) atomicAdd(err, 1);
-    }
-    for (int c = lane; c < N; c += 64) {
-      const float x = to_f<T>(lr[c]);
-      if (logits_f32) logits_f32[(size_t)row * N + c] = x;
-      if (dlogits) {
-        float t = 0.f;
-        for (int k = 0; k < K; ++k) {                                  // duplicates add up
-          const int idk = lane_i(id, k);
-          const float wk = lane_f(w, k);
-          t += idk == c ? wk : 0.f;
-        }
-        dlogits[(size_t)row * N + c] = from_f<T>(bad ? __builtin_nanf("") : (W * expf(x - lse) - t) * gscale / (float)B);
-      }
-    }
-    if (acc) thirds = row_thirds(wave_min_i(best), id, lane < K ? counts[(size_t)row * K + lane] : 0, K, lane);
-  }
-  if (acc) block_add_thirds(acc, thirds);
-}
-
-__global__ __launch_bounds__(256) void challenge_accuracy_kernel(const float* __restrict__ logits, const int* __restrict__ ids, const int* __restrict__ counts,
-                                                                 int K, unsigned long long* acc, int B, int N) {
-  const int lane = threadIdx.x & 63;
-  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  int thirds = -1;
-  if (row < B) {
-    const float* x = logits + (size_t)row * N;
-    float m = -INFINITY;
-    for (int c = lane; c < N; c += 64) m = fmaxf(m, x[c]);
-    m = wave_max(m);
-    int best = N;
-    for (int c = lane; c < N; c += 64) if (x[c] == m) best = min(best, c);
-    thirds = row_thirds(wave_min_i(best), lane < K ? ids[(size_t)row * K + lane] : -1, lane < K ? counts[(size_t)row * K + lane] : 0, K, lane);
-  }
-  block_add_thirds(acc, thirds);
-}
-
-extern "C" int vqa_answer_scores(const long long* answers, int* ids, float* weights, int* counts, int B, int A, int N, int mode, int* err,
-                                 hipStream_t st) {
-  if (!answers || !ids || !weights || !counts || B <= 0 || A <= 0 || A > 64 || N <= 0 || (mode != 0 && mode != 1)) return VQA_EARG;
-  hipLaunchKernelGGL(answer_scores_kernel, dim3((B + 3) / 4), dim3(256), 0, st, answers, ids, weights, counts, B, A, N, mode, err);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-// vqa_cross_entropy with sparse soft targets; ws as there (B floats: the row terms are folded in row order, bit-reproducible)
-extern "C" int vqa_cross_entropy_soft(int dtype, const void* logits, const int* ids, const float* weights, int K, float* loss, void* dlogits,
-                                      float* logits_f32, int B, int N, float gscale, int* err, float* ws, const int* counts,
-                                      unsigned long long* acc, hipStream_t st) {
-  if (!logits || !ids || !weights || K <= 0 || K > 64 || B <= 0 || N <= 0 || (acc && !counts)) return VQA_EARG;
-  dim3 grid((B + 3) / 4);
-  DT(hipLaunchKernelGGL(cross_entropy_soft_kernel<float>, grid, dim3(256), 0, st, (const float*)logits, ids, weights, K, loss, (float*)dlogits, logits_f32,
-                        B, N, gscale, err, ws, counts, acc),
-     hipLaunchKernelGGL(cross_entropy_soft_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)logits, ids, weights, K, loss, (bf16_t*)dlogits, logits_f32,
-                        B, N, gscale, err, ws, counts, acc));
-  if (ws && loss) launch_fold(ws, B, 1, 1, loss, 1, nullptr, st);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-extern "C" int vqa_challenge_accuracy_update(const float* logits, const int* ids, const int* counts, int K, unsigned long long* acc, int B, int N,
-                                             hipStream_t st) {
-  if (!logits || !ids || !counts || !acc || K <= 0 || K > 64 || B <= 0 || N <= 0) return VQA_EARG;
-  hipLaunchKernelGGL(challenge_accuracy_kernel, dim3((B + 3) / 4), dim3(256), 0, st, logits, ids, counts, K, acc, B, N);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Sigmoid + binary cross-entropy against the soft answer scores (the VQA v2 recipe: every answer is its own yes/no problem, so
-// several annotator answers can be right at once and a question without an in-vocabulary answer still pushes every logit down).
-//   loss    += (1/B) * sum_b sum_c [ max(x,0) + log1p(exp(-|x|)) - x*t ]      (F.binary_cross_entropy_with_logits, "sum", / B)
-//   dlogits  = (sigmoid(x) - t) * gscale / B
-// with cross_entropy_soft_kernel's sparse t, its layout (one wave per question, lane k holds slot k), its bad-target rule, its
-// ws / fold and its fused challenge accuracy.  The softplus sum runs over the whole row (lane c takes c, c + 64, ... in ascending
-// order, then the butterfly); the x*t part comes from the K slots in slot order, as the soft kernel forms `dot`.  Both forms are
-// the stable ones: exp only ever sees -|x|, so x = +-90 stays finite, and sigmoid(x) = {1, e} / (1 + e) with e = exp(-|x|).
-// A row with t == 0 everywhere is NOT a zero row here (under cross-entropy it is): it gets sigmoid(x) * gscale / B.
-// The column loops run a wave-uniform trip count (c0 uniform, c = c0 + lane masked by c < N), so the readlanes inside them are
-// executed by every lane.
-// ---------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void bce_soft_kernel(const T* __restrict__ logits, const int* __restrict__ ids, const float* __restrict__ weights,
-                                                       int K, float* loss, T* __restrict__ dlogits, float* __restrict__ logits_f32, int B, int N,
-                                                       float gscale, int* err, float* part, const int* __restrict__ counts, unsigned long long* acc) {
-  const int lane = threadIdx.x & 63;
-  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  int thirds = -1;
-  if (row < B) {                                                         // (wave-uniform: a wave owns one row)
-    const T* lr = logits + (size_t)row * N;
-    float m = -INFINITY;
-    if (acc) {
-      for (int c = lane; c < N; c += 64) m = fmaxf(m, to_f<T>(lr[c]));
-      m = wave_max(m);
-    }
-    float sp = 0.f;
-    int best = N;
-    for (int c = lane; c < N; c += 64) {
-      const float x = to_f<T>(lr[c]);
-      sp += fmaxf(x, 0.f) + log1pf(expf(-fabsf(x)));
-      if (acc && x == m) best = min(best, c);                            // arg-max, ties -> lowest index (c ascends per lane)
-    }
-    sp = wave_sum(sp);
-    // the slots, exactly as in cross_entropy_soft_kernel: -1 is empty, an id < -1 or >= N is never read and rejects the row
-    const int id = lane < K ? ids[(size_t)row * K + lane] : -1;
-    const bool used = id >= 0 && id < N;
-    const bool bad = __ballot(id < -1 || id >= N) != 0ull;
-    const float w = used ? weights[(size_t)row * K + lane] : 0.f;
-    const float xk = used ? to_f<T>(lr[id]) : 0.f;
-    float dot = 0.f;
-    for (int k = 0; k < K; ++k) dot += lane_f(w, k) * lane_f(xk, k);     // slot order: sum_k w_k * x[id_k] = sum_c x[c] * t[c]
-    if (lane == 0) {
-      const float term = bad ? __builtin_nanf("") : (sp - dot) / (float)B;
-      if (part) part[row] = term;
-      else if (loss) atomicAdd(loss, term);
-      if (bad && err) atomicAdd(err, 1);
-    }
-    if (dlogits || logits_f32) {
-      for (int c0 = 0; c0 < N; c0 += 64) {                               // uniform trip count: every lane runs the readlanes below
-        const int c = c0 + lane;
-        const bool in = c < N;
-        const float x = in ? to_f<T>(lr[c]) : 0.f;
-        if (in && logits_f32) logits_f32[(size_t)row * N + c] = x;
-        if (dlogits) {
-          float t = 0.f;
-          for (int k = 0; k < K; ++k) {                                  // duplicates add up
-            const int idk = lane_i(id, k);
-            const float wk = lane_f(w, k);
-            t += idk == c ? wk : 0.f;
-          }
-          const float e = expf(-fabsf(x));
-          const float sg = (x >= 0.f ? 1.f : e) / (1.f + e);
-          if (in) dlogits[(size_t)row * N + c] = from_f<T>(bad ? __builtin_nanf("") : (sg - t) * gscale / (float)B);
-        }
-      }
-    }
-    if (acc) thirds = row_thirds(wave_min_i(best), id, lane < K ? counts[(size_t)row * K + lane] : 0, K, lane);
-  }
-  if (acc) block_add_thirds(acc, thirds);                                // (holds a barrier: reached by every thread, row or not)
-}
-
-// vqa_cross_entropy_soft's arguments; nothing is launched on an argument error
-extern "C" int vqa_bce_soft(int dtype, const void* logits, const int* ids, const float* weights, int K, float* loss, void* dlogits,
-                            float* logits_f32, int B, int N, float gscale, int* err, float* ws, const int* counts, unsigned long long* acc,
-                            hipStream_t st) {
-  if (!logits || !ids || !weights || K < 1 || K > 64 || B < 1 || N < 1 || (acc && !counts) || (dtype != 0 && dtype != 1)) return VQA_EARG;
-  if (!(fabsf(gscale) <= 3.402823466e38f)) return VQA_EARG;              // (NaN fails the comparison too)
-  dim3 grid((B + 3) / 4);
-  DT(hipLaunchKernelGGL(bce_soft_kernel<float>, grid, dim3(256), 0, st, (const float*)logits, ids, weights, K, loss, (float*)dlogits, logits_f32,
-                        B, N, gscale, err, ws, counts, acc),
-     hipLaunchKernelGGL(bce_soft_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)logits, ids, weights, K, loss, (bf16_t*)dlogits, logits_f32,
-                        B, N, gscale, err, ws, counts, acc));
-  if (ws && loss) launch_fold(ws, B, 1, 1, loss, 1, nullptr, st);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Cross entropy with nn.CrossEntropyLoss's constructor options (training/train.py:120): class weights w[N], ignore_index and label
-// smoothing eps, reduction "mean".  keep[b] = target b is not ignore_index, wy[b] = keep[b] * w[t_b], W = sum_b wy[b],
-// Sw = sum_c w[c], lp = log_softmax(x):
-//   loss    += [ (1-eps) * sum_b wy[b] * (-lp[b][t_b]) + eps/N * sum_b keep[b] * sum_c w[c] * (-lp[b][c]) ] / W
-//   dlogits  = [ (1-eps) * wy[b] * (p[b][c] - [c == t_b]) + eps/N * keep[b] * (Sw * p[b][c] - w[c]) ] * gscale / W
-// One wave per row and cross_entropy_kernel's operation order; without weights, smoothing and ignored rows W is (float)B, the
-// factor (1-eps) * wy is 1.0f and the smoothing branch is not taken: the same bits as cross_entropy_kernel.
-// W and Sw are needed before the first gradient element: EVERY wave sums the B gathered weights and the N weights itself, lane c
-// taking the indices c, c + 64, ... in ascending order and then the butterfly -- one fixed order, the same bits in every wave, no
-// second launch and no host sync.  (Without weights W is a count of kept rows, taken in integers.)
-// sum_c w[c] * lp[c] = sum_c w[c] * (x[c] - m) - log(s) * Sw rides in the pass that forms s = sum exp(x - m); x - m instead of the
-// plain x keeps the cancellation against lse * Sw out of it when a row sits at +-300.  With weights or smoothing the whole row is
-// evaluated in that log-softmax form, lp = (x - m) - log(s), which stays at fp32 accuracy for rows far from zero; without them
-// the kernel keeps cross_entropy_kernel's lse = m + log(s), lse - x_t and exp(x - lse) for its bits (and its accuracy there).
-// A bad target (outside [0, N) and not ignore_index) is cross_entropy_kernel's: *err += 1, NaN term, NaN row; it counts in W with
-// weight 1 (unweighted: W = number of rows that are not ignored, so the default call divides by B like cross_entropy_kernel).
-// W == 0 (every row ignored, or every kept row has weight 0): the loss is NaN as in torch, dlogits is ZERO (torch: zero
-// unweighted, NaN weighted -- a deliberate deviation, the step then runs on a zero gradient) and *empty += 1.
-// acc = VQAAccuracy's {correct, correct_top5, total} over the kept rows with accuracy_kernel's rank rule, in the same pass.
-// ---------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void cross_entropy_opts_kernel(const T* __restrict__ logits, const long long* __restrict__ targets,
-                                                                 const float* __restrict__ cw, long long ignore_index, int has_ignore, float eps,
-                                                                 float* loss, T* __restrict__ dlogits, float* __restrict__ logits_f32, int B, int N,
-                                                                 float gscale, int* err, float* part, unsigned long long* acc, int* empty) {
-  const int lane = threadIdx.x & 63;
-  const int row = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  if (row >= B) return;                                                 // (wave-uniform: a wave owns one row)
-  float W, Sw;
-  if (cw) {
-    float a = 0.f;
-    for (int b = lane; b < B; b += 64) {
-      const long long tb = targets[b];
-      float w = 0.f;
-      if (!(has_ignore && tb == ignore_index)) {
-        w = 1.f;                                                        // a bad target: never read out of bounds
-        if (tb >= 0 && tb < (long long)N) w = cw[tb];
-      }
-      a += w;
-    }
-    W = wave_sum(a);
-    a = 0.f;
-    for (int c = lane; c < N; c += 64) a += cw[c];
-    Sw = wave_sum(a);
-  } else {
-    int k = 0;
-    for (int b = lane; b < B; b += 64) k += (has_ignore && targets[b] == ignore_index) ? 0 : 1;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) k += __shfl_xor(k, o, 64);
-    W = (float)k;
-    Sw = (float)N;
-  }
-  const bool none = W == 0.f;
-  if (row == 0 && lane == 0 && none && empty) atomicAdd(empty, 1);
-  const T* lr = logits + (size_t)row * N;
-  const long long t64 = targets[row];
-  if (has_ignore && t64 == ignore_index) {                              // ignored: no loss term, a zero gradient row, not counted
-    if (lane == 0) {
-      const float term = none ? __builtin_nanf("") : 0.f;
-      if (part) part[row] = term;
-      else if (loss) atomicAdd(loss, term);
-    }
-    for (int c = lane; c < N; c += 64) {
-      if (logits_f32) logits_f32[(size_t)row * N + c] = to_f<T>(lr[c]);
-      if (dlogits) dlogits[(size_t)row * N + c] = from_f<T>(0.f);
-    }
-    return;
-  }
-  const bool bad = t64 < 0 || t64 >= (long long)N;
-  const int t = bad ? 0 : (int)t64;
-  const bool smooth = eps != 0.f;
-  const bool lsm = smooth || cw;                                        // log-softmax form (see above); else cross_entropy_kernel's
-  float m = -INFINITY;
-  for (int c = lane; c < N; c += 64) m = fmaxf(m, to_f<T>(lr[c]));
-  m = wave_max(m);
-  const float xt = to_f<T>(lr[t]);
-  float s = 0.f, wx = 0.f, rank = 0.f;
-  for (int c = lane; c < N; c += 64) {
-    const float x = to_f<T>(lr[c]);
-    s += expf(x - m);
-    if (smooth) wx += (cw ? cw[c] : 1.f) * (x - m);
-    if (acc) rank += (x > xt || (x == xt && c < t)) ? 1.f : 0.f;
-  }
-  s = wave_sum(s);
-  if (smooth) wx = wave_sum(wx);
-  if (acc) rank = wave_sum(rank);
-  const float logs = logf(s);
-  const float lse = m + logs;
-  const float c1 = (1.f - eps) * (bad || !cw ? 1.f : cw[t]);            // (1-eps) * wy
-  const float epsn = eps / (float)N;
-  if (lane == 0) {
-    float term = c1 * (lsm ? logs - (xt - m) : lse - xt);
-    if (smooth) term += epsn * (logs * Sw - wx);
-    term = (bad || none) ? __builtin_nanf("") : term / W;
-    if (part) part[row] = term;
-    else if (loss) atomicAdd(loss, term);
-    if (bad && err) atomicAdd(err, 1);
-    if (acc) {                                                          // a bad target counts as wrong, like accuracy_kernel
-      if (!bad && rank < 0.5f) atomicAdd(acc + 0, 1ull);
-      if (!bad && rank < 4.5f) atomicAdd(acc + 1, 1ull);
-      atomicAdd(acc + 2, 1ull);
-    }
-  }
-  for (int c = lane; c < N; c += 64) {
-    const float x = to_f<T>(lr[c]);
-    if (logits_f32) logits_f32[(size_t)row * N + c] = x;
-    if (dlogits) {
-      const float p = lsm ? expf((x - m) - logs) : expf(x - lse);
-      float g = c1 * (p - (c == t ? 1.f : 0.f));
-      if (smooth) g += epsn * (Sw * p - (cw ? cw[c] : 1.f));
-      g = g * gscale / W;
-      dlogits[(size_t)row * N + c] = from_f<T>(bad ? __builtin_nanf("") : (none ? 0.f : g));
-    }
-  }
-}
-
-// vqa_cross_entropy's arguments and ws (B floats or nullptr), then the options; class_weight nullptr = all ones, has_ignore 0 = no
-// target is ignored, acc / empty optional.  Nothing is launched on an argument error.
-extern "C" int vqa_cross_entropy_opts(int dtype, const void* logits, const long long* targets, float* loss, void* dlogits, float* logits_f32,
-                                      int B, int N, float gscale, int* err, float* ws, const float* class_weight, long long ignore_index,
-                                      int has_ignore, float label_smoothing, unsigned long long* acc, int* empty, hipStream_t st) {
-  if (!logits || !targets || B <= 0 || N <= 0 || (dtype != 0 && dtype != 1)) return VQA_EARG;
-  if (!(label_smoothing >= 0.f && label_smoothing <= 1.f) || !(fabsf(gscale) <= 3.402823466e38f)) return VQA_EARG;   // (NaN fails both)
-  dim3 grid((B + 3) / 4);
-  DT(hipLaunchKernelGGL(cross_entropy_opts_kernel<float>, grid, dim3(256), 0, st, (const float*)logits, targets, class_weight, ignore_index,
-                        has_ignore, label_smoothing, loss, (float*)dlogits, logits_f32, B, N, gscale, err, ws, acc, empty),
-     hipLaunchKernelGGL(cross_entropy_opts_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)logits, targets, class_weight, ignore_index,
-                        has_ignore, label_smoothing, loss, (bf16_t*)dlogits, logits_f32, B, N, gscale, err, ws, acc, empty));
-  if (ws && loss) launch_fold(ws, B, 1, 1, loss, 1, nullptr, st);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
 }
 
 // ---------------------------------------------------------------------------------------------

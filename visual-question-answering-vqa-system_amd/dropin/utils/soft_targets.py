@@ -90,41 +90,43 @@ def answer_scores(annotator_ids: torch.Tensor, num_answers: int, normalize: bool
     return SoftTargets(ids, weights, counts)
 
 
-# torch.ops.vqa_hip.soft_cross_entropy(logits, ids, weights, need_grad) -> (loss scalar, d loss / d logits or an empty tensor)
-@torch.library.custom_op("vqa_hip::soft_cross_entropy", mutates_args=(), device_types="cuda")
-def _soft_cross_entropy_op(logits: torch.Tensor, ids: torch.Tensor, weights: torch.Tensor, need_grad: bool) -> Tuple[torch.Tensor, torch.Tensor]:
-    L = _pkg()._lib
-    lg = logits.detach().contiguous()
-    B, N = lg.shape
-    loss = torch.zeros((), device=lg.device, dtype=torch.float32)
-    err = torch.zeros(1, device=lg.device, dtype=torch.int32)
-    ws = torch.empty((B,), device=lg.device, dtype=torch.float32)
-    dlogits = torch.empty_like(lg) if need_grad else lg.new_empty((0,))
-    L.call("vqa_cross_entropy_soft", L.dt(lg), lg.data_ptr(), ids.data_ptr(), weights.data_ptr(), ids.shape[1], loss.data_ptr(),
-           dlogits.data_ptr() if need_grad else None, None, B, N, 1.0, err.data_ptr(), ws.data_ptr(), None, None)
-    bad = int(err.item())                                      # the one sync of this (slow) path: nn.CrossEntropyLoss raises here too
-    if bad:
-        raise IndexError(f"{bad} row(s) with an answer id out of range [-1, {N})")
-    return loss, dlogits
+def _soft_loss_op(name: str, entry: str):
+    """Define torch.ops.vqa_hip.<name>(logits, ids, weights, need_grad) -> (loss scalar, d loss / d logits or an empty tensor): one
+    launch of the C entry `entry` (vqa_cross_entropy_soft's arguments) for the loss and its gradient, with its fake and its autograd."""
+    @torch.library.custom_op(f"vqa_hip::{name}", mutates_args=(), device_types="cuda")
+    def op(logits: torch.Tensor, ids: torch.Tensor, weights: torch.Tensor, need_grad: bool) -> Tuple[torch.Tensor, torch.Tensor]:
+        L = _pkg()._lib
+        lg = logits.detach().contiguous()
+        B, N = lg.shape
+        loss = torch.zeros((), device=lg.device, dtype=torch.float32)
+        err = torch.zeros(1, device=lg.device, dtype=torch.int32)
+        ws = torch.empty((B,), device=lg.device, dtype=torch.float32)
+        dlogits = torch.empty_like(lg) if need_grad else lg.new_empty((0,))
+        L.call(entry, L.dt(lg), lg.data_ptr(), ids.data_ptr(), weights.data_ptr(), ids.shape[1], loss.data_ptr(),
+               dlogits.data_ptr() if need_grad else None, None, B, N, 1.0, err.data_ptr(), ws.data_ptr(), None, None)
+        bad = int(err.item())                                  # the one sync of this (slow) path: nn.CrossEntropyLoss raises here too
+        if bad:
+            raise IndexError(f"{bad} row(s) with an answer id out of range [-1, {N})")
+        return loss, dlogits
+
+    @op.register_fake
+    def _(logits, ids, weights, need_grad):
+        return logits.new_empty((), dtype=torch.float32), (torch.empty_like(logits) if need_grad else logits.new_empty((0,)))
+
+    def setup(ctx, inputs, output):
+        ctx.save_for_backward(output[1])
+
+    def backward(ctx, gloss, _gdl):
+        (dlogits,) = ctx.saved_tensors
+        if dlogits.numel() == 0:
+            raise RuntimeError(f"{name} was called with need_grad=False: there is no gradient to return")
+        return dlogits * gloss.to(dlogits.dtype), None, None, None
+
+    torch.library.register_autograd(f"vqa_hip::{name}", backward, setup_context=setup)
 
 
-@_soft_cross_entropy_op.register_fake
-def _(logits, ids, weights, need_grad):
-    return logits.new_empty((), dtype=torch.float32), (torch.empty_like(logits) if need_grad else logits.new_empty((0,)))
-
-
-def _sce_setup(ctx, inputs, output):
-    ctx.save_for_backward(output[1])
-
-
-def _sce_backward(ctx, gloss, _gdl):
-    (dlogits,) = ctx.saved_tensors
-    if dlogits.numel() == 0:
-        raise RuntimeError("soft_cross_entropy was called with need_grad=False: there is no gradient to return")
-    return dlogits * gloss.to(dlogits.dtype), None, None, None
-
-
-torch.library.register_autograd("vqa_hip::soft_cross_entropy", _sce_backward, setup_context=_sce_setup)
+_soft_loss_op("soft_cross_entropy", "vqa_cross_entropy_soft")
+_soft_loss_op("soft_bce", "vqa_bce_soft")
 
 
 class SoftTargetCrossEntropy(nn.Module):
@@ -137,43 +139,6 @@ class SoftTargetCrossEntropy(nn.Module):
         soft.validate(logits.shape[0], logits.device)
         need = torch.is_grad_enabled() and logits.requires_grad
         return torch.ops.vqa_hip.soft_cross_entropy(logits, soft.ids, soft.weights, need)[0]
-
-
-# torch.ops.vqa_hip.soft_bce(logits, ids, weights, need_grad) -> (loss scalar, d loss / d logits or an empty tensor)
-@torch.library.custom_op("vqa_hip::soft_bce", mutates_args=(), device_types="cuda")
-def _soft_bce_op(logits: torch.Tensor, ids: torch.Tensor, weights: torch.Tensor, need_grad: bool) -> Tuple[torch.Tensor, torch.Tensor]:
-    L = _pkg()._lib
-    lg = logits.detach().contiguous()
-    B, N = lg.shape
-    loss = torch.zeros((), device=lg.device, dtype=torch.float32)
-    err = torch.zeros(1, device=lg.device, dtype=torch.int32)
-    ws = torch.empty((B,), device=lg.device, dtype=torch.float32)
-    dlogits = torch.empty_like(lg) if need_grad else lg.new_empty((0,))
-    L.call("vqa_bce_soft", L.dt(lg), lg.data_ptr(), ids.data_ptr(), weights.data_ptr(), ids.shape[1], loss.data_ptr(),
-           dlogits.data_ptr() if need_grad else None, None, B, N, 1.0, err.data_ptr(), ws.data_ptr(), None, None)
-    bad = int(err.item())                                      # the one sync of this (slow) path
-    if bad:
-        raise IndexError(f"{bad} row(s) with an answer id out of range [-1, {N})")
-    return loss, dlogits
-
-
-@_soft_bce_op.register_fake
-def _(logits, ids, weights, need_grad):
-    return logits.new_empty((), dtype=torch.float32), (torch.empty_like(logits) if need_grad else logits.new_empty((0,)))
-
-
-def _sbce_setup(ctx, inputs, output):
-    ctx.save_for_backward(output[1])
-
-
-def _sbce_backward(ctx, gloss, _gdl):
-    (dlogits,) = ctx.saved_tensors
-    if dlogits.numel() == 0:
-        raise RuntimeError("soft_bce was called with need_grad=False: there is no gradient to return")
-    return dlogits * gloss.to(dlogits.dtype), None, None, None
-
-
-torch.library.register_autograd("vqa_hip::soft_bce", _sbce_backward, setup_context=_sbce_setup)
 
 
 class SoftTargetBCEWithLogits(nn.Module):
