@@ -162,6 +162,22 @@ int vqa_stem_wgrad(const float* img, const void* dy, float* dw /* [64][7][7][3] 
 /* same, with the stem BN+ReLU+MaxPool backward apply fused in: dy is rebuilt per row from y, dpool, idx, coef, bcoef */
 int vqa_stem_wgrad_fused(const float* img, const void* y, const void* dpool, const uint8_t* idx, const float* coef,
                          const float* bcoef, float* dw, int B, int H, int W, float* ws, long long ws_floats, hipStream_t stream);
+/* The same four kernels fed from the uint8 HWC batch a decoder / the GPU input pipeline holds (img_hwc [B][H][W][3], a pixel at
+ * ((b*H + ih)*W + iw)*3 + c; VQA_EARG from 2^31 - 1 bytes on): `table` is the bf16 [3][256] block vqa_u8_norm_table wrote,
+ * table[c][v] = bf16((float(v)/255 - mean[c]) / std[c]) -- vqa_image_normalize's expression and the bf16 rounding the fp32 kernels
+ * apply to their input -- so every output is bit-equal to the fp32 entry's on vqa_image_normalize's (unflipped) output.  The padding
+ * outside the image is 0.0 in normalised space.  Same shapes, grids and scratch as the fp32 entries (the _blocks / _ok queries hold
+ * for both).  vqa_u8_norm_table: one workgroup; VQA_EARG for a non-finite mean or a zero / non-finite std. */
+int vqa_u8_norm_table(float mean0, float mean1, float mean2, float std0, float std1, float std2, void* table, hipStream_t stream);
+int vqa_stem_conv_u8(const uint8_t* img_hwc, const void* wstem, void* out, float* stats, int B, int H, int W, const void* table,
+                     hipStream_t stream);
+int vqa_stem_conv_pool_u8(const uint8_t* img_hwc, const void* wstem, const float* coef, void* out, int B, int H, int W, const void* table,
+                          hipStream_t stream);
+int vqa_stem_wgrad_u8(const uint8_t* img_hwc, const void* dy, float* dw, int B, int H, int W, float* ws, long long ws_floats,
+                      const void* table, hipStream_t stream);
+int vqa_stem_wgrad_fused_u8(const uint8_t* img_hwc, const void* y, const void* dpool, const uint8_t* idx, const float* coef,
+                            const float* bcoef, float* dw, int B, int H, int W, float* ws, long long ws_floats, const void* table,
+                            hipStream_t stream);
 /* Data gradient of the stem conv (the gradient with respect to the input image), an implicit GEMM over 2x2 image quads.  No atomics:
  * every image element is written exactly once (bit-reproducible).
  * vqa_stem_dgrad_pack: w_krsc [64][7][7][3] fp32 -> wpk, the packed [16][1024] operand in dtype (1: bf16, 0: fp32), 16*1024 elements.

@@ -30,6 +30,11 @@ def load_dropin_soft_targets():
     return _load_dropin_file("vqa_hip_dropin_utils_soft_targets", "utils", "soft_targets.py")
 
 
+def load_dropin_byte_images():
+    """The drop-in `utils.byte_images` (ByteImages: a uint8 HWC batch the model, the trainer and the input pipeline take as it is)."""
+    return _load_dropin_file("vqa_hip_dropin_utils_byte_images", "utils", "byte_images.py")
+
+
 def load_dropin_losses():
     """The drop-in `utils.losses` (CrossEntropyLoss with weight / ignore_index / label_smoothing as one fused launch)."""
     return _load_dropin_file("vqa_hip_dropin_utils_losses", "utils", "losses.py")

@@ -57,6 +57,11 @@ SIGNATURES = {
     "vqa_stem_wgrad_blocks": [I, I, I],
     "vqa_stem_wgrad": [P, P, P, I, I, I, P, LL, P],
     "vqa_stem_wgrad_fused": [P, P, P, P, P, P, P, I, I, I, P, LL, P],
+    "vqa_u8_norm_table": [F, F, F, F, F, F, P, P],
+    "vqa_stem_conv_u8": [P, P, P, P, I, I, I, P, P],
+    "vqa_stem_conv_pool_u8": [P, P, P, P, I, I, I, P, P],
+    "vqa_stem_wgrad_u8": [P, P, P, I, I, I, P, LL, P, P],
+    "vqa_stem_wgrad_fused_u8": [P, P, P, P, P, P, P, I, I, I, P, LL, P, P],
     "vqa_stem_dgrad_pack": [I, P, P, P],
     "vqa_stem_dgrad": [I, P, P, P, I, I, I, P],
     "vqa_stem_dgrad_fused_ok": [I, I, I],

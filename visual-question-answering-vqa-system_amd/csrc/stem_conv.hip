@@ -64,6 +64,118 @@ __device__ __forceinline__ void stem_fill_patch(bf16_t* __restrict__ patch, int 
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Image sources.  Each of the three dedicated kernels is one __device__ body templated on where its patch comes from, behind thin
+// __global__ entries: ImgF32 is the normalised NCHW fp32 batch (the entries that have always existed: same symbols, same code),
+// ImgU8 the uint8 HWC batch a decoder / the GPU input pipeline holds (ByteImages: the *_u8 entries).  A fill is three steps --
+// load the raw element, turn it into the patch value, store the bf16 -- and a source names its part of each:
+//   load(b, c, ih, iw, H, W)  raw element at an in-image position
+//   pick(ok, raw)             the raw element, or the padding outside the image: 0.0 in normalised space (ImgU8: the marker PAD --
+//                             never byte 0, whose table entry is (0 - mean) / std)
+//   bits(raw, c)              the bf16 that goes to LDS.  ImgF32: f2bf(raw).  ImgU8: table[c][raw], a bf16 [3][256] table that
+//                             vqa_u8_norm_table built as f2bf((float(v) / 255 - mean[c]) / std[c]) -- image_normalize_kernel's
+//                             expression followed by the f2bf of the fp32 fill, so the patch holds the SAME bits either way and
+//                             everything downstream is bit-equal; PAD gives 0.
+// The table (1536 B) is read through the vector cache with a bounds-checked buffer load, not staged in LDS: the u8 kernels then have
+// exactly their siblings' LDS footprint, hence the same nsplit, grid, scratch size and accumulation order at every shape, which is
+// what makes the weight gradient bit-equal to the fp32 route by construction; all 768 entries stay resident in the 32 KB L1.
+// A pixel of the HWC batch is at ((b*H + ih)*W + iw)*3 + c: the resource covers B*H*W*3 bytes (32-bit offsets).
+// ------------------------------------------------------------------------------------------------
+struct ImgF32 {
+  typedef float raw_t;
+  __amdgpu_buffer_rsrc_t rs;
+  __device__ __forceinline__ ImgF32(const float* img, const bf16_t*, int nelem)
+      : rs(__builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(img), 0, nelem * 4, 0x00020000)) {}
+  __device__ __forceinline__ float load(int b, int c, int ih, int iw, int H, int W) const {
+    return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (((b * 3 + c) * H + ih) * W + iw) * 4, 0, 0));
+  }
+  static __device__ __forceinline__ float pick(bool ok, float raw) { return ok ? raw : 0.f; }
+  __device__ __forceinline__ bf16_t bits(float v, int) const { return f2bf(v); }
+};
+struct ImgU8 {
+  typedef uint32_t raw_t;
+  static constexpr uint32_t PAD = 0x100;                               // no byte value: a position outside the image
+  __amdgpu_buffer_rsrc_t rs, rsTab;
+  __device__ __forceinline__ ImgU8(const uint8_t* img, const bf16_t* table, int nelem)
+      : rs(__builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(img), 0, nelem, 0x00020000)),
+        rsTab(__builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(table), 0, 3 * 256 * 2, 0x00020000)) {}
+  __device__ __forceinline__ uint32_t load(int b, int c, int ih, int iw, int H, int W) const {
+    return __builtin_amdgcn_raw_buffer_load_b8(rs, ((b * H + ih) * W + iw) * 3 + c, 0, 0);
+  }
+  static __device__ __forceinline__ uint32_t pick(bool ok, uint32_t raw) { return ok ? raw : PAD; }
+  __device__ __forceinline__ bf16_t bits(uint32_t raw, int c) const {
+    const bf16_t t = __builtin_amdgcn_raw_buffer_load_b16(rsTab, (c * 256 + (int)(raw & 0xffu)) * 2, 0, 0);
+    return raw == PAD ? (bf16_t)0 : t;
+  }
+};
+
+// bf16 table[c][v] = f2bf((float(v) / 255 - mean[c]) / std[c]): ToTensor, Normalize (IEEE division, torch's operation order, as
+// image_normalize_kernel) and the f2bf of the fp32 patch fill.  One workgroup, one thread per byte value, plain vector stores.
+__global__ __launch_bounds__(256) void u8_norm_table_kernel(float m0, float m1, float m2, float s0, float s1, float s2,
+                                                            bf16_t* __restrict__ table) {
+  const int v = threadIdx.x;
+  const float mean[3] = {m0, m1, m2}, sd[3] = {s0, s1, s2};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float t = (float)v / 255.0f;
+    table[c * 256 + v] = f2bf((t - mean[c]) / sd[c]);
+  }
+}
+
+// stem_fill_patch for the uint8 HWC batch (W % 4 == 0): an item is four pixels of one input row -- 12 consecutive bytes, one
+// 12-byte load -- whose values go through the table and are scattered to the three channel rows of the patch.
+template <int PROWS, int XO, int CH>
+__device__ __forceinline__ void stem_fill_patch_u8(bf16_t* __restrict__ patch, int PW, const ImgU8& src, int b, int ih_base,
+                                                   int H, int W, int tid) {
+  static_assert(XO & 1, "odd column offset");
+  typedef __attribute__((ext_vector_type(3))) uint32_t u32x3;
+  const int W4 = W >> 2, nitems = PROWS * W4, nh = PW - W;
+  const float inv_w4 = 1.0f / (float)W4, inv_nh = 1.0f / (float)nh;
+  for (int i = tid; i < 3 * PROWS * nh; i += 256) {                  // halo columns [0, XO) and [W + XO, PW)
+    const int row = (int)(((float)i + 0.5f) * inv_nh), k = i - row * nh;
+    patch[row * PW + (k < XO ? k : W + k)] = 0;
+  }
+  for (int base = tid; base < nitems; base += 256 * CH) {
+    u32x3 v[CH]; int dst[CH]; bool in[CH];
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+      const int id = base + 256 * i;
+      dst[i] = -1; in[i] = false;
+      v[i] = u32x3{0u, 0u, 0u};
+      if (id < nitems) {
+        const int pr = (int)(((float)id + 0.5f) * inv_w4), j = id - pr * W4;
+        const int ih = ih_base + pr;
+        dst[i] = pr * PW + 4 * j + XO;
+        in[i] = ih >= 0 && ih < H;
+        if (in[i]) v[i] = __builtin_bit_cast(u32x3, __builtin_amdgcn_raw_buffer_load_b96(src.rs, ((b * H + ih) * W + 4 * j) * 3, 0, 0));
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < CH; ++i) {
+      if (dst[i] < 0) continue;
+      bf16_t t[12];                                                    // byte k of the item: pixel k / 3, channel k % 3
+#pragma unroll
+      for (int k = 0; k < 12; ++k) t[k] = src.bits(ImgU8::pick(in[i], (v[i][k >> 2] >> (8 * (k & 3))) & 0xffu), k % 3);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        bf16_t* d = patch + c * PROWS * PW + dst[i];
+        d[0] = t[c];
+        *reinterpret_cast<uint32_t*>(d + 1) = (uint32_t)t[3 + c] | ((uint32_t)t[6 + c] << 16);
+        d[3] = t[9 + c];
+      }
+    }
+  }
+}
+// the vector fill of a source
+template <int PROWS, int XO>
+__device__ __forceinline__ void stem_fill_vec(bf16_t* __restrict__ patch, int PW, const ImgF32& src, int b, int ih_base, int H, int W, int tid) {
+  stem_fill_patch<PROWS, XO, 8>(patch, PW, src.rs, b, ih_base, H, W, tid);
+}
+template <int PROWS, int XO>
+__device__ __forceinline__ void stem_fill_vec(bf16_t* __restrict__ patch, int PW, const ImgU8& src, int b, int ih_base, int H, int W, int tid) {
+  stem_fill_patch_u8<PROWS, XO, 4>(patch, PW, src, b, ih_base, H, W, tid);
+}
+
 // wstem[n][(c*7+r)*8+s] = w[n][r][s][c] (KRSC fp32 master), zero for s == 7 and pairs 21..23
 __global__ void stem_pack_kernel(const float* __restrict__ w, bf16_t* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -74,8 +186,9 @@ __global__ void stem_pack_kernel(const float* __restrict__ w, bf16_t* __restrict
   out[i] = f2bf(v);
 }
 
-__global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict__ img, const bf16_t* __restrict__ wst, bf16_t* __restrict__ out,
-                                                        float* __restrict__ stats, int H, int W, int Ho, int Wo) {
+template <class SRC, class PIX>
+__device__ __forceinline__ void stem_conv_body(const PIX* __restrict__ img, const bf16_t* __restrict__ tab, const bf16_t* __restrict__ wst,
+                                               bf16_t* __restrict__ out, float* __restrict__ stats, int H, int W, int Ho, int Wo) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int PW = 2 * Wo + 8;                       // patch width (x = iw + 3), multiple of 8
   bf16_t* patch = reinterpret_cast<bf16_t*>(smem);                 // [3][PR][PW]
@@ -92,21 +205,20 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
     *reinterpret_cast<u32x4*>(&Wl[n * LDW + kv * 8]) = *reinterpret_cast<const u32x4*>(&wst[n * KP + kv * 8]);
   }
   const int ih_base = 2 * oh0 - 3;
-  const __amdgpu_buffer_rsrc_t rsImg = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(img), 0, (int)gridDim.x / rblocks * 3 * H * W * 4, 0x00020000);   // 32-bit offsets
+  const SRC src(img, tab, (int)gridDim.x / rblocks * 3 * H * W);       // 32-bit offsets
   for (int x = tid; x < PW; x += 256) {                    // lanes walk x (coalesced); all 3*PR row loads are issued
     const int iw = x - 3;                                    // back to back before the first use (latency overlapped)
     const bool cok = iw >= 0 && iw < W;
-    float vals[3 * PR];
+    typename SRC::raw_t vals[3 * PR];
 #pragma unroll
     for (int row = 0; row < 3 * PR; ++row) {
       const int c = row / PR, pr = row - c * PR, ih = ih_base + pr;
       const bool ok = cok && ih >= 0 && ih < H;
       const int ihc = min(max(ih, 0), H - 1), iwc = min(max(iw, 0), W - 1);      // always-valid address: unconditional load
-      const float t = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsImg, (((b * 3 + c) * H + ihc) * W + iwc) * 4, 0, 0));
-      vals[row] = ok ? t : 0.f;
+      vals[row] = SRC::pick(ok, src.load(b, c, ihc, iwc, H, W));
     }
 #pragma unroll
-    for (int row = 0; row < 3 * PR; ++row) patch[row * PW + x] = f2bf(vals[row]);
+    for (int row = 0; row < 3 * PR; ++row) patch[row * PW + x] = src.bits(vals[row], row / PR);
   }
   __syncthreads();
 
@@ -174,6 +286,15 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
     }
   }
 }
+__global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict__ img, const bf16_t* __restrict__ wst, bf16_t* __restrict__ out,
+                                                        float* __restrict__ stats, int H, int W, int Ho, int Wo) {
+  stem_conv_body<ImgF32>(img, (const bf16_t*)nullptr, wst, out, stats, H, W, Ho, Wo);
+}
+__global__ __launch_bounds__(256) void stem_conv_u8_kernel(const uint8_t* __restrict__ img, const bf16_t* __restrict__ tab,
+                                                           const bf16_t* __restrict__ wst, bf16_t* __restrict__ out,
+                                                           float* __restrict__ stats, int H, int W, int Ho, int Wo) {
+  stem_conv_body<ImgU8>(img, tab, wst, out, stats, H, W, Ho, Wo);
+}
 
 
 // ------------------------------------------------------------------------------------------------
@@ -199,120 +320,16 @@ __device__ __forceinline__ float pool_max(float a, float b) { return (b > a || b
 __global__ __launch_bounds__(256, 2) void stem_conv_pool_kernel(const float* __restrict__ img, const bf16_t* __restrict__ wst,
                                                                 const float* __restrict__ coef, bf16_t* __restrict__ out,
                                                                 int B, int H, int W, int Ho, int Wo, int Hp, int Wp, int ctiles, int PW, int dbg) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  bf16_t* patch = reinterpret_cast<bf16_t*>(smem);                 // [3][PRP][PW], x = iw + 5
-  bf16_t* Wl = patch + 3 * PRP * PW;                                // [64][LDW]
-  bf16_t* Cst = Wl;                                                 // [4 waves][8][LDCS] once the B fragments are in registers
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, li = lane & 15;
-  const int pblocks = Hp / PRB;
-  const int b = blockIdx.x / pblocks, ph0 = (blockIdx.x - b * pblocks) * PRB;
-
-  for (int v = tid; v < 64 * (KP / 8); v += 256) {
-    const int n = v / (KP / 8), kv = v - n * (KP / 8);
-    *reinterpret_cast<u32x4*>(&Wl[n * LDW + kv * 8]) = *reinterpret_cast<const u32x4*>(&wst[n * KP + kv * 8]);
-  }
-  const int ih_base = 4 * ph0 - 5;                                   // input row of patch row 0: 2 * (2 * ph0 - 1) - 3
-  const __amdgpu_buffer_rsrc_t rsImg = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(img), 0, B * 3 * H * W * 4, 0x00020000);
-  if (dbg & 8) {}
-  else if (!(W & 3)) stem_fill_patch<PRP, 5, 8>(patch, PW, rsImg, b, ih_base, H, W, tid);
-  else
-  for (int x = tid; x < PW; x += 256) {
-    const int iw = x - 5;
-    const bool cok = iw >= 0 && iw < W;
-    const int iwc = min(max(iw, 0), W - 1);
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {                                    // one channel's 23 rows in flight at a time
-      float vals[PRP];
-#pragma unroll
-      for (int pr = 0; pr < PRP; ++pr) {
-        const int ih = ih_base + pr;
-        const int ihc = min(max(ih, 0), H - 1);
-        const float t = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsImg, (((b * 3 + c) * H + ihc) * W + iwc) * 4, 0, 0));
-        vals[pr] = (cok && ih >= 0 && ih < H) ? t : 0.f;
-      }
-#pragma unroll
-      for (int pr = 0; pr < PRP; ++pr) patch[(c * PRP + pr) * PW + x] = f2bf(vals[pr]);
-    }
-  }
-  __syncthreads();
-  bf16x8 bfr[6][4];
-#pragma unroll
-  for (int kk = 0; kk < 6; ++kk)
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-      bfr[kk][nt] = *reinterpret_cast<const bf16x8*>(&Wl[(nt * 16 + li) * LDW + kk * 32 + g * 8]);
-  float sc[4], sh[4];
-#pragma unroll
-  for (int nt = 0; nt < 4; ++nt) { sc[nt] = coef[nt * 16 + li]; sh[nt] = coef[64 + nt * 16 + li]; }
-  __syncthreads();                                                   // Wl is dead: C staging may overwrite it
-  if (dbg & 4) { if (tid == 0) out[(size_t)blockIdx.x * 64] = f2bf(sc[0] + (float)bfr[0][0][0]); return; }
-
-  bf16_t* mycs = Cst + wave * 8 * LDCS;
-  for (int t = wave; t < ctiles; t += 4) {
-    const int c0 = 14 * t - 1;                                        // conv column of accumulator row p = 0
-    // conv row i of the block (conv row 2*ph0 - 1 + i) -> BN + ReLU -> horizontal 3-max at stride 2: h[nt][0] = pooled column 2g,
-    // h[nt][1] = pooled column 2g + 1 (garbage for g == 3: never stored)
-    auto row = [&](int i, float (&h)[4][2]) {
-      f32x4 acc[4];
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) acc[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (!(dbg & 1))
-#pragma unroll
-      for (int kk = 0; kk < 6; ++kk) {
-        int pair = kk * 4 + g;
-        pair = pair > 20 ? 20 : pair;
-        const int c = pair / 7, r = pair - c * 7;
-        const uint32_t* ap = reinterpret_cast<const uint32_t*>(&patch[(c * PRP + 2 * i + r) * PW + 28 * t + 2 * li]);
-        u32x4 raw = {ap[0], ap[1], ap[2], ap[3]};
-        const bf16x8 af = __builtin_bit_cast(bf16x8, raw);
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfr[kk][nt], acc[nt], 0, 0, 0);
-      }
-      if (dbg & 2) {
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) { h[nt][0] = acc[nt][0] + acc[nt][1]; h[nt][1] = acc[nt][2] + acc[nt][3]; }
-        return;
-      }
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) {
-        float v[4];
-#pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) {
-          const int col = c0 + 4 * g + r4;
-          const float a = acc[nt][r4] * sc[nt] + sh[nt];
-          v[r4] = ((unsigned)col < (unsigned)Wo) ? (a < 0.f ? 0.f : a) : 0.f;
-        }
-        const float nx = __shfl_down(v[0], 16, 64);                   // column 4g + 4
-        h[nt][0] = pool_max(pool_max(v[0], v[1]), v[2]);
-        h[nt][1] = pool_max(pool_max(v[2], v[3]), nx);
-      }
-    };
-    float hp[4][2], h1[4][2], h2[4][2];
-    if (ph0 > 0) row(0, hp);                                          // conv row 2*ph0 - 1 (row -1 of the image: outside)
-    else {
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt) { hp[nt][0] = 0.f; hp[nt][1] = 0.f; }
-    }
-#pragma unroll 1
-    for (int k = 0; k < PRB; ++k) {
-      row(2 * k + 1, h1);
-      row(2 * k + 2, h2);
-      // this lane's two pooled columns x four channel tiles -> wave-private staging -> 16-byte row stores
-#pragma unroll
-      for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const float o = pool_max(pool_max(hp[nt][q], h1[nt][q]), h2[nt][q]);
-          mycs[(2 * g + q) * LDCS + nt * 16 + li] = f2bf(o);
-          hp[nt][q] = h2[nt][q];
-        }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      const int px = lane >> 3, cv = lane & 7, pw = 7 * t + px;
-      if (px < 7 && pw < Wp)
-        *reinterpret_cast<u32x4*>(&out[((((size_t)b * Hp + ph0 + k) * Wp + pw) * 64) + cv * 8]) = *reinterpret_cast<const u32x4*>(&mycs[px * LDCS + cv * 8]);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
-  }
+  typedef ImgF32 SRC;
+  const bf16_t* const tab = nullptr;
+#include "stem_conv_pool_body.h"
+}
+__global__ __launch_bounds__(256, 2) void stem_conv_pool_u8_kernel(const uint8_t* __restrict__ img, const bf16_t* __restrict__ tab,
+                                                                   const bf16_t* __restrict__ wst, const float* __restrict__ coef,
+                                                                   bf16_t* __restrict__ out, int B, int H, int W, int Ho, int Wo, int Hp,
+                                                                   int Wp, int ctiles, int PW, int dbg) {
+  typedef ImgU8 SRC;
+#include "stem_conv_pool_body.h"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -330,11 +347,11 @@ constexpr int LDD = 64 + 4;        // dy row stride
 
 // FUSED = true: dy is never materialised -- it is rebuilt per row from the raw conv output y, the pooled gradient + argmax
 // (stem_route) and the BatchNorm backward coefficients (dy = A*g + B*y + C), i.e. vqa_stem_bwd_apply folded into the staging.
-template <bool FUSED>
-__global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict__ img, const bf16_t* __restrict__ dy, float* __restrict__ dw,
-                                                         int B, int H, int W, int Ho, int Wo, const bf16_t* __restrict__ dpool,
-                                                         const uint8_t* __restrict__ idx, const float* __restrict__ coef,
-                                                         const float* __restrict__ bc, int Hp, int Wp, int nsplit, float* __restrict__ ws) {
+template <bool FUSED, class SRC, class PIX>
+__device__ __forceinline__ void stem_wgrad_body(const PIX* __restrict__ img, const bf16_t* __restrict__ tab, const bf16_t* __restrict__ dy,
+                                                float* __restrict__ dw, int B, int H, int W, int Ho, int Wo, const bf16_t* __restrict__ dpool,
+                                                const uint8_t* __restrict__ idx, const float* __restrict__ coef,
+                                                const float* __restrict__ bc, int Hp, int Wp, int nsplit, float* __restrict__ ws) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int PW = 2 * Wo + 8;
   const int Wh = Wo / nsplit;                                        // pixels per unit: a row is contracted in nsplit pieces so that
@@ -362,7 +379,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
   // 185 v_lshl_add_u64 in this kernel, which is VALU-bound in its staging phase)
   const __amdgpu_buffer_rsrc_t rsP = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(FUSED ? dpool : dy), 0, FUSED ? B * Hp * Wp * 64 * 2 : 0, 0x00020000);
   const __amdgpu_buffer_rsrc_t rsI = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(FUSED ? idx : reinterpret_cast<const uint8_t*>(dy)), 0, FUSED ? B * Hp * Wp * 64 : 0, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsImg = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(img), 0, B * 3 * H * W * 4, 0x00020000);
+  const SRC src(img, tab, B * 3 * H * W);
   const __amdgpu_buffer_rsrc_t rsDy = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(dy), 0, B * Ho * Wo * 64 * 2, 0x00020000);
   f32x4 acc[4][3];                                                   // wave owns k2 tiles 3*wave .. 3*wave+2, all 4 n tiles
 #pragma unroll
@@ -380,17 +397,16 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
     for (int x = tid; x < PW; x += 256) {
       const int iw = x - 3;
       const bool cok = iw >= 0 && iw < W;
-      float vals[3 * PRW];
+      typename SRC::raw_t vals[3 * PRW];
 #pragma unroll
       for (int row = 0; row < 3 * PRW; ++row) {
         const int c = row / PRW, pr = row - c * PRW, ih = ih_base + pr;
         const bool ok = cok && ih >= 0 && ih < H;
         const int ihc = min(max(ih, 0), H - 1), iwc = min(max(iw, 0), W - 1);
-        const float t = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsImg, (((b * 3 + c) * H + ihc) * W + iwc) * 4, 0, 0));
-        vals[row] = ok ? t : 0.f;
+        vals[row] = SRC::pick(ok, src.load(b, c, ihc, iwc, H, W));
       }
 #pragma unroll
-      for (int row = 0; row < 3 * PRW; ++row) patch[row * PW + x] = f2bf(vals[row]);
+      for (int row = 0; row < 3 * PRW; ++row) patch[row * PW + x] = src.bits(vals[row], row / PRW);
     }
     for (int unit = 0; unit < RBW * nsplit; ++unit) {
       const int orow = unit / nsplit, px0 = (unit - orow * nsplit) * Wh;
@@ -484,6 +500,21 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
       }
   }
 }
+template <bool FUSED>
+__global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict__ img, const bf16_t* __restrict__ dy, float* __restrict__ dw,
+                                                         int B, int H, int W, int Ho, int Wo, const bf16_t* __restrict__ dpool,
+                                                         const uint8_t* __restrict__ idx, const float* __restrict__ coef,
+                                                         const float* __restrict__ bc, int Hp, int Wp, int nsplit, float* __restrict__ ws) {
+  stem_wgrad_body<FUSED, ImgF32>(img, (const bf16_t*)nullptr, dy, dw, B, H, W, Ho, Wo, dpool, idx, coef, bc, Hp, Wp, nsplit, ws);
+}
+template <bool FUSED>
+__global__ __launch_bounds__(256) void stem_wgrad_u8_kernel(const uint8_t* __restrict__ img, const bf16_t* __restrict__ tab,
+                                                            const bf16_t* __restrict__ dy, float* __restrict__ dw, int B, int H, int W, int Ho,
+                                                            int Wo, const bf16_t* __restrict__ dpool, const uint8_t* __restrict__ idx,
+                                                            const float* __restrict__ coef, const float* __restrict__ bc, int Hp, int Wp,
+                                                            int nsplit, float* __restrict__ ws) {
+  stem_wgrad_body<FUSED, ImgU8>(img, tab, dy, dw, B, H, W, Ho, Wo, dpool, idx, coef, bc, Hp, Wp, nsplit, ws);
+}
 
 extern "C" int vqa_slab_reduce(const float* ws, float* dw, int nslabs, long long n, hipStream_t st);
 
@@ -512,6 +543,36 @@ static int stem_wgrad_grid(int B, int Ho, int Wo, size_t* shm_out) {
   return nblocks < cap ? nblocks : cap;
 }
 
+// the image batch must be addressable with 32-bit buffer offsets: B*3*H*W elements of esize bytes
+static bool stem_img_fits(int B, int H, int W, size_t esize) { return (size_t)B * 3 * H * W * esize < 0x7fffffffull; }
+
+// The *_u8 entries read the uint8 HWC batch through the table of vqa_u8_norm_table.  The table lives in the vector cache, not in LDS
+// (see ImgU8), so stem_nsplit has nothing to add for them: nsplit, grid and scratch are the fp32 entries', and vqa_stem_wgrad_blocks
+// sizes the scratch of all four.
+template <bool FUSED, bool U8>
+static int stem_wgrad_launch(const void* img, const void* table, const void* y, const void* dpool, const uint8_t* idx, const float* coef,
+                             const float* bcoef, float* dw, int B, int H, int W, float* ws, long long ws_floats, hipStream_t st) {
+  const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1, Hp = (Ho + 2 - 3) / 2 + 1, Wp = (Wo + 2 - 3) / 2 + 1;
+  if (!img || !y || !dw || (U8 && !table) || (FUSED && (!dpool || !idx || !coef || !bcoef)) || Ho % RBW || Wo % 16 || Wo > 256) return VQA_EARG;
+  if ((size_t)B * Ho * Wo * 64 * 2 >= 0x7fffffffull || !stem_img_fits(B, H, W, U8 ? 1 : 4)) return VQA_EARG;     // 32-bit buffer offsets
+  const int nsplit = stem_nsplit(Wo);
+  const size_t shm = stem_wgrad_shm(Wo, nsplit);
+  if (shm > 160 * 1024) return VQA_EARG;
+  const int grid = stem_wgrad_grid(B, Ho, Wo, nullptr);
+  float* w = (ws && ws_floats >= (long long)grid * 64 * 147) ? ws : nullptr;
+  if constexpr (U8) {
+    (void)vqa_ensure_lds(reinterpret_cast<const void*>(&stem_wgrad_u8_kernel<FUSED>), shm);
+    hipLaunchKernelGGL(stem_wgrad_u8_kernel<FUSED>, dim3(grid), dim3(256), shm, st, (const uint8_t*)img, (const bf16_t*)table, (const bf16_t*)y,
+                       dw, B, H, W, Ho, Wo, (const bf16_t*)dpool, idx, coef, bcoef, FUSED ? Hp : 0, FUSED ? Wp : 0, nsplit, w);
+  } else {
+    (void)vqa_ensure_lds(reinterpret_cast<const void*>(&stem_wgrad_kernel<FUSED>), shm);
+    hipLaunchKernelGGL(stem_wgrad_kernel<FUSED>, dim3(grid), dim3(256), shm, st, (const float*)img, (const bf16_t*)y, dw, B, H, W, Ho, Wo,
+                       (const bf16_t*)dpool, idx, coef, bcoef, FUSED ? Hp : 0, FUSED ? Wp : 0, nsplit, w);
+  }
+  VQA_LAUNCH_CHECK();
+  return w ? vqa_slab_reduce(w, dw, grid, 64 * 147, st) : VQA_OK;
+}
+
 extern "C" {
 
 // number of workgroups (= rows of the statistics slab) or 0 when the shape is not supported by this kernel
@@ -528,11 +589,30 @@ int vqa_stem_pack(const float* w_krsc, void* wstem /* [64][192] bf16 */, hipStre
 // bf16 only.  img NCHW fp32 [B][3][H][W]; out NHWC bf16 [B][Ho][Wo][64]; stats [vqa_stem_conv_blocks][2][64] or NULL
 int vqa_stem_conv(const float* img, const void* wstem, void* out, float* stats, int B, int H, int W, hipStream_t st) {
   const int nb = vqa_stem_conv_blocks(B, H, W);
-  if (!img || !wstem || !out || nb <= 0 || (size_t)B * 3 * H * W * 4 >= 0x7fffffffull) return VQA_EARG;      // 32-bit buffer offsets into the image
+  if (!img || !wstem || !out || nb <= 0 || !stem_img_fits(B, H, W, 4)) return VQA_EARG;      // 32-bit buffer offsets into the image
   const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1, PW = 2 * Wo + 8;
   const size_t shm = (size_t)(3 * PR * PW + 64 * LDW) * 2 + 4 * 64 * 2 * 4;
   (void)vqa_ensure_lds(reinterpret_cast<const void*>(&stem_conv_kernel), shm);
   hipLaunchKernelGGL(stem_conv_kernel, dim3(nb), dim3(256), shm, st, img, (const bf16_t*)wstem, (bf16_t*)out, stats, H, W, Ho, Wo);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+// the same from the uint8 HWC batch [B][H][W][3] and the table of vqa_u8_norm_table: bit-equal to vqa_stem_conv on vqa_image_normalize's output
+int vqa_stem_conv_u8(const uint8_t* img_hwc, const void* wstem, void* out, float* stats, int B, int H, int W, const void* table, hipStream_t st) {
+  const int nb = vqa_stem_conv_blocks(B, H, W);
+  if (!img_hwc || !table || !wstem || !out || nb <= 0 || !stem_img_fits(B, H, W, 1)) return VQA_EARG;
+  const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1, PW = 2 * Wo + 8;
+  const size_t shm = (size_t)(3 * PR * PW + 64 * LDW) * 2 + 4 * 64 * 2 * 4;
+  (void)vqa_ensure_lds(reinterpret_cast<const void*>(&stem_conv_u8_kernel), shm);
+  hipLaunchKernelGGL(stem_conv_u8_kernel, dim3(nb), dim3(256), shm, st, img_hwc, (const bf16_t*)table, (const bf16_t*)wstem, (bf16_t*)out,
+                     stats, H, W, Ho, Wo);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+// table [3][256] bf16 <- f2bf((v / 255 - mean[c]) / std[c]) for every byte value v (see ImgU8): what the *_u8 entries look bytes up in
+int vqa_u8_norm_table(float mean0, float mean1, float mean2, float std0, float std1, float std2, void* table, hipStream_t st) {
+  const float ms[6] = {mean0, mean1, mean2, std0, std1, std2};
+  for (int i = 0; i < 6; ++i) if (!(ms[i] - ms[i] == 0.f)) return VQA_EARG;                  // NaN or infinite
+  if (!table || std0 == 0.f || std1 == 0.f || std2 == 0.f) return VQA_EARG;
+  hipLaunchKernelGGL(u8_norm_table_kernel, dim3(1), dim3(256), 0, st, mean0, mean1, mean2, std0, std1, std2, (bf16_t*)table);
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
 
@@ -562,6 +642,18 @@ int vqa_stem_conv_pool(const float* img, const void* wstem, const float* coef, v
                      B, H, W, Ho, Wo, Hp, Wp, ctiles, PW, vqa_env_int("VQA_STEMCP_DBG", 0));
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
+// the same from the uint8 HWC batch (shapes: vqa_stem_conv_pool_ok, whose byte bound holds a fortiori for one byte per element)
+int vqa_stem_conv_pool_u8(const uint8_t* img_hwc, const void* wstem, const float* coef, void* out, int B, int H, int W, const void* table,
+                          hipStream_t st) {
+  int ctiles = 0, PW = 0;
+  const size_t shm = stem_conv_pool_shm(H, W, &ctiles, &PW);
+  if (!img_hwc || !table || !wstem || !coef || !out || !vqa_stem_conv_pool_ok(B, H, W)) return VQA_EARG;
+  const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1, Hp = (Ho + 2 - 3) / 2 + 1, Wp = (Wo + 2 - 3) / 2 + 1;
+  (void)vqa_ensure_lds(reinterpret_cast<const void*>(&stem_conv_pool_u8_kernel), shm);
+  hipLaunchKernelGGL(stem_conv_pool_u8_kernel, dim3(B * (Hp / PRB)), dim3(256), shm, st, img_hwc, (const bf16_t*)table, (const bf16_t*)wstem,
+                     coef, (bf16_t*)out, B, H, W, Ho, Wo, Hp, Wp, ctiles, PW, vqa_env_int("VQA_STEMCP_DBG", 0));
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
 
 // workgroups of the stem weight-gradient kernels (0: unsupported shape): their deterministic two-pass accumulation needs a scratch
 // of (this many) * 64*147 floats
@@ -573,43 +665,22 @@ int vqa_stem_wgrad_blocks(int B, int H, int W) {
 
 // bf16 only.  dw [64][7][7][3] fp32 (+=).  Same shape support as vqa_stem_conv.  ws: scratch (see vqa_stem_wgrad_blocks) or NULL (atomics)
 int vqa_stem_wgrad(const float* img, const void* dy, float* dw, int B, int H, int W, float* ws, long long ws_floats, hipStream_t st) {
-  const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1;
-  if (!img || !dy || !dw || Ho % RBW || Wo % 16 || Wo > 256) return VQA_EARG;
-  if ((size_t)B * Ho * Wo * 64 * 2 >= 0x7fffffffull || (size_t)B * 3 * H * W * 4 >= 0x7fffffffull) return VQA_EARG;     // 32-bit buffer offsets
-  const int nsplit = stem_nsplit(Wo);
-  const int PW = 2 * Wo + 8, MP = (Wo / nsplit + 31) / 32 * 32;
-  const size_t shm = (size_t)(3 * PRW * PW + MP * LDA + MP * LDD) * 2;
-  if (shm > 160 * 1024) return VQA_EARG;
-  (void)vqa_ensure_lds(reinterpret_cast<const void*>(&stem_wgrad_kernel<false>), shm);
-  int nblocks = B * (Ho / RBW);
-  const int cap = 256 * (int)((160 * 1024) / shm > 4 ? 4 : (160 * 1024) / shm);
-  int grid = nblocks < cap ? nblocks : cap;
-  float* w = (ws && ws_floats >= (long long)grid * 64 * 147) ? ws : nullptr;
-  hipLaunchKernelGGL(stem_wgrad_kernel<false>, dim3(grid), dim3(256), shm, st, img, (const bf16_t*)dy, dw, B, H, W, Ho, Wo,
-                     (const bf16_t*)nullptr, (const uint8_t*)nullptr, (const float*)nullptr, (const float*)nullptr, 0, 0, nsplit, w);
-  VQA_LAUNCH_CHECK();
-  return w ? vqa_slab_reduce(w, dw, grid, 64 * 147, st) : VQA_OK;
+  return stem_wgrad_launch<false, false>(img, nullptr, dy, nullptr, nullptr, nullptr, nullptr, dw, B, H, W, ws, ws_floats, st);
+}
+int vqa_stem_wgrad_u8(const uint8_t* img_hwc, const void* dy, float* dw, int B, int H, int W, float* ws, long long ws_floats,
+                      const void* table, hipStream_t st) {
+  return stem_wgrad_launch<false, true>(img_hwc, table, dy, nullptr, nullptr, nullptr, nullptr, dw, B, H, W, ws, ws_floats, st);
 }
 // Fused stem BatchNorm/ReLU/MaxPool backward + weight gradient: dy = A*g + B*y + C is rebuilt on the fly from the raw conv
 // output y [B][Ho][Wo][64], the pooled gradient dpool [B][Hp][Wp][64] + argmax idx, coef (4*64) and bcoef (3*64).
 int vqa_stem_wgrad_fused(const float* img, const void* y, const void* dpool, const uint8_t* idx, const float* coef, const float* bcoef,
                          float* dw, int B, int H, int W, float* ws, long long ws_floats, hipStream_t st) {
-  const int Ho = (H + 6 - 7) / 2 + 1, Wo = (W + 6 - 7) / 2 + 1, Hp = (Ho + 2 - 3) / 2 + 1, Wp = (Wo + 2 - 3) / 2 + 1;
-  if (!img || !y || !dpool || !idx || !coef || !bcoef || !dw || Ho % RBW || Wo % 16 || Wo > 256) return VQA_EARG;
-  if ((size_t)B * Ho * Wo * 64 * 2 >= 0x7fffffffull || (size_t)B * 3 * H * W * 4 >= 0x7fffffffull) return VQA_EARG;     // 32-bit buffer offsets
-  const int nsplit = stem_nsplit(Wo);
-  const int PW = 2 * Wo + 8, MP = (Wo / nsplit + 31) / 32 * 32;
-  const size_t shm = (size_t)(3 * PRW * PW + MP * LDA + MP * LDD) * 2;
-  if (shm > 160 * 1024) return VQA_EARG;
-  (void)vqa_ensure_lds(reinterpret_cast<const void*>(&stem_wgrad_kernel<true>), shm);
-  int nblocks = B * (Ho / RBW);
-  const int cap = 256 * (int)((160 * 1024) / shm > 4 ? 4 : (160 * 1024) / shm);
-  int grid = nblocks < cap ? nblocks : cap;
-  float* w = (ws && ws_floats >= (long long)grid * 64 * 147) ? ws : nullptr;
-  hipLaunchKernelGGL(stem_wgrad_kernel<true>, dim3(grid), dim3(256), shm, st, img, (const bf16_t*)y, dw, B, H, W, Ho, Wo,
-                     (const bf16_t*)dpool, idx, coef, bcoef, Hp, Wp, nsplit, w);
-  VQA_LAUNCH_CHECK();
-  return w ? vqa_slab_reduce(w, dw, grid, 64 * 147, st) : VQA_OK;
+  return stem_wgrad_launch<true, false>(img, nullptr, y, dpool, idx, coef, bcoef, dw, B, H, W, ws, ws_floats, st);
+}
+int vqa_stem_wgrad_fused_u8(const uint8_t* img_hwc, const void* y, const void* dpool, const uint8_t* idx, const float* coef,
+                            const float* bcoef, float* dw, int B, int H, int W, float* ws, long long ws_floats, const void* table,
+                            hipStream_t st) {
+  return stem_wgrad_launch<true, true>(img_hwc, table, y, dpool, idx, coef, bcoef, dw, B, H, W, ws, ws_floats, st);
 }
 
 }  // extern "C"

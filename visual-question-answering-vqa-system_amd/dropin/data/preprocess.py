@@ -38,6 +38,18 @@ def _pkg():
     return importlib.import_module(os.path.basename(here))
 
 
+def _byte_images(u8: torch.Tensor, mean, std):
+    """output="bytes": the uint8 [B, H, W, 3] batch as a ByteImages (utils/byte_images.py) carrying this pipeline's mean / std -- the
+    model and the trainer take it as it is and normalise inside the stem kernels; `.to_float()` is the output="float" batch."""
+    return _pkg().load_dropin_byte_images().ByteImages(u8, mean, std)
+
+
+def _check_output(output: str) -> bool:
+    if output not in ("float", "bytes"):
+        raise ValueError(f'output must be "float" or "bytes", got {output!r}')
+    return output == "bytes"
+
+
 class DeviceImageNormalizer:
     """uint8 [B, H, W, 3] (cuda) -> float32 [B, 3, H, W] normalised; `flip`: optional bool/uint8 [B] (horizontal flip per sample)."""
 
@@ -67,8 +79,9 @@ class DeviceColorJitter:
     """transforms.ColorJitter(brightness, contrast, saturation, hue) -> ToTensor -> Normalize on the GPU for a uint8 [B, H, W, 3] batch
     (data/preprocess.py:77-84).  Arguments as torchvision's: a float x means factors drawn from [max(0, 1 - x), 1 + x] (hue: [-x, x],
     x <= 0.5), a (lo, hi) pair is used as is, 0 / None switches the adjustment off.  `__call__(images_u8, order=None, factors=None,
-    generator=None, return_u8=False)`: per-image permutations `order` ([B, 4] of 0 brightness, 1 contrast, 2 saturation, 3 hue) and
-    `factors` ([B, 4]: brightness, contrast, saturation factor, hue factor; NaN = off) are drawn here unless given."""
+    generator=None, return_u8=False, output="float")`: per-image permutations `order` ([B, 4] of 0 brightness, 1 contrast, 2 saturation,
+    3 hue) and `factors` ([B, 4]: brightness, contrast, saturation factor, hue factor; NaN = off) are drawn here unless given.
+    output="bytes": the pass writes the uint8 result only (no float batch is allocated) and a ByteImages is returned."""
 
     def __init__(self, brightness=0.0, contrast=0.0, saturation=0.0, hue=0.0, mean: Sequence[float] = IMAGENET_MEAN,
                  std: Sequence[float] = IMAGENET_STD):
@@ -103,7 +116,8 @@ class DeviceColorJitter:
                         else torch.empty(B, dtype=torch.float64).uniform_(r[0], r[1], generator=generator))
         return order, torch.stack(cols, 1)
 
-    def __call__(self, images_u8: torch.Tensor, order=None, factors=None, generator=None, return_u8: bool = False):
+    def __call__(self, images_u8: torch.Tensor, order=None, factors=None, generator=None, return_u8: bool = False, output: str = "float"):
+        as_bytes = _check_output(output)
         x = images_u8
         if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[-1] != 3:
             raise RuntimeError("DeviceColorJitter expects a uint8 [B, H, W, 3] batch")
@@ -125,10 +139,12 @@ class DeviceColorJitter:
         od = order.to(x.device).contiguous()
         fd = factors.to(torch.float32).to(x.device).contiguous()       # Image.blend takes its factor as a C float
         sums = torch.empty(B, dtype=torch.int64, device=x.device)
-        out = torch.empty((B, 3, H, W), dtype=torch.float32, device=x.device)
-        u8 = torch.empty_like(x) if return_u8 else None
+        out = None if as_bytes else torch.empty((B, 3, H, W), dtype=torch.float32, device=x.device)
+        u8 = torch.empty_like(x) if (return_u8 or as_bytes) else None
         self._L.call("vqa_image_color_jitter", x.data_ptr(), od.data_ptr(), fd.data_ptr(), B, H, W, None if u8 is None else u8.data_ptr(),
-                     out.data_ptr(), *self.mean, *self.std, sums.data_ptr())
+                     None if out is None else out.data_ptr(), *self.mean, *self.std, sums.data_ptr())
+        if as_bytes:
+            return _byte_images(u8, self.mean, self.std)
         return (out, u8) if return_u8 else out
 
 
@@ -138,7 +154,9 @@ class DeviceImageResizer:
     return_u8=False)` -> float32 [B, 3, out, out] (and the uint8 [B, out, out, 3] PIL would return, for inspection / parity).
     size: the Resize target (224; 256 in the augmented pipeline); crop: RandomCrop size (None: no crop); crop_yx: [B][2] window
     origins inside the resized image (host ints), flip: [B] flags; jitter: a `DeviceColorJitter` applied behind crop and flip (the
-    training pipeline's order, data/preprocess.py:70-84), `jitter_params` = (order, factors) to fix its draws."""
+    training pipeline's order, data/preprocess.py:70-84), `jitter_params` = (order, factors) to fix its draws.
+    output="bytes": a ByteImages of the uint8 [B, out, out, 3] batch instead -- resize, crop, flip (and the jitter) happen in uint8
+    anyway, so the same launches run without their float output and `.to_float()` of the result is the output="float" batch."""
 
     def __init__(self, size: int = 224, crop: Optional[int] = None, mean: Sequence[float] = IMAGENET_MEAN, std: Sequence[float] = IMAGENET_STD,
                  device="cuda", jitter: Optional["DeviceColorJitter"] = None):
@@ -151,8 +169,10 @@ class DeviceImageResizer:
         self._L = _pkg()._lib
         self._stage, self._stage_ev, self._stage_i = [None, None], [None, None], 0
 
-    def __call__(self, images, crop_yx=None, flip: Optional[torch.Tensor] = None, return_u8: bool = False, jitter_params=None, generator=None):
+    def __call__(self, images, crop_yx=None, flip: Optional[torch.Tensor] = None, return_u8: bool = False, jitter_params=None, generator=None,
+                 output: str = "float"):
         import ctypes as C
+        as_bytes = _check_output(output)
         n = len(images)
         if n == 0:
             raise RuntimeError("DeviceImageResizer: empty batch")
@@ -206,20 +226,26 @@ class DeviceImageResizer:
             self._L.call("vqa_image_resize", packed.data_ptr(), Oa, Ha, Wa, crop, n, S, S, Oo, Oo, mid.data_ptr(), None,
                          None if f is None else f.data_ptr(), *self.mean, *self.std, ws.data_ptr(), int(wsb))
             order, factors = jitter_params if jitter_params is not None else (None, None)
-            return self.jitter(mid, order=order, factors=factors, generator=generator, return_u8=return_u8)
-        out = torch.empty((n, 3, Oo, Oo), dtype=torch.float32, device=self.device)
-        u8 = torch.empty((n, Oo, Oo, 3), dtype=torch.uint8, device=self.device) if return_u8 else None
+            return self.jitter(mid, order=order, factors=factors, generator=generator, return_u8=return_u8, output=output)
+        out = None if as_bytes else torch.empty((n, 3, Oo, Oo), dtype=torch.float32, device=self.device)
+        u8 = torch.empty((n, Oo, Oo, 3), dtype=torch.uint8, device=self.device) if (return_u8 or as_bytes) else None
         self._L.call("vqa_image_resize", packed.data_ptr(), Oa, Ha, Wa, crop, n, S, S, Oo, Oo, None if u8 is None else u8.data_ptr(),
-                     out.data_ptr(), None if f is None else f.data_ptr(), *self.mean, *self.std, ws.data_ptr(), int(wsb))
+                     None if out is None else out.data_ptr(), None if f is None else f.data_ptr(), *self.mean, *self.std, ws.data_ptr(), int(wsb))
+        if as_bytes:
+            return _byte_images(u8, self.mean, self.std)
         return (out, u8) if return_u8 else out
 
 
 def gpu_collate_fn(batch, device="cuda", normalizer: Optional[DeviceImageNormalizer] = None, flip_p: float = 0.0, generator=None,
-                   resizer: Optional[DeviceImageResizer] = None):
+                   resizer: Optional[DeviceImageResizer] = None, output: str = "float"):
     """`vqa_collate_fn` (data/preprocess.py:285-315) for items whose image is still a uint8 HWC array / tensor (decoded, not yet
     transformed): (image_u8 [H,W,3], token_ids [L], attention_mask [L], answer_idx).  With `resizer` the images may have any sizes
     (Resize on the GPU); without it they must already share one size.  Returns the same dict ('images' float32 [B,3,H,W] normalised
-    on the GPU, 'token_ids', 'attention_mask', 'answers' int64), all on `device`."""
+    on the GPU, 'token_ids', 'attention_mask', 'answers' int64), all on `device`.
+    output="bytes": 'images' is a ByteImages (uint8 [B,H,W,3] with the pipeline's mean / std) for model(...) / HipTrainer.step --
+    no float batch is written; its `.to_float()` equals the output="float" images for the same generator state (the random draws are
+    the same).  Without a resizer the flip is applied to the uint8 batch by indexing."""
+    as_bytes = _check_output(output)
     flip = None
     if flip_p > 0.0:
         flip = torch.rand(len(batch), generator=generator) < flip_p
@@ -228,11 +254,18 @@ def gpu_collate_fn(batch, device="cuda", normalizer: Optional[DeviceImageNormali
         if resizer.out != resizer.size:              # RandomCrop origins (data/preprocess.py:71), drawn like torchvision: uniform over the valid range
             hi = resizer.size - resizer.out + 1
             crop_yx = torch.randint(0, hi, (len(batch), 2), generator=generator).tolist()
-        images = resizer([item[0] for item in batch], crop_yx=crop_yx, flip=flip, generator=generator)
+        images = resizer([item[0] for item in batch], crop_yx=crop_yx, flip=flip, generator=generator, output=output)
     else:
         norm = normalizer or DeviceImageNormalizer()
         imgs = torch.stack([torch.as_tensor(item[0]) for item in batch]).to(device, non_blocking=True)
-        images = norm(imgs, flip)
+        if as_bytes:
+            if imgs.dtype != torch.uint8 or imgs.dim() != 4 or imgs.shape[-1] != 3:
+                raise RuntimeError("gpu_collate_fn expects uint8 [H, W, 3] images")
+            if flip is not None:                     # RandomHorizontalFlip on the bytes: flagged samples read their columns backwards
+                imgs = torch.where(flip.to(imgs.device).view(-1, 1, 1, 1), imgs.flip(2), imgs)
+            images = _byte_images(imgs.contiguous(), norm.mean, norm.std)
+        else:
+            images = norm(imgs, flip)
     return {
         "images": images,
         "token_ids": torch.stack([torch.as_tensor(item[1], dtype=torch.long) for item in batch]).to(device),

@@ -32,6 +32,22 @@ def _pkg():
     return importlib.import_module(os.path.basename(here))
 
 
+ByteImages = _pkg().load_dropin_byte_images().ByteImages       # uint8 HWC images as they are (dropin/utils/byte_images.py)
+
+
+_is_bytes = _pkg().kernels.is_byte_images                      # (recognised by its members: utils.byte_images has several import names)
+
+def _op_images(model, images: torch.Tensor):
+    """The image operand of a custom op as the engine takes it: ops carry tensors only, so a ByteImages travels as its uint8 data
+    (a plain uint8 tensor was cast to float before it got here) and is wrapped again with the mean / std forward() left behind."""
+    return ByteImages(images, *model._byte_norm) if images.dtype == torch.uint8 else images
+
+
+def _image_hw(images: torch.Tensor):
+    """(H, W) of an op's image operand: NCHW floats, or the uint8 HWC data of a ByteImages."""
+    return (images.shape[1], images.shape[2]) if images.dtype == torch.uint8 else (images.shape[2], images.shape[3])
+
+
 class _Node(nn.Module):
     """Anonymous container; the module tree only exists to give parameters their reference names."""
 
@@ -57,7 +73,7 @@ def _vqa_forward_op(images: torch.Tensor, token_ids: torch.Tensor, mask: Optiona
     # for a caller that synchronises every step (training/train.py:211)
     model = _MODELS[handle]
     plan, model._pending_plan = model._pending_plan, None
-    logits, aux, tape = model._engine.forward(images, token_ids, mask, training, want_aux, need_tape=True, plan=plan)
+    logits, aux, tape = model._engine.forward(_op_images(model, images), token_ids, mask, training, want_aux, need_tape=True, plan=plan)
     model._last_aux = aux              # aux tensors are detached by construction (side channel, not graph outputs)
     model._tape_seq += 1
     model._tapes[model._tape_seq] = tape
@@ -119,7 +135,8 @@ def _vqa_forward_grouped_op(images: torch.Tensor, token_ids: torch.Tensor, mask:
                             flat_params: torch.Tensor, handle: int, training: bool) -> torch.Tensor:
     model = _MODELS[handle]
     plan, model._pending_plan = model._pending_plan, None
-    logits, _, tape = model._engine.forward(images, token_ids, mask, training, False, need_tape=True, kv_index=image_index, plan=plan)
+    logits, _, tape = model._engine.forward(_op_images(model, images), token_ids, mask, training, False, need_tape=True, kv_index=image_index,
+                                            plan=plan)
     model._tape_seq += 1
     model._tapes[model._tape_seq] = tape
     while len(model._tapes) > model.max_live_tapes:
@@ -154,7 +171,7 @@ def _grouped_setup_ctx(ctx, inputs, output):
     handle = inputs[5]
     ctx.handle = handle
     ctx.tape_id = _MODELS[handle]._tape_seq
-    ctx.image_shape = (inputs[0].shape[0], inputs[0].shape[2], inputs[0].shape[3])
+    ctx.image_shape = (inputs[0].shape[0],) + _image_hw(inputs[0])
 
 
 def _grouped_backward(ctx, dlogits):
@@ -208,7 +225,7 @@ def _setup_ctx(ctx, inputs, output):
     handle = inputs[4]
     ctx.handle = handle
     ctx.tape_id = _MODELS[handle]._tape_seq
-    ctx.image_hw = (inputs[0].shape[2], inputs[0].shape[3])
+    ctx.image_hw = _image_hw(inputs[0])
 
 
 def _backward(ctx, dlogits):
@@ -307,8 +324,8 @@ def _aux_encoders_op(images: torch.Tensor, token_ids: torch.Tensor, mask: Option
                      handle: int, training: bool) -> Tuple[torch.Tensor, torch.Tensor]:
     model = _MODELS[handle]
     plan, model._pending_plan = model._pending_plan, None
-    logits, aux, tape = model._engine.forward(images, token_ids, mask, training, True, need_tape=True, plan=plan)
-    hw = (_final_hw(images.shape[2]), _final_hw(images.shape[3]))
+    logits, aux, tape = model._engine.forward(_op_images(model, images), token_ids, mask, training, True, need_tape=True, plan=plan)
+    hw = tuple(_final_hw(v) for v in _image_hw(images))
     if tuple(aux["image_features"].shape[1:]) != (512,) + hw:              # the fake below derives the same shape from the geometry
         raise RuntimeError(f"image_features {tuple(aux['image_features'].shape)} disagrees with the stem / stage geometry {hw}")
     tape["_aux"] = (logits, aux)
@@ -323,8 +340,9 @@ def _aux_encoders_op(images: torch.Tensor, token_ids: torch.Tensor, mask: Option
 def _(images, token_ids, mask, flat_params, handle, training):
     m = _MODELS[handle]
     B, L = token_ids.shape
-    return (images.new_empty((images.shape[0], 512, _final_hw(images.shape[2]), _final_hw(images.shape[3]))),
-            images.new_empty((B, L, m.embed_dim)))
+    H, W = _image_hw(images)
+    return (images.new_empty((images.shape[0], 512, _final_hw(H), _final_hw(W)), dtype=torch.float32),
+            images.new_empty((B, L, m.embed_dim), dtype=torch.float32))
 
 
 def _aux_encoders_setup(ctx, inputs, output):
@@ -636,6 +654,7 @@ class VQAModel(nn.Module):
         self._infer_precision = "bf16"             # residual-block convs of the eval (Conv+BN folded) path: set_inference_precision
         self._on_segment = None
         self._pending_plan = None                   # fine-tuning plan handed to the next custom-op forward (finetune.Plan)
+        self._byte_norm = None                      # (mean, std) of the ByteImages whose uint8 data the next custom-op forward carries
         self._plan_cache: Dict[str, Any] = {}
         self._last_aux = None
         self._tapes: Dict[int, Any] = {}
@@ -772,6 +791,9 @@ class VQAModel(nn.Module):
         """image_index (extension, inference only): images is [U, 3, H, W], token_ids [N, L] and question i is asked of image
         image_index[i]; the result equals forward(images[image_index], token_ids, attention_mask) while the image half runs once per
         image (see answer()).
+        images may be a ByteImages (extension; utils/byte_images.py): the uint8 HWC batch as decoded, normalised inside the stem
+        kernels -- every result equals forward(images.to_float(), ...) bit for bit; so may the images of forward_grouped,
+        encode_images, encode_features, predict and predict_topk.  An image gradient needs float images (TypeError).
         images may be an ImageFeatures (extension; encode_features): the image encoder, frozen and in eval mode, does not run, and
         everything after it is this forward -- eval, or training under autograd with gradients to the other three parts (then
         image_index is forward_grouped's, and return_aux raises NotImplementedError)."""
@@ -782,11 +804,12 @@ class VQAModel(nn.Module):
         if image_index is not None:
             return self._forward_indexed(images, token_ids, attention_mask, return_aux, image_index)
         eng = self._ensure_engine()
-        images = images.contiguous().float()
+        images, norm = self._image_operand(images)
         token_ids = token_ids.contiguous().long()
         maskf = None if attention_mask is None else attention_mask.contiguous().float()
         params = self._param_list()
         if torch.is_grad_enabled() and (images.requires_grad or any(p.requires_grad for p in params)):
+            self._byte_norm = norm               # (the ops below carry tensors: _op_images wraps the bytes again)
             # tapes are kept by id (gradient accumulation / loss1 + loss2: several forwards, then their backwards), oldest dropped
             # beyond max_live_tapes.  Images that require grad take this path even when no parameter does (a frozen model under
             # saliency / adversarial attacks): the flat buffer then goes in untracked, so no parameter receives a .grad, and the
@@ -808,10 +831,25 @@ class VQAModel(nn.Module):
             # the serving case: api/inference.py:228,296 calls model(image, ids, mask) under no_grad at B = 1 ... a few; ~190 launches
             # of a few microseconds are host-bound there, so the captured HIP graph of this shape is replayed (same kernels, same
             # logits); the result is copied out of the graph's static buffer so callers own what they get, like the reference
-            logits, aux = self.forward_graphed(images, token_ids, attention_mask).clone(), None
+            logits, aux = self.forward_graphed(self._eng_images(images, norm), token_ids, attention_mask).clone(), None
         else:
-            logits, aux, _ = eng.forward(images, token_ids, maskf, self.training, return_aux, need_tape=False, plan=self._modes_plan())
+            logits, aux, _ = eng.forward(self._eng_images(images, norm), token_ids, maskf, self.training, return_aux, need_tape=False,
+                                         plan=self._modes_plan())
         return (logits, aux) if return_aux else (logits, None)
+
+    def _image_operand(self, images):
+        """What every entry does with its `images` argument: (tensor, norm).  A float (or any plain) tensor becomes the contiguous
+        float32 NCHW batch the kernels read and norm is None -- a plain uint8 tensor too: 0 ... 255 as floats, as ever.  A ByteImages
+        gives its uint8 HWC data as it is and norm = (mean, std); its lookup table is made here, ahead of any graph capture."""
+        if _is_bytes(images):
+            self._pkg.kernels.u8_norm_table(images.data.device, images.mean, images.std)
+            return images.data, (images.mean, images.std)
+        return images.contiguous().float(), None
+
+    @staticmethod
+    def _eng_images(images: torch.Tensor, norm):
+        """The engine's image operand from _image_operand's pair (also from a graph's static copy of the tensor)."""
+        return images if norm is None else ByteImages(images, *norm)
 
     def _forward_aux_graph(self, images, token_ids, maskf, flat):
         feat, text = torch.ops.vqa_hip.vqa_aux_encoders(images, token_ids, maskf, flat, self._handle, self.training)
@@ -836,15 +874,16 @@ class VQAModel(nn.Module):
             raise RuntimeError("forward_graphed is the inference path: call model.eval() first")
         if not images.is_cuda:
             raise RuntimeError("VQAModel (HIP) got CPU inputs; this implementation only runs on an MI355X (no CPU fallback)")
+        images, norm = self._image_operand(images)           # (ByteImages: the static image buffer is uint8, and mean / std are in the key)
         key = (tuple(images.shape), tuple(token_ids.shape), attention_mask is not None, self._flat.data_ptr(), self._ensure_engine().fold_eval,
-               getattr(self._engine, "fuse_stem_eval", None), self._infer_precision)
+               getattr(self._engine, "fuse_stem_eval", None), self._infer_precision) + (() if norm is None else (norm,))
         g = self._graphs.pop(key, None)
         if g is None:
-            st_img = images.detach().clone().contiguous().float()
+            st_img = images.detach().clone()
             st_ids = token_ids.detach().clone().contiguous().long()
             st_msk = None if attention_mask is None else attention_mask.detach().clone().contiguous().float()
             with torch.no_grad():
-                graph, out = self._capture(lambda: self._forward_eager_eval(st_img, st_ids, st_msk))
+                graph, out = self._capture(lambda: self._forward_eager_eval(self._eng_images(st_img, norm), st_ids, st_msk))
             g = (graph, st_img, st_ids, st_msk, out)
         self._graph_put(key, g)                      # (re)inserted at the young end of the LRU order
         graph, st_img, st_ids, st_msk, out = g
@@ -932,9 +971,9 @@ class VQAModel(nn.Module):
             if not isinstance(out, ImageFeatures):
                 raise TypeError("encode_features: `out` must be an ImageFeatures")
             self._check_features(out, "encode_features(out=)")
-            if isinstance(at, bool) or int(at) != at or at < 0 or at + images.shape[0] > out.num_images:
-                raise IndexError(f"encode_features: rows [{at}, {at + images.shape[0]}) do not fit a bank of {out.num_images} images")
-        feat = eng.encode_features(images.contiguous().float())
+            if isinstance(at, bool) or int(at) != at or at < 0 or at + len(images) > out.num_images:
+                raise IndexError(f"encode_features: rows [{at}, {at + len(images)}) do not fit a bank of {out.num_images} images")
+        feat = eng.encode_features(self._eng_images(*self._image_operand(images)))
         if out is None:
             return ImageFeatures(feat, self._feat_stamp(eng), self._handle)
         if tuple(feat.shape[1:]) != tuple(out._t.shape[1:]):
@@ -1044,7 +1083,7 @@ class VQAModel(nn.Module):
     def _forward_indexed(self, images, token_ids, attention_mask, return_aux, image_index):
         self._inference_only("forward(image_index=...)", images)
         eng = self._ensure_engine()
-        images = images.contiguous().float()
+        images, norm = self._image_operand(images)
         token_ids = token_ids.contiguous().long()
         U, N = images.shape[0], token_ids.shape[0]
         idx = self._image_index(image_index, U, N, images.device)
@@ -1053,12 +1092,12 @@ class VQAModel(nn.Module):
         maskf = None if attention_mask is None else attention_mask.contiguous().float()
         if (self.graph_inference and not return_aux and 0 < N <= self.graph_max_batch and not torch.cuda.is_current_stream_capturing()):
             key = ("image_index", tuple(images.shape), tuple(token_ids.shape), maskf is not None, self._flat.data_ptr(), eng.fold_eval,
-                   eng.fuse_stem_eval, self._infer_precision)
+                   eng.fuse_stem_eval, self._infer_precision) + (() if norm is None else (norm,))
             g = self._graphs.pop(key, None)
             if g is None:
                 st_img, st_ids, st_idx = images.detach().clone(), token_ids.detach().clone(), idx.clone()
                 st_msk = None if maskf is None else maskf.detach().clone()
-                graph, out = self._capture(lambda: eng.answer(eng.encode_images(st_img), st_ids, st_msk, st_idx)[0])
+                graph, out = self._capture(lambda: eng.answer(eng.encode_images(self._eng_images(st_img, norm)), st_ids, st_msk, st_idx)[0])
                 g = (graph, st_img, st_ids, st_msk, st_idx, out)
             self._graph_put(key, g)                  # (re)inserted at the young end of the LRU order
             graph, st_img, st_ids, st_msk, st_idx, out = g
@@ -1067,7 +1106,7 @@ class VQAModel(nn.Module):
                 st_msk.copy_(maskf)
             graph.replay()
             return out.clone(), None
-        logits, aux = eng.answer(eng.encode_images(images, want_aux=return_aux), token_ids, maskf, idx, want_aux=return_aux)
+        logits, aux = eng.answer(eng.encode_images(self._eng_images(images, norm), want_aux=return_aux), token_ids, maskf, idx, want_aux=return_aux)
         return (logits, aux) if return_aux else (logits, None)
 
     def forward_grouped(self, images: torch.Tensor, token_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
@@ -1091,7 +1130,7 @@ class VQAModel(nn.Module):
             return self._forward_features(images, token_ids, attention_mask, return_aux, image_index, grouped=True)
         if not images.is_cuda:
             raise RuntimeError("VQAModel (HIP) got CPU inputs; this implementation only runs on an MI355X (no CPU fallback)")
-        U, N = images.shape[0], token_ids.shape[0]
+        U, N = len(images), token_ids.shape[0]
         idx = self._image_index(image_index, U, N, images.device)
         params = self._param_list()
         recording = torch.is_grad_enabled() and (images.requires_grad or any(p.requires_grad for p in params))
@@ -1101,17 +1140,18 @@ class VQAModel(nn.Module):
         if not self.training and not recording:
             return self.forward(images, token_ids, attention_mask, return_aux=return_aux, image_index=image_index)
         eng = self._ensure_engine()
-        images = images.contiguous().float()
+        images, norm = self._image_operand(images)
         token_ids = token_ids.contiguous().long()
         maskf = None if attention_mask is None else attention_mask.contiguous().float()
         if idx is None:
             idx = self._implied_index(U, N, images.device)
         if recording:
+            self._byte_norm = norm
             flat = _FlatParams.apply(self._flat, self._handle, *params) if any(p.requires_grad for p in params) else self._flat
             self._pending_plan = self._finetune_plan(params, images.requires_grad, self.training)
             logits = torch.ops.vqa_hip.vqa_forward_grouped(images, token_ids, maskf, idx, flat, self._handle, self.training)
             return logits, None
-        logits, aux, _ = eng.forward(images, token_ids, maskf, self.training, return_aux, need_tape=False, kv_index=idx,
+        logits, aux, _ = eng.forward(self._eng_images(images, norm), token_ids, maskf, self.training, return_aux, need_tape=False, kv_index=idx,
                                      plan=self._modes_plan())
         return (logits, aux) if return_aux else (logits, None)
 
@@ -1129,8 +1169,8 @@ class VQAModel(nn.Module):
             raise RuntimeError("VQAModel (HIP) got CPU inputs; this implementation only runs on an MI355X (no CPU fallback)")
         self._inference_only("encode_images", images)
         eng = self._ensure_engine()
-        ctx = eng.encode_images(images.contiguous().float(), want_aux=True)
-        return ImageContext(images.shape[0], ctx, self._ctx_stamp(eng), self._handle)
+        ctx = eng.encode_images(self._eng_images(*self._image_operand(images)), want_aux=True)
+        return ImageContext(len(images), ctx, self._ctx_stamp(eng), self._handle)
 
     def answer(self, context: ImageContext, token_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                image_index: Optional[torch.Tensor] = None, return_aux: bool = False) -> Tuple[torch.Tensor, Optional[Dict]]:
@@ -1257,18 +1297,19 @@ class VQAModel(nn.Module):
             raise RuntimeError("VQAModel (HIP) got CPU inputs; this implementation only runs on an MI355X (no CPU fallback)")
         self._inference_only("predict_topk", images)
         eng = self._ensure_engine()
-        images = images.contiguous().float()
+        images, norm = self._image_operand(images)
+        nkey = () if norm is None else (norm,)
         token_ids = token_ids.contiguous().long()
         maskf = None if attention_mask is None else attention_mask.contiguous().float()
         U, N = images.shape[0], token_ids.shape[0]
         if image_index is None:
             k, amask, scale = self._topk_args(top_k, answer_mask, temperature, U, images.device)
             key = (tuple(images.shape), tuple(token_ids.shape), maskf is not None, self._flat.data_ptr(), eng.fold_eval,
-                   getattr(eng, "fuse_stem_eval", None), self._infer_precision)
+                   getattr(eng, "fuse_stem_eval", None), self._infer_precision) + nkey
             feed = [images, token_ids, maskf]
             graphed = self.graph_inference and 0 < U <= self.graph_max_batch and not torch.cuda.is_current_stream_capturing()
             plan = None if graphed else self._modes_plan()           # (forward()'s two eval routes)
-            fn = lambda x, ids, msk: eng.forward(x, ids, msk, False, False, need_tape=False, lowp_logits=True, plan=plan)[0]
+            fn = lambda x, ids, msk: eng.forward(self._eng_images(x, norm), ids, msk, False, False, need_tape=False, lowp_logits=True, plan=plan)[0]
             return self._topk_route(key, U, lambda: [None if t is None else t.detach().clone() for t in feed], feed, fn,
                                     k, amask, scale, return_logits)
         idx = self._image_index(image_index, U, N, images.device)
@@ -1276,9 +1317,9 @@ class VQAModel(nn.Module):
             idx = self._implied_index(U, N, images.device)
         k, amask, scale = self._topk_args(top_k, answer_mask, temperature, N, images.device)
         key = ("image_index", tuple(images.shape), tuple(token_ids.shape), maskf is not None, self._flat.data_ptr(), eng.fold_eval,
-               eng.fuse_stem_eval, self._infer_precision)
+               eng.fuse_stem_eval, self._infer_precision) + nkey
         feed = [images, token_ids, maskf, idx]
-        fn = lambda x, ids, msk, ix: eng.answer(eng.encode_images(x), ids, msk, ix, lowp_logits=True)[0]
+        fn = lambda x, ids, msk, ix: eng.answer(eng.encode_images(self._eng_images(x, norm)), ids, msk, ix, lowp_logits=True)[0]
         return self._topk_route(key, N, lambda: [None if t is None else t.detach().clone() for t in feed], feed, fn,
                                 k, amask, scale, return_logits)
 

@@ -59,6 +59,11 @@ def pick_concurrent_streams(device, n: int, avoid=(), tries: int = 12):
     return tuple(chosen)
 
 
+def _image_shape(images):
+    """(B, 3, H, W) of an image operand: the NCHW fp32 tensor, or a ByteImages (uint8 HWC; dropin/utils/byte_images.py)."""
+    return images.shape_nchw if K.is_byte_images(images) else tuple(images.shape)
+
+
 def stem_fcoef(gamma: torch.Tensor, beta: torch.Tensor) -> torch.Tensor:
     """Coefficient block (0, 0, beta, 1/gamma) [4][C] that makes vqa_bn_bwd_reduce, fed with y := the POOLED stem output, form the
     stem's BatchNorm-backward sums: where pooled > 0 it equals gamma*xhat + beta, so (pooled - beta) * (1/gamma) is xhat
@@ -623,11 +628,11 @@ class HipEngine:
         self.begin_step(for_backward=need_tape)
         if ctrain and self.fuse_bn_finalize and self.dtype == torch.bfloat16:
             self._acc_reset()                     # one memset for every BatchNorm accumulator of this forward
-        tape: dict = {"training": ctrain, "B": images.shape[0], "Bq": token_ids.shape[0]}     # image rows, question rows
+        tape: dict = {"training": ctrain, "B": _image_shape(images)[0], "Bq": token_ids.shape[0]}     # image rows, question rows
         if plan is not None and need_tape:
             tape["plan"] = plan
         training = ctrain                         # from here on `training` is the CNN's mode (BatchNorm)
-        B = images.shape[0]
+        B = _image_shape(images)[0]
         pdrop = cfg["dropout"] if ttrain else 0.0          # text encoder
         pfus = cfg["dropout"] if ftrain else 0.0           # projector and cross-attention layers
         phead = cfg["answer_dropout"] if htrain else 0.0
@@ -800,11 +805,16 @@ class HipEngine:
         """conv7x7/2 (from the NCHW fp32 image) + BN + ReLU + maxpool, A1.  keep: the caller's tape wants the stem's activations (the
         one-launch inference form keeps none).  Returns (pooled [B*Hp*Wp][64], Hp, Wp, tape record | None)."""
         T, dev = self.dtype, images.device
-        B, _, IH, IW = images.shape
+        B, _, IH, IW = _image_shape(images)
         H1, W1 = (IH + 6 - 7) // 2 + 1, (IW + 6 - 7) // 2 + 1
         M = B * H1 * W1
         sgeom = (B, IH, IW, 3, H1, W1, 7, 7, 2, 3)
         Hp, Wp = (H1 + 2 - 3) // 2 + 1, (W1 + 2 - 3) // 2 + 1
+        if K.is_byte_images(images) and not (self.stem_w2 is not None and K.stem_conv_blocks(B, IH, IW) > 0):
+            # ByteImages: the dedicated bf16 kernels read the bytes themselves (the one-launch inference stem falls back to the
+            # two-kernel form, so that form's shape test decides); everything else -- the fp32 compute dtype, a shape only the
+            # generic igemm / wgrad with LOADER_STEM take -- normalises once and runs the float route as it is
+            images = images.to_float()
         if self.fuse_stem_eval and not training and not keep and self.stem_w2 is not None:
             # inference: the whole stem in one launch, the 112 x 112 conv output is never stored (no argmax: there is no backward)
             x = K.stem_conv_pool(images, self.stem_w2, self._bn_coef("image_encoder.stem.1", None, 0, 64, M, False), B, IH, IW)
@@ -1154,7 +1164,7 @@ class HipEngine:
             raise RuntimeError("encode_images runs the Conv+BN-folded eval path (fold_eval = True)")
         self._site = 0
         self.begin_step(for_backward=False)
-        U = images.shape[0]
+        U = _image_shape(images)[0]
         x, H, W, _ = self._stem_fwd(images, False, False)
         feat, H, W, C, _ = self._stages_fwd(x, U, H, W, False, False)
         return self._context_of(feat, U, H, W, C, want_aux)
@@ -1165,7 +1175,7 @@ class HipEngine:
         the compute dtype -- what forward_features() and context_from_features() start from."""
         self._site = 0
         self.begin_step(for_backward=False)
-        U = images.shape[0]
+        U = _image_shape(images)[0]
         x, H, W, _ = self._stem_fwd(images, False, False)
         feat, H, W, C, _ = self._stages_fwd(x, U, H, W, False, False)
         return feat.view(U, H, W, C)
@@ -1321,6 +1331,9 @@ class HipEngine:
         """G: flat fp32 gradient buffer (same layout as the parameters), accumulated into (+=).  The three parts below (head,
         fusion, encoders) run back to back without joining their side streams in between.  want_input_grad: also return the
         gradient with respect to the images (fp32 NCHW [B][3][H][W], complete on the current stream); None otherwise."""
+        if want_input_grad and "stem" in tape and K.is_byte_images(tape["stem"]["images"]):
+            raise TypeError("backward: an image gradient was asked of ByteImages; gradients belong to float images "
+                            "(pass images.to_float().requires_grad_())")
         self._bwd_begin()
         plan = tape.get("plan")
         if plan is not None and want_input_grad and not plan.images_grad:
@@ -1703,6 +1716,9 @@ class HipEngine:
         Bq, IH, IW, _, H1, W1 = st["geom"][:6]
         if fused is None:
             fused = self.stem_w2 is not None and K.stem_conv_blocks(B, IH, IW) > 0
+        images = st["images"]                     # NCHW fp32, or the ByteImages the dedicated forward read
+        if K.is_byte_images(images) and (not fused or want_dimg):
+            images = images.to_float()            # the generic weight gradient reads floats; an image gradient belongs to float images
         # BatchNorm-backward sums of the stem WITHOUT touching the 112x112 tensors: every pooling window routes its gradient to
         # exactly one position (its argmax), whose post-ReLU value is the pooled output itself, so
         #   sum g       = sum_windows dpool * [pooled > 0]
@@ -1732,14 +1748,7 @@ class HipEngine:
             pass                                  # (fine-tuning: the stem conv is frozen -- only the image gradient below)
         elif fused:
             # dy (B x 112 x 112 x 64) is never written: the weight-gradient kernel rebuilds it row by row
-            dwv = self._gslice(G, "image_encoder.stem.0.weight")
-            e0 = K.prof_begin()
-            ws, wsf = K.stem_wgrad_scratch(dxc.device, B, IH, IW)
-            call("vqa_stem_wgrad_fused", ptr(st["images"]), ptr(st["y"]), ptr(dxc), ptr(st["idx"]), ptr(st["coef"]), ptr(bc), ptr(dwv), B, IH, IW,
-                 ptr(ws), wsf)
-            if e0 is not None:
-                K.prof_end(e0, "stem_wgrad_kernel<true>", 2.0 * B * H1 * W1 * 64 * 147,
-                           B * 3 * IH * IW * 4 + B * H1 * W1 * 64 * 2 + dxc.numel() * 3)
+            K.stem_wgrad_fused(images, st["y"], dxc, st["idx"], st["coef"], bc, self._gslice(G, "image_encoder.stem.0.weight"), B, IH, IW)
         if fused:
             if want_dimg:
                 if K.stem_dgrad_fused_ok(B, IH, IW):
@@ -1752,7 +1761,7 @@ class HipEngine:
             dy = torch.empty_like(st["y"])
             call("vqa_stem_bwd_apply", dt(T), ptr(dxc), ptr(st["idx"]), ptr(st["y"]), ptr(st["coef"]), ptr(bc), ptr(dy), B, H1, W1, 64)
             if not skip_w:
-                K.wgrad(dy, st["images"], LY.mat_of(G, self.E["image_encoder.stem.0.weight"]), B * H1 * W1, 64, 147, st["geom"], dtype=T,
+                K.wgrad(dy, images, LY.mat_of(G, self.E["image_encoder.stem.0.weight"]), B * H1 * W1, 64, 147, st["geom"], dtype=T,
                         loader=K.LOADER_STEM)
             if want_dimg:
                 dimg = K.stem_dgrad(dy, wpk, B, IH, IW)

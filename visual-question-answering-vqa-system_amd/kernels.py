@@ -310,14 +310,62 @@ def dgrad_s2(dy, dyd, wt, B, H, W, C, Ho, Wo, N, R, pad, *, dtype):
     return out
 
 
+def is_byte_images(x) -> bool:
+    """A ByteImages of the drop-in utils.byte_images, recognised by its members (that module can be imported under several names)."""
+    return hasattr(x, "shape_nchw") and hasattr(x, "to_float") and hasattr(x, "mean") and hasattr(x, "std")
+
+
+_U8_TABLES = {}
+
+
+def u8_norm_table(device, mean, std):
+    """The bf16 [3][256] table the *_u8 stem entries look bytes up in, built once per (device, mean, std) by vqa_u8_norm_table and
+    kept: table[c][v] = bf16((v / 255 - mean[c]) / std[c])."""
+    key = (str(device), tuple(mean), tuple(std))
+    t = _U8_TABLES.get(key)
+    if t is None:
+        if torch.cuda.is_current_stream_capturing():          # (a table made inside a capture would live in that graph's pool)
+            raise RuntimeError("u8_norm_table: the table of a new (mean, std) cannot be built while a HIP graph is being captured")
+        t = torch.empty((3, 256), device=device, dtype=torch.bfloat16)
+        call("vqa_u8_norm_table", *(float(v) for v in mean), *(float(v) for v in std), ptr(t))
+        _U8_TABLES[key] = t
+    return t
+
+
+def _img_of(img):
+    """(device pointer, norm-table pointer | None, bytes per element, entry / symbol suffix) of a stem kernel's image operand: the NCHW
+    fp32 tensor, or a ByteImages (uint8 HWC and its table)."""
+    if is_byte_images(img):
+        return ptr(img.data), ptr(u8_norm_table(img.data.device, img.mean, img.std)), 1, "_u8"
+    return ptr(img), None, 4, ""
+
+
+def _img_device(img):
+    return img.data.device if is_byte_images(img) else img.device
+
+
 def stem_wgrad(img, dy, dw, B, H, W):
-    """bf16 stem weight gradient: dw [64][7][7][3] fp32 += dy^T im2col(img)."""
+    """bf16 stem weight gradient: dw [64][7][7][3] fp32 += dy^T im2col(img).  img: NCHW fp32, or a ByteImages."""
     Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+    ip, tab, esz, sfx = _img_of(img)
     e0 = prof_begin()
-    ws, wsf = stem_wgrad_scratch(img.device, B, H, W)
-    call("vqa_stem_wgrad", ptr(img), ptr(dy), ptr(dw), B, H, W, ptr(ws), wsf)
+    ws, wsf = stem_wgrad_scratch(_img_device(img), B, H, W)
+    call("vqa_stem_wgrad" + sfx, ip, ptr(dy), ptr(dw), B, H, W, ptr(ws), wsf, *(() if tab is None else (tab,)))
     if e0 is not None:
-        prof_end(e0, "stem_wgrad_kernel<false>", 2.0 * B * Ho * Wo * 64 * 147, B * 3 * H * W * 4 + B * Ho * Wo * 64 * 2)
+        prof_end(e0, f"stem_wgrad{sfx}_kernel<false>", 2.0 * B * Ho * Wo * 64 * 147, B * 3 * H * W * esz + B * Ho * Wo * 64 * 2)
+
+
+def stem_wgrad_fused(img, y, dpool, idx, coef, bc, dw, B, H, W):
+    """Fused stem BatchNorm/ReLU/MaxPool backward + weight gradient (vqa_stem_wgrad_fused): dy is rebuilt per row from y, dpool, idx,
+    coef and bc and never written.  img: NCHW fp32, or a ByteImages."""
+    Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+    ip, tab, esz, sfx = _img_of(img)
+    e0 = prof_begin()
+    ws, wsf = stem_wgrad_scratch(dpool.device, B, H, W)
+    call("vqa_stem_wgrad_fused" + sfx, ip, ptr(y), ptr(dpool), ptr(idx), ptr(coef), ptr(bc), ptr(dw), B, H, W, ptr(ws), wsf,
+         *(() if tab is None else (tab,)))
+    if e0 is not None:
+        prof_end(e0, f"stem_wgrad{sfx}_kernel<true>", 2.0 * B * Ho * Wo * 64 * 147, B * 3 * H * W * esz + B * Ho * Wo * 64 * 2 + dpool.numel() * 3)
 
 
 def stem_wgrad_scratch(device, B, H, W):
@@ -371,30 +419,33 @@ def stem_conv_blocks(B, H, W) -> int:
 
 
 def stem_conv(img, wstem, B, H, W, want_stats):
-    """bf16 stem conv 7x7/2 from the NCHW fp32 image.  Returns (y [B*Ho*Wo, 64] bf16, stats slab | None, blocks)."""
+    """bf16 stem conv 7x7/2 from the NCHW fp32 image, or from a ByteImages.  Returns (y [B*Ho*Wo, 64] bf16, stats slab | None, blocks)."""
     nb = stem_conv_blocks(B, H, W)
     Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
-    y = torch.empty((B * Ho * Wo, 64), device=img.device, dtype=torch.bfloat16)
-    stats = torch.empty((nb, 2, 64), device=img.device, dtype=torch.float32) if want_stats else None
+    ip, tab, esz, sfx = _img_of(img)
+    dev = _img_device(img)
+    y = torch.empty((B * Ho * Wo, 64), device=dev, dtype=torch.bfloat16)
+    stats = torch.empty((nb, 2, 64), device=dev, dtype=torch.float32) if want_stats else None
     e0 = prof_begin()
-    call("vqa_stem_conv", ptr(img), ptr(wstem), ptr(y), ptr(stats), B, H, W)
+    call("vqa_stem_conv" + sfx, ip, ptr(wstem), ptr(y), ptr(stats), B, H, W, *(() if tab is None else (tab,)))
     if e0 is not None:
-        prof_end(e0, "stem_conv_kernel", 2.0 * B * Ho * Wo * 64 * 147, B * 3 * H * W * 4 + B * Ho * Wo * 64 * 2)
+        prof_end(e0, f"stem_conv{sfx}_kernel", 2.0 * B * Ho * Wo * 64 * 147, B * 3 * H * W * esz + B * Ho * Wo * 64 * 2)
     return y, stats, nb
 
 
 def stem_conv_pool(img, wstem, coef, B, H, W):
-    """Inference stem in one launch: conv7x7/2 + BatchNorm (running statistics) + ReLU + MaxPool3x3/2 from the NCHW fp32 image.
+    """Inference stem in one launch: conv7x7/2 + BatchNorm (running statistics) + ReLU + MaxPool3x3/2 from the NCHW fp32 image or a ByteImages.
     Returns the pooled activation [B*Hp*Wp, 64] bf16, or None when the shape is not supported (the caller takes the two-kernel path)."""
     if not L.count("vqa_stem_conv_pool_ok", B, H, W):
         return None
     Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
     Hp, Wp = (Ho + 2 - 3) // 2 + 1, (Wo + 2 - 3) // 2 + 1
-    x = torch.empty((B * Hp * Wp, 64), device=img.device, dtype=torch.bfloat16)
+    ip, tab, esz, sfx = _img_of(img)
+    x = torch.empty((B * Hp * Wp, 64), device=_img_device(img), dtype=torch.bfloat16)
     e0 = prof_begin()
-    call("vqa_stem_conv_pool", ptr(img), ptr(wstem), ptr(coef), ptr(x), B, H, W)
+    call("vqa_stem_conv_pool" + sfx, ip, ptr(wstem), ptr(coef), ptr(x), B, H, W, *(() if tab is None else (tab,)))
     if e0 is not None:
-        prof_end(e0, "stem_conv_pool_kernel", 2.0 * B * Ho * Wo * 64 * 147, B * 3 * H * W * 4 + B * Hp * Wp * 64 * 2)
+        prof_end(e0, f"stem_conv_pool{sfx}_kernel", 2.0 * B * Ho * Wo * 64 * 147, B * 3 * H * W * esz + B * Hp * Wp * 64 * 2)
     return x
 
 

@@ -101,6 +101,7 @@ def step_key(*, features: bool, images, token_ids, attention_mask, image_index, 
     which buffers -- and nothing that only decides values (the tensors' contents, lr, betas, eps, weight decay, max_norm, the EMA
     decay and warm-up flag, the step number: those reach the graph through its static inputs and the state block).
     images / token_ids / attention_mask / image_index: tensors or None (shape and dtype enter; the mask and the index also by presence);
+    images may be a ByteImages: its data's shape and dtype and its mean / std enter (the lookup table is baked into the graph);
     targets: a label tensor, or SoftTargets (ids / weights / counts: K and whether counts ride along);
     plan: finetune.Plan or None (trainable tuple and modes); loss_opts: (label_smoothing, ignore_index, id of the class-weight buffer);
     metrics: the tracker object or None (its identity: the graph writes that object's device counters);
@@ -113,6 +114,10 @@ def step_key(*, features: bool, images, token_ids, attention_mask, image_index, 
         tsig = ("soft", _sig(targets.ids), _sig(targets.weights), _sig(getattr(targets, "counts", None)))
     else:
         tsig = ("hard", _sig(targets))
-    return ("features" if features else "images", _sig(images), _sig(token_ids), _sig(attention_mask), _sig(image_index), tsig,
+    if hasattr(images, "shape_nchw"):             # ByteImages: the graph's table is the one of this mean / std
+        images_sig = ("bytes", _sig(images.data), tuple(images.mean), tuple(images.std))
+    else:
+        images_sig = _sig(images)
+    return ("features" if features else "images", images_sig, _sig(token_ids), _sig(attention_mask), _sig(image_index), tsig,
             None if plan is None else (tuple(plan.trainable), tuple(plan.modes)), str(loss_kind), loss_opts, bool(ema),
             None if metrics is None else id(metrics), int(flat_ptr), int(wsrc_ptr), table_id)

@@ -18,6 +18,7 @@ import torch.distributed as dist
 
 from . import ema as EMA
 from . import finetune as FT
+from . import kernels as K
 from . import layout as LY
 from . import stepgraph as SG
 from ._lib import call, dt, ptr
@@ -345,6 +346,9 @@ class HipTrainer:
         loss and a ZERO gradient: the step still runs AdamW on it (weight decay and the moments' decay apply), which is what the
         reference loop does with torch when every target is ignored; torch's NaN gradient in the weighted case is not reproduced.
         Such steps are counted on the device and check() raises ValueError for them.
+        images may be a ByteImages (dropin/utils/byte_images.py: the uint8 HWC batch as decoded, on the device): the stem kernels
+        normalise while they load and the step equals the one on images.to_float() bit for bit; step_graphed then keeps a uint8 static
+        image buffer and files the graph under the batch's mean / std as well.
         images may be an ImageFeatures (VQAModel.encode_features; with image_index: of the U images): the image encoder, which must be
         frozen and in eval mode, does not run, and everything after it is the same step -- the launches of the images step without the
         CNN forward, bit for bit.  RuntimeError before any launch when an image_encoder parameter requires grad, the image encoder is
@@ -378,13 +382,16 @@ class HipTrainer:
                             f"(got {type(metrics).__name__} with {'SoftTargets' if soft else 'a label tensor'})")
         if metrics is not None and soft and targets.counts is None:
             raise TypeError(f"HipTrainer.{who}: VQAChallengeAccuracy needs SoftTargets that carry `counts`")
+        byt = images if K.is_byte_images(images) else None       # ByteImages: uint8 [B,H,W,3] (its constructor checked rank and channels)
+        if byt is not None:
+            images = byt.data
         for name, t in (("images", images), ("token_ids", token_ids)) + ((("targets", targets),) if not soft else ()):
             if not (isinstance(t, torch.Tensor) and t.device == dev):
                 raise RuntimeError(f"HipTrainer.{who}: `{name}` must be a tensor on {dev} (there is no CPU path)")
         Bq = token_ids.shape[0] if (image_index is not None and token_ids.dim() == 2) else images.shape[0]
         if soft:
             targets.validate(Bq, dev)
-        if images.dim() != 4 or (feats is None and images.shape[1] != 3) or token_ids.dim() != 2 or token_ids.shape[0] != Bq or (not soft and targets.shape != (Bq,)):
+        if images.dim() != 4 or (feats is None and byt is None and images.shape[1] != 3) or token_ids.dim() != 2 or token_ids.shape[0] != Bq or (not soft and targets.shape != (Bq,)):
             raise RuntimeError(f"HipTrainer.{who}: expected images [B,3,H,W], token_ids [B,L], targets [B]"
                                + ("" if image_index is None else " with B questions"))
         # fine-tuning: requires_grad and the parts' modes, resolved on every step (finetune.Plan; None: the plain step)
@@ -402,7 +409,9 @@ class HipTrainer:
             raise RuntimeError(f"HipTrainer.{who}: `attention_mask` must be a [B,L] tensor on {dev} (or None)")
         eng._pos_enc(token_ids.shape[1])                   # (a question that is too long is refused here, before anything is counted)
         # the kernels read raw pointers: enforce the dtypes / contiguity VQAModel.forward enforces (vqa_model.py drop-in)
-        if feats is None:
+        if byt is not None:
+            images = byt                                   # the bytes go to the engine as they are (and to the graph's static buffer)
+        elif feats is None:
             images = images.contiguous().float()
         token_ids = token_ids.contiguous().long()
         if not soft:
@@ -580,9 +589,12 @@ class HipTrainer:
 
     @staticmethod
     def _tensors_of(x):
-        """The tensors of one step input, in a fixed order: a tensor itself, the fields of SoftTargets that are present."""
+        """The tensors of one step input, in a fixed order: a tensor itself, the fields of SoftTargets that are present, the uint8
+        data of a ByteImages."""
         if _is_soft(x):
             return [t for t in (x.ids, x.weights, x.counts) if t is not None]
+        if K.is_byte_images(x):
+            return [x.data]
         return [x]
 
     def _capture_step(self, c):
@@ -597,6 +609,8 @@ class HipTrainer:
             if _is_soft(c[name]):
                 it = iter(copies)
                 cc[name] = type(c[name])(*(None if f is None else next(it) for f in (c[name].ids, c[name].weights, c[name].counts)))
+            elif K.is_byte_images(c[name]):                # a uint8 static buffer; mean / std are part of the key (the table is baked in)
+                cc[name] = type(c[name])(copies[0], c[name].mean, c[name].std)
             else:
                 cc[name] = copies[0]
         sig = self._copy_sig
