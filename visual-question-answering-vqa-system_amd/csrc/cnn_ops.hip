@@ -1157,7 +1157,6 @@ static inline int px_grid(size_t npix, int C, int VEC) { const size_t lr = 256 /
 static inline unsigned long long magic40(unsigned d) { return ((1ull << 40) + d - 1) / d; }   // (x * m) >> 40 == x / d for x*d < 2^40
 static inline int ew_grid(size_t n) { size_t g = (n + 255) / 256; return (int)(g > 16384 ? 16384 : (g ? g : 1)); }
 static inline int row_grid(size_t rows, int lanes_r) { size_t g = (rows + lanes_r - 1) / lanes_r; return (int)(g > 8192 ? 8192 : (g ? g : 1)); }
-#define DT(call_f, call_b) do { if (dtype) { call_b; } else { call_f; } } while (0)
 
 extern "C" {
 

@@ -216,6 +216,8 @@ static_assert(sizeof(vqa_group_hyper) == 128 && alignof(vqa_group_hyper) == 16 &
               "vqa_group_hyper: two arrays of 16 floats in a 16-byte aligned block");
 
 #define VQA_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)
+// an entry's `int dtype` argument picks the launch: 0 = the fp32 instantiation (call_f), 1 = the bf16 one (call_b)
+#define DT(call_f, call_b) do { if (dtype) { call_b; } else { call_f; } } while (0)
 
 // dst0[c] (c < n0) / dst1[c - n0] += sum over rows r < nrows of part[r * stride + c], rows in index order (fold_rows_kernel).  Defined in
 // token_ops.hip, where the kernel lives: other translation units launch it through this, so its device code exists once.

@@ -1,12 +1,11 @@
-// Token-side kernels for gfx950: embedding+positional encoding, LayerNorm, multi-head attention
-// (self: keys masked with -inf, cross: unmasked), masked mean-pool, sigmoid gate, bias/ReLU/dropout
+// Token-side kernels for gfx950: embedding+positional encoding, LayerNorm, masked mean-pool, sigmoid gate, bias/ReLU/dropout
 // backward, the fixed-order folds and the dtype casts.  (The optimizer tail -- L2 norm, clip, AdamW, weight EMA -- is optim_ops.hip;
-// everything that reads the answer logits -- losses, metrics, answer scores, top-k -- is loss_ops.hip.)
+// everything that reads the answer logits -- losses, metrics, answer scores, top-k -- is loss_ops.hip; multi-head attention is
+// attention.hip.)
 //   embedding*sqrt(d)+pe      models/text_encoder.py:504-510, :112-114
 //   LayerNorm                 models/text_encoder.py:390,395,519 ; cross_attention.py:286-287,295 ; fusion.py:326
-//   attention                 models/text_encoder.py:237-258 ; models/cross_attention.py:176-198
 //   masked mean / gate        models/fusion.py:303-320, :160-166
-// Rows are tokens ([B*L][D], D contiguous).  One 64-lane wave owns one row / one (batch, head).
+// Rows are tokens ([B*L][D], D contiguous).  One 64-lane wave owns one row.
 #include <cstdlib>
 #include "common.h"
 
@@ -405,128 +404,6 @@ __global__ __launch_bounds__(512) void layernorm_bwd_bf16v_kernel(const bf16_t* 
 }
 
 // ---------------------------------------------------------------------------------------------
-// Attention, one wave per (batch, head).  q/k/v/ctx are token-major with row strides ld* (elements);
-// head h occupies columns [h*hd, (h+1)*hd).  probs [B][H][Lq][Lk] fp32 holds softmax BEFORE dropout.
-// IDX (vqa_attention_fwd_idx, inference): the K / V / kmask rows of query batch b are those of image kv_index[b] (n_kv images of
-// Lk rows each); an index outside [0, n_kv) loads nothing and writes NaN to that batch's probs and ctx rows.
-// ---------------------------------------------------------------------------------------------
-template <typename T, bool IDX = false>
-__global__ __launch_bounds__(256) void attn_fwd_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
-                                                      int ldq, int ldk, int ldv, const float* __restrict__ kmask, float* __restrict__ probs,
-                                                      T* __restrict__ ctx, int ldc, int H, int Lq, int Lk, int hd, float scale, float p, uint64_t seed,
-                                                      const int* __restrict__ kv_index, int n_kv) {
-  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
-  extern __shared__ float sm[];
-  const int b = blockIdx.x / H, h = blockIdx.x - b * H, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ldh = hd + 1, ldp = Lk + 1;
-  int kb = b;                                                        // batch of the K / V / kmask rows
-  if constexpr (IDX) {
-    kb = kv_index[b];
-    if (kb < 0 || kb >= n_kv) {                                      // whole block leaves together (before any barrier)
-      for (int i = tid; i < Lq * Lk; i += 256) probs[((size_t)(b * H + h) * Lq) * Lk + i] = NAN;
-      for (int i = tid; i < Lq * hd; i += 256) { const int r = i / hd, d = i - r * hd; ctx[(size_t)(b * Lq + r) * ldc + h * hd + d] = from_f<T>(NAN); }
-      return;
-    }
-  }
-  float* Qs = sm; float* Ks = Qs + Lq * ldh; float* Vs = Ks + Lk * ldh; float* Ps = Vs + Lk * ldh;
-  for (int i = tid; i < Lq * hd; i += 256) { const int r = i / hd, d = i - r * hd; Qs[r * ldh + d] = to_f<T>(q[(size_t)(b * Lq + r) * ldq + h * hd + d]); }
-  for (int i = tid; i < Lk * hd; i += 256) {
-    const int r = i / hd, d = i - r * hd;
-    Ks[r * ldh + d] = to_f<T>(k[(size_t)(kb * Lk + r) * ldk + h * hd + d]);
-    Vs[r * ldh + d] = to_f<T>(v[(size_t)(kb * Lk + r) * ldv + h * hd + d]);
-  }
-  __syncthreads();
-  for (int i = tid; i < Lq * Lk; i += 256) {
-    const int r = i / Lk, c = i - r * Lk;
-    float s = 0.f;
-    for (int d = 0; d < hd; ++d) s += Qs[r * ldh + d] * Ks[c * ldh + d];
-    s = s / scale;                                                  // divide by sqrt(hd) before masking
-    if (kmask && kmask[kb * Lk + c] == 0.f) s = -INFINITY;
-    Ps[r * ldp + c] = s;
-  }
-  __syncthreads();
-  float* pg = probs + ((size_t)(b * H + h) * Lq) * Lk;
-  for (int r = wave; r < Lq; r += 4) {
-    float m = -INFINITY;
-    for (int c = lane; c < Lk; c += 64) m = fmaxf(m, Ps[r * ldp + c]);
-    m = wave_max(m);
-    float sum = 0.f;
-    for (int c = lane; c < Lk; c += 64) { const float e = expf(Ps[r * ldp + c] - m); Ps[r * ldp + c] = e; sum += e; }   // all -inf row -> NaN like torch
-    sum = wave_sum(sum);
-    for (int c = lane; c < Lk; c += 64) {
-      float pr = Ps[r * ldp + c] / sum;
-      pg[(size_t)r * Lk + c] = pr;
-      if (p > 0.f) pr = drop_keep32(drop_key(seed), (uint32_t)(((size_t)(b * H + h) * Lq + r) * Lk + c), p) ? pr / (1.f - p) : 0.f;
-      Ps[r * ldp + c] = pr;
-    }
-  }
-  __syncthreads();
-  for (int i = tid; i < Lq * hd; i += 256) {
-    const int r = i / hd, d = i - r * hd;
-    float a = 0.f;
-    for (int c = 0; c < Lk; ++c) a += Ps[r * ldp + c] * Vs[c * ldh + d];
-    ctx[(size_t)(b * Lq + r) * ldc + h * hd + d] = from_f<T>(a);
-  }
-}
-
-// DPR: dprobs [B][H][Lq][Lk] (fp32, like probs) is an upstream gradient on the saved softmax, added to dP before the row sums
-// (vqa_attention_bwd_dp); read per (q, k) pair along the rows exactly like probs (lane = key: coalesced).
-template <typename T, bool DPR>
-__global__ __launch_bounds__(256) void attn_bwd_kernel(const T* __restrict__ dctx, int ldc, const T* __restrict__ q, const T* __restrict__ k,
-                                                      const T* __restrict__ v, int ldq, int ldk, int ldv, const float* __restrict__ probs,
-                                                      T* __restrict__ dq, T* __restrict__ dk, T* __restrict__ dv, int lddq, int lddk, int lddv,
-                                                      int H, int Lq, int Lk, int hd, float scale, float p, uint64_t seed,
-                                                      const float* __restrict__ dprobs) {
-  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
-  extern __shared__ float sm[];
-  const int b = blockIdx.x / H, h = blockIdx.x - b * H, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ldh = hd + 1, ldp = Lk + 1;
-  float* Qs = sm; float* Os = Qs + Lq * ldh; float* Ks = Os + Lq * ldh; float* Vs = Ks + Lk * ldh;
-  float* Ps = Vs + Lk * ldh; float* Ds = Ps + Lq * ldp;             // Ps: dropped probs, Ds: dS
-  for (int i = tid; i < Lq * hd; i += 256) {
-    const int r = i / hd, d = i - r * hd;
-    Qs[r * ldh + d] = to_f<T>(q[(size_t)(b * Lq + r) * ldq + h * hd + d]);
-    Os[r * ldh + d] = to_f<T>(dctx[(size_t)(b * Lq + r) * ldc + h * hd + d]);
-  }
-  for (int i = tid; i < Lk * hd; i += 256) {
-    const int r = i / hd, d = i - r * hd;
-    Ks[r * ldh + d] = to_f<T>(k[(size_t)(b * Lk + r) * ldk + h * hd + d]);
-    Vs[r * ldh + d] = to_f<T>(v[(size_t)(b * Lk + r) * ldv + h * hd + d]);
-  }
-  __syncthreads();
-  const float* pg = probs + ((size_t)(b * H + h) * Lq) * Lk;
-  for (int r = wave; r < Lq; r += 4) {
-    float t = 0.f;
-    for (int c = lane; c < Lk; c += 64) {
-      const float pr = pg[(size_t)r * Lk + c];
-      float ks = 1.f;
-      if (p > 0.f) ks = drop_keep32(drop_key(seed), (uint32_t)(((size_t)(b * H + h) * Lq + r) * Lk + c), p) ? 1.f / (1.f - p) : 0.f;
-      float dpd = 0.f;
-      for (int d = 0; d < hd; ++d) dpd += Os[r * ldh + d] * Vs[c * ldh + d];
-      float dp = dpd * ks;
-      if constexpr (DPR) dp += dprobs[((size_t)(b * H + h) * Lq + r) * Lk + c];
-      Ps[r * ldp + c] = pr * ks;
-      Ds[r * ldp + c] = dp;
-      t += dp * pr;
-    }
-    t = wave_sum(t);
-    for (int c = lane; c < Lk; c += 64) Ds[r * ldp + c] = pg[(size_t)r * Lk + c] * (Ds[r * ldp + c] - t) / scale;
-  }
-  __syncthreads();
-  for (int i = tid; i < Lq * hd; i += 256) {
-    const int r = i / hd, d = i - r * hd;
-    float a = 0.f;
-    for (int c = 0; c < Lk; ++c) a += Ds[r * ldp + c] * Ks[c * ldh + d];
-    dq[(size_t)(b * Lq + r) * lddq + h * hd + d] = from_f<T>(a);
-  }
-  for (int i = tid; i < Lk * hd; i += 256) {
-    const int c = i / hd, d = i - c * hd;
-    float a = 0.f, e = 0.f;
-    for (int r = 0; r < Lq; ++r) { a += Ds[r * ldp + c] * Qs[r * ldh + d]; e += Ps[r * ldp + c] * Os[r * ldh + d]; }
-    dk[(size_t)(b * Lk + c) * lddk + h * hd + d] = from_f<T>(a);
-    dv[(size_t)(b * Lk + c) * lddv + h * hd + d] = from_f<T>(e);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
 // masked mean over L:  out[b][col0+d] = sum_l x[b][l][d]*m[b][l] / max(sum_l m[b][l], 1)   (mask null -> plain mean)
 // ---------------------------------------------------------------------------------------------
 template <typename T>
@@ -739,21 +616,7 @@ __global__ void convert_kernel(const TI* __restrict__ in, TO* __restrict__ out, 
 }
 
 // ---------------------------------------------------------------------------------------------
-#define DT(call_f, call_b) do { if (dtype) { call_b; } else { call_f; } } while (0)
 static inline unsigned g1(size_t n) { return (unsigned)((n + 255) / 256); }
-
-template <bool DPR>
-static int attention_bwd_valu(int dtype, const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
-                              const float* probs, const float* dprobs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv,
-                              int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t st) {
-  const size_t shm = ((size_t)(2 * Lq + 2 * Lk) * (hd + 1) + (size_t)2 * Lq * (Lk + 1)) * 4;
-  if (shm > 160 * 1024) return VQA_EARG;
-  const float scale = sqrtf((float)hd);
-  (void)vqa_ensure_lds(dtype ? reinterpret_cast<const void*>(&attn_bwd_kernel<bf16_t, DPR>) : reinterpret_cast<const void*>(&attn_bwd_kernel<float, DPR>), shm);
-  DT(hipLaunchKernelGGL((attn_bwd_kernel<float, DPR>), dim3(B * H), dim3(256), shm, st, (const float*)dctx, ldc, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, probs, (float*)dq, (float*)dk, (float*)dv, lddq, lddk, lddv, H, Lq, Lk, hd, scale, p, seed, dprobs),
-     hipLaunchKernelGGL((attn_bwd_kernel<bf16_t, DPR>), dim3(B * H), dim3(256), shm, st, (const bf16_t*)dctx, ldc, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, probs, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, lddq, lddk, lddv, H, Lq, Lk, hd, scale, p, seed, dprobs));
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
 
 extern "C" {
 
@@ -851,38 +714,6 @@ int vqa_layernorm_bwd(int dtype, const void* dout, const void* x, const float* g
   }
   if (part_ln && !defer_fold) vqa_launch_fold(part_ln, g.nb, (size_t)2 * D, 2 * D, dgamma, D, dbeta, st);
   VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-int vqa_attention_fwd(int dtype, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const float* kmask, float* probs,
-                      void* ctx, int ldc, int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t st) {
-  const size_t shm = ((size_t)(Lq + 2 * Lk) * (hd + 1) + (size_t)Lq * (Lk + 1)) * 4;
-  if (shm > 160 * 1024) return VQA_EARG;
-  const float scale = sqrtf((float)hd);
-  (void)vqa_ensure_lds(dtype ? reinterpret_cast<const void*>(&attn_fwd_kernel<bf16_t>) : reinterpret_cast<const void*>(&attn_fwd_kernel<float>), shm);
-  DT(hipLaunchKernelGGL(attn_fwd_kernel<float>, dim3(B * H), dim3(256), shm, st, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, kmask, probs, (float*)ctx, ldc, H, Lq, Lk, hd, scale, p, seed, nullptr, 0),
-     hipLaunchKernelGGL(attn_fwd_kernel<bf16_t>, dim3(B * H), dim3(256), shm, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, kmask, probs, (bf16_t*)ctx, ldc, H, Lq, Lk, hd, scale, p, seed, nullptr, 0));
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-int vqa_attention_fwd_idx(int dtype, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const int* kv_index, int n_kv,
-                          const float* kmask, float* probs, void* ctx, int ldc, int B, int H, int Lq, int Lk, int hd, hipStream_t st) {
-  if (!kv_index || n_kv < 0) return VQA_EARG;
-  const size_t shm = ((size_t)(Lq + 2 * Lk) * (hd + 1) + (size_t)Lq * (Lk + 1)) * 4;
-  if (shm > 160 * 1024) return VQA_EARG;
-  const float scale = sqrtf((float)hd);
-  (void)vqa_ensure_lds(dtype ? reinterpret_cast<const void*>(&attn_fwd_kernel<bf16_t, true>) : reinterpret_cast<const void*>(&attn_fwd_kernel<float, true>), shm);
-  DT(hipLaunchKernelGGL((attn_fwd_kernel<float, true>), dim3(B * H), dim3(256), shm, st, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, kmask, probs, (float*)ctx, ldc, H, Lq, Lk, hd, scale, 0.f, 0ull, kv_index, n_kv),
-     hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, true>), dim3(B * H), dim3(256), shm, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, kmask, probs, (bf16_t*)ctx, ldc, H, Lq, Lk, hd, scale, 0.f, 0ull, kv_index, n_kv));
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-int vqa_attention_bwd(int dtype, const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
-                      const float* probs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv,
-                      int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t st) {
-  return attention_bwd_valu<false>(dtype, dctx, ldc, q, k, v, ldq, ldk, ldv, probs, nullptr, dq, dk, dv, lddq, lddk, lddv, B, H, Lq, Lk, hd, p, seed, st);
-}
-int vqa_attention_bwd_dp(int dtype, const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
-                         const float* probs, const float* dprobs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv,
-                         int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t st) {
-  if (!dprobs) return VQA_EARG;
-  return attention_bwd_valu<true>(dtype, dctx, ldc, q, k, v, ldq, ldk, ldv, probs, dprobs, dq, dk, dv, lddq, lddk, lddv, B, H, Lq, Lk, hd, p, seed, st);
 }
 int vqa_masked_pool_fwd(int dtype, const void* x, const float* mask, void* out, int ldo, int col0, int B, int L, int D, hipStream_t st) {
   DT(hipLaunchKernelGGL(masked_pool_fwd_kernel<float>, dim3(B), dim3(256), 0, st, (const float*)x, mask, (float*)out, ldo, col0, L, D),
@@ -1014,829 +845,6 @@ int vqa_convert(int dtype_in, int dtype_out, const void* in, void* out, long lon
   else if (dtype_in && !dtype_out) hipLaunchKernelGGL((convert_kernel<bf16_t, float>), dim3(g), dim3(256), 0, st, (const bf16_t*)in, (float*)out, (size_t)n);
   else if (!dtype_in) hipLaunchKernelGGL((convert_kernel<float, float>), dim3(g), dim3(256), 0, st, (const float*)in, (float*)out, (size_t)n);
   else hipLaunchKernelGGL((convert_kernel<bf16_t, bf16_t>), dim3(g), dim3(256), 0, st, (const bf16_t*)in, (bf16_t*)out, (size_t)n);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-
-}  // extern "C"
-
-// ---------------------------------------------------------------------------------------------
-// bf16 MFMA attention forward: one wave per (batch, head), Lq <= 32 queries, Lk <= 64 keys, head dim HD in {32, 64}.
-//   S^T (keys x queries) = K . Q^T         v_mfma_f32_32x32x16_bf16, operands loaded straight from global as 16-byte fragments
-//   row softmax over keys: the query sits on the lane, its keys in the 32 accumulator registers of the two key tiles
-//     (+ one exchange with lane^32); probabilities go to the caller through an LDS staging tile (coalesced rows)
-//   ctx = P . V = (P^T)^T . V: the bf16-rounded accumulator registers ARE the A operand of the next MFMA (no lane movement);
-//     V is staged in LDS and read transposed with ds_read_b64_tr_b16 in the matching (permuted) k order.
-// Same masking semantics as the reference: keys with kmask == 0 get -inf before the softmax (an all-masked row is NaN).
-// ---------------------------------------------------------------------------------------------
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-// NKT = key tiles of 32 (2: Lk <= 64, the 49 image tokens / 20 text tokens; 5: Lk <= 160, the 144 image tokens of the 384x384
-// stress shape), WPB = waves (= (batch, head) problems) per workgroup: the wave-private LDS tiles of NKT = 5 fit two per CU.
-// IDX (vqa_attention_fwd_mfma_idx, inference): K / V / kmask rows of image kv_index[b] (n_kv images); out of range -> NaN rows.
-template <int HD, int NKT, int WPB, bool IDX = false>
-__global__ __launch_bounds__(WPB * 64, 1) void attn_fwd_mfma_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v,
-                                                            int ldq, int ldk, int ldv, const float* __restrict__ kmask, float* __restrict__ probs,
-                                                            bf16_t* __restrict__ ctx, int ldc, int BH, int H, int Lq, int Lk, float p, uint64_t seed,
-                                                            const int* __restrict__ kv_index, int n_kv) {
-  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
-  constexpr int LDV = HD;                       // V tile row stride (elements): 64 / 128 bytes, 8-byte aligned for the transposed reads
-  constexpr int KR = NKT * 32;                  // key rows of the tiles
-  constexpr int LDP = KR + 1;                   // probability staging row stride (floats)
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int bh = blockIdx.x * WPB + wave;
-  bf16_t* Vs = reinterpret_cast<bf16_t*>(smem) + wave * (KR * LDV);
-  float* Ps = reinterpret_cast<float*>(smem + WPB * KR * LDV * 2) + wave * (32 * LDP);
-  if (bh >= BH) return;                         // whole wave exits together; no block-level barrier is used below
-  const int b = bh / H, h = bh - b * H;
-  const int r = lane & 31, hh = lane >> 5;
-  const float inv_scale = 1.0f / sqrtf((float)HD);
-  int kb = b;                                   // batch of the K / V / kmask rows
-  if constexpr (IDX) {
-    kb = __builtin_amdgcn_readfirstlane(kv_index[b]);
-    if (kb < 0 || kb >= n_kv) {                 // the whole wave leaves together
-      for (int i = lane; i < Lq * Lk; i += 64) probs[(size_t)bh * Lq * Lk + i] = NAN;
-      for (int i = lane; i < Lq * HD; i += 64) ctx[(size_t)(b * Lq + i / HD) * ldc + h * HD + i % HD] = f2bf(NAN);
-      return;
-    }
-  }
-
-  // ---- V -> LDS (rows >= Lk zero), 16-byte vectors
-  for (int i = lane; i < KR * (HD / 8); i += 64) {
-    const int row = i / (HD / 8), cv = i - row * (HD / 8);
-    u32x4 val = {0u, 0u, 0u, 0u};
-    if (row < Lk) val = *reinterpret_cast<const u32x4*>(v + (size_t)(kb * Lk + row) * ldv + h * HD + cv * 8);
-    *reinterpret_cast<u32x4*>(&Vs[row * LDV + cv * 8]) = val;
-  }
-  // ---- S^T = K Q^T
-  f32x16 st[NKT];
-#pragma unroll
-  for (int t = 0; t < NKT; ++t)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) st[t][e] = 0.f;
-#pragma unroll
-  for (int ks = 0; ks < HD / 16; ++ks) {
-    bf16x8 qf = {};
-    if (r < Lq) qf = *reinterpret_cast<const bf16x8*>(q + (size_t)(b * Lq + r) * ldq + h * HD + ks * 16 + 8 * hh);
-#pragma unroll
-    for (int t = 0; t < NKT; ++t) {
-      bf16x8 kf = {};
-      if (32 * t + r < Lk) kf = *reinterpret_cast<const bf16x8*>(k + (size_t)(kb * Lk + 32 * t + r) * ldk + h * HD + ks * 16 + 8 * hh);
-      st[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf, st[t], 0, 0, 0);
-    }
-  }
-  // ---- scale, mask, softmax over keys (query = lane&31; keys: (e&3) + 8*(e>>2) + 4*hh + 32*t)
-  float m = -INFINITY;
-#pragma unroll
-  for (int t = 0; t < NKT; ++t)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int key = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
-      float s = st[t][e] * inv_scale;
-      if (key >= Lk || (kmask && kmask[kb * Lk + key] == 0.f)) s = -INFINITY;
-      st[t][e] = s;
-      m = fmaxf(m, s);
-    }
-  m = fmaxf(m, __shfl_xor(m, 32, 64));
-  float sum = 0.f;
-#pragma unroll
-  for (int t = 0; t < NKT; ++t)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { const float ex = expf(st[t][e] - m); st[t][e] = ex; sum += ex; }   // all -inf row -> NaN like torch
-  sum += __shfl_xor(sum, 32, 64);
-  const float rs = 1.0f / sum;
-  const size_t prow = ((size_t)bh * Lq + r) * Lk;
-#pragma unroll
-  for (int t = 0; t < NKT; ++t)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int key = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
-      float pr = st[t][e] * rs;
-      if (sum != sum || m != m) pr = st[t][e] / sum;                       // keep NaN propagation exact (0 * inf etc.)
-      Ps[r * LDP + key] = pr;
-      if (p > 0.f && r < Lq && key < Lk) pr = drop_keep32(drop_key(seed), (uint32_t)(prow + key), p) ? pr / (1.f - p) : 0.f;
-      st[t][e] = pr;
-    }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                     // wave-private LDS: V tile + probabilities are visible
-  for (int i = lane; i < Lq * Lk; i += 64) { const int qi = i / Lk, kj = i - qi * Lk; probs[(size_t)bh * Lq * Lk + i] = Ps[qi * LDP + kj]; }
-  // ---- ctx = P V : A operand = bf16(accumulator registers 8s..8s+7), B operand = V rows in the matching permuted key order
-  f32x16 o[HD / 32];
-#pragma unroll
-  for (int c = 0; c < HD / 32; ++c)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) o[c][e] = 0.f;
-  const int g2 = (lane >> 4) & 1, li = lane & 15, qd = li >> 2, pp = li & 3;
-  typedef __attribute__((ext_vector_type(8))) short i16x8;
-#pragma unroll
-  for (int t = 0; t < NKT; ++t)
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      bf16x8 af;
-#pragma unroll
-      for (int jj = 0; jj < 8; ++jj) af[jj] = (__bf16)st[t][8 * s + jj];
-#pragma unroll
-      for (int c = 0; c < HD / 32; ++c) {
-        const bf16_t* vb = Vs + (32 * t + 16 * s + 4 * hh + qd) * LDV + c * 32 + 16 * g2 + 4 * pp;
-        i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((i16x4 __attribute__((address_space(3)))*)(vb));
-        i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((i16x4 __attribute__((address_space(3)))*)(vb + 8 * LDV));
-        i16x8 tt = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        o[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, __builtin_bit_cast(bf16x8, tt), o[c], 0, 0, 0);
-      }
-    }
-#pragma unroll
-  for (int c = 0; c < HD / 32; ++c)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int qi = (e & 3) + 8 * (e >> 2) + 4 * hh;
-      if (qi < Lq) ctx[(size_t)(b * Lq + qi) * ldc + h * HD + c * 32 + r] = f2bf(o[c][e]);
-    }
-}
-
-extern "C" int vqa_attention_fwd_mfma(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const float* kmask, float* probs,
-                                      void* ctx, int ldc, int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t st) {
-  if (!q || !k || !v || !probs || !ctx || Lq > 32 || Lk > 160 || (hd != 32 && hd != 64) || (ldq % 8) || (ldk % 8) || (ldv % 8)) return VQA_EARG;
-  const int BH = B * H;
-  auto go = [&](auto kern, int nkt, int wpb) {
-    const size_t shm = (size_t)wpb * (nkt * 32) * hd * 2 + (size_t)wpb * 32 * (nkt * 32 + 1) * 4;
-    (void)vqa_ensure_lds(reinterpret_cast<const void*>(kern), shm);
-    hipLaunchKernelGGL(kern, dim3((BH + wpb - 1) / wpb), dim3(wpb * 64), shm, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv,
-                       kmask, probs, (bf16_t*)ctx, ldc, BH, H, Lq, Lk, p, seed, nullptr, 0);
-  };
-  if (Lk <= 64) { if (hd == 32) go(&attn_fwd_mfma_kernel<32, 2, 4>, 2, 4); else go(&attn_fwd_mfma_kernel<64, 2, 4>, 2, 4); }
-  else { if (hd == 32) go(&attn_fwd_mfma_kernel<32, 5, 2>, 5, 2); else go(&attn_fwd_mfma_kernel<64, 5, 2>, 5, 2); }
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-
-extern "C" int vqa_attention_fwd_mfma_idx(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const int* kv_index, int n_kv,
-                                          const float* kmask, float* probs, void* ctx, int ldc, int B, int H, int Lq, int Lk, int hd, hipStream_t st) {
-  if (!q || !k || !v || !kv_index || n_kv < 0 || !probs || !ctx || Lq > 32 || Lk > 160 || (hd != 32 && hd != 64) || (ldq % 8) || (ldk % 8) || (ldv % 8))
-    return VQA_EARG;
-  const int BH = B * H;
-  auto go = [&](auto kern, int nkt, int wpb) {
-    const size_t shm = (size_t)wpb * (nkt * 32) * hd * 2 + (size_t)wpb * 32 * (nkt * 32 + 1) * 4;
-    (void)vqa_ensure_lds(reinterpret_cast<const void*>(kern), shm);
-    hipLaunchKernelGGL(kern, dim3((BH + wpb - 1) / wpb), dim3(wpb * 64), shm, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv,
-                       kmask, probs, (bf16_t*)ctx, ldc, BH, H, Lq, Lk, 0.f, 0ull, kv_index, n_kv);
-  };
-  if (Lk <= 64) { if (hd == 32) go(&attn_fwd_mfma_kernel<32, 2, 4, true>, 2, 4); else go(&attn_fwd_mfma_kernel<64, 2, 4, true>, 2, 4); }
-  else { if (hd == 32) go(&attn_fwd_mfma_kernel<32, 5, 2, true>, 5, 2); else go(&attn_fwd_mfma_kernel<64, 5, 2, true>, 5, 2); }
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// bf16 MFMA attention backward: one wave per (batch, head), Lq <= 32, Lk <= 32*NKT (NKT = 2 or 5), head dim HD in {32, 64}.
-// dP is formed TWICE from the same global 16-byte fragments (MFMAs are free at this size):
-//   orientation 1  dP^T = V . dctx^T   (lane = query, registers = keys)   -> row sums t[q], dS -> dQ = dS . K
-//   orientation 2  dP   = dctx . V^T   (lane = key,   registers = queries) -> dS, dropped P  -> dK = dS^T . Q, dV = Pd^T . dctx
-// In both, the bf16-rounded accumulator registers are the A operand of the following MFMA (as in the forward kernel) and the
-// B operand (K, Q or dctx rows) is read transposed from a wave-private LDS tile in the matching permuted order.
-// probs is the softmax BEFORE dropout saved by the forward; the dropout mask is regenerated from (seed, index).
-// DPR (vqa_attention_bwd_mfma_dp): dprobs [B][H][Lq][Lk] fp32, an upstream gradient on that softmax, is staged in a wave-private LDS
-// tile by the same coalesced row copy as probs and added to dP in both orientations: dP = ks * (dctx V^T) + dprobs.
-// ---------------------------------------------------------------------------------------------
-template <int HD>
-__device__ __forceinline__ bf16x8 attn_ldsB(const bf16_t* tile, int row0, int c, int hh, int g2, int qd, int pp) {
-  typedef __attribute__((ext_vector_type(8))) short i16x8;
-  const bf16_t* vb = tile + (row0 + 4 * hh + qd) * HD + c * 32 + 16 * g2 + 4 * pp;
-  i16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((i16x4 __attribute__((address_space(3)))*)(vb));
-  i16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((i16x4 __attribute__((address_space(3)))*)(vb + 8 * HD));
-  i16x8 tt = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8, tt);
-}
-
-template <int HD, int NKT, int WPB, bool DPR>
-__global__ __launch_bounds__(WPB * 64, 1) void attn_bwd_mfma_kernel(const bf16_t* __restrict__ dctx, int ldc, const bf16_t* __restrict__ q,
-                                                            const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int ldq, int ldk, int ldv,
-                                                            const float* __restrict__ probs, bf16_t* __restrict__ dq, bf16_t* __restrict__ dk,
-                                                            bf16_t* __restrict__ dv, int lddq, int lddk, int lddv, int BH, int H, int Lq, int Lk,
-                                                            float p, uint64_t seed, const float* __restrict__ dprobs) {
-  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
-  constexpr int KR = NKT * 32;
-  constexpr int LDP = KR + 1;
-  constexpr int WAVE_BYTES = (KR + 32 + 32) * HD * 2 + 32 * LDP * 4 + 32 * 4 + (DPR ? 32 * LDP * 4 : 0);
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int bh = blockIdx.x * WPB + wave;
-  if (bh >= BH) return;                         // whole wave exits together; only wave-private LDS, no block barrier below
-  char* base = smem + (size_t)wave * WAVE_BYTES;
-  bf16_t* Ks = reinterpret_cast<bf16_t*>(base);            // [KR][HD]
-  bf16_t* Qs = Ks + KR * HD;                               // [32][HD]
-  bf16_t* Os = Qs + 32 * HD;                               // [32][HD]  (dctx)
-  float* Ps = reinterpret_cast<float*>(Os + 32 * HD);      // [32][LDP]
-  float* Ts = Ps + 32 * LDP;                               // [32]
-  float* DPs = Ts + 32;                                    // [32][LDP]  (DPR only: dprobs)
-  const int b = bh / H, h = bh - b * H;
-  const int r = lane & 31, hh = lane >> 5;
-  const int g2 = (lane >> 4) & 1, li = lane & 15, qd = li >> 2, pp = li & 3;
-  const float inv_scale = 1.0f / sqrtf((float)HD);
-  const float keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
-
-  // ---- K, Q, dctx -> LDS (16-byte vectors, padding rows zero); probabilities -> LDS
-  for (int i = lane; i < KR * (HD / 8); i += 64) {
-    const int row = i / (HD / 8), cv = i - row * (HD / 8);
-    u32x4 val = {0u, 0u, 0u, 0u};
-    if (row < Lk) val = *reinterpret_cast<const u32x4*>(k + (size_t)(b * Lk + row) * ldk + h * HD + cv * 8);
-    *reinterpret_cast<u32x4*>(&Ks[row * HD + cv * 8]) = val;
-  }
-  for (int i = lane; i < 32 * (HD / 8); i += 64) {
-    const int row = i / (HD / 8), cv = i - row * (HD / 8);
-    u32x4 a = {0u, 0u, 0u, 0u}, o = {0u, 0u, 0u, 0u};
-    if (row < Lq) {
-      a = *reinterpret_cast<const u32x4*>(q + (size_t)(b * Lq + row) * ldq + h * HD + cv * 8);
-      o = *reinterpret_cast<const u32x4*>(dctx + (size_t)(b * Lq + row) * ldc + h * HD + cv * 8);
-    }
-    *reinterpret_cast<u32x4*>(&Qs[row * HD + cv * 8]) = a;
-    *reinterpret_cast<u32x4*>(&Os[row * HD + cv * 8]) = o;
-  }
-  for (int i = lane; i < Lq * Lk; i += 64) { const int qi = i / Lk, kj = i - qi * Lk; Ps[qi * LDP + kj] = probs[(size_t)bh * Lq * Lk + i]; }
-  if constexpr (DPR)
-    for (int i = lane; i < Lq * Lk; i += 64) { const int qi = i / Lk, kj = i - qi * Lk; DPs[qi * LDP + kj] = dprobs[(size_t)bh * Lq * Lk + i]; }
-
-  // ---- both orientations of dP = dctx V^T from the same global fragments
-  f32x16 d1[NKT], d2[NKT];
-#pragma unroll
-  for (int t = 0; t < NKT; ++t)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { d1[t][e] = 0.f; d2[t][e] = 0.f; }
-#pragma unroll
-  for (int ks = 0; ks < HD / 16; ++ks) {
-    bf16x8 of = {};
-    if (r < Lq) of = *reinterpret_cast<const bf16x8*>(dctx + (size_t)(b * Lq + r) * ldc + h * HD + ks * 16 + 8 * hh);
-#pragma unroll
-    for (int t = 0; t < NKT; ++t) {
-      bf16x8 vf = {};
-      if (32 * t + r < Lk) vf = *reinterpret_cast<const bf16x8*>(v + (size_t)(b * Lk + 32 * t + r) * ldv + h * HD + ks * 16 + 8 * hh);
-      d1[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, of, d1[t], 0, 0, 0);      // rows = keys, cols = queries
-      d2[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(of, vf, d2[t], 0, 0, 0);      // rows = queries, cols = keys
-    }
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                     // LDS tiles written above are visible to the whole wave
-
-  // ---- orientation 1: query = r, keys = 32t + (e&3) + 8(e>>2) + 4hh
-  const size_t prow = ((size_t)bh * Lq + r) * Lk;
-  float tq = 0.f;
-#pragma unroll
-  for (int t = 0; t < NKT; ++t)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int key = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
-      const bool ok = r < Lq && key < Lk;
-      const float pr = ok ? Ps[r * LDP + key] : 0.f;
-      float ks = 1.f;
-      if (p > 0.f && ok) ks = drop_keep32(drop_key(seed), (uint32_t)(prow + key), p) ? keep : 0.f;
-      float dp = ok ? d1[t][e] * ks : 0.f;
-      if constexpr (DPR) dp += ok ? DPs[r * LDP + key] : 0.f;
-      tq += dp * pr;
-      d1[t][e] = dp;
-    }
-  tq += __shfl_xor(tq, 32, 64);
-  if (hh == 0) Ts[r] = tq;
-#pragma unroll
-  for (int t = 0; t < NKT; ++t)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int key = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
-      const float pr = (r < Lq && key < Lk) ? Ps[r * LDP + key] : 0.f;
-      d1[t][e] = pr * (d1[t][e] - tq) * inv_scale;                     // dS[query r][key]
-    }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  // dQ = dS K
-  f32x16 oq[HD / 32];
-#pragma unroll
-  for (int c = 0; c < HD / 32; ++c)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) oq[c][e] = 0.f;
-#pragma unroll
-  for (int t = 0; t < NKT; ++t)
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      bf16x8 af;
-#pragma unroll
-      for (int jj = 0; jj < 8; ++jj) af[jj] = (__bf16)d1[t][8 * s2 + jj];
-#pragma unroll
-      for (int c = 0; c < HD / 32; ++c)
-        oq[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, attn_ldsB<HD>(Ks, 32 * t + 16 * s2, c, hh, g2, qd, pp), oq[c], 0, 0, 0);
-    }
-#pragma unroll
-  for (int c = 0; c < HD / 32; ++c)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int qi = (e & 3) + 8 * (e >> 2) + 4 * hh;
-      if (qi < Lq) dq[(size_t)(b * Lq + qi) * lddq + h * HD + c * 32 + r] = f2bf(oq[c][e]);
-    }
-
-  // ---- orientation 2: key = 32t + r, queries = (e&3) + 8(e>>2) + 4hh ; dK = dS^T Q, dV = Pd^T dctx
-#pragma unroll
-  for (int t = 0; t < NKT; ++t) {
-    const int key = 32 * t + r;
-    f32x16 ds2, pd2;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int qi = (e & 3) + 8 * (e >> 2) + 4 * hh;
-      const bool ok = qi < Lq && key < Lk;
-      const float pr = ok ? Ps[qi * LDP + key] : 0.f;
-      float ks = 1.f;
-      if (p > 0.f && ok) ks = drop_keep32(drop_key(seed), (uint32_t)(((size_t)bh * Lq + qi) * Lk + key), p) ? keep : 0.f;
-      float dp = ok ? d2[t][e] * ks : 0.f;
-      if constexpr (DPR) dp += ok ? DPs[qi * LDP + key] : 0.f;
-      const float tt = ok ? Ts[qi] : 0.f;
-      ds2[e] = pr * (dp - tt) * inv_scale;
-      pd2[e] = pr * ks;
-    }
-    f32x16 okk[HD / 32], ovv[HD / 32];
-#pragma unroll
-    for (int c = 0; c < HD / 32; ++c)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) { okk[c][e] = 0.f; ovv[c][e] = 0.f; }
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      bf16x8 as, ap;
-#pragma unroll
-      for (int jj = 0; jj < 8; ++jj) { as[jj] = (__bf16)ds2[8 * s2 + jj]; ap[jj] = (__bf16)pd2[8 * s2 + jj]; }
-#pragma unroll
-      for (int c = 0; c < HD / 32; ++c) {
-        okk[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as, attn_ldsB<HD>(Qs, 16 * s2, c, hh, g2, qd, pp), okk[c], 0, 0, 0);
-        ovv[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap, attn_ldsB<HD>(Os, 16 * s2, c, hh, g2, qd, pp), ovv[c], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < HD / 32; ++c)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int kj = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
-        if (kj < Lk) {
-          dk[(size_t)(b * Lk + kj) * lddk + h * HD + c * 32 + r] = f2bf(okk[c][e]);
-          dv[(size_t)(b * Lk + kj) * lddv + h * HD + c * 32 + r] = f2bf(ovv[c][e]);
-        }
-      }
-  }
-}
-
-template <bool DPR>
-static int attention_bwd_mfma(const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
-                              const float* probs, const float* dprobs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv,
-                              int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t st) {
-  if (!dctx || !q || !k || !v || !probs || !dq || !dk || !dv || (DPR && !dprobs) || Lq > 32 || Lk > 160 || (hd != 32 && hd != 64) ||
-      (ldq % 8) || (ldk % 8) || (ldv % 8) || (ldc % 8)) return VQA_EARG;
-  const int BH = B * H;
-  auto go = [&](auto kern, int nkt, int wpb) {
-    const size_t shm = (size_t)wpb * ((nkt * 32 + 32 + 32) * hd * 2 + 32 * (nkt * 32 + 1) * 4 + 32 * 4 + (DPR ? 32 * (nkt * 32 + 1) * 4 : 0));
-    (void)vqa_ensure_lds(reinterpret_cast<const void*>(kern), shm);
-    hipLaunchKernelGGL(kern, dim3((BH + wpb - 1) / wpb), dim3(wpb * 64), shm, st, (const bf16_t*)dctx, ldc, (const bf16_t*)q, (const bf16_t*)k,
-                       (const bf16_t*)v, ldq, ldk, ldv, probs, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, lddq, lddk, lddv, BH, H, Lq, Lk, p, seed, dprobs);
-  };
-  if (Lk <= 64) { if (hd == 32) go(&attn_bwd_mfma_kernel<32, 2, 4, DPR>, 2, 4); else go(&attn_bwd_mfma_kernel<64, 2, 4, DPR>, 2, 4); }
-  else { if (hd == 32) go(&attn_bwd_mfma_kernel<32, 5, 2, DPR>, 5, 2); else go(&attn_bwd_mfma_kernel<64, 5, 2, DPR>, 5, 2); }
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-
-extern "C" int vqa_attention_bwd_mfma(const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
-                                      const float* probs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv,
-                                      int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t st) {
-  return attention_bwd_mfma<false>(dctx, ldc, q, k, v, ldq, ldk, ldv, probs, nullptr, dq, dk, dv, lddq, lddk, lddv, B, H, Lq, Lk, hd, p, seed, st);
-}
-extern "C" int vqa_attention_bwd_mfma_dp(const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
-                                         const float* probs, const float* dprobs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv,
-                                         int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed, hipStream_t st) {
-  return attention_bwd_mfma<true>(dctx, ldc, q, k, v, ldq, ldk, ldv, probs, dprobs, dq, dk, dv, lddq, lddk, lddv, B, H, Lq, Lk, hd, p, seed, st);
-}
-
-// ---------------------------------------------------------------------------------------------
-// Many questions per image in TRAINING (VQAModel.forward_grouped, HipTrainer.step(image_index=)).
-//   vqa_index_csr              questions of each image in ascending question order (CSR), one workgroup, no host sync
-//   vqa_attention_fwd(_mfma)_idx_train   the indexed forwards with dropout: the mask of (question b, head, i, j) is the one
-//                              vqa_attention_fwd(_mfma) draws for batch b (identity index -> bit-equal)
-//   vqa_attention_bwd(_mfma)_idx         dQ per question, dK / dV per IMAGE: one workgroup (VALU) or wave (MFMA) per (image, head)
-//                              keeps the image's dK / dV in fp32 accumulators while it sweeps that image's questions in CSR order,
-//                              then rounds once and stores once.  No float atomics: the sums run in a fixed order (bit-reproducible).
-//                              One question per image: the products and their order are those of vqa_attention_bwd(_mfma)
-//                              (bit-equal); an image without questions gets zeros.
-// ---------------------------------------------------------------------------------------------
-
-// Counting sort of kv_index [N] into offsets [U+1] / order [N]; cur: U ints of dynamic LDS (counts, then per-image cursors).
-// Placement is stable: question i's slot = cursor of its image + #{earlier questions of the same image in its chunk of 1024}.
-// An index outside [0, U) writes -1 to every offset and order entry (the status the backward kernels check).
-__global__ __launch_bounds__(1024) void index_csr_kernel(const int* __restrict__ kv_index, int N, int U, int* __restrict__ offsets,
-                                                         int* __restrict__ order) {
-  extern __shared__ int cur[];
-  __shared__ int part[1024];
-  __shared__ int keys[1024];
-  __shared__ int bad;
-  const int tid = threadIdx.x;
-  if (tid == 0) bad = 0;
-  for (int u = tid; u < U; u += 1024) cur[u] = 0;
-  __syncthreads();
-  for (int i = tid; i < N; i += 1024) {
-    const int u = kv_index[i];
-    if (u < 0 || u >= U) bad = 1;
-    else atomicAdd(&cur[u], 1);                 // integer counts: order-independent
-  }
-  __syncthreads();
-  if (bad) {                                    // block-uniform
-    for (int u = tid; u <= U; u += 1024) offsets[u] = -1;
-    for (int i = tid; i < N; i += 1024) order[i] = -1;
-    return;
-  }
-  // exclusive scan of the counts: thread t owns images [u0, u1)
-  const int per = (U + 1023) / 1024, u0 = min(tid * per, U), u1 = min(u0 + per, U);
-  int s = 0;
-  for (int u = u0; u < u1; ++u) s += cur[u];
-  part[tid] = s;
-  __syncthreads();
-  for (int o = 1; o < 1024; o <<= 1) {          // inclusive scan of the 1024 partial sums
-    const int v = tid >= o ? part[tid - o] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  int run = part[tid] - s;
-  for (int u = u0; u < u1; ++u) { const int c = cur[u]; offsets[u] = run; cur[u] = run; run += c; }
-  if (tid == 1023) offsets[U] = part[1023];
-  __syncthreads();
-  for (int base = 0; base < N; base += 1024) {
-    const int i = base + tid, n = min(1024, N - base);
-    const int key = i < N ? kv_index[i] : -1;
-    keys[tid] = key;
-    __syncthreads();
-    int rank = 0;
-    bool last = true;
-    if (i < N) {
-      for (int j = 0; j < n; ++j)
-        if (keys[j] == key) { if (j < tid) ++rank; else if (j > tid) last = false; }
-      order[cur[key] + rank] = i;
-    }
-    __syncthreads();
-    if (i < N && last) cur[key] += rank + 1;
-    __syncthreads();
-  }
-}
-
-// VALU form: one workgroup per (image u, head h); NACC accumulators per thread and tensor (Lk * hd <= 256 * NACC).
-// Per question: the per-(batch, head) body of attn_bwd_kernel (DPR = false) with b = the question, K / V of image u.
-template <typename T, int NACC>
-__global__ __launch_bounds__(256) void attn_bwd_idx_kernel(const T* __restrict__ dctx, int ldc, const T* __restrict__ q, const T* __restrict__ k,
-                                                          const T* __restrict__ v, int ldq, int ldk, int ldv, const float* __restrict__ probs,
-                                                          T* __restrict__ dq, T* __restrict__ dk, T* __restrict__ dv, int lddq, int lddk, int lddv,
-                                                          int H, int Lq, int Lk, int hd, float scale, float p, uint64_t seed,
-                                                          const int* __restrict__ offsets, const int* __restrict__ order, int N) {
-  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
-  extern __shared__ float sm[];
-  const int u = blockIdx.x / H, h = blockIdx.x - u * H, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ldh = hd + 1, ldp = Lk + 1;
-  float* Qs = sm; float* Os = Qs + Lq * ldh; float* Ks = Os + Lq * ldh; float* Vs = Ks + Lk * ldh;
-  float* Ps = Vs + Lk * ldh; float* Ds = Ps + Lq * ldp;
-  const int nkd = Lk * hd;
-  int beg = offsets[u], end = offsets[u + 1];
-  if (beg < 0 || end < beg || end > N) {        // CSR status error (an index out of range): NaN, never a wrong sum
-    for (int i = tid; i < nkd; i += 256) {
-      const int c = i / hd, d = i - c * hd;
-      dk[(size_t)(u * Lk + c) * lddk + h * hd + d] = from_f<T>(NAN);
-      dv[(size_t)(u * Lk + c) * lddv + h * hd + d] = from_f<T>(NAN);
-    }
-    return;
-  }
-  for (int i = tid; i < nkd; i += 256) {
-    const int r = i / hd, d = i - r * hd;
-    Ks[r * ldh + d] = to_f<T>(k[(size_t)(u * Lk + r) * ldk + h * hd + d]);
-    Vs[r * ldh + d] = to_f<T>(v[(size_t)(u * Lk + r) * ldv + h * hd + d]);
-  }
-  float ak[NACC], av[NACC];
-#pragma unroll
-  for (int jj = 0; jj < NACC; ++jj) { ak[jj] = 0.f; av[jj] = 0.f; }
-  for (int jq = beg; jq < end; ++jq) {
-    const int b = order[jq];
-    if (b < 0 || b >= N) continue;              // block-uniform
-    __syncthreads();                            // the previous question's readers of Qs / Os / Ps / Ds are done
-    for (int i = tid; i < Lq * hd; i += 256) {
-      const int r = i / hd, d = i - r * hd;
-      Qs[r * ldh + d] = to_f<T>(q[(size_t)(b * Lq + r) * ldq + h * hd + d]);
-      Os[r * ldh + d] = to_f<T>(dctx[(size_t)(b * Lq + r) * ldc + h * hd + d]);
-    }
-    __syncthreads();
-    const float* pg = probs + ((size_t)(b * H + h) * Lq) * Lk;
-    for (int r = wave; r < Lq; r += 4) {
-      float t = 0.f;
-      for (int c = lane; c < Lk; c += 64) {
-        const float pr = pg[(size_t)r * Lk + c];
-        float ks = 1.f;
-        if (p > 0.f) ks = drop_keep32(drop_key(seed), (uint32_t)(((size_t)(b * H + h) * Lq + r) * Lk + c), p) ? 1.f / (1.f - p) : 0.f;
-        float dpd = 0.f;
-        for (int d = 0; d < hd; ++d) dpd += Os[r * ldh + d] * Vs[c * ldh + d];
-        const float dp = dpd * ks;
-        Ps[r * ldp + c] = pr * ks;
-        Ds[r * ldp + c] = dp;
-        t += dp * pr;
-      }
-      t = wave_sum(t);
-      for (int c = lane; c < Lk; c += 64) Ds[r * ldp + c] = pg[(size_t)r * Lk + c] * (Ds[r * ldp + c] - t) / scale;
-    }
-    __syncthreads();
-    for (int i = tid; i < Lq * hd; i += 256) {
-      const int r = i / hd, d = i - r * hd;
-      float a = 0.f;
-      for (int c = 0; c < Lk; ++c) a += Ds[r * ldp + c] * Ks[c * ldh + d];
-      dq[(size_t)(b * Lq + r) * lddq + h * hd + d] = from_f<T>(a);
-    }
-#pragma unroll
-    for (int jj = 0; jj < NACC; ++jj) {
-      const int i = tid + jj * 256;
-      if (i < nkd) {
-        const int c = i / hd, d = i - c * hd;
-        float a = ak[jj], e = av[jj];
-        for (int r = 0; r < Lq; ++r) { a += Ds[r * ldp + c] * Qs[r * ldh + d]; e += Ps[r * ldp + c] * Os[r * ldh + d]; }
-        ak[jj] = a; av[jj] = e;
-      }
-    }
-  }
-#pragma unroll
-  for (int jj = 0; jj < NACC; ++jj) {
-    const int i = tid + jj * 256;
-    if (i < nkd) {
-      const int c = i / hd, d = i - c * hd;
-      dk[(size_t)(u * Lk + c) * lddk + h * hd + d] = from_f<T>(ak[jj]);
-      dv[(size_t)(u * Lk + c) * lddv + h * hd + d] = from_f<T>(av[jj]);
-    }
-  }
-}
-
-// MFMA form: one wave per (image u, head h); the per-question body of attn_bwd_mfma_kernel (DPR = false).  The fp32 dK / dV
-// accumulators live in a wave-private LDS area in the MFMA accumulator layout, lane-private ([tile][c][e][lane]: no bank
-// conflicts, no cross-lane traffic); each question's orientation-2 MFMAs start from them instead of from zero.
-template <int HD, int NKT, int WPB>
-__global__ __launch_bounds__(WPB * 64, 1) void attn_bwd_mfma_idx_kernel(const bf16_t* __restrict__ dctx, int ldc, const bf16_t* __restrict__ q,
-                                                                const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, int ldq, int ldk, int ldv,
-                                                                const float* __restrict__ probs, bf16_t* __restrict__ dq, bf16_t* __restrict__ dk,
-                                                                bf16_t* __restrict__ dv, int lddq, int lddk, int lddv, int UH, int H, int Lq, int Lk,
-                                                                float p, uint64_t seed, const int* __restrict__ offsets,
-                                                                const int* __restrict__ order, int N) {
-  seed = drop_resolve(seed);                        // (a flagged seed word names the step-state block: common.h)
-  constexpr int KR = NKT * 32;
-  constexpr int LDP = KR + 1;
-  constexpr int NACC = NKT * (HD / 32) * 16;    // accumulator registers per lane and tensor
-  constexpr int WAVE_BYTES = (KR + 32 + 32) * HD * 2 + 32 * LDP * 4 + 32 * 4 + 2 * NACC * 64 * 4;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int uh = blockIdx.x * WPB + wave;
-  if (uh >= UH) return;                         // whole wave exits together; only wave-private LDS, no block barrier below
-  char* base = smem + (size_t)wave * WAVE_BYTES;
-  bf16_t* Ks = reinterpret_cast<bf16_t*>(base);            // [KR][HD]
-  bf16_t* Qs = Ks + KR * HD;                               // [32][HD]
-  bf16_t* Os = Qs + 32 * HD;                               // [32][HD]  (dctx)
-  float* Ps = reinterpret_cast<float*>(Os + 32 * HD);      // [32][LDP]
-  float* Ts = Ps + 32 * LDP;                               // [32]
-  float* Ak = Ts + 32;                                     // [NACC][64] dK accumulators
-  float* Av = Ak + NACC * 64;                              // [NACC][64] dV accumulators
-  const int u = uh / H, h = uh - u * H;
-  const int r = lane & 31, hh = lane >> 5;
-  const int g2 = (lane >> 4) & 1, li = lane & 15, qd = li >> 2, pp = li & 3;
-  const float inv_scale = 1.0f / sqrtf((float)HD);
-  const float keep = p > 0.f ? 1.f / (1.f - p) : 1.f;
-  const int beg = __builtin_amdgcn_readfirstlane(offsets[u]), end = __builtin_amdgcn_readfirstlane(offsets[u + 1]);
-  if (beg < 0 || end < beg || end > N) {        // CSR status error (an index out of range): NaN, never a wrong sum
-    for (int i = lane; i < Lk * HD; i += 64) {
-      const int c = i / HD, d = i - c * HD;
-      dk[(size_t)(u * Lk + c) * lddk + h * HD + d] = f2bf(NAN);
-      dv[(size_t)(u * Lk + c) * lddv + h * HD + d] = f2bf(NAN);
-    }
-    return;
-  }
-  for (int i = lane; i < KR * (HD / 8); i += 64) {
-    const int row = i / (HD / 8), cv = i - row * (HD / 8);
-    u32x4 val = {0u, 0u, 0u, 0u};
-    if (row < Lk) val = *reinterpret_cast<const u32x4*>(k + (size_t)(u * Lk + row) * ldk + h * HD + cv * 8);
-    *reinterpret_cast<u32x4*>(&Ks[row * HD + cv * 8]) = val;
-  }
-  for (int i = 0; i < NACC; ++i) { Ak[i * 64 + lane] = 0.f; Av[i * 64 + lane] = 0.f; }
-
-  for (int jq = beg; jq < end; ++jq) {
-    const int b = __builtin_amdgcn_readfirstlane(order[jq]);
-    if (b < 0 || b >= N) continue;              // wave-uniform
-    const int bh = b * H + h;                   // the question's (batch, head): probs, dropout index, dQ
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // the previous question's LDS reads are complete
-    for (int i = lane; i < 32 * (HD / 8); i += 64) {
-      const int row = i / (HD / 8), cv = i - row * (HD / 8);
-      u32x4 a = {0u, 0u, 0u, 0u}, o = {0u, 0u, 0u, 0u};
-      if (row < Lq) {
-        a = *reinterpret_cast<const u32x4*>(q + (size_t)(b * Lq + row) * ldq + h * HD + cv * 8);
-        o = *reinterpret_cast<const u32x4*>(dctx + (size_t)(b * Lq + row) * ldc + h * HD + cv * 8);
-      }
-      *reinterpret_cast<u32x4*>(&Qs[row * HD + cv * 8]) = a;
-      *reinterpret_cast<u32x4*>(&Os[row * HD + cv * 8]) = o;
-    }
-    for (int i = lane; i < Lq * Lk; i += 64) { const int qi = i / Lk, kj = i - qi * Lk; Ps[qi * LDP + kj] = probs[(size_t)bh * Lq * Lk + i]; }
-
-    f32x16 d1[NKT], d2[NKT];
-#pragma unroll
-    for (int t = 0; t < NKT; ++t)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) { d1[t][e] = 0.f; d2[t][e] = 0.f; }
-#pragma unroll
-    for (int ks = 0; ks < HD / 16; ++ks) {
-      bf16x8 of = {};
-      if (r < Lq) of = *reinterpret_cast<const bf16x8*>(dctx + (size_t)(b * Lq + r) * ldc + h * HD + ks * 16 + 8 * hh);
-#pragma unroll
-      for (int t = 0; t < NKT; ++t) {
-        bf16x8 vf = {};
-        if (32 * t + r < Lk) vf = *reinterpret_cast<const bf16x8*>(v + (size_t)(u * Lk + 32 * t + r) * ldv + h * HD + ks * 16 + 8 * hh);
-        d1[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, of, d1[t], 0, 0, 0);
-        d2[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(of, vf, d2[t], 0, 0, 0);
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-
-    // ---- orientation 1: row sums, dS, dQ = dS K
-    const size_t prow = ((size_t)bh * Lq + r) * Lk;
-    float tq = 0.f;
-#pragma unroll
-    for (int t = 0; t < NKT; ++t)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int key = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
-        const bool ok = r < Lq && key < Lk;
-        const float pr = ok ? Ps[r * LDP + key] : 0.f;
-        float ks = 1.f;
-        if (p > 0.f && ok) ks = drop_keep32(drop_key(seed), (uint32_t)(prow + key), p) ? keep : 0.f;
-        const float dp = ok ? d1[t][e] * ks : 0.f;
-        tq += dp * pr;
-        d1[t][e] = dp;
-      }
-    tq += __shfl_xor(tq, 32, 64);
-    if (hh == 0) Ts[r] = tq;
-#pragma unroll
-    for (int t = 0; t < NKT; ++t)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int key = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
-        const float pr = (r < Lq && key < Lk) ? Ps[r * LDP + key] : 0.f;
-        d1[t][e] = pr * (d1[t][e] - tq) * inv_scale;
-      }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    f32x16 oq[HD / 32];
-#pragma unroll
-    for (int c = 0; c < HD / 32; ++c)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) oq[c][e] = 0.f;
-#pragma unroll
-    for (int t = 0; t < NKT; ++t)
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        bf16x8 af;
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) af[jj] = (__bf16)d1[t][8 * s2 + jj];
-#pragma unroll
-        for (int c = 0; c < HD / 32; ++c)
-          oq[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, attn_ldsB<HD>(Ks, 32 * t + 16 * s2, c, hh, g2, qd, pp), oq[c], 0, 0, 0);
-      }
-#pragma unroll
-    for (int c = 0; c < HD / 32; ++c)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int qi = (e & 3) + 8 * (e >> 2) + 4 * hh;
-        if (qi < Lq) dq[(size_t)(b * Lq + qi) * lddq + h * HD + c * 32 + r] = f2bf(oq[c][e]);
-      }
-
-    // ---- orientation 2: dK += dS^T Q, dV += Pd^T dctx, starting from the accumulators
-#pragma unroll
-    for (int t = 0; t < NKT; ++t) {
-      const int key = 32 * t + r;
-      f32x16 ds2, pd2;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int qi = (e & 3) + 8 * (e >> 2) + 4 * hh;
-        const bool ok = qi < Lq && key < Lk;
-        const float pr = ok ? Ps[qi * LDP + key] : 0.f;
-        float ks = 1.f;
-        if (p > 0.f && ok) ks = drop_keep32(drop_key(seed), (uint32_t)(((size_t)bh * Lq + qi) * Lk + key), p) ? keep : 0.f;
-        const float dp = ok ? d2[t][e] * ks : 0.f;
-        const float tt = ok ? Ts[qi] : 0.f;
-        ds2[e] = pr * (dp - tt) * inv_scale;
-        pd2[e] = pr * ks;
-      }
-      f32x16 okk[HD / 32], ovv[HD / 32];
-#pragma unroll
-      for (int c = 0; c < HD / 32; ++c)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int a = ((t * (HD / 32) + c) * 16 + e) * 64 + lane;
-          okk[c][e] = Ak[a]; ovv[c][e] = Av[a];
-        }
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        bf16x8 as, ap;
-#pragma unroll
-        for (int jj = 0; jj < 8; ++jj) { as[jj] = (__bf16)ds2[8 * s2 + jj]; ap[jj] = (__bf16)pd2[8 * s2 + jj]; }
-#pragma unroll
-        for (int c = 0; c < HD / 32; ++c) {
-          okk[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(as, attn_ldsB<HD>(Qs, 16 * s2, c, hh, g2, qd, pp), okk[c], 0, 0, 0);
-          ovv[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ap, attn_ldsB<HD>(Os, 16 * s2, c, hh, g2, qd, pp), ovv[c], 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int c = 0; c < HD / 32; ++c)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int a = ((t * (HD / 32) + c) * 16 + e) * 64 + lane;
-          Ak[a] = okk[c][e]; Av[a] = ovv[c][e];
-        }
-    }
-  }
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  for (int t = 0; t < NKT; ++t)
-#pragma unroll
-    for (int c = 0; c < HD / 32; ++c)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int kj = 32 * t + (e & 3) + 8 * (e >> 2) + 4 * hh;
-        const int a = ((t * (HD / 32) + c) * 16 + e) * 64 + lane;
-        if (kj < Lk) {
-          dk[(size_t)(u * Lk + kj) * lddk + h * HD + c * 32 + r] = f2bf(Ak[a]);
-          dv[(size_t)(u * Lk + kj) * lddv + h * HD + c * 32 + r] = f2bf(Av[a]);
-        }
-      }
-}
-
-extern "C" {
-
-int vqa_index_csr(const int* kv_index, int N, int U, int* offsets, int* order, hipStream_t st) {
-  if (N < 0 || U < 0 || U > 32768 || !offsets || (N > 0 && (!kv_index || !order))) return VQA_EARG;
-  const size_t shm = (size_t)(U > 0 ? U : 1) * 4;
-  (void)vqa_ensure_lds(reinterpret_cast<const void*>(&index_csr_kernel), shm);
-  hipLaunchKernelGGL(index_csr_kernel, dim3(1), dim3(1024), shm, st, kv_index, N, U, offsets, order);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-
-int vqa_attention_fwd_idx_train(int dtype, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const int* kv_index,
-                                int n_kv, const float* kmask, float* probs, void* ctx, int ldc, int B, int H, int Lq, int Lk, int hd,
-                                float p, unsigned long long seed, hipStream_t st) {
-  if (!kv_index || n_kv < 0 || !(p >= 0.f && p < 1.f)) return VQA_EARG;
-  const size_t shm = ((size_t)(Lq + 2 * Lk) * (hd + 1) + (size_t)Lq * (Lk + 1)) * 4;
-  if (shm > 160 * 1024) return VQA_EARG;
-  const float scale = sqrtf((float)hd);
-  (void)vqa_ensure_lds(dtype ? reinterpret_cast<const void*>(&attn_fwd_kernel<bf16_t, true>) : reinterpret_cast<const void*>(&attn_fwd_kernel<float, true>), shm);
-  DT(hipLaunchKernelGGL((attn_fwd_kernel<float, true>), dim3(B * H), dim3(256), shm, st, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, kmask, probs, (float*)ctx, ldc, H, Lq, Lk, hd, scale, p, seed, kv_index, n_kv),
-     hipLaunchKernelGGL((attn_fwd_kernel<bf16_t, true>), dim3(B * H), dim3(256), shm, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, kmask, probs, (bf16_t*)ctx, ldc, H, Lq, Lk, hd, scale, p, seed, kv_index, n_kv));
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-
-int vqa_attention_fwd_mfma_idx_train(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const int* kv_index, int n_kv,
-                                     const float* kmask, float* probs, void* ctx, int ldc, int B, int H, int Lq, int Lk, int hd, float p,
-                                     unsigned long long seed, hipStream_t st) {
-  if (!q || !k || !v || !kv_index || n_kv < 0 || !probs || !ctx || Lq > 32 || Lk > 160 || (hd != 32 && hd != 64) || (ldq % 8) || (ldk % 8) ||
-      (ldv % 8) || !(p >= 0.f && p < 1.f))
-    return VQA_EARG;
-  const int BH = B * H;
-  auto go = [&](auto kern, int nkt, int wpb) {
-    const size_t shm = (size_t)wpb * (nkt * 32) * hd * 2 + (size_t)wpb * 32 * (nkt * 32 + 1) * 4;
-    (void)vqa_ensure_lds(reinterpret_cast<const void*>(kern), shm);
-    hipLaunchKernelGGL(kern, dim3((BH + wpb - 1) / wpb), dim3(wpb * 64), shm, st, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv,
-                       kmask, probs, (bf16_t*)ctx, ldc, BH, H, Lq, Lk, p, seed, kv_index, n_kv);
-  };
-  if (Lk <= 64) { if (hd == 32) go(&attn_fwd_mfma_kernel<32, 2, 4, true>, 2, 4); else go(&attn_fwd_mfma_kernel<64, 2, 4, true>, 2, 4); }
-  else { if (hd == 32) go(&attn_fwd_mfma_kernel<32, 5, 2, true>, 5, 2); else go(&attn_fwd_mfma_kernel<64, 5, 2, true>, 5, 2); }
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-
-int vqa_attention_bwd_idx(int dtype, const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
-                          const float* probs, const int* offsets, const int* order, int n_kv, void* dq, void* dk, void* dv,
-                          int lddq, int lddk, int lddv, int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed,
-                          hipStream_t st) {
-  if (!dctx || !q || !k || !v || !probs || !offsets || (B > 0 && !order) || !dq || !dk || !dv || n_kv < 0 || B < 0 || H <= 0 ||
-      Lq <= 0 || Lk <= 0 || hd <= 0 || !(p >= 0.f && p < 1.f))
-    return VQA_EARG;
-  const size_t shm = ((size_t)(2 * Lq + 2 * Lk) * (hd + 1) + (size_t)2 * Lq * (Lk + 1)) * 4;
-  const long long nkd = (long long)Lk * hd;
-  if (shm > 160 * 1024 || nkd > 256 * 40) return VQA_EARG;
-  if (n_kv == 0) return VQA_OK;
-  const float scale = sqrtf((float)hd);
-  auto go = [&](auto kf, auto kb) {
-    (void)vqa_ensure_lds(dtype ? reinterpret_cast<const void*>(kb) : reinterpret_cast<const void*>(kf), shm);
-    DT(hipLaunchKernelGGL(kf, dim3(n_kv * H), dim3(256), shm, st, (const float*)dctx, ldc, (const float*)q, (const float*)k, (const float*)v, ldq, ldk, ldv, probs, (float*)dq, (float*)dk, (float*)dv, lddq, lddk, lddv, H, Lq, Lk, hd, scale, p, seed, offsets, order, B),
-       hipLaunchKernelGGL(kb, dim3(n_kv * H), dim3(256), shm, st, (const bf16_t*)dctx, ldc, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, ldq, ldk, ldv, probs, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, lddq, lddk, lddv, H, Lq, Lk, hd, scale, p, seed, offsets, order, B));
-  };
-  if (nkd <= 256 * 16) go(&attn_bwd_idx_kernel<float, 16>, &attn_bwd_idx_kernel<bf16_t, 16>);
-  else go(&attn_bwd_idx_kernel<float, 40>, &attn_bwd_idx_kernel<bf16_t, 40>);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-
-int vqa_attention_bwd_mfma_idx(const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
-                               const float* probs, const int* offsets, const int* order, int n_kv, void* dq, void* dk, void* dv,
-                               int lddq, int lddk, int lddv, int B, int H, int Lq, int Lk, int hd, float p, unsigned long long seed,
-                               hipStream_t st) {
-  if (!dctx || !q || !k || !v || !probs || !offsets || (B > 0 && !order) || !dq || !dk || !dv || n_kv < 0 || B < 0 || H <= 0 ||
-      Lq <= 0 || Lq > 32 || Lk <= 0 || Lk > 160 || (hd != 32 && hd != 64) || (ldq % 8) || (ldk % 8) || (ldv % 8) || (ldc % 8) ||
-      !(p >= 0.f && p < 1.f))
-    return VQA_EARG;
-  if (n_kv == 0) return VQA_OK;
-  const int UH = n_kv * H;
-  auto go = [&](auto kern, int nkt, int wpb) {
-    const size_t nacc = (size_t)nkt * (hd / 32) * 16;
-    const size_t shm = (size_t)wpb * ((nkt * 32 + 32 + 32) * hd * 2 + 32 * (nkt * 32 + 1) * 4 + 32 * 4 + 2 * nacc * 64 * 4);
-    (void)vqa_ensure_lds(reinterpret_cast<const void*>(kern), shm);
-    hipLaunchKernelGGL(kern, dim3((UH + wpb - 1) / wpb), dim3(wpb * 64), shm, st, (const bf16_t*)dctx, ldc, (const bf16_t*)q, (const bf16_t*)k,
-                       (const bf16_t*)v, ldq, ldk, ldv, probs, (bf16_t*)dq, (bf16_t*)dk, (bf16_t*)dv, lddq, lddk, lddv, UH, H, Lq, Lk, p, seed,
-                       offsets, order, B);
-  };
-  if (Lk <= 64) { if (hd == 32) go(&attn_bwd_mfma_idx_kernel<32, 2, 2>, 2, 2); else go(&attn_bwd_mfma_idx_kernel<64, 2, 2>, 2, 2); }
-  else { if (hd == 32) go(&attn_bwd_mfma_idx_kernel<32, 5, 1>, 5, 1); else go(&attn_bwd_mfma_idx_kernel<64, 5, 1>, 5, 1); }
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
 
