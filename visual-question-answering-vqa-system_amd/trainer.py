@@ -21,6 +21,7 @@ from . import finetune as FT
 from . import kernels as K
 from . import layout as LY
 from . import stepgraph as SG
+from . import trainer_state as TS
 from ._lib import call, dt, ptr
 
 
@@ -659,6 +660,88 @@ class HipTrainer:
         KeyError for a missing parameter, ValueError for a shape mismatch (nothing is written then)."""
         EMA.load_state_dict(self.model, self._need_ema("load_ema_state_dict"), sd)
         self._ema_cnn_stamp = None
+
+    # ---- the whole trainer state (trainer_state.py): stop a run and continue it
+    def state_dict(self):
+        """Everything a run needs to continue, as a torch.optim.AdamW state dict plus one block: {"state": {i: {"step", "exp_avg",
+        "exp_avg_sq"}}, "param_groups": [...], "hip_trainer": {...}} -- plain containers and CPU tensors, so torch.save and
+        torch.load(weights_only=True) carry it, and it fits the `optimizer_state_dict` slot of the reference's checkpoints.  The
+        moments of every parameter in the Parameter's own shape (a never-updated one: zeros, step 0); `step` of parameter j is
+        calls - skipped steps - lag[j], the number the AdamW kernels form; one param group (model.parameters() order) without
+        trainer groups, one per trainer group with lr * lr_scale and the group's effective decay otherwise, with the keys the installed
+        torch.optim.AdamW writes, so the dict loads into a torch.optim.AdamW over the same parameters or groups.  The block holds what
+        torch has no place for: the parameter name of every index, calls and the counters check() reads, the frozen-time lags and
+        their classes, the hyper-parameters and the groups' live values, the weight average, ema_decay / ema_warmup and the dropout
+        stream (the engine's seed_base and step_id).  The model's own state (weights, BatchNorm buffers) is model.state_dict()'s.
+        One host synchronisation.  RuntimeError inside ema_weights()."""
+        if self._ema_swapped:
+            raise RuntimeError("HipTrainer.state_dict inside ema_weights(): the model holds the averaged weights; leave the block first")
+        bad = [int(x) for x in self._bad.tolist()]
+        eng = self.engine
+        return TS.export(self.model._param_entries, [n for n, _ in self.model.named_parameters()], self.m, self.v, calls=self.calls,
+                         skipped_ever=bad[2], bad_targets=bad[:2], empty=int(self._empty.item()), lag=self._lag.tolist(),
+                         lag_class=self._lag_class, ever_frozen=self._ever_frozen, lr=self.lr, betas=self.betas, eps=self.eps,
+                         weight_decay=self.wd, max_grad_norm=self.max_norm, groups=self.param_groups, ema=self.ema,
+                         ema_decay=self.ema_decay, ema_warmup=self.ema_warmup, seed_base=eng.seed_base, step_id=eng.step_id)
+
+    def load_state_dict(self, sd):
+        """The inverse of state_dict(), and the way in for a dict a torch.optim.AdamW wrote.  Everything is validated on the host
+        first: a ValueError leaves the trainer as it was.
+        With the "hip_trainer" block (an exact resume; load the model's state_dict first): parameters are matched by name; the
+        moments, the average, calls and the counters, the lags and their classes, lr / betas / eps / weight decay / max_grad_norm
+        (live attributes again), the groups' live values and the engine's seed_base / step_id are restored, and the run continues
+        bit for bit.  ValueError for an unknown version, a missing or unknown parameter name, a wrong shape, groups whose membership
+        differs from this trainer's, and an average in the dict when this trainer was built without ema_decay.  A trainer WITH
+        ema_decay given a dict without an average restarts the average from the model's current weights, as its constructor does, and
+        keeps its own ema_decay / ema_warmup.
+        Without the block (torch.optim.AdamW.state_dict()): only the moments and the step numbers are read.  Index i is the i-th
+        parameter of the concatenated param_groups: model.parameters() order for the one group of a trainer without groups; with
+        trainer groups the dict's group sizes must equal theirs.  An index without state gets zero moments and step 0; calls becomes
+        the largest step, no step counts as skipped, and parameters whose steps differ get lags (the range kernels honour them).  A
+        trainer without groups takes lr, betas, eps and weight_decay from the one group, as torch does; a trainer with groups keeps
+        its live values.  The counters of check(), the average and the dropout stream keep their values.  ValueError for amsgrad,
+        maximize or decoupled_weight_decay=False.
+        After either load the bf16 operand copy is re-cast at the next step, the optimizer's range table and the groups' device block
+        are rebuilt, and every captured step graph is dropped: step_graphed behaves like a fresh trainer's.  One host
+        synchronisation.  RuntimeError inside ema_weights()."""
+        if self._ema_swapped:
+            raise RuntimeError("HipTrainer.load_state_dict inside ema_weights(): the model holds the averaged weights; leave the block first")
+        r = TS.load(self.model._param_entries, [n for n, _ in self.model.named_parameters()], sd, self.m, self.v, self.ema,
+                    self.param_groups)
+        dev = self.G.device
+        self.calls = r["calls"]
+        self._lag.copy_(torch.tensor(r["lag"], dtype=torch.int32))
+        self._lag_class = list(r["lag_class"])
+        self._ever_frozen = r["ever_frozen"]
+        if r["bad_targets"] is None:
+            self._bad[2:3].fill_(r["skipped_ever"])
+        else:
+            self._bad.copy_(torch.tensor(r["bad_targets"] + [r["skipped_ever"]], dtype=torch.int32))
+            self._empty.fill_(r["empty"])
+        for attr, key in (("lr", "lr"), ("betas", "betas"), ("eps", "eps"), ("wd", "weight_decay"), ("max_norm", "max_grad_norm"),
+                          ("ema_decay", "ema_decay"), ("ema_warmup", "ema_warmup")):
+            if r[key] is not None:
+                setattr(self, attr, r[key])
+        if r["group_values"] is not None:
+            for g, (scale, wd) in zip(self.param_groups, r["group_values"]):
+                g["lr_scale"], g["weight_decay"] = scale, wd
+        if r["ema"] == "loaded":
+            self._ema_cnn_stamp = None
+        elif r["ema"] == "restart":
+            with torch.no_grad():
+                self.ema.copy_(self.model._flat)
+            self._ema_cnn_stamp = self._cnn_stamp()
+        if r["rng"] is not None:
+            self.engine.seed_base, self.engine.step_id = r["rng"]["seed_base"], r["rng"]["step_id"]
+        self._copy_sig = None
+        self._group_written = None
+        self._mask = None
+        self._ranges = None
+        self.reducer.set_trainable(None)                   # (with the mask: the next step's _set_mask narrows it again where parts are frozen)
+        if dev.type == "cuda":
+            torch.cuda.synchronize()                       # a dropped graph's private pool must outlive its last replay in flight
+        self._graphs.clear()
+        self._graph_seen.clear()
 
     @contextlib.contextmanager
     def ema_weights(self):
