@@ -157,6 +157,10 @@ IGEMM_STAGES = [
     (249, 512, 7, 128 * 10000 + 128 * 10 + 1),
 ]
 LINEARS = [(17, 1024, 256, False), (33, 32, 10, True), (196, 512, 256, True)]          # M, Kin, N, offset
+# the folded eval block's shortcut: 1x1 / stride 2 / pad 0 (the IGEMM_CONV geometry) and 1x1 / stride 1
+IGEMM_SHORTCUT = [(2, 64, 128, 14, 1, 2, 0, True), (2, 64, 128, 14, 1, 1, 0, True)]
+LINEAR_SCALAR_RELU2 = (33, 32, 10, True)                                                   # N % VEC != 0: the scalar epilogue branch
+MIN_SIGN_FLIPS = 0.05         # least share of outputs on either side of the ReLU-placement test (see infer_epilogue)
 STEM_LOADER_HW = 40
 CONV8P = [(3, 14, 14, 256, 256), (5, 7, 7, 512, 512), (1, 5, 9, 64, 256), (1, 6, 10, 64, 128), (5, 7, 7, 128, 384)]   # B, H, W, C, N
 CONV8P_S2 = [(3, 9, 11, 64, 256), (4, 28, 28, 128, 256)]
@@ -192,6 +196,83 @@ def conv_case(B, Cin, Cout, H, W, R, stride, pad, rng, offset=False, want_dgrad=
         d["dx"] = rows(dgrad_ref(dy, w, stride, pad, (H, W)))
         d["dbound"] = reduction_bound(R * R * Cout, dy, w)
     return d
+
+
+def infer_epilogue(y, seed):
+    """Integer bias [N] and residual addend [M][N] for the epilogues of the folded eval block on the exact product y [M][N], and
+    v = y + bias.  The bias is minus the rounded mean of y plus an integer in [-768, 768] per column: ReLU clips about half of v
+    whichever generator drew y, and a short reduction (|y - mean| ~ 60 at K = 64) still reaches the zone where bf16 rounds
+    (|v| >= 256).  The addend is 4 * [-256, 256] (exact in bf16, as wide as v itself), so that
+    a fair share of outputs has v > 0 with v + addend < 0 and as many the reverse: there relu(v) + a, relu(v + a) and v + a all
+    differ, and a ReLU on the wrong side of the addend changes bits."""
+    N = y.shape[1]
+    bias = ints((N,), 768, seed) - y.mean().round()
+    add = 4 * ints(tuple(y.shape), 256, seed + 1)
+    return dict(bias=bias, add=add, v=y + bias, ebound=float(bias.abs().max()) + float(add.abs().max()))
+
+
+def conv1_expect(e, dtype):
+    """relu = 1: relu(acc + bias) in fp32, then the compute dtype"""
+    return expect(torch.relu(e["v"]), dtype)
+
+
+def shortcut_expect(e, dtype):
+    return expect(e["v"], dtype)
+
+
+def conv2_expect(e, dtype):
+    """relu = 2: acc + bias in fp32 -> the compute dtype -> + addend -> ReLU -> rounded again"""
+    return expect(torch.relu(expect(e["v"], dtype).double() + e["add"]), dtype)
+
+
+def relu_before_addend(e, dtype):
+    """what a kernel with the ReLU on the wrong side of the addend would store"""
+    return expect(torch.relu(expect(e["v"], dtype).double()) + e["add"], dtype)
+
+
+def sign_flip_shares(e):
+    """(share with v > 0 and v + addend < 0, share with v < 0 and v + addend > 0)"""
+    v, s = e["v"], e["v"] + e["add"]
+    return float(((v > 0) & (s < 0)).double().mean()), float(((v < 0) & (s > 0)).double().mean())
+
+
+def assert_infer_epilogue(e):
+    """The conditions on the reference that make the three forms worth running: ReLU clips a real share of v and keeps one, the
+    kept values land on bf16 ties and roundings, both sign flips reach MIN_SIGN_FLIPS, and moving the ReLU changes stored values."""
+    v = e["v"]
+    clipped = float((v <= 0).double().mean())
+    assert 0.2 <= clipped <= 0.8, clipped
+    assert_wide_shares(v[v > 0])
+    down, up = sign_flip_shares(e)
+    assert down >= MIN_SIGN_FLIPS and up >= MIN_SIGN_FLIPS, (down, up)
+    for dtype in (torch.float32, BF):
+        moved = float((conv2_expect(e, dtype).double() != relu_before_addend(e, dtype).double()).double().mean())
+        assert moved >= MIN_SIGN_FLIPS, (dtype, moved)
+        assert float((conv2_expect(e, dtype) == 0).double().mean()) >= 0.2
+
+
+def conv_infer_case(B, Cin, Cout, H, W, R, stride, pad, rng, offset=False):
+    """conv_case plus the folded eval block's epilogue operands (key "e") and the bound that includes them."""
+    return with_infer_epilogue(conv_case(B, Cin, Cout, H, W, R, stride, pad, rng, offset), infer_seed(B, Cin, Cout, H, R, stride))
+
+
+def infer_seed(B, Cin, Cout, H, R, stride):
+    return 1500 + B + Cin + Cout + H + R + stride
+
+
+def with_infer_epilogue(d, seed):
+    """adds the epilogue operands to a case that holds the exact product d["y"] and its bound"""
+    d["e"] = infer_epilogue(d["y"], seed)
+    d["ibound"] = d["bound"] + d["e"]["ebound"]
+    return d
+
+
+def linear_relu2_case(M, Kin, N, rng, offset=False):
+    """x [M][Kin], w [N][Kin] and the same epilogue operands on y = x w^T (the scalar epilogue branch when N % VEC != 0)."""
+    a, b = rng
+    seed = 2500 + M + Kin + N
+    x, w = ints((M, Kin), a, seed, offset), ints((N, Kin), b, seed + 1, offset)
+    return with_infer_epilogue(dict(x=x, w=w, y=x @ w.t(), bound=reduction_bound(Kin, x, w)), seed + 2)
 
 
 def linear_case(M, Kin, N, rng, offset=False):

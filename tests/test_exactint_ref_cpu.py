@@ -78,12 +78,52 @@ def test_igemm_conv_cases(case):
     if stride == 1:
         X.assert_exact_range(d["dbound"] + 64)                      # (+ the epilogue addend)
         X.assert_wide_shares(d["dx"])
+    # the folded eval block's epilogues on the same product: bias + ReLU, bias alone, bias + addend + ReLU after it
+    i = X.with_infer_epilogue(d, X.infer_seed(B, Cin, Cout, H, R, stride))
+    X.assert_exact_range(i["ibound"])
+    assert i["ibound"] > d["bound"]
+    X.assert_infer_epilogue(i["e"])
     if B >= 16:                                                    # (a window-loader stage case: stored outputs only, no statistics)
         return
     n = X.conv_case(B, Cin, Cout, H, H, R, stride, pad, NARROW, False)
     X.assert_exact_range(n["bound"])
     X.assert_resummed(n["y"])
     X.assert_resummed(X.rne_bf16(n["y"]).double())
+
+
+@pytest.mark.parametrize("case", X.IGEMM_SHORTCUT)
+def test_shortcut_cases(case):
+    B, Cin, Cout, H, R, stride, pad, off = case
+    assert R == 1 and pad == 0
+    d = X.conv_infer_case(B, Cin, Cout, H, H, R, stride, pad, WIDE, off)
+    X.assert_exact_range(d["ibound"])
+    X.assert_infer_epilogue(d["e"])
+    v = d["e"]["v"]
+    X.assert_wide_shares(v)                                         # the shortcut stores v itself, negatives included
+    assert float(v.min()) < -256 and float(d["e"]["bias"].min()) < 0 < float(d["e"]["bias"].max())
+
+
+def test_infer_epilogue_orders_on_hand_picked_values():
+    """The three expectations on values where each rounding and the ReLU's place can be read off by hand (bf16)."""
+    v = torch.tensor([[257.0, 259.0, -300.0, 100.0, 513.0]], dtype=torch.float64)
+    add = torch.tensor([[2.0, -400.0, 400.0, -100.0, -2.0]], dtype=torch.float64)
+    e = dict(v=v, add=add)
+    assert X.conv1_expect(e, X.BF).tolist() == [[256.0, 260.0, 0.0, 100.0, 512.0]]
+    assert X.shortcut_expect(e, X.BF).tolist() == [[256.0, 260.0, -300.0, 100.0, 512.0]]
+    # 257 -> 256, + 2 = 258 (exact); 259 -> 260, - 400 < 0 -> 0; -300 + 400 = 100 (a ReLU before the addend gives 400);
+    # 100 - 100 = 0; 513 -> 512, - 2 = 510 (one rounding of 511 would give 512)
+    assert X.conv2_expect(e, X.BF).tolist() == [[258.0, 0.0, 100.0, 0.0, 510.0]]
+    assert X.relu_before_addend(e, X.BF).tolist() == [[258.0, -140.0, 400.0, 0.0, 510.0]]
+    assert X.conv2_expect(e, torch.float32).tolist() == [[259.0, 0.0, 100.0, 0.0, 511.0]]
+    assert X.sign_flip_shares(e) == (0.2, 0.2)
+
+
+def test_linear_scalar_relu2_case():
+    M, Kin, N, off = X.LINEAR_SCALAR_RELU2
+    assert (M, Kin, N, off) in X.LINEARS and N % 8 != 0 and N % 4 != 0           # neither the bf16 nor the fp32 vector width divides N
+    d = X.linear_relu2_case(M, Kin, N, WIDE, off)
+    X.assert_exact_range(d["ibound"])
+    X.assert_infer_epilogue(d["e"])
 
 
 @pytest.mark.parametrize("case", X.LINEARS)

@@ -5,8 +5,9 @@ Every comparison is torch.equal / integer equality: there is no tolerance in thi
 first (a condition on the inputs; tests/test_exactint_ref_cpu.py proves the same bounds and the tie shares without a GPU).
 
 Rounding orders the kernels document, encoded here exactly:
-  vqa_igemm         acc + bias, ReLU (relu = 1) in fp32 -> the compute dtype (first rounding) -> + addend * (addmask > 0) -> rounded
-                    again -> * (outmask > 0).  Slab / accumulator statistics: bf16 sums the STORED (rounded) values, fp32 the accumulators.
+  vqa_igemm         acc + bias, ReLU (relu = 1) in fp32 -> the compute dtype (first rounding) -> + addend * (addmask > 0) -> ReLU
+                    (relu = 2: after the addend, the folded eval block) -> rounded again -> * (outmask > 0).  Slab / accumulator
+                    statistics: bf16 sums the STORED (rounded) values, fp32 the accumulators.
   vqa_conv8p        same epilogue; statistics and the BatchNorm-backward sums are those of the STORED bf16 tile.
   vqa_conv3x3_c64p  same epilogue; statistics are those of the fp32 ACCUMULATORS; the BatchNorm-backward sums use the stored value.
   vqa_linear_dgrad_act   the value rounded to the compute dtype, masked by (outact > 0), times the keep scale, rounded.
@@ -130,6 +131,61 @@ def test_igemm_conv_forward_dgrad_epilogues(case, dtype):
         same(got, epilogue_expect(base, kw, add, am, om, dtype))
 
 
+def _infer_operands(d, dtype):
+    e = d["e"]
+    return dev(e["bias"], F32), dev(e["add"], dtype)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", X.IGEMM_CONV)
+def test_igemm_folded_block_conv1_and_conv2_forms(case, dtype):
+    """The epilogues of the Conv+BN-folded eval block on every conv geometry: conv1 = bias + ReLU (relu = 1), conv2 = bias + residual
+    addend + ReLU AFTER the addend (relu = 2).  About 15 % of the outputs have conv + bias > 0 and conv + bias + addend < 0 and as
+    many the reverse (asserted on the reference in test_exactint_ref_cpu.py): a ReLU before the addend, a dropped bias or a single
+    rounding in place of two all change stored bits."""
+    K = sub("kernels")
+    B, Cin, Cout, H, R, stride, pad, off = case
+    d = X.conv_infer_case(B, Cin, Cout, H, H, R, stride, pad, WIDE, off)
+    X.assert_exact_range(d["ibound"])
+    bias, add = _infer_operands(d, dtype)
+    (a1, _, _), _, _, _ = _igemm_fwd(K, d, case, dtype, bias=bias, relu=1)
+    same(a1, X.conv1_expect(d["e"], dtype))
+    (out, _, _), _, _, _ = _igemm_fwd(K, d, case, dtype, bias=bias, addend=add, relu=2)
+    want = X.conv2_expect(d["e"], dtype)
+    assert not torch.equal(want, X.relu_before_addend(d["e"], dtype))
+    same(out, want)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", X.IGEMM_SHORTCUT, ids=["1x1s2", "1x1s1"])
+def test_igemm_folded_block_shortcut_form(case, dtype):
+    """The folded shortcut: 1x1 conv, pad 0, bias, no ReLU (negative values are stored as they are)."""
+    K = sub("kernels")
+    B, Cin, Cout, H, R, stride, pad, off = case
+    d = X.conv_infer_case(B, Cin, Cout, H, H, R, stride, pad, WIDE, off)
+    X.assert_exact_range(d["ibound"])
+    bias, _ = _infer_operands(d, dtype)
+    (res, _, _), _, _, _ = _igemm_fwd(K, d, case, dtype, bias=bias)
+    want = X.shortcut_expect(d["e"], dtype)
+    assert float(want.min()) < 0
+    same(res, want)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_igemm_scalar_epilogue_relu_after_addend(dtype):
+    """N = 10 is no multiple of the vector width: the epilogue's scalar branch, with bias + addend + relu = 2 and with bias + ReLU."""
+    K = sub("kernels")
+    M, Kin, N, off = X.LINEAR_SCALAR_RELU2
+    d = X.linear_relu2_case(M, Kin, N, WIDE, off)
+    X.assert_exact_range(d["ibound"])
+    bias, add = _infer_operands(d, dtype)
+    args = (dev(d["x"], dtype), K.pack_rows(dev(d["w"], F32), dtype), M, N, Kin, K.linear_geom(M, Kin))
+    out, _, _ = K.igemm(*args, dtype=dtype, bias=bias, addend=add, relu=2)
+    same(out, X.conv2_expect(d["e"], dtype))
+    a1, _, _ = K.igemm(*args, dtype=dtype, bias=bias, relu=1)
+    same(a1, X.conv1_expect(d["e"], dtype))
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("case", X.IGEMM_CONV)
 def test_igemm_statistics_slab_and_accumulator(case, dtype):
@@ -165,6 +221,11 @@ def test_igemm_window_loader_variants(case):
     X.assert_exact_range(max(d["bound"], d["dbound"]))
     (y, _, _), _, _, _ = _igemm_fwd(K, d, (B, C, C, H, 3, 1, 1), BF)
     same(y, X.rne_bf16(d["y"]))
+    # the folded eval block's conv1 form (bias + ReLU) through the same window loader
+    X.with_infer_epilogue(d, X.infer_seed(B, C, C, H, 3, 1))
+    X.assert_exact_range(d["ibound"])
+    (a1, _, _), _, _, _ = _igemm_fwd(K, d, (B, C, C, H, 3, 1, 1), BF, bias=dev(d["e"]["bias"], F32), relu=1)
+    same(a1, X.conv1_expect(d["e"], BF))
     wt = K.pack_transpose(krsc(d["w"]).view(C, 9, C), BF)
     dx, _, _ = K.igemm(dev(X.nhwc(d["dy"]), BF), wt, M, C, Kw, geom, dtype=BF, transposed=1)
     same(dx, X.rne_bf16(d["dx"]))

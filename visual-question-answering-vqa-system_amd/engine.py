@@ -607,8 +607,8 @@ class HipEngine:
         Conv+BN-folded eval route in eval mode, the training forward (running statistics updated) without kept activations in train
         mode.  The backward of such a tape prunes what nothing needs (see _plan_of).
         lowp_logits: return the logits in the compute dtype (the trainer's loss kernel reads bf16 and leaves the fp32 copy itself).
-        record: a dict that receives {residual block prefix: (input, output)} of the folded eval path, and under "mxfp8" also
-        {prefix + ".a1": MXFP8 a1 (codes, scales)} (tests).
+        record: a dict that receives {residual block prefix: (input, output)} of the folded eval path and {prefix + ".a1": conv1's
+        output a1} -- the tensor, or under "mxfp8" the MXFP8 a1 (codes, scales) (tests).
         kv_index (many questions per image, training included): int32 [N] on the device, every entry in [0, U) (the caller checks);
         images holds U images, token_ids N questions, and question i attends to image kv_index[i].  The image half (CNN, projector,
         norm_kv, K | V) runs at U images, the question half at N; the tape keeps the image index as CSR (vqa_index_csr) for the
@@ -879,8 +879,7 @@ class HipEngine:
                         out, _, _ = K.igemm(a1, w2, M, Cout, 9 * Cout, (B, Ho, Wo, Cout, Ho, Wo, 3, 3, 1, 1), dtype=T, bias=b2, addend=res, relu=2)
                     if record is not None:
                         record[p] = (x, out)
-                        if foldmx is not None:
-                            record[p + ".a1"] = a1q
+                        record[p + ".a1"] = a1q if foldmx is not None else a1
                     x, H, W, C = out, Ho, Wo, Cout
                     continue
                 facc = training and self.fuse_bn_finalize and T == torch.bfloat16
