@@ -574,6 +574,41 @@ int vqa_adamw_groups_ema_dev(float* p, const float* g, float* m, float* v, const
    for n > 0 a NULL or not 16-byte-aligned src / dst, a NULL index, n_src == 0, or 2^24 or more chunks (n * ceil(row_bytes / 16384)).  n == 0 launches nothing. */
 int vqa_gather_rows(const void* src, const int* index, void* dst, int n, long long row_bytes, int n_src, hipStream_t stream);
 
+/* ---- explaining an answer (csrc/explain_ops.hip; VQAModel.explain, Explanation.render) ----------------------------
+ * All four accumulate in fp32 in a fixed order (no float atomics: the same bits on every run) and return status 1000 without a
+ * launch for a NULL operand, a size < 1, a dtype other than 0 (fp32) / 1 (bf16) and the shapes named below.
+ *
+ * vqa_class_seed: the class whose score is explained, and the seed of its backward.  logits [B][N] in dtype (unit column stride,
+ * row stride ld >= N); ids int64 [B] or NULL.
+ *   chosen[b]     = ids[b], or without ids the arg-max of row b in vqa_softmax_topk's order: value descending, ties to the lower
+ *                   index, a NaN ranks first -- chosen == the index vqa_softmax_topk(K = 1) returns
+ *   dlogits[b][j] = 1 where j == chosen[b], else 0       ([B][N] contiguous, in the dtype of logits; an id outside [0, N) -- the
+ *                   caller checks the range -- gives an all-zero row)
+ * vqa_gradcam: Grad-CAM of NHWC features.  feat, dfeat [B][P][C] in dtype (16-byte aligned), cam fp32 [B][P].
+ *   alpha[b][c] = (1/P) sum_p dfeat[b][p][c]
+ *   cam[b][p]   = max(0, sum_c alpha[b][c] * feat[b][p][c])
+ *   normalize != 0: cam[b][p] /= max_p cam[b][p] (a correctly rounded fp32 division; a row whose maximum is 0 stays all zero).
+ *   One pass over each operand, one workgroup per image.  C must be a multiple of 8 and at most 1024.
+ * vqa_attention_map: where the question looked.  caw fp32 [ncl][B][H][L][P] (the cross-attention probabilities of every layer in
+ * one buffer), mask fp32 [B][L] (non-zero = real token) or NULL (every token is real), out fp32 [B][P].
+ *   out[b][p] = (1 / (ncl * H * n_b)) sum_l sum_h sum_{t real} caw[l][b][h][t][p],  n_b = the number of real tokens of question b
+ *   -- the mean over layers and heads of the reference's get_attention_visualization, averaged over the real tokens; each row sums
+ *   to 1, and a question without a real token gives NaN (0 / 0), as its logits are.  normalize as in vqa_gradcam.  L * P <= 8192.
+ * vqa_heatmap_render: a map as a picture.  map fp32 [B][Hm][Wm], base uint8 [B][H][W][3] or NULL, lut uint8 [256][3], out uint8
+ * [B][H][W][3].  Per output pixel (y, x):
+ *   t   = bilinear sample of map[b] at F.interpolate's align_corners=False source position: sy = max(0, (y + 0.5) * Hm / H - 0.5),
+ *         rows y0 = floor(sy) and min(y0 + 1, Hm - 1) with weights 1 - (sy - y0) and sy - y0; columns likewise; fp32 throughout
+ *   i   = clamp(floor(t * 255 + 0.5), 0, 255); a NaN t gives 0
+ *   out = floor(alpha * lut[i][ch] + (1 - alpha) * base[b][y][x][ch] + 0.5) per channel, or lut[i][ch] without a base.
+ *   alpha must lie in [0, 1]. */
+int vqa_class_seed(int dtype, const void* logits, long long ld, const long long* ids, long long* chosen, void* dlogits, int B, int N,
+                   hipStream_t stream);
+int vqa_gradcam(int dtype, const void* feat, const void* dfeat, float* cam, int B, int P, int C, int normalize, hipStream_t stream);
+int vqa_attention_map(const float* caw, const float* mask, float* out, int ncl, int B, int H, int L, int P, int normalize,
+                      hipStream_t stream);
+int vqa_heatmap_render(const float* map, const uint8_t* base, const uint8_t* lut, uint8_t* out, int B, int Hm, int Wm, int H, int W,
+                       float alpha, hipStream_t stream);
+
 /* ---- input pipeline on the GPU -----------------------------------------------------------------
  * vqa_image_normalize: torchvision ToTensor + Normalize of data/preprocess.py:34-35,117-121 -- uint8 HWC [B][H][W][3] ->
  * float32 NCHW, (u/255 - mean[c]) / std[c] in torch's operation order (bit-identical), optional per-sample horizontal flip

@@ -152,6 +152,10 @@ SIGNATURES = {
     "vqa_adamw_groups_ema": [P, P, P, P, P, I, LL, F, F, F, F, F, LL, P, F, F, P, P, P, P, I, P, P, F, I, P, P, P],
     "vqa_adamw_groups_dev": [P, P, P, P, P, I, LL, P, P, P, P, P, P, I, P, P, P, P],
     "vqa_adamw_groups_ema_dev": [P, P, P, P, P, I, LL, P, P, P, P, P, P, I, P, P, P, P, P],
+    "vqa_class_seed": [I, P, LL, P, P, P, I, I, P],
+    "vqa_gradcam": [I, P, P, P, I, I, I, I, P],
+    "vqa_attention_map": [P, P, P, I, I, I, I, I, I, P],
+    "vqa_heatmap_render": [P, P, P, P, I, I, I, I, I, F, P],
 }
 _RET_LL = {"vqa_image_resize_ws", "vqa_wgrad_group_ws", "vqa_spatial_bwd_scratch", "vqa_se_bwd_scratch", "vqa_layernorm_bwd_ws", "vqa_bias_act_bwd_ws"}                       # return a size (long long)
 _NO_STATUS = _RET_LL | {"vqa_wgrad3x3_c64_blocks", "vqa_bn_acc_words", "vqa_bn_apply_pool_chunks", "vqa_se_bwd_blocks", "vqa_wgrad3x3_c128_blocks", "vqa_layernorm_bwd_folds", "vqa_bias_act_bwd_fold_rows", "vqa_conv3x3_c64p_blocks", "vqa_stem_wgrad_blocks", "vqa_igemm_mtiles", "vqa_igemm_variant", "vqa_bn_bwd_blocks", "vqa_stem_conv_blocks", "vqa_stem_conv_pool_ok", "vqa_stem_dgrad_fused_ok", "vqa_wgrad3x3_c64_bn_ok", "vqa_conv8p_ok"}   # return a count, not a status

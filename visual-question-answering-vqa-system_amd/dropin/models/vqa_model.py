@@ -9,6 +9,8 @@ Extension (training): `forward_grouped(images, token_ids, attention_mask, image_
 through it; `group_by_image(image_ids)` turns a batch's image ids into that form.
 Extension (inference only): `predict_topk(...)` / `answer_topk(context, ...)` return the k best answers with their probabilities
 (`TopK`) from one extra launch inside the captured graph, with an optional answer whitelist and softmax temperature.
+Extension (inference only): `explain(...)` returns Grad-CAM and cross-attention maps over the image-feature grid (`Explanation`) from
+an eval-mode taped forward and a backward that stops at the image features; `Explanation.render(...)` turns one into uint8 pictures.
 There is no CPU path: calling forward with CPU tensors, or without the built extension, raises.
 """
 from __future__ import annotations
@@ -518,6 +520,36 @@ class TopK(NamedTuple):
             answers = [{"answer": decode(i), "probability": p, "index": i} for i, p in zip(irow, prow)]
             out.append({"answers": answers, "top_answer": answers[0]["answer"], "confidence": answers[0]["probability"]})
         return out
+
+
+EXPLAIN_METHODS = ("gradcam", "attention")
+
+
+class Explanation(NamedTuple):
+    """Where the model looked for N questions (VQAModel.explain): maps over the image-feature grid, on the device."""
+    logits: torch.Tensor                     # float32 [N, num_answers]: the eval-mode taped forward's
+    answers: torch.Tensor                    # int64 [N]: the class each map explains (given, or the arg-max of logits)
+    gradcam: Optional[torch.Tensor] = None   # float32 [N, Hf, Wf]: Grad-CAM of the image features for that class
+    attention: Optional[torch.Tensor] = None   # float32 [N, Hf, Wf]: cross-attention, mean over layers, heads and real tokens
+
+    def render(self, which: str = "gradcam", base=None, alpha: float = 0.5, colormap: Optional[torch.Tensor] = None,
+               size: Optional[Tuple[int, int]] = None) -> torch.Tensor:
+        """The map `which` as pictures, uint8 [N, H, W, 3] on the device, one launch (kernels.heatmap_render): upsampled bilinearly
+        (F.interpolate, align_corners=False), looked up in `colormap` (uint8 [256, 3]; None: kernels.default_colormap()) and blended
+        over `base` as alpha * colour + (1 - alpha) * base.  base: a ByteImages, a uint8 [N, H, W, 3] device tensor, or None (the
+        colours alone).  size = (H, W) defaults to the base's and is required without one.  Map values are taken as [0, 1] (what
+        explain(normalize=True) returns; others are clamped, a NaN takes the table's first entry).  ValueError for a map that was not
+        computed, an alpha outside [0, 1], or a base / colour table / size of the wrong type or shape."""
+        K = _pkg().kernels
+        alpha = K.check_alpha(alpha)
+        if which not in EXPLAIN_METHODS:
+            raise ValueError(f"render: `which` must be one of {EXPLAIN_METHODS}, got {which!r}")
+        maps = getattr(self, which)
+        if maps is None:
+            raise ValueError(f"render: this Explanation holds no {which!r} map (ask explain() for it with methods=)")
+        if _is_bytes(base):
+            base = base.data
+        return K.heatmap_render(maps, size=size, base=base, alpha=alpha, colormap=colormap)
 
 
 class ImageContext:
@@ -1356,6 +1388,71 @@ class VQAModel(nn.Module):
         graphed = self.graph_inference and 0 < N <= self.graph_max_batch and not torch.cuda.is_current_stream_capturing()
         feed = [ec["kv"], token_ids, maskf, idx if (graphed or idx is not None) else self._implied_index(U, N, dev)]
         return self._topk_route(key, N, init, feed, fn, k, amask, scale, return_logits)
+
+    # ---- explaining an answer (extension, inference only)
+    def explain(self, images, token_ids: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, answers: Optional[torch.Tensor] = None,
+                methods=EXPLAIN_METHODS, normalize: bool = True) -> Explanation:
+        """Where the model looked, per question, on the image-feature grid (7 x 7 at 224 x 224):
+          "gradcam"    Grad-CAM of the image features for the explained class c: relu(sum_k alpha_k * feat_k) with alpha_k the spatial
+                       mean of d logits[:, c] / d feat_k.  The backward of that one score stops at the image features: no weight
+                       gradient, no gradient buffer, no CNN or text-encoder backward (HipEngine.explain_route).
+          "attention"  the cross-attention probabilities, mean over layers, heads and the question's real tokens: the reference's
+                       get_attention_visualization averaged over the question.  Each map sums to 1 before normalisation; an
+                       all-padding question gives NaN, as its logits are.  ValueError for a model without cross-attention layers.
+        answers: int64 [N] (any integer dtype, CPU or device) -- the class to explain per question -- or None for the arg-max of this
+        call's own logits (ties to the lower index).  Range-checked as an image index is: free for a CPU tensor, one device-to-host
+        read for a device tensor; IndexError outside [0, num_answers).  normalize: each map divided by its maximum (a map that is all
+        zero stays zero).  images: float NCHW or a ByteImages (the same result bit for bit).
+        Inference only: train mode raises RuntimeError (eval mode is NOT set for the caller); it runs with and without
+        torch.no_grad() and never touches autograd, parameters' .grad, BatchNorm buffers, dropout seeds or a trainer's state, so it
+        may be called between two training steps.  The logits are the eval-mode TAPED forward's (what model(...) gives under
+        autograd in eval mode), not the Conv+BN-folded inference path's; in bf16 the two differ by rounding.  Eager: not captured.
+        ValueError for unknown or empty methods, or answers of another shape or dtype, before anything is launched."""
+        if isinstance(methods, str):
+            methods = (methods,)
+        methods = tuple(methods)
+        if not methods or any(m not in EXPLAIN_METHODS for m in methods) or len(set(methods)) != len(methods):
+            raise ValueError(f"explain: methods must be a non-empty selection of {EXPLAIN_METHODS}, got {methods!r}")
+        if isinstance(images, ImageFeatures):
+            raise TypeError("explain: takes images (float NCHW or ByteImages), not ImageFeatures")
+        N = token_ids.shape[0]
+        n_img = images.shape_nchw[0] if _is_bytes(images) else images.shape[0]
+        if token_ids.dim() != 2 or n_img != N:
+            raise ValueError(f"explain: one question [N, L] per image expected; got {n_img} images and token_ids {tuple(token_ids.shape)}")
+        if answers is not None:
+            if not isinstance(answers, torch.Tensor):
+                answers = torch.as_tensor(answers)
+            if answers.dim() != 1 or answers.shape[0] != N:
+                raise ValueError(f"explain: answers must be 1-D with one class per question ({N}); got shape {tuple(answers.shape)}")
+            answers = _checked_index(answers, self.num_answers, "explain: answers")
+        if "attention" in methods and not self.config["num_cross_layers"]:
+            raise ValueError("explain: \"attention\" needs a model with cross-attention layers (num_cross_layers = 0)")
+        if self.training or any(self._part_modes()):
+            raise RuntimeError("explain is inference only: call model.eval() first (every part in eval mode)")
+        if not (images.data if _is_bytes(images) else images).is_cuda or not token_ids.is_cuda:
+            raise RuntimeError("VQAModel (HIP) got CPU inputs; this implementation only runs on an MI355X (no CPU path)")
+        eng = self._ensure_engine()
+        K = self._pkg.kernels
+        with torch.no_grad():
+            images, norm = self._image_operand(images)
+            dev = images.device
+            token_ids = token_ids.contiguous().long()
+            maskf = None if attention_mask is None else attention_mask.contiguous().float()
+            if answers is not None:
+                answers = answers.to(device=dev, dtype=torch.int64).contiguous()
+            plan = self.__dict__.get("_explain_plan")
+            if plan is None:
+                plan = self.__dict__["_explain_plan"] = self._pkg.finetune.explain_plan(self._param_entries)
+            r = eng.explain_route(self._eng_images(images.detach(), norm), token_ids, maskf, plan, class_ids=answers,
+                                  want_dfeat="gradcam" in methods, want_caw="attention" in methods)
+            Hf, Wf, Cf = r["Hf"], r["Wf"], r["Cf"]
+            logits = r["logits"] if r["logits"].dtype == torch.float32 else r["logits"].float()
+            cam = att = None
+            if "gradcam" in methods:
+                cam = K.gradcam(r["feat"], r["dfeat"], N, Hf * Wf, Cf, normalize=normalize).view(N, Hf, Wf)
+            if "attention" in methods:
+                att = K.attention_map(r["caw"], maskf, normalize=normalize).view(N, Hf, Wf)
+        return Explanation(logits, r["chosen"], cam, att)
 
     graph_inference = True        # eval-mode no-grad forward()/predict() replay a captured HIP graph up to graph_max_batch
     graph_max_batch = 64          # (the serving case, api/inference.py:196-323: model(...) at B = 1 ... a few)

@@ -295,6 +295,10 @@ class HipEngine:
             self.wsrc = self.flat
         if not stem:                              # (every route that runs _stem_fwd packs the stem operands in its own begin_step)
             return
+        self._pack_stem()
+
+    def _pack_stem(self):
+        """The stem conv's forward operands from the fp32 master (begin_step; explain_route)."""
         bk = 64 if self.dtype == torch.bfloat16 else 32
         kp = (147 + bk - 1) // bk * bk
         self.stem_kp = kp
@@ -556,6 +560,9 @@ class HipEngine:
 
     def _ln_bwd(self, dout, x, prefix, stats, G, addend=None, p=0.0, seed=0, dadd=None, period=1):
         eg, eb = self.E[prefix + ".weight"], self.E[prefix + ".bias"]
+        if self._plan is not None and self._plan.no_param_grads:
+            # only dx is wanted: the kernel leaves its d gamma / d beta partials in scratch and their folds are never launched
+            return K.layernorm_bwd(dout, x, self.P(prefix + ".weight"), stats, None, None, addend=addend, drop_p=p, seed=seed, foldq=[])
         return K.layernorm_bwd(dout, x, self.P(prefix + ".weight"), stats, G[eg.offset: eg.offset + eg.numel],
                                G[eb.offset: eb.offset + eb.numel], addend=addend, drop_p=p, seed=seed, dadd=dadd, period=period,
                                foldq=self._foldq)
@@ -830,17 +837,18 @@ class HipEngine:
         call("vqa_stem_pool_fwd", dt(T), ptr(y), ptr(coef), ptr(x), ptr(idx), B, H1, W1, 64)
         return x, Hp, Wp, (dict(images=images, y=y, coef=coef, idx=idx, geom=sgeom, H1=H1, W1=W1) if keep else None)
 
-    def _stages_fwd(self, x, B, H, W, training, keep, record=None, after_stage=None):
+    def _stages_fwd(self, x, B, H, W, training, keep, record=None, after_stage=None, fold=None):
         """Residual stages with their SE / spatial attention, A2-A5, from the pooled stem output x [B*H*W][64].  Eval without kept
         activations (not training, not keep, fold_eval) runs the Conv+BN-folded blocks, bf16 or MXFP8 (infer_precision; `record`
         as in forward()); everything else the training blocks with their BatchNorm routes.  keep: the stage records are returned
         for the tape (otherwise a stage's activations are freed as the next stage runs).  after_stage(s): called when stage s has
-        been issued (forward() issues the text encoder behind stage 1 there).
+        been issued (forward() issues the text encoder behind stage 1 there).  fold: False keeps an eval pass without kept activations
+        on the BatchNorm-as-its-own-pass blocks a taped eval forward runs (explain_route: the same bits as that forward); None: fold_eval.
         Returns (features [B*H*W][C], H, W, C, stage records)."""
         T, dev, C = self.dtype, x.device, 64
         if self.infer_precision not in ("bf16", "mxfp8"):
             raise ValueError(f"unknown infer_precision {self.infer_precision!r}")
-        folded = self._fold_bn() if (self.fold_eval and not training and not keep) else None
+        folded = self._fold_bn() if ((self.fold_eval if fold is None else fold) and not training and not keep) else None
         foldmx, xq = None, None                   # MXFP8 folded weights; MXFP8 copy of the current block input (if one exists)
         if folded is not None and self.infer_precision == "mxfp8":
             if T != torch.bfloat16:
@@ -1227,6 +1235,70 @@ class HipEngine:
             aux = self._aux_of(ctx["feat"], U, ctx["Hf"], ctx["Wf"], ctx["Cf"], ctx["img"], enc, cat, fused, probs_all)
         return logits, aux
 
+    # ------------------------------------------------------------------ explaining an answer (inference only)
+    def explain_route(self, images, token_ids: torch.Tensor, maskf: Optional[torch.Tensor], plan, class_ids: Optional[torch.Tensor] = None,
+                      want_dfeat: bool = True, want_caw: bool = False) -> dict:
+        """An eval-mode taped forward and the backward of one class score per question that STOPS at the image features.
+        plan: finetune.explain_plan -- nothing trains, no image gradient, no text-encoder backward, and the fusion part still hands dfeat
+        on.  The forward is forward(training=False, need_tape=True)'s, part by part and bit for bit (residual blocks with BatchNorm as its
+        own pass on the running statistics, never the Conv+BN fold), except that the CNN keeps no activation beyond `feat` (the stem takes
+        its one-launch inference form in bf16) and the text encoder keeps none; vqa_class_seed picks the class (class_ids: int64 [B] on
+        the device, range-checked by the caller; None: the arg-max) and seeds _head_bwd -> _fusion_bwd.  Under the plan no
+        weight-gradient launch is issued, no LayerNorm / bias / position-embedding fold runs, and no gradient buffer exists: the
+        parameter buffer stands in as the base address _frozen_g measures from and is never written.
+        Leaves the training state alone: no count_step, no seed (dropout is 0 everywhere: _seed is stubbed out for the call), no
+        _site / step_id, the one-shot _wsrc_fresh and the trainer's packed backward operands are neither read nor written (the bf16
+        operand copy is cast again from the fp32 master, with the values it holds already; this route's own backward operands are
+        packed into a buffer of their own, one launch from the second call on), no tape is handed out, nothing gets a .grad.
+        Everything runs on the current stream but what _fusion_bwd itself puts on the text stream (joined before returning).
+        Returns {"logits": [B][N] compute dtype, "chosen": int64 [B], "feat" / "dfeat": [B*Hf*Wf][Cf] compute dtype (dfeat None unless
+        want_dfeat), "caw": fp32 [ncl][B][heads][L][Hf*Wf] | None, "Hf", "Wf", "Cf"}."""
+        if plan is None or not plan.no_param_grads or any(plan.modes):
+            raise RuntimeError("explain_route needs finetune.explain_plan: eval mode, nothing trains, the feature gradient wanted")
+        cfg = self.cfg
+        ncl = cfg["num_cross_layers"]
+        if want_caw and not ncl:
+            raise ValueError("attention maps need at least one cross-attention layer")
+        B = _image_shape(images)[0]
+        Bt, L = token_ids.shape
+        self._pos_enc(L)
+        own = self.__dict__.setdefault("_explain_operands", dict(plan={}, table=None, buf=None, gen=0))
+        saved = (self._wt, self._wt_plan, self._wt_table, self._wt_buf, self._wt_gen)
+        self._wt, self._wt_plan, self._wt_table, self._wt_buf, self._wt_gen = {}, own["plan"], own["table"], own["buf"], own["gen"]
+        self._seed = lambda: 0                    # (instance attribute over the method: the forward parts ask for a seed per dropout site)
+        try:
+            if self.dtype == torch.bfloat16:
+                self.ensure_operand_copy()
+                call("vqa_convert", 0, 1, ptr(self.flat), ptr(self.wsrc), self.flat.numel())
+            else:
+                self.wsrc = self.flat
+            self._pack_stem()
+            if want_dfeat:
+                self._pack_planned()
+            tape: dict = {"training": False, "B": B, "Bq": Bt, "plan": plan}
+            x, H, W, _ = self._stem_fwd(images, False, False)
+            feat, Hf, Wf, Cf, _ = self._stages_fwd(x, B, H, W, False, False, fold=False)
+            ntok = Hf * Wf
+            enc, q0 = self._text_fwd(token_ids, maskf, 0.0, None, hoist_q=self.hoist_cross and ncl >= 1)
+            img, tape["proj"] = self._projector_fwd(feat, ntok, 0.0)
+            q, _, caw = self._cross_layers_fwd(enc, img, Bt, L, ntok, 0.0, want_caw, q0=q0, tape=tape)
+            logits, _, _, tape["pool"], tape["head"] = self._tail_fwd(q, enc, maskf, Bt, L, 0.0, True)
+            chosen, dlogits = K.class_seed(logits, class_ids)
+            dfeat = None
+            if want_dfeat:
+                G = self.flat
+                self._deferred, self._keep, self._wgq, self._foldq, self._foldq2 = [], [], [], [], []
+                self._plan, self._bwd_G = plan, G
+                seg = self._seg_fn(None)
+                dfeat, _ = self._fusion_bwd(tape, self._head_bwd(tape, dlogits, G, seg), G, seg)
+                self._bwd_join()
+        finally:
+            self._plan, self._bwd_G = None, None
+            self.__dict__.pop("_seed", None)
+            own.update(plan=self._wt_plan, table=self._wt_table, buf=self._wt_buf, gen=self._wt_gen)
+            self._wt, self._wt_plan, self._wt_table, self._wt_buf, self._wt_gen = saved
+        return dict(logits=logits, chosen=chosen, feat=feat, dfeat=dfeat, caw=caw, Hf=Hf, Wf=Wf, Cf=Cf)
+
     def _attn_block_bwd(self, rec, dout, G, dkv_addend=None, kv_side=False, addend_event=None, dprobs=None):
         """Returns (d q_in, d kv_in, event) ; for self-attention d kv_in is folded into d q_in.
         dprobs: fp32 gradient on the saved softmax rec["probs"] (aux['cross_attention_weights']) -> the _dp attention backward.
@@ -1359,6 +1431,8 @@ class HipEngine:
         pl = self._plan
         if pl is None:
             return False
+        if pl.no_param_grads:                     # (G is only a base address there: nothing may be written through it)
+            return True
         return pl.frozen((t.data_ptr() - self._bwd_G.data_ptr()) // 4, t.numel())
 
     # The same backward in three separately callable parts, split where it reports its segments (graph-connected aux outputs:

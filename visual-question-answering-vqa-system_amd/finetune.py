@@ -84,13 +84,19 @@ class Plan:
     fusion_bwd   the fusion backward runs (a fusion parameter trains, or a gradient must pass it on)
     need_dfused  the answer head hands a gradient to the fusion part
     need_dfeat / need_denc   the fusion part hands a gradient to the CNN / the text encoder
+    features_grad   the gradient at the image features is itself the result (explain_plan): the fusion part hands it on although
+                    no CNN backward follows
+    no_param_grads  such a plan with nothing to train: the backward writes no parameter gradient at all, so its gradient buffer
+                    is never read or written (the engine hands the parameter buffer in as a base address for frozen())
     """
 
     def __init__(self, param_entries: Sequence[LY.Entry], trainable: Sequence[bool], modes: Tuple[bool, bool, bool, bool],
-                 images_grad: bool):
+                 images_grad: bool, features_grad: bool = False):
         self.modes = tuple(bool(m) for m in modes)
         self.trainable = tuple(bool(t) for t in trainable)
         self.images_grad = bool(images_grad)
+        self.features_grad = bool(features_grad)
+        self.no_param_grads = self.features_grad and not any(self.trainable)
         names = [e.name for e in param_entries]
         tr = dict(zip(names, self.trainable))
 
@@ -104,7 +110,7 @@ class Plan:
         else:
             self.cnn_low = next((s for s in STAGES if any_of(f"image_encoder.stage{s}.")), None)
         self.text = any_of("text_encoder.")
-        self.need_dfeat = self.cnn_low is not None
+        self.need_dfeat = self.cnn_low is not None or self.features_grad
         self.need_denc = self.text
         self.fusion_bwd = any_of("fusion.") or self.need_dfeat or self.need_denc
         self.need_dfused = self.fusion_bwd
@@ -134,7 +140,7 @@ class Plan:
         return out
 
     def key(self):
-        return (self.modes, self.trainable, self.images_grad)
+        return (self.modes, self.trainable, self.images_grad) + ((True,) if self.features_grad else ())
 
 
 def resolve(param_entries, params, modes, images_grad, cache: Optional[dict] = None) -> Optional[Plan]:
@@ -150,6 +156,13 @@ def resolve(param_entries, params, modes, images_grad, cache: Optional[dict] = N
     if cache is not None:
         cache["key"], cache["plan"] = key, plan
     return plan
+
+
+def explain_plan(param_entries) -> Plan:
+    """The plan of the backward that stops at the image features (HipEngine.explain_route): every part in eval mode, nothing trains, no
+    image gradient, no text-encoder backward -- and the fusion part still hands dfeat on.  No weight-gradient launch is issued under
+    it (every slot is frozen) and the CNN keeps no tape."""
+    return Plan(param_entries, (False,) * len(param_entries), (False,) * 4, False, features_grad=True)
 
 
 # ---- parameter groups: a learning-rate scale and a weight decay per group of parameters (HipTrainer(param_groups=...))

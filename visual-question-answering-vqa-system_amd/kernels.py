@@ -816,3 +816,109 @@ def cross_entropy_opts(logits, targets, *, class_weight=None, ignore_index=None,
          ptr(err), ptr(ws), ptr(class_weight), 0 if ignore_index is None else int(ignore_index), int(ignore_index is not None),
          float(label_smoothing), ptr(acc), ptr(empty))
     return loss, dlogits
+
+
+# ----------------------------------------------------------------------------------------------
+# explaining an answer (csrc/explain_ops.hip; include/vqa_hip.h has the formulas)
+# ----------------------------------------------------------------------------------------------
+def class_seed(logits, ids=None):
+    """The class to explain per row of logits [B][N] (fp32 or bf16, unit column stride, any row stride >= N) and the one-hot seed of its
+    backward, one launch (vqa_class_seed).  ids: int64 [B] on the device (the caller checks the range), or None for the row's arg-max in
+    softmax_topk's order (ties to the lower index, a NaN first).  Returns (chosen int64 [B], dlogits [B][N] in the dtype of logits)."""
+    B, N = logits.shape
+    if logits.stride(1) != 1 and N > 1:
+        raise ValueError("class_seed: logits need a unit column stride")
+    ld = logits.stride(0) if B > 1 else max(logits.stride(0), N)
+    if ids is not None and (ids.dtype != torch.int64 or tuple(ids.shape) != (B,) or ids.device != logits.device or not ids.is_contiguous()):
+        raise ValueError(f"class_seed: ids must be a contiguous int64 [{B}] tensor on {logits.device}")
+    chosen = torch.empty((B,), device=logits.device, dtype=torch.int64)
+    dlogits = torch.empty((B, N), device=logits.device, dtype=logits.dtype)
+    call("vqa_class_seed", dt(logits), ptr(logits), ld, ptr(ids), ptr(chosen), ptr(dlogits), B, N)
+    return chosen, dlogits
+
+
+def gradcam(feat, dfeat, B, P, C, normalize=True):
+    """Grad-CAM of the NHWC features: feat, dfeat [B][P][C] (any shape with B * P * C elements, contiguous, one dtype: fp32 or bf16)
+    -> fp32 [B][P] = max(0, sum_c mean_p(dfeat)[c] * feat[p][c]), divided by its row maximum when normalize (vqa_gradcam)."""
+    if feat.dtype != dfeat.dtype or feat.numel() != B * P * C or dfeat.numel() != B * P * C or not (feat.is_contiguous() and dfeat.is_contiguous()):
+        raise ValueError(f"gradcam: feat and dfeat must be contiguous tensors of {B} x {P} x {C} elements in one dtype")
+    cam = torch.empty((B, P), device=feat.device, dtype=torch.float32)
+    call("vqa_gradcam", dt(feat), ptr(feat), ptr(dfeat), ptr(cam), B, P, C, int(bool(normalize)))
+    return cam
+
+
+def attention_map(caw, maskf=None, normalize=True):
+    """Mean of the cross-attention probabilities caw fp32 [ncl][B][H][L][P] over layers, heads and the real tokens of each question
+    (maskf: fp32 [B][L], non-zero = real token; None: all) -> fp32 [B][P] (vqa_attention_map)."""
+    if caw.dim() != 5 or caw.dtype != torch.float32 or not caw.is_contiguous():
+        raise ValueError("attention_map: caw must be a contiguous fp32 [ncl, B, H, L, P] tensor")
+    ncl, B, H, L, P = caw.shape
+    if maskf is not None and (maskf.dtype != torch.float32 or tuple(maskf.shape) != (B, L) or maskf.device != caw.device or not maskf.is_contiguous()):
+        raise ValueError(f"attention_map: the mask must be a contiguous fp32 [{B}, {L}] tensor on {caw.device}")
+    out = torch.empty((B, P), device=caw.device, dtype=torch.float32)
+    call("vqa_attention_map", ptr(caw), ptr(maskf), ptr(out), ncl, B, H, L, P, int(bool(normalize)))
+    return out
+
+
+def check_alpha(alpha) -> float:
+    """The blend weight of heatmap_render: a number in [0, 1] (ValueError otherwise)."""
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, float)) or not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha must be a number in [0, 1], got {alpha!r}")
+    return float(alpha)
+
+
+def default_colormap() -> torch.Tensor:
+    """The default colour table, uint8 [256][3] on the CPU: piecewise linear through a few anchor colours (dark blue, blue, cyan,
+    yellow, red, dark red at equal distances), rounded to the nearest level.  Built in integer arithmetic: the same bytes everywhere."""
+    anchors = ((0, 0, 128), (0, 0, 255), (0, 255, 255), (255, 255, 0), (255, 0, 0), (128, 0, 0))
+    seg = len(anchors) - 1
+    rows = []
+    for i in range(256):
+        k = min(i * seg // 255, seg - 1)
+        num = i * seg - k * 255                       # position inside segment k, in 1/255ths
+        rows.append([(a * (255 - num) + b * num + 127) // 255 for a, b in zip(anchors[k], anchors[k + 1])])
+    return torch.tensor(rows, dtype=torch.uint8)
+
+
+_COLORMAPS = {}
+
+
+def heatmap_render(maps, size=None, base=None, alpha=0.5, colormap=None):
+    """A batch of maps as pictures, one launch (vqa_heatmap_render): maps fp32 [B][Hm][Wm] on the device are upsampled bilinearly
+    (F.interpolate, align_corners=False) to size = (H, W), looked up in the colour table (uint8 [256][3]; None: default_colormap())
+    and, with a base (uint8 [B][H][W][3] on the device), blended over it as alpha * colour + (1 - alpha) * base.  size defaults to
+    the base's.  Returns uint8 [B][H][W][3].  Usable on any fp32 map (Grad-CAM, attention, an input-gradient saliency)."""
+    alpha = check_alpha(alpha)
+    if not isinstance(maps, torch.Tensor) or maps.dim() != 3 or maps.dtype != torch.float32:
+        raise ValueError("heatmap_render: maps must be an fp32 [B, Hm, Wm] tensor")
+    B, Hm, Wm = maps.shape
+    if base is not None:
+        if (not isinstance(base, torch.Tensor) or base.dtype != torch.uint8 or base.dim() != 4 or base.shape[0] != B or base.shape[3] != 3
+                or base.device != maps.device):
+            raise ValueError(f"heatmap_render: the base must be a uint8 [{B}, H, W, 3] tensor on {maps.device}, got "
+                             + (f"{base.dtype} {tuple(base.shape)} on {base.device}" if isinstance(base, torch.Tensor) else type(base).__name__))
+        if size is None:
+            size = (base.shape[1], base.shape[2])
+        elif tuple(size) != (base.shape[1], base.shape[2]):
+            raise ValueError(f"heatmap_render: size {tuple(size)} differs from the base's {tuple(base.shape[1:3])}")
+        base = base.contiguous()
+    if size is None:
+        raise ValueError("heatmap_render: without a base the output size (H, W) is required")
+    H, W = (int(v) for v in size)
+    if H < 1 or W < 1:
+        raise ValueError(f"heatmap_render: size must be positive, got {tuple(size)}")
+    if colormap is None:
+        key = str(maps.device)
+        colormap = _COLORMAPS.get(key)
+        if colormap is None:
+            colormap = _COLORMAPS[key] = default_colormap().to(maps.device)
+    elif (not isinstance(colormap, torch.Tensor) or colormap.dtype != torch.uint8 or tuple(colormap.shape) != (256, 3)):
+        raise ValueError("heatmap_render: the colour table must be a uint8 [256, 3] tensor")
+    else:
+        colormap = colormap.to(maps.device).contiguous()
+    if not maps.is_cuda:
+        raise RuntimeError("heatmap_render: the maps are on the CPU; this implementation only runs on an MI355X (no CPU path)")
+    maps = maps.contiguous()
+    out = torch.empty((B, H, W, 3), device=maps.device, dtype=torch.uint8)
+    call("vqa_heatmap_render", ptr(maps), ptr(base), ptr(colormap), ptr(out), B, Hm, Wm, H, W, alpha)
+    return out
