@@ -1,6 +1,6 @@
-"""float64 references of the residual blocks' BatchNorm kernels (csrc/cnn_ops.hip: bn_reduce_partials / bn_finalize / bn_eval_coef /
-bn_apply / bn_apply_pool / bn_apply_acc / bn_bwd_reduce / bn_bwd_finalize / bn_bwd_apply / bn_bwd_apply_acc, and bn_acc_coef with
-the fixed-point accumulator helpers of csrc/common.h), their operand generators, their bounds, and a host encoder / decoder of the
+"""float64 references of the residual blocks' BatchNorm kernels (csrc/batchnorm.hip: bn_reduce_partials / bn_finalize / bn_eval_coef /
+bn_fwd in its plain, pool and accumulator forms / bn_bwd_reduce / bn_bwd_finalize / bn_bwd_apply with and without accumulators, and
+bn_acc_coef with the fixed-point accumulator helpers of csrc/common.h), their operand generators, their bounds, and a host encoder / decoder of the
 accumulator format.  Plain torch on the CPU, nothing of the package.  test_bn_ref_cpu.py validates all of it without a GPU
 (autograd, exact round trips, sign margins, mutants); test_gpu_batchnorm_fp64.py judges the kernels against it.
 
@@ -10,8 +10,8 @@ values (bf16 / fp32 tensors, fp32 coefficients) and compute in fp64.
 Bounds.  u = 2^-24 (one fp32 rounding of a result r costs at most u |r|), one bf16 store costs 2^-8 |ref| (the project's figure; the
 fp32 error e in front of it is carried as e (1 + 2^-8)).  Every bound is per element or per channel.
   forward (apply_bound):  n u M, M = |y scale| + |shift| [+ |res| | + |res rscale| + |rshift|] the sum of the magnitudes the
-    expression adds, n = 2 / 3 / 5 the roundings of  y*scale + shift  [+ res | + (res*rscale + rshift)]  counted in bn_apply_kernel;
-    plus |y| d_scale + d_shift (+ |res| d_rscale + d_rshift) where the kernel derived the coefficients itself (bn_apply_acc).
+    expression adds, n = 2 / 3 / 5 the roundings of  y*scale + shift  [+ res | + (res*rscale + rshift)]  counted in bn_fwd_kernel;
+    plus |y| d_scale + d_shift (+ |res| d_rscale + d_rshift) where the kernel derived the coefficients itself (vqa_bn_apply_acc).
   statistics (coef_ref): with s, q the fp64 sums of the fp32 partials (d_s, d_q = 2 T 2^-53 sum|partial| for a T-term fp64
     sum done twice, by the kernel and by torch; 0 for the integer accumulators),
       d_mean = d_s / count + 2^-52 |mean|

@@ -1,405 +1,13 @@
-// HBM-bound CNN-side kernels for gfx950: BatchNorm (train statistics, apply, backward), the stem's fused
-// BN+ReLU+MaxPool, squeeze-excitation and spatial attention.  Activations are NHWC with T = float | bf16,
+// HBM-bound CNN-side kernels for gfx950: the stem's fused BN+ReLU+MaxPool tail (it shares stem_route.h with stem_conv.hip),
+// squeeze-excitation, spatial attention and the NHWC <-> NCHW converters.  Activations are NHWC with T = float | bf16,
 // every per-channel statistic / coefficient is fp32, every global access is a 16-byte vector.
-//   BatchNorm2d        models/cnn_backbone.py:151,158,246,351 (nn.BatchNorm2d defaults)
+// (The residual blocks' BatchNorm -- statistics, apply, backward -- is csrc/batchnorm.hip.)
+//   BatchNorm2d        models/cnn_backbone.py:351 (the stem's; nn.BatchNorm2d defaults)
 //   ReLU + MaxPool     models/cnn_backbone.py:352-353
-//   residual add+ReLU  models/cnn_backbone.py:194-195
 //   SEAttention        models/attention_modules.py:109-136
 //   SpatialAttention   models/attention_modules.py:223-243
 #include "common.h"
 #include "stem_route.h"
-
-// ---------------------------------------------------------------------------------------------
-// BatchNorm statistics: reduce the igemm partial slab [tiles][2][C] -> mean / invstd / scale / shift
-// ---------------------------------------------------------------------------------------------
-__global__ void bn_reduce_partials_kernel(const float* __restrict__ part, double* __restrict__ acc, int tiles, int C) {
-  // grid (ceil(C/64), G); block 256 = 4 tile-lanes x 64 channels
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63), tl = threadIdx.x >> 6;
-  __shared__ double sh[2][4][64];
-  double s = 0.0, q = 0.0;
-  if (c < C) {
-    // 8 slab rows in flight per thread: the loop is latency-bound, not bandwidth-bound
-    const int step = gridDim.y * 4;
-    int t = blockIdx.y * 4 + tl;
-    for (; t + 7 * step < tiles; t += 8 * step) {
-      float a[8], b[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { a[u] = part[((size_t)(t + u * step) * 2) * C + c]; b[u] = part[((size_t)(t + u * step) * 2 + 1) * C + c]; }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { s += (double)a[u]; q += (double)b[u]; }
-    }
-    for (; t < tiles; t += step) {
-      s += (double)part[((size_t)t * 2) * C + c];
-      q += (double)part[((size_t)t * 2 + 1) * C + c];
-    }
-  }
-  sh[0][tl][threadIdx.x & 63] = s; sh[1][tl][threadIdx.x & 63] = q;
-  __syncthreads();
-  if (tl == 0 && c < C) {
-    for (int i = 1; i < 4; ++i) { s += sh[0][i][threadIdx.x]; q += sh[1][i][threadIdx.x]; }
-    acc[((size_t)blockIdx.y * 2) * C + c] = s;
-    acc[((size_t)blockIdx.y * 2 + 1) * C + c] = q;
-  }
-}
-
-// coef layout (fp32, 4*C): scale | shift | mean | invstd
-__global__ void bn_finalize_kernel(const double* __restrict__ acc, int G, int C, double count, const float* __restrict__ gamma,
-                                   const float* __restrict__ beta, float* running_mean, float* running_var, long long* nbt,
-                                   float momentum, float eps, float* __restrict__ coef) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  double s = 0.0, q = 0.0;
-  int g = 0;
-  for (; g + 8 <= G; g += 8) {
-    double a[8], b[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) { a[u] = acc[((size_t)(g + u) * 2) * C + c]; b[u] = acc[((size_t)(g + u) * 2 + 1) * C + c]; }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) { s += a[u]; q += b[u]; }
-  }
-  for (; g < G; ++g) { s += acc[((size_t)g * 2) * C + c]; q += acc[((size_t)g * 2 + 1) * C + c]; }
-  const double mean = s / count;
-  double var = q / count - mean * mean;
-  if (var < 0.0) var = 0.0;
-  const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-  const float sc = gamma[c] * invstd;
-  coef[c] = sc; coef[C + c] = beta[c] - (float)mean * sc; coef[2 * C + c] = (float)mean; coef[3 * C + c] = invstd;
-  if (running_mean) {
-    const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-    running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * (float)mean;
-    running_var[c] = (1.f - momentum) * running_var[c] + momentum * (float)unbiased;
-    if (c == 0 && nbt) *nbt += 1;
-  }
-}
-
-__global__ void bn_eval_coef_kernel(int C, const float* gamma, const float* beta, const float* rm, const float* rv, float eps, float* coef) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  const float invstd = 1.0f / sqrtf(rv[c] + eps);
-  const float sc = gamma[c] * invstd;
-  coef[c] = sc; coef[C + c] = beta[c] - rm[c] * sc; coef[2 * C + c] = rm[c]; coef[3 * C + c] = invstd;
-}
-
-// out = [relu]( y*scale+shift  [+ res*rscale+rshift | + res] ).  Each thread owns one 16-byte channel vector
-// (coefficients stay in registers) and walks rows; a block covers 256/cv consecutive rows = one contiguous span.
-// RES: 0 = none, 1 = + res (identity), 2 = + res*rscale+rshift (the 1x1 shortcut's BatchNorm)
-template <typename T, int RES>
-__global__ __launch_bounds__(256) void bn_apply_kernel(const T* __restrict__ y, const float* __restrict__ coef, const T* __restrict__ res,
-                                const float* __restrict__ rcoef, T* __restrict__ out, size_t rows, int C, int relu) {
-  constexpr int VEC = Vec16<T>::N;
-  const int cv = C / VEC, lanes_r = 256 / cv;
-  const int c0 = (threadIdx.x % cv) * VEC, myr = threadIdx.x / cv;
-  float sc[VEC], sh[VEC], rs[RES == 2 ? VEC : 1], rh[RES == 2 ? VEC : 1];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    sc[j] = coef[c0 + j]; sh[j] = coef[C + c0 + j];
-    if (RES == 2) { rs[j] = rcoef[c0 + j]; rh[j] = rcoef[C + c0 + j]; }
-  }
-#pragma unroll 2
-  for (size_t r = (size_t)blockIdx.x * lanes_r + myr; r < rows; r += (size_t)gridDim.x * lanes_r) {
-    const size_t off = r * C + c0;
-    Vec16<T> v = ldg16(y + off), rr, o;
-    if (RES) rr = ldg16(res + off);
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      float x = v.get(j) * sc[j] + sh[j];
-      if (RES == 1) x += rr.get(j);
-      if (RES == 2) x += rr.get(j) * rs[j] + rh[j];
-      o.set(j, (relu && x < 0.f) ? 0.f : x);   // NaN-propagating ReLU like torch
-    }
-    stg16(out + off, o);
-  }
-}
-
-// The same map for the LAST residual block of a stage, with the squeeze-excitation global average pool folded in
-// (models/cnn_backbone.py:194-197 -> models/attention_modules.py:109-112): a workgroup owns rows [chunk*rpc, (chunk+1)*rpc) of ONE
-// sample and also writes the column sums of the values it stores (bf16-rounded, exactly what a pooling pass would read back) to
-// part[b][chunk][C]; se_pool_fc_kernel folds the chunks in index order.  Saves the pooling pass's read of the stage output.
-template <typename T, int RES>
-__global__ __launch_bounds__(256) void bn_apply_pool_kernel(const T* __restrict__ y, const float* __restrict__ coef, const T* __restrict__ res,
-                                                            const float* __restrict__ rcoef, T* __restrict__ out, int HW, int C, int relu, int rpc,
-                                                            float* __restrict__ part) {
-  constexpr int VEC = Vec16<T>::N;
-  const int cv = C / VEC, lanes_r = 256 / cv;
-  const int c0 = (threadIdx.x % cv) * VEC, myr = threadIdx.x / cv;
-  float sc[VEC], sh[VEC], rs[RES == 2 ? VEC : 1], rh[RES == 2 ? VEC : 1], acc[VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    sc[j] = coef[c0 + j]; sh[j] = coef[C + c0 + j]; acc[j] = 0.f;
-    if (RES == 2) { rs[j] = rcoef[c0 + j]; rh[j] = rcoef[C + c0 + j]; }
-  }
-  const int b = blockIdx.y, r0 = blockIdx.x * rpc, r1 = min(HW, r0 + rpc);
-  const size_t base = (size_t)b * HW * C + c0;
-#pragma unroll 2
-  for (int r = r0 + myr; r < r1; r += lanes_r) {
-    const size_t off = base + (size_t)r * C;
-    Vec16<T> v = ldg16(y + off), rr, o;
-    if (RES) rr = ldg16(res + off);
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      float x = v.get(j) * sc[j] + sh[j];
-      if (RES == 1) x += rr.get(j);
-      if (RES == 2) x += rr.get(j) * rs[j] + rh[j];
-      o.set(j, (relu && x < 0.f) ? 0.f : x);
-      acc[j] += o.get(j);
-    }
-    stg16(out + off, o);
-  }
-  __shared__ float shs[256 * VEC];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) shs[threadIdx.x * VEC + j] = acc[j];
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += 256) {
-    const int v = c / VEC, j = c - v * VEC;
-    float t = 0.f;
-    for (int r = 0; r < lanes_r; ++r) t += shs[(r * cv + v) * VEC + j];
-    part[((size_t)b * gridDim.x + blockIdx.x) * C + c] = t;
-  }
-}
-
-// Train-mode BatchNorm whose batch statistics arrive as fixed-point accumulators (common.h acc_add_fixed; filled by the conv
-// kernel's epilogue): every thread finalizes the coefficients of ITS channels in the prologue (fp64, same formulas as
-// bn_finalize_kernel), the first workgroup also publishes coef[4][C] (scale | shift | mean | invstd: the backward reads it) and
-// updates running_mean / running_var / num_batches_tracked (nn.BatchNorm2d defaults).  No finalize launch in between.
-// (BnAcc / bn_acc_coef: common.h -- shared with the stage-1 patch kernels, which finalize the statistics of their INPUT's BatchNorm)
-// RES: 0 none, 1 + res, 2 + BatchNorm(res) with its own accumulators.  POOL: grid (chunks, B), SE pooling sums to part (see above).
-template <typename T, int RES, bool POOL>
-__global__ __launch_bounds__(256) void bn_apply_acc_kernel(const T* __restrict__ y, BnAcc f, const T* __restrict__ res, BnAcc fr,
-                                                           T* __restrict__ out, size_t rows, int HW, int C, int relu, int rpc, double inv_count,
-                                                           double unbias, float momentum, float eps, float* __restrict__ part) {
-  constexpr int VEC = Vec16<T>::N;
-  const int cv = C / VEC, lanes_r = 256 / cv;
-  const int c0 = (threadIdx.x % cv) * VEC, myr = threadIdx.x / cv;
-  const bool writer = blockIdx.x == 0 && blockIdx.y == 0;
-  extern __shared__ float cf[];                // [2 | 4][C]: scale, shift (, residual scale, shift)
-  for (int c = threadIdx.x; c < C; c += 256) {
-    bn_acc_coef(f, C, c, inv_count, unbias, momentum, eps, writer, cf[c], cf[C + c]);
-    if (RES == 2) bn_acc_coef(fr, C, c, inv_count, unbias, momentum, eps, writer, cf[2 * C + c], cf[3 * C + c]);
-  }
-  __syncthreads();
-  float sc[VEC], sh[VEC], rs[RES == 2 ? VEC : 1], rh[RES == 2 ? VEC : 1], acc[POOL ? VEC : 1];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    sc[j] = cf[c0 + j]; sh[j] = cf[C + c0 + j];
-    if (RES == 2) { rs[j] = cf[2 * C + c0 + j]; rh[j] = cf[3 * C + c0 + j]; }
-    if (POOL) acc[j] = 0.f;
-  }
-  size_t r, r1, rstep, base = c0;
-  if (POOL) { const int r0 = blockIdx.x * rpc; r = r0 + myr; r1 = min(HW, r0 + rpc); rstep = lanes_r; base += (size_t)blockIdx.y * HW * C; }
-  else { r = (size_t)blockIdx.x * lanes_r + myr; r1 = rows; rstep = (size_t)gridDim.x * lanes_r; }
-#pragma unroll 2
-  for (; r < r1; r += rstep) {
-    const size_t off = base + r * C;
-    Vec16<T> v = ldg16(y + off), rr, o;
-    if (RES) rr = ldg16(res + off);
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      float x = v.get(j) * sc[j] + sh[j];
-      if (RES == 1) x += rr.get(j);
-      if (RES == 2) x += rr.get(j) * rs[j] + rh[j];
-      o.set(j, (relu && x < 0.f) ? 0.f : x);
-      if (POOL) acc[j] += o.get(j);
-    }
-    stg16(out + off, o);
-  }
-  if constexpr (POOL) {
-    __shared__ float shs[256 * VEC];
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) shs[threadIdx.x * VEC + j] = acc[j];
-    __syncthreads();
-    for (int c = threadIdx.x; c < C; c += 256) {
-      const int v = c / VEC, j = c - v * VEC;
-      float t = 0.f;
-      for (int q = 0; q < lanes_r; ++q) t += shs[(q * cv + v) * VEC + j];
-      part[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * C + c] = t;
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// BatchNorm backward.  g = dout * (out > 0) (relu) or dout.  Partial sums per block -> slab [blocks][3][C]:
-//   0: sum g   1: sum g*xhat(y)   2: sum g*xhat(y2) (second BN sharing g: the 1x1 shortcut)
-// ---------------------------------------------------------------------------------------------
-template <typename T, bool SELF, bool DUAL>
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T* __restrict__ dout, const T* __restrict__ outact, const T* __restrict__ y,
-                                                            const float* __restrict__ coef, const T* __restrict__ y2,
-                                                            const float* __restrict__ coef2, float* __restrict__ slab, size_t rows, int C,
-                                                            unsigned long long* __restrict__ facc) {
-  constexpr int VEC = Vec16<T>::N;
-  const int cv = C / VEC;                 // vectors per row
-  const int lanes_r = 256 / cv;           // rows processed concurrently by the block (C <= 256*VEC)
-  const int myv = threadIdx.x % cv, myr = threadIdx.x / cv, c0 = myv * VEC;
-  float sg[VEC], sx[VEC], sx2[DUAL ? VEC : 1], mean[VEC], inv[VEC], ms[SELF ? VEC : 1], mh[SELF ? VEC : 1], mean2[DUAL ? VEC : 1], inv2[DUAL ? VEC : 1];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    sg[j] = sx[j] = 0.f; mean[j] = coef[2 * C + c0 + j]; inv[j] = coef[3 * C + c0 + j];
-    if (DUAL) { sx2[j] = 0.f; mean2[j] = coef2[2 * C + c0 + j]; inv2[j] = coef2[3 * C + c0 + j]; }
-    if (SELF) { ms[j] = coef[c0 + j]; mh[j] = coef[C + c0 + j]; }
-  }
-#pragma unroll 2
-  for (size_t r = (size_t)blockIdx.x * lanes_r + myr; r < rows; r += (size_t)gridDim.x * lanes_r) {
-    const size_t off = r * C + c0;
-    Vec16<T> d = ldg16(dout + off), yy = ldg16(y + off), o, y2v;
-    if (!SELF && outact) o = ldg16(outact + off);
-    if (DUAL) y2v = ldg16(y2 + off);
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      float g = d.get(j);
-      if (SELF) { if (!(yy.get(j) * ms[j] + mh[j] > 0.f)) g = 0.f; }       // relu(bn(y)) > 0 recomputed from y
-      else if (outact && !(o.get(j) > 0.f)) g = 0.f;
-      sg[j] += g;
-      sx[j] += g * (yy.get(j) - mean[j]) * inv[j];
-      if (DUAL) sx2[j] += g * (y2v.get(j) - mean2[j]) * inv2[j];
-    }
-  }
-  extern __shared__ float shm[];          // [3][256][VEC]
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    shm[(0 * 256 + threadIdx.x) * VEC + j] = sg[j];
-    shm[(1 * 256 + threadIdx.x) * VEC + j] = sx[j];
-    shm[(2 * 256 + threadIdx.x) * VEC + j] = DUAL ? sx2[j] : 0.f;
-  }
-  __syncthreads();
-  for (int o = threadIdx.x; o < 3 * C; o += 256) {
-    const int k = o / C, c = o - k * C, v = c / VEC, j = c - v * VEC;
-    float s = 0.f;
-    for (int r = 0; r < lanes_r; ++r) s += shm[(k * 256 + r * cv + v) * VEC + j];
-    if (facc) {                               // fixed point: order-free, no finalize launch; replica blockIdx.x % R
-      const int R = acc_replicas(C);
-      if (k < 2 || DUAL) acc_add_fixed(facc, (size_t)R * 3 * C, ((size_t)(blockIdx.x % R) * 3 + k) * C + c, s);
-    }
-    else slab[((size_t)blockIdx.x * 3 + k) * C + c] = s;
-  }
-}
-
-// reduce slab over blocks; emit dgamma/dbeta (+=) and the apply coefficients  dy = A*g + Bc*y + Cc
-// bcoef layout (3*C): A | Bc | Cc
-__global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* __restrict__ slab, int nblk, int C, int which, double count,
-                                       const float* __restrict__ gamma, const float* __restrict__ coef, int training,
-                                       float* dgamma, float* dbeta, float* __restrict__ bcoef) {
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63), tl = threadIdx.x >> 6;
-  __shared__ double sh[2][16][64];
-  double sg = 0.0, sx = 0.0;
-  if (c < C) {
-    int b = tl;
-    for (; b + 7 * 16 < nblk; b += 8 * 16) {               // 8 slab rows in flight per thread (latency-bound loop)
-      float a[8], x[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { a[u] = slab[((size_t)(b + 16 * u) * 3) * C + c]; x[u] = slab[((size_t)(b + 16 * u) * 3 + which) * C + c]; }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { sg += a[u]; sx += x[u]; }
-    }
-    for (; b < nblk; b += 16) { sg += slab[((size_t)b * 3) * C + c]; sx += slab[((size_t)b * 3 + which) * C + c]; }
-  }
-  sh[0][tl][threadIdx.x & 63] = sg; sh[1][tl][threadIdx.x & 63] = sx;
-  __syncthreads();
-  if (tl != 0 || c >= C) return;
-  for (int i = 1; i < 16; ++i) { sg += sh[0][i][threadIdx.x]; sx += sh[1][i][threadIdx.x]; }
-  if (dgamma) dgamma[c] += (float)sx;
-  if (dbeta) dbeta[c] += (float)sg;
-  const float mean = coef[2 * C + c], invstd = coef[3 * C + c], gi = gamma[c] * invstd;
-  if (training) {
-    const float mg = (float)(sg / count), mgx = (float)(sx / count);
-    bcoef[c] = gi; bcoef[C + c] = -gi * invstd * mgx; bcoef[2 * C + c] = gi * (mean * invstd * mgx - mg);
-  } else { bcoef[c] = gi; bcoef[C + c] = 0.f; bcoef[2 * C + c] = 0.f; }
-}
-
-// dy = A*g + B*y + C ; optional second output dy2 = A2*g + B2*y2 + C2 ; optional gout = g (T) for the identity path
-// SELF: the ReLU mask is relu(bn(y)) > 0 recomputed from y with mcoef (scale, shift); otherwise outact > 0 (or none).
-// DUAL: second BN (1x1 shortcut) sharing g.  Specialised so unused coefficient sets cost no registers.
-template <typename T, bool SELF, bool DUAL>
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T* __restrict__ dout, const T* __restrict__ outact, const T* __restrict__ y,
-                                    const float* __restrict__ bc, T* __restrict__ dy, const T* __restrict__ y2,
-                                    const float* __restrict__ bc2, T* __restrict__ dy2, size_t rows, int C,
-                                    const float* __restrict__ mcoef) {
-  constexpr int VEC = Vec16<T>::N;
-  const int cv = C / VEC, lanes_r = 256 / cv;
-  const int c0 = (threadIdx.x % cv) * VEC, myr = threadIdx.x / cv;
-  float a[VEC], b[VEC], c[VEC], a2[DUAL ? VEC : 1], b2[DUAL ? VEC : 1], c2[DUAL ? VEC : 1], ms[SELF ? VEC : 1], mh[SELF ? VEC : 1];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    a[j] = bc[c0 + j]; b[j] = bc[C + c0 + j]; c[j] = bc[2 * C + c0 + j];
-    if (DUAL) { a2[j] = bc2[c0 + j]; b2[j] = bc2[C + c0 + j]; c2[j] = bc2[2 * C + c0 + j]; }
-    if (SELF) { ms[j] = mcoef[c0 + j]; mh[j] = mcoef[C + c0 + j]; }
-  }
-#pragma unroll 2
-  for (size_t r = (size_t)blockIdx.x * lanes_r + myr; r < rows; r += (size_t)gridDim.x * lanes_r) {
-    const size_t off = r * C + c0;
-    Vec16<T> d = ldg16(dout + off), yy = ldg16(y + off), o, y2v, rr, r2;
-    if (!SELF && outact) o = ldg16(outact + off);
-    if (DUAL) y2v = ldg16(y2 + off);
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      float g = d.get(j);
-      if (SELF) { if (!(yy.get(j) * ms[j] + mh[j] > 0.f)) g = 0.f; }
-      else if (outact && !(o.get(j) > 0.f)) g = 0.f;
-      rr.set(j, a[j] * g + b[j] * yy.get(j) + c[j]);
-      if (DUAL) r2.set(j, a2[j] * g + b2[j] * y2v.get(j) + c2[j]);
-    }
-    stg16(dy + off, rr);
-    if (DUAL) stg16(dy2 + off, r2);
-  }
-}
-
-// The same map with the finalize folded into the prologue: the column sums arrive as a fixed-point accumulator facc[vqa_bn_acc_words(3, C)]
-// (R replicas x [3][C] in a hi and a lo plane, the flag word between the planes: common.h),
-// every thread derives A | B | C of its channels (formulas of bn_bwd_finalize_kernel, training mode), the first workgroup adds
-// d gamma / d beta (and the shortcut BatchNorm's, DUAL) into the gradient buffer.
-template <typename T, bool SELF, bool DUAL>
-__global__ __launch_bounds__(256) void bn_bwd_apply_acc_kernel(const T* __restrict__ dout, const T* __restrict__ outact, const T* __restrict__ y,
-                                    const unsigned long long* __restrict__ facc, const float* __restrict__ gamma, const float* __restrict__ coef,
-                                    float* dgamma, float* dbeta, T* __restrict__ dy, const T* __restrict__ y2, const float* __restrict__ gamma2,
-                                    const float* __restrict__ coef2, float* dgamma2, float* dbeta2, T* __restrict__ dy2, size_t rows, int C,
-                                    double inv_count) {
-  constexpr int VEC = Vec16<T>::N;
-  const int cv = C / VEC, lanes_r = 256 / cv;
-  const int c0 = (threadIdx.x % cv) * VEC, myr = threadIdx.x / cv;
-  const bool writer = blockIdx.x == 0;
-  const int R = acc_replicas(C);
-  const bool bad = acc_flagged(facc, R, 3, C);
-  extern __shared__ float cf[];                // [3 | 6][C]: A, B, C (, A2, B2, C2): one evaluation per channel and workgroup
-  for (int ch = threadIdx.x; ch < C; ch += 256) {
-    double sg = acc_read_fixed(facc, R, 3, C, 0, ch), sx = acc_read_fixed(facc, R, 3, C, 1, ch);
-    if (bad) sg = sx = __builtin_nan("");
-    const float mean = coef[2 * C + ch], invstd = coef[3 * C + ch], gi = gamma[ch] * invstd;
-    const float mg = (float)(sg * inv_count), mgx = (float)(sx * inv_count);
-    cf[ch] = gi; cf[C + ch] = -gi * invstd * mgx; cf[2 * C + ch] = gi * (mean * invstd * mgx - mg);
-    if (writer) { dgamma[ch] += (float)sx; dbeta[ch] += (float)sg; }
-    if (DUAL) {
-      double sx2 = acc_read_fixed(facc, R, 3, C, 2, ch);
-      if (bad) sx2 = __builtin_nan("");
-      const float mean2 = coef2[2 * C + ch], inv2 = coef2[3 * C + ch], gi2 = gamma2[ch] * inv2, mgx2 = (float)(sx2 * inv_count);
-      cf[3 * C + ch] = gi2; cf[4 * C + ch] = -gi2 * inv2 * mgx2; cf[5 * C + ch] = gi2 * (mean2 * inv2 * mgx2 - mg);
-      if (writer) { dgamma2[ch] += (float)sx2; dbeta2[ch] += (float)sg; }
-    }
-  }
-  __syncthreads();
-  float a[VEC], b[VEC], c[VEC], a2[DUAL ? VEC : 1], b2[DUAL ? VEC : 1], c2[DUAL ? VEC : 1], ms[SELF ? VEC : 1], mh[SELF ? VEC : 1];
-#pragma unroll
-  for (int j = 0; j < VEC; ++j) {
-    const int ch = c0 + j;
-    a[j] = cf[ch]; b[j] = cf[C + ch]; c[j] = cf[2 * C + ch];
-    if (DUAL) { a2[j] = cf[3 * C + ch]; b2[j] = cf[4 * C + ch]; c2[j] = cf[5 * C + ch]; }
-    if (SELF) { ms[j] = coef[ch]; mh[j] = coef[C + ch]; }
-  }
-#pragma unroll 2
-  for (size_t r = (size_t)blockIdx.x * lanes_r + myr; r < rows; r += (size_t)gridDim.x * lanes_r) {
-    const size_t off = r * C + c0;
-    Vec16<T> d = ldg16(dout + off), yy = ldg16(y + off), o, y2v, rr, r2;
-    if (!SELF && outact) o = ldg16(outact + off);
-    if (DUAL) y2v = ldg16(y2 + off);
-#pragma unroll
-    for (int j = 0; j < VEC; ++j) {
-      float g = d.get(j);
-      if (SELF) { if (!(yy.get(j) * ms[j] + mh[j] > 0.f)) g = 0.f; }
-      else if (outact && !(o.get(j) > 0.f)) g = 0.f;
-      rr.set(j, a[j] * g + b[j] * yy.get(j) + c[j]);
-      if (DUAL) r2.set(j, a2[j] * g + b2[j] * y2v.get(j) + c2[j]);
-    }
-    stg16(dy + off, rr);
-    if (DUAL) stg16(dy2 + off, r2);
-  }
-}
 
 // ---------------------------------------------------------------------------------------------
 // Stem tail: BN + ReLU + MaxPool3x3/2 p1 fused (the 112x112 activation is never written)
@@ -534,7 +142,7 @@ __global__ __launch_bounds__(256) void se_pool_fc_kernel(const T* __restrict__ x
   for (int c = threadIdx.x; c < C; c += 256) {
     const int v = c / VEC, j = c - v * VEC;
     float t = 0.f;
-    if (part) { for (int k = 0; k < chunks; ++k) t += part[((size_t)b * chunks + k) * C + c]; }    // column sums left by bn_apply_pool_kernel
+    if (part) { for (int k = 0; k < chunks; ++k) t += part[((size_t)b * chunks + k) * C + c]; }    // column sums left by vqa_bn_apply_pool / vqa_bn_apply_acc (batchnorm.hip)
     else { for (int r = 0; r < lanes_r; ++r) t += sh[(r * cv + v) * VEC + j]; }
     t /= (float)HW;
     pl[c] = t; pooled[(size_t)b * C + c] = t;
@@ -1156,160 +764,8 @@ __global__ void nchw_to_nhwc_kernel(const float* __restrict__ in, T* __restrict_
 static inline int px_grid(size_t npix, int C, int VEC) { const size_t lr = 256 / (C / VEC), g = (npix + lr - 1) / lr; return (int)(g > 16384 ? 16384 : (g ? g : 1)); }
 static inline unsigned long long magic40(unsigned d) { return ((1ull << 40) + d - 1) / d; }   // (x * m) >> 40 == x / d for x*d < 2^40
 static inline int ew_grid(size_t n) { size_t g = (n + 255) / 256; return (int)(g > 16384 ? 16384 : (g ? g : 1)); }
-static inline int row_grid(size_t rows, int lanes_r) { size_t g = (rows + lanes_r - 1) / lanes_r; return (int)(g > 8192 ? 8192 : (g ? g : 1)); }
 
 extern "C" {
-
-// part: igemm slab [tiles][2][C]; scratch: >= 64*2*C doubles; coef out: 4*C floats. running_* / nbt may be null.
-int vqa_bn_stats_finalize(const float* part, int tiles, int C, double count, const float* gamma, const float* beta,
-                          float* running_mean, float* running_var, long long* nbt, float momentum, float eps,
-                          double* scratch, float* coef, hipStream_t st) {
-  if (!part || !scratch || !coef || tiles <= 0 || C <= 0) return VQA_EARG;
-  int G = (tiles + 63) / 64; if (G > 64) G = 64; if (G < 1) G = 1;
-  hipLaunchKernelGGL(bn_reduce_partials_kernel, dim3((C + 63) / 64, G), dim3(256), 0, st, part, scratch, tiles, C);
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, st, scratch, G, C, count, gamma, beta,
-                     running_mean, running_var, nbt, momentum, eps, coef);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-int vqa_bn_eval_coef(int C, const float* gamma, const float* beta, const float* rm, const float* rv, float eps, float* coef, hipStream_t st) {
-  hipLaunchKernelGGL(bn_eval_coef_kernel, dim3((C + 255) / 256), dim3(256), 0, st, C, gamma, beta, rm, rv, eps, coef);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-int vqa_bn_apply(int dtype, const void* y, const float* coef, const void* res, const float* rcoef, void* out, long long numel, int C, int relu, hipStream_t st) {
-  const int VEC = dtype ? 8 : 4;
-  if (C % VEC || numel % C || C / VEC > 256 || 256 % (C / VEC)) return VQA_EARG;
-  const size_t rows = (size_t)numel / C;
-  const int grid = row_grid(rows, 256 / (C / VEC));
-#define BN_APPLY(TT, R) hipLaunchKernelGGL((bn_apply_kernel<TT, R>), dim3(grid), dim3(256), 0, st, (const TT*)y, coef, (const TT*)res, rcoef, (TT*)out, rows, C, relu)
-  const int mode = !res ? 0 : (rcoef ? 2 : 1);
-  if (dtype) { if (mode == 0) BN_APPLY(bf16_t, 0); else if (mode == 1) BN_APPLY(bf16_t, 1); else BN_APPLY(bf16_t, 2); }
-  else { if (mode == 0) BN_APPLY(float, 0); else if (mode == 1) BN_APPLY(float, 1); else BN_APPLY(float, 2); }
-#undef BN_APPLY
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-// rows of one sample a workgroup of vqa_bn_apply_pool owns (14 passes of the workgroup) and the resulting chunks per sample
-static inline int pool_rpc(int C, int VEC) { return (256 / (C / VEC)) * 14; }
-int vqa_bn_apply_pool_chunks(int dtype, int HW, int C) {
-  const int VEC = dtype ? 8 : 4;
-  if (C % VEC || C / VEC > 256 || 256 % (C / VEC) || HW <= 0) return 0;
-  return (HW + pool_rpc(C, VEC) - 1) / pool_rpc(C, VEC);
-}
-// bn_apply of a stage's last block + the SE pooling sums: part [B][vqa_bn_apply_pool_chunks][C] floats (vqa_se_fwd folds them)
-int vqa_bn_apply_pool(int dtype, const void* y, const float* coef, const void* res, const float* rcoef, void* out, int B, int HW, int C,
-                      int relu, float* part, hipStream_t st) {
-  const int VEC = dtype ? 8 : 4;
-  const int chunks = vqa_bn_apply_pool_chunks(dtype, HW, C);
-  if (!y || !coef || !out || !part || B <= 0 || chunks <= 0 || B > 65535) return VQA_EARG;
-  const int rpc = pool_rpc(C, VEC);
-#define BN_APPLYP(TT, R) hipLaunchKernelGGL((bn_apply_pool_kernel<TT, R>), dim3(chunks, B), dim3(256), 0, st, (const TT*)y, coef, (const TT*)res, rcoef, (TT*)out, HW, C, relu, rpc, part)
-  const int mode = !res ? 0 : (rcoef ? 2 : 1);
-  if (dtype) { if (mode == 0) BN_APPLYP(bf16_t, 0); else if (mode == 1) BN_APPLYP(bf16_t, 1); else BN_APPLYP(bf16_t, 2); }
-  else { if (mode == 0) BN_APPLYP(float, 0); else if (mode == 1) BN_APPLYP(float, 1); else BN_APPLYP(float, 2); }
-#undef BN_APPLYP
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-// Train-mode BatchNorm apply whose statistics are fixed-point accumulators acc[vqa_bn_acc_words(2, C)] (filled by the producing conv launched
-// with stats_mode = 1): finalize + running-statistics update + apply (+ residual | + BatchNorm(res) from racc, + ReLU) in ONE launch;
-// coef_out / rcoef_out [4][C] are published for the backward.  pool_part != NULL: the SE-pooling variant (vqa_bn_apply_pool).
-// 64-bit words of a fixed-point accumulator for K sums of C channels (replicas + flag, even): what the caller zeroes and passes
-int vqa_bn_acc_words(int K, int C) { const long long w = 2ll * acc_replicas(C) * K * C + 1; return (int)((w + 1) / 2 * 2); }   // hi plane | flag | lo plane (common.h)
-int vqa_bn_apply_acc(int dtype, const void* y, const unsigned long long* acc, const float* gamma, const float* beta, float* rm, float* rv,
-                     long long* nbt, float* coef_out, const void* res, const unsigned long long* racc, const float* rgamma, const float* rbeta,
-                     float* rrm, float* rrv, long long* rnbt, float* rcoef_out, void* out, int B, int HW, int C, int relu, double count,
-                     float momentum, float eps, float* pool_part, hipStream_t st) {
-  const int VEC = dtype ? 8 : 4;
-  if (!y || !acc || !gamma || !beta || !coef_out || !out || B <= 0 || HW <= 0 || C % VEC || C / VEC > 256 || 256 % (C / VEC)) return VQA_EARG;
-  if (racc && (!res || !rgamma || !rbeta || !rcoef_out)) return VQA_EARG;
-  if (pool_part && racc) return VQA_EARG;
-  BnAcc f = {acc, gamma, beta, rm, rv, nbt, coef_out}, fr = {racc, rgamma, rbeta, rrm, rrv, rnbt, rcoef_out};
-  const size_t rows = (size_t)B * HW;
-  const int lanes_r = 256 / (C / VEC);
-  int g1 = row_grid(rows, lanes_r);
-  // every workgroup finalizes all C channels in its prologue (R replicas x 2 planes x 2 sums of 8-byte loads + fp64 per channel): with 2048
-  // workgroups the prologues read more bytes than the stage-4 tensor holds.  tools/bn_grid_sweep.py, B = 512: 1024 (plain) / 512 (+ residual)
-  // workgroups are 3 .. 18 % faster than 2048 at every stage; 256 loses the latency cover again
-  { const int cap = vqa_env_int("VQA_BN_GRID", res ? 512 : 1024); if (g1 > cap) g1 = cap; }
-  dim3 grid(g1);
-  int rpc = 0;
-  const double inv_count = 1.0 / count, unbias = count > 1.0 ? count / (count - 1.0) : 1.0;
-  const size_t shm = (size_t)(racc ? 4 : 2) * C * sizeof(float);
-  if (pool_part) {
-    const int chunks = vqa_bn_apply_pool_chunks(dtype, HW, C);
-    if (chunks <= 0 || B > 65535) return VQA_EARG;
-    rpc = pool_rpc(C, VEC); grid = dim3(chunks, B);
-  }
-#define BN_ACC(TT, R, PL) hipLaunchKernelGGL((bn_apply_acc_kernel<TT, R, PL>), grid, dim3(256), shm, st, (const TT*)y, f, (const TT*)res, fr, (TT*)out, rows, HW, C, \
-    relu, rpc, inv_count, unbias, momentum, eps, pool_part)
-  const int mode = !res ? 0 : (racc ? 2 : 1);
-  if (dtype) {
-    if (pool_part) { if (mode == 0) BN_ACC(bf16_t, 0, true); else BN_ACC(bf16_t, 1, true); }
-    else { if (mode == 0) BN_ACC(bf16_t, 0, false); else if (mode == 1) BN_ACC(bf16_t, 1, false); else BN_ACC(bf16_t, 2, false); }
-  } else {
-    if (pool_part) { if (mode == 0) BN_ACC(float, 0, true); else BN_ACC(float, 1, true); }
-    else { if (mode == 0) BN_ACC(float, 0, false); else if (mode == 1) BN_ACC(float, 1, false); else BN_ACC(float, 2, false); }
-  }
-#undef BN_ACC
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-int vqa_bn_bwd_blocks(long long rows) { long long g = (rows + 63) / 64; const int cap = vqa_env_int("VQA_BNR_GRID", rows < 65536 ? 256 : 512); return (int)(g > cap ? cap : (g < 1 ? 1 : g)); }
-// slab: [vqa_bn_bwd_blocks(rows)][3][C] floats
-// acc_mode = 1: `slab` is a fixed-point accumulator unsigned long long [vqa_bn_acc_words(3, C)] (replicas x two planes + flag, common.h; zeroed by the
-// caller) instead of a float slab
-int vqa_bn_bwd_reduce(int dtype, const void* dout, const void* outact, const void* y, const float* coef, const void* y2, const float* coef2,
-                      float* slab, long long rows, int C, int self_mask, int acc_mode, hipStream_t st) {
-  const int VEC = dtype ? 8 : 4;
-  if (C % VEC || C / VEC > 256 || 256 % (C / VEC)) return VQA_EARG;
-  const int nb = vqa_bn_bwd_blocks(rows);
-  const size_t shm = (size_t)3 * 256 * VEC * 4;
-#define BWD_RED(TT, S, D) hipLaunchKernelGGL((bn_bwd_reduce_kernel<TT, S, D>), dim3(nb), dim3(256), shm, st, (const TT*)dout, (const TT*)outact, \
-    (const TT*)y, coef, (const TT*)y2, coef2, acc_mode ? nullptr : slab, (size_t)rows, C, acc_mode ? (unsigned long long*)slab : nullptr)
-  if (self_mask && (y2 || outact)) return VQA_EARG;
-  if (dtype) { if (self_mask) BWD_RED(bf16_t, true, false); else if (y2) BWD_RED(bf16_t, false, true); else BWD_RED(bf16_t, false, false); }
-  else { if (self_mask) BWD_RED(float, true, false); else if (y2) BWD_RED(float, false, true); else BWD_RED(float, false, false); }
-#undef BWD_RED
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-int vqa_bn_bwd_finalize(const float* slab, int nblk, int C, int which, double count, const float* gamma, const float* coef, int training,
-                        float* dgamma, float* dbeta, float* bcoef, hipStream_t st) {
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 63) / 64), dim3(1024), 0, st, slab, nblk, C, which, count, gamma, coef, training, dgamma, dbeta, bcoef);
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-// BatchNorm backward apply with the finalize folded in (training mode): facc[vqa_bn_acc_words(3, C)] fixed-point sums from vqa_bn_bwd_reduce /
-// vqa_se_bwd in accumulate mode; d gamma / d beta (+=) are written by the first workgroup.  y2 / gamma2 / coef2 / dgamma2 / dbeta2 / dy2:
-// the 1x1 shortcut's BatchNorm sharing g (all or none).  self_mask: ReLU mask recomputed from y (coef scale | shift), outact unused.
-int vqa_bn_bwd_apply_acc(int dtype, const void* dout, const void* outact, const void* y, const unsigned long long* facc, const float* gamma,
-                         const float* coef, float* dgamma, float* dbeta, void* dy, const void* y2, const float* gamma2, const float* coef2,
-                         float* dgamma2, float* dbeta2, void* dy2, long long numel, int C, double count, int self_mask, hipStream_t st) {
-  const int VEC = dtype ? 8 : 4;
-  if (!dout || !y || !facc || !gamma || !coef || !dgamma || !dbeta || !dy || C % VEC || numel % C || C / VEC > 256 || 256 % (C / VEC)) return VQA_EARG;
-  if (y2 && (!gamma2 || !coef2 || !dgamma2 || !dbeta2 || !dy2)) return VQA_EARG;
-  if (self_mask && (y2 || outact)) return VQA_EARG;
-  const size_t rows = (size_t)numel / C;
-  int grid = row_grid(rows, 256 / (C / VEC));
-  { const int cap = vqa_env_int("VQA_BNB_GRID", 512); if (grid > cap) grid = cap; }     // (prologue amortisation, as vqa_bn_apply_acc: -4 .. -20 % against 2048)
-  const size_t shm = (size_t)(y2 ? 6 : 3) * C * sizeof(float);
-  const double inv_count = 1.0 / count;
-#define BWD_ACC(TT, S, D) hipLaunchKernelGGL((bn_bwd_apply_acc_kernel<TT, S, D>), dim3(grid), dim3(256), shm, st, (const TT*)dout, (const TT*)outact, \
-    (const TT*)y, facc, gamma, coef, dgamma, dbeta, (TT*)dy, (const TT*)y2, gamma2, coef2, dgamma2, dbeta2, (TT*)dy2, rows, C, inv_count)
-  if (dtype) { if (self_mask) BWD_ACC(bf16_t, true, false); else if (y2) BWD_ACC(bf16_t, false, true); else BWD_ACC(bf16_t, false, false); }
-  else { if (self_mask) BWD_ACC(float, true, false); else if (y2) BWD_ACC(float, false, true); else BWD_ACC(float, false, false); }
-#undef BWD_ACC
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
-int vqa_bn_bwd_apply(int dtype, const void* dout, const void* outact, const void* y, const float* bc, void* dy,
-                     const void* y2, const float* bc2, void* dy2, long long numel, int C, const float* mask_coef, hipStream_t st) {
-  const int VEC = dtype ? 8 : 4;
-  if (C % VEC || numel % C || C / VEC > 256 || 256 % (C / VEC)) return VQA_EARG;
-  const size_t rows = (size_t)numel / C;
-  const int grid = row_grid(rows, 256 / (C / VEC));
-#define BWD_APPLY(TT, S, D) hipLaunchKernelGGL((bn_bwd_apply_kernel<TT, S, D>), dim3(grid), dim3(256), 0, st, (const TT*)dout, (const TT*)outact, \
-    (const TT*)y, bc, (TT*)dy, (const TT*)y2, bc2, (TT*)dy2, rows, C, mask_coef)
-  if (mask_coef && (y2 || outact)) return VQA_EARG;
-  if (dtype) { if (mask_coef) BWD_APPLY(bf16_t, true, false); else if (y2) BWD_APPLY(bf16_t, false, true); else BWD_APPLY(bf16_t, false, false); }
-  else { if (mask_coef) BWD_APPLY(float, true, false); else if (y2) BWD_APPLY(float, false, true); else BWD_APPLY(float, false, false); }
-#undef BWD_APPLY
-  VQA_LAUNCH_CHECK(); return VQA_OK;
-}
 
 int vqa_stem_pool_fwd(int dtype, const void* y, const float* coef, void* out, uint8_t* idx, int B, int H, int W, int C, hipStream_t st) {
   const int VEC = dtype ? 8 : 4, Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
@@ -1335,7 +791,7 @@ int vqa_stem_bwd_apply(int dtype, const void* dpool, const uint8_t* idx, const v
 int vqa_se_fwd(int dtype, const void* x, const float* w1, const float* w2, float* pooled, float* hidden, float* scale, void* out,
                int B, int HW, int C, int Cr, const float* pool_part, int pool_chunks, hipStream_t st) {
   const int VEC = dtype ? 8 : 4;
-  if (C % VEC || C / VEC > 256 || 256 % (C / VEC) || Cr < 1 || Cr > C) return VQA_EARG;
+  if (!bn_vec_ok(dtype, C) || Cr < 1 || Cr > C) return VQA_EARG;
   if (pool_part && pool_chunks != vqa_bn_apply_pool_chunks(dtype, HW, C)) return VQA_EARG;
   const size_t shm = ((size_t)256 * VEC + C + Cr) * 4;
   DT(hipLaunchKernelGGL(se_pool_fc_kernel<float>, dim3(B), dim3(256), shm, st, (const float*)x, w1, w2, pooled, hidden, scale, HW, C, Cr, pool_part, pool_chunks),
@@ -1349,7 +805,7 @@ int vqa_se_fwd(int dtype, const void* x, const float* w1, const float* w2, float
 // rows of the BatchNorm-backward slab vqa_se_bwd fills when bn_slab is given (= workgroups of its apply pass)
 int vqa_se_bwd_blocks(int dtype, int B, int HW, int C) {
   const int VEC = dtype ? 8 : 4;
-  if (C % VEC || C / VEC > 256 || 256 % (C / VEC)) return 0;
+  if (!bn_vec_ok(dtype, C)) return 0;
   const int g = px_grid((size_t)B * HW, C, VEC);
   return g > 2048 ? 2048 : g;          // slab rows vqa_bn_bwd_finalize folds (it is sized for <= ~1k rows: 16384 rows cost it +90 us)
 }
@@ -1368,7 +824,7 @@ int vqa_se_bwd(int dtype, const void* dout, const void* x, const float* w1, cons
   const int VEC = dtype ? 8 : 4;
   // Cr <= C (the model's bottleneck is C / se_reduction) bounds the dynamic LDS of the launches below that do not raise the limit:
   // shm <= shm2 <= (1024 * 8 + 4 * 2048) * 4 = 64 KB at bf16 C = 2048
-  if (C % VEC || C / VEC > 256 || 256 % (C / VEC) || Cr < 1 || Cr > C) return VQA_EARG;
+  if (!bn_vec_ok(dtype, C) || Cr < 1 || Cr > C) return VQA_EARG;
   if ((bn_slab != nullptr) != (bn_y != nullptr) || (bn_slab != nullptr) != (bn_coef != nullptr)) return VQA_EARG;
   if ((dw1 != nullptr) != (dw2 != nullptr)) return VQA_EARG;       // both NULL: data gradient only (frozen SE weights)
   float* dz2 = scratch; float* dh = dz2 + (size_t)B * C; float* dpool = dh + (size_t)B * Cr;
@@ -1427,7 +883,7 @@ int vqa_se_bwd(int dtype, const void* dout, const void* x, const float* w1, cons
 int vqa_spatial_fwd(int dtype, const void* x, const float* w, float* pooled2, int* amax, float* amap, void* out, int B, int H, int W, int C, hipStream_t st) {
   const int VEC = dtype ? 8 : 4;
   const size_t npix = (size_t)B * H * W;
-  if (C <= 0 || C % VEC || npix >= (1ull << 28) || C / VEC > 256 || 256 % (C / VEC)) return VQA_EARG;      // before any launch: a refused call writes nothing
+  if (!bn_vec_ok(dtype, C) || npix >= (1ull << 28)) return VQA_EARG;      // before any launch: a refused call writes nothing
   const int pg = (int)((npix + 3) / 4 > 8192 ? 8192 : (npix + 3) / 4);
   DT(hipLaunchKernelGGL(spatial_pool_kernel<float>, dim3(pg), dim3(256), 0, st, (const float*)x, pooled2, amax, npix, C),
      hipLaunchKernelGGL(spatial_pool_kernel<bf16_t>, dim3(pg), dim3(256), 0, st, (const bf16_t*)x, pooled2, amax, npix, C));
@@ -1443,7 +899,7 @@ int vqa_spatial_bwd(int dtype, const void* dout, const void* x, const float* w, 
                     float* scratch, void* dx, float* dw, int B, int H, int W, int C, hipStream_t st) {
   const int VEC = dtype ? 8 : 4;
   const size_t npix = (size_t)B * H * W;
-  if (C <= 0 || C % VEC || npix >= (1ull << 28) || C / VEC > 256 || 256 % (C / VEC)) return VQA_EARG;      // before any launch: a refused call writes nothing
+  if (!bn_vec_ok(dtype, C) || npix >= (1ull << 28)) return VQA_EARG;      // before any launch: a refused call writes nothing
   float* dpre = scratch; float* dpool2 = dpre + npix; float* wpart = dpool2 + 2 * npix;
   const int pg = (int)((npix + 3) / 4 > 8192 ? 8192 : (npix + 3) / 4);
   DT(hipLaunchKernelGGL(spatial_bwd_reduce_kernel<float>, dim3(pg), dim3(256), 0, st, (const float*)dout, (const float*)x, amap, dpre, npix, C),

@@ -219,6 +219,12 @@ static_assert(sizeof(vqa_group_hyper) == 128 && alignof(vqa_group_hyper) == 16 &
 // an entry's `int dtype` argument picks the launch: 0 = the fp32 instantiation (call_f), 1 = the bf16 one (call_b)
 #define DT(call_f, call_b) do { if (dtype) { call_b; } else { call_f; } } while (0)
 
+// The shape every kernel that gives a thread one 16-byte channel vector and a 256-thread workgroup whole rows asks for (BatchNorm, SE,
+// spatial attention): C a positive multiple of the vector (8 bf16 | 4 fp32), at most 256 vectors, a count that divides 256.
+static inline bool bn_vec_ok(int dtype, int C) { const int VEC = dtype ? 8 : 4; return C > 0 && !(C % VEC || C / VEC > 256 || 256 % (C / VEC)); }
+// chunks per sample of the pooling BatchNorm forward (batchnorm.hip); vqa_se_fwd (cnn_ops.hip) checks its pool_chunks against it
+extern "C" int vqa_bn_apply_pool_chunks(int dtype, int HW, int C);
+
 // dst0[c] (c < n0) / dst1[c - n0] += sum over rows r < nrows of part[r * stride + c], rows in index order (fold_rows_kernel).  Defined in
 // token_ops.hip, where the kernel lives: other translation units launch it through this, so its device code exists once.
 void vqa_launch_fold(const float* part, int nrows, size_t stride, int ncols, float* dst0, int n0, float* dst1, hipStream_t st);

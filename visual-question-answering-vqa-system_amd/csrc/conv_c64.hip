@@ -42,7 +42,7 @@ struct C64Params {
 // Round 4: training-mode "Conv3x3 + BN + ReLU" (models/cnn_backbone.py:182-187) without the normalised tensor.  The 8-wave patch
 // kernels already hold their input patch in LDS for nine taps; when the input is relu(bn1(y1)) they take y1 and apply
 // scale / shift / ReLU to the patch IN LDS, once per block, right after it has landed -- a1 is never written or read (stage 1 at
-// B = 512: 205 MB each way per residual block, a whole bn_apply pass).  Same arithmetic as bn_apply_acc_kernel (fp32 fma of the
+// B = 512: 205 MB each way per residual block, a whole bn_apply pass).  Same arithmetic as bn_fwd_kernel's accumulator form (batchnorm.hip) (fp32 fma of the
 // bf16 value, NaN-propagating ReLU, one rounding to bf16), so conv(patch) is bit-identical to conv(bn_apply(y1)).
 // Padding stays ZERO, not relu(shift): halo columns are never touched (zeroed once, DMA never writes them), rows outside the image
 // are skipped (the DMA wrote zeros there).  A thread keeps ONE channel chunk (8 channels: 16 coefficient registers, re-read from LDS
@@ -89,7 +89,7 @@ __device__ __forceinline__ void patch_bn_relu(char* patch, int W, int PWc, int i
   }
 }
 // scale | shift of the input's BatchNorm into LDS cf[2][64] (call with >= 64 threads, then a barrier).  mode 2: finalized here from
-// the fixed-point statistics (workgroup 0 publishes coef[4][64] and updates the running statistics, like bn_apply_acc_kernel)
+// the fixed-point statistics (workgroup 0 publishes coef[4][64] and updates the running statistics, like bn_fwd_kernel<.., ACC>)
 __device__ __forceinline__ void pre_bn_coef(int mode, const float* pre_coef, const BnAcc& pre, double inv_count, double unbias, float momentum,
                                             float eps, float* cf, int tid) {
   if (tid < 64) {
