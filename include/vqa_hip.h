@@ -567,6 +567,33 @@ int vqa_adamw_groups_ema_dev(float* p, const float* g, float* m, float* v, const
                              int nf, void* p_bf16, float* ema, const int* group_of_range, const vqa_group_hyper* groups,
                              hipStream_t stream);
 
+/* ---- the non-finite guard (HipTrainer(nonfinite="skip" | "raise")): a step whose gradient is not finite never happened ----------
+   vqa_sumsq_guard / vqa_sumsq_ranges_guard: vqa_sumsq / vqa_sumsq_ranges -- the same partial kernels, grids and fold order, so out[]
+   holds the same bits -- whose ONE folding block also judges the step and writes the EFFECTIVE skip word, the word every vqa_adamw*
+   entry takes as `skip` (and the lag update behind the range entries honours):
+     bad_step (device int, may be NULL): rows of this step with an out-of-range target.  != 0: word[0] = bad_step[0], bad[0] += it,
+       bad[1] += 1 (device int[2], may be NULL; the caller's to reset); the step stays a bad-target step and `nonfinite` rests;
+     else out[0] NaN or +-inf (a NaN or inf element, or finite elements whose squares overflow the sum, as torch's norm would be inf):
+       word[0] = 1, nonfinite[0] += 1 (the caller's to reset), nonfinite[1] += 1 (never reset);
+     else word[0] = 0 and no counter is written.
+   The AdamW launch behind it is given `word` as skip and a counter array of its own as skipped (skipped[2] = launches that did not
+   count as a step, for whichever reason: Adam's step number stays calls - skipped[2]).  No launch is added to a step.
+   vqa_buffers_save / vqa_buffers_restore: the BatchNorm running buffers, which the forward overwrites before the verdict exists.
+   table: `rows` (1 ... 65535) int64 rows {device address (4-byte aligned), size in 32-bit words, word offset into scratch}; save copies
+   every buffer into scratch (ahead of the forward), restore copies them back when word[0] != 0 and does nothing otherwise (behind
+   the guarded norm).  Stable addresses: both can be captured.  The table is trusted as written.
+   vqa_nonfinite_scan: counts[j] += non-finite elements of g[lo_j, hi_j) for the P (1 ... 2^20) int64 rows {lo, hi} of table (integer
+   atomics: exact in any order; what lies between the rows -- the layout's alignment padding -- is not read).  The caller zeroes counts.
+   Status 1000 without a launch: a NULL g / out / word / nonfinite / table / scratch / counts, n < 0, rows or P out of range, and what
+   vqa_sumsq_ranges refuses. */
+int vqa_sumsq_guard(const float* g, long long n, float* out /* as vqa_sumsq */, const int* bad_step, int* word, int* bad, int* nonfinite,
+                    hipStream_t stream);
+int vqa_sumsq_ranges_guard(const float* g, const long long* table, int R, long long n, float* out, const int* bad_step, int* word,
+                           int* bad, int* nonfinite, hipStream_t stream);
+int vqa_buffers_save(const long long* table, int rows, void* scratch, hipStream_t stream);
+int vqa_buffers_restore(const long long* table, int rows, void* scratch, const int* word, hipStream_t stream);
+int vqa_nonfinite_scan(const float* g, const long long* table, int P, int* counts, hipStream_t stream);
+
 /* Row gather for cached image features (VQAModel.encode_features, ImageFeatures.select): dst[i] = src[index[i]] for i < n, rows of
    row_bytes bytes of any element type.  src holds n_src rows; index is device int32 [n] with every entry in [0, n_src) -- the caller
    checks the range; an entry outside it leaves its destination row unwritten and reads nothing.  16-byte vector loads and stores, one

@@ -152,6 +152,11 @@ SIGNATURES = {
     "vqa_adamw_groups_ema": [P, P, P, P, P, I, LL, F, F, F, F, F, LL, P, F, F, P, P, P, P, I, P, P, F, I, P, P, P],
     "vqa_adamw_groups_dev": [P, P, P, P, P, I, LL, P, P, P, P, P, P, I, P, P, P, P],
     "vqa_adamw_groups_ema_dev": [P, P, P, P, P, I, LL, P, P, P, P, P, P, I, P, P, P, P, P],
+    "vqa_sumsq_guard": [P, LL, P, P, P, P, P, P],
+    "vqa_sumsq_ranges_guard": [P, P, I, LL, P, P, P, P, P, P],
+    "vqa_buffers_save": [P, I, P, P],
+    "vqa_buffers_restore": [P, I, P, P, P],
+    "vqa_nonfinite_scan": [P, P, I, P, P],
     "vqa_class_seed": [I, P, LL, P, P, P, I, I, P],
     "vqa_gradcam": [I, P, P, P, I, I, I, I, P],
     "vqa_attention_map": [P, P, P, I, I, I, I, I, I, P],

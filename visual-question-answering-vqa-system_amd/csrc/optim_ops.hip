@@ -29,10 +29,32 @@ __global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g,
   if (blockIdx.x == 0) for (size_t i = nv * 4 + threadIdx.x; i < n; i += blockDim.x) s += g[i] * g[i];
   block_sum_store(s, out + 1 + blockIdx.x);
 }
-__global__ __launch_bounds__(256) void sumsq_final_kernel(float* out, int nparts) {
+// GUARD (HipTrainer(nonfinite=...)): the block that folds the partials also judges the step, in the same launch.  The gradient is
+// non-finite when its sum of squares is NaN or inf (exponent bits all ones: a NaN or inf element, or finite elements whose squares
+// overflow -- torch's norm is inf there too).  word[0] becomes the EFFECTIVE skip word the AdamW kernels and adamw_lag_kernel read:
+// the rows with an out-of-range target when there are any (such a step stays a bad-target step: bad[0] += rows, bad[1] += 1, the
+// non-finite counters rest), else 1 for a non-finite gradient (nonfinite[0] += 1 -- the caller's to reset --, nonfinite[1] += 1,
+// never reset), else 0 (no counter is written).  One thread, plain stores; the fold is the unguarded kernel's, statement for statement.
+__device__ __forceinline__ bool nonfinite_f32(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+struct SumsqGuard { const int* bad_step; int* word; int* bad; int* nonfinite; };
+template <bool GUARD>
+__global__ __launch_bounds__(256) void sumsq_final_kernel(float* out, int nparts, SumsqGuard gd) {
   float s = 0.f;
   for (int i = threadIdx.x; i < nparts; i += 256) s += out[1 + i];
   block_sum_store(s, out);
+  if constexpr (GUARD) {
+    if (threadIdx.x == 0) {                     // (the thread that stored out[0] reads it back)
+      const int rows = gd.bad_step ? *gd.bad_step : 0;
+      int w = rows;
+      if (rows != 0) {
+        if (gd.bad) { gd.bad[0] += rows; gd.bad[1] += 1; }
+      } else if (nonfinite_f32(out[0])) {
+        w = 1;
+        gd.nonfinite[0] += 1; gd.nonfinite[1] += 1;
+      }
+      *gd.word = w;
+    }
+  }
 }
 
 // A table of TRAINABLE ranges (fine-tuning with frozen parameters, trainer.py): elements outside every range are never read or
@@ -243,6 +265,33 @@ __global__ void adamw_lag_kernel(int* __restrict__ lag, const int* __restrict__ 
   for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < nf; k += gridDim.x * blockDim.x) lag[frozen[k]] += 1;
 }
 
+// The BatchNorm running buffers of a guarded step: by the time the gradient is judged the forward has overwritten them, so they are
+// copied into one flat scratch ahead of the forward (save) and copied back behind the guarded norm when the effective skip word is
+// set (restore; word == nullptr: save).  table: int64 rows {device address, 32-bit words, word offset into the scratch}, one workgroup
+// per row; the buffers are fp32 or int64, so every size is whole words and every address 4-byte aligned.
+__global__ __launch_bounds__(256) void buffers_copy_kernel(const long long* __restrict__ table, uint32_t* __restrict__ scratch,
+                                                           const int* __restrict__ word) {
+  if (word && *word == 0) return;
+  const long long* row = table + 3 * (size_t)blockIdx.x;
+  uint32_t* buf = reinterpret_cast<uint32_t*>((uintptr_t)row[0]);
+  const long long nw = row[1];
+  uint32_t* sc = scratch + row[2];
+  if (word) { for (long long i = threadIdx.x; i < nw; i += 256) buf[i] = sc[i]; }
+  else      { for (long long i = threadIdx.x; i < nw; i += 256) sc[i] = buf[i]; }
+}
+// Non-finite elements of the flat gradient per parameter: table = int64 rows {lo, hi} of P parameters (the padding behind hi belongs
+// to no row), counts[P] += (integer atomics: exact whatever the order).  grid (P, NONFINITE_SCAN_SLICES).
+constexpr int NONFINITE_SCAN_SLICES = 16;
+__global__ __launch_bounds__(256) void nonfinite_scan_kernel(const float* __restrict__ g, const long long* __restrict__ table,
+                                                             int* __restrict__ counts) {
+  const long long lo = table[2 * (size_t)blockIdx.x], hi = table[2 * (size_t)blockIdx.x + 1];
+  int c = 0;
+  for (long long i = lo + (long long)blockIdx.y * 256 + threadIdx.x; i < hi; i += (long long)gridDim.y * 256) c += nonfinite_f32(g[i]) ? 1 : 0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(counts + blockIdx.x, c);
+}
+
 // One thread writes the step-state block (plain stores): launched eagerly on the stream right before a captured step is replayed; the
 // values travel as kernel arguments, which the runtime copies at launch.
 __global__ void step_state_set_kernel(vqa_step_state* state, long long calls, unsigned long long seed_step, float lr, float b1, float b2,
@@ -315,14 +364,45 @@ extern "C" {
 int vqa_sumsq(const float* g, long long n, float* out, hipStream_t st) {
   const unsigned blocks = blocks_of((size_t)n / 4, 2048);
   hipLaunchKernelGGL(sumsq_kernel, dim3(blocks), dim3(256), 0, st, g, (size_t)n, out);
-  hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, st, out, (int)blocks);
+  hipLaunchKernelGGL(sumsq_final_kernel<false>, dim3(1), dim3(256), 0, st, out, (int)blocks, SumsqGuard{});
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
 int vqa_sumsq_ranges(const float* g, const long long* table, int R, long long n, float* out, hipStream_t st) {
   if (!ranges_args_ok(R, n, 0, nullptr, nullptr)) return VQA_EARG;
   const unsigned blocks = blocks_of((size_t)n / 4, 2048);
   hipLaunchKernelGGL(sumsq_ranges_kernel, dim3(blocks), dim3(256), 0, st, g, table, R, n, out);
-  hipLaunchKernelGGL(sumsq_final_kernel, dim3(1), dim3(256), 0, st, out, (int)blocks);
+  hipLaunchKernelGGL(sumsq_final_kernel<false>, dim3(1), dim3(256), 0, st, out, (int)blocks, SumsqGuard{});
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+// The two norms with the non-finite guard in their fold block (same partial kernels, same grids, same fold: out[] has the same bits).
+int vqa_sumsq_guard(const float* g, long long n, float* out, const int* bad_step, int* word, int* bad, int* nonfinite, hipStream_t st) {
+  if (!g || !out || n < 0 || !word || !nonfinite) return VQA_EARG;
+  const unsigned blocks = blocks_of((size_t)n / 4, 2048);
+  hipLaunchKernelGGL(sumsq_kernel, dim3(blocks), dim3(256), 0, st, g, (size_t)n, out);
+  hipLaunchKernelGGL(sumsq_final_kernel<true>, dim3(1), dim3(256), 0, st, out, (int)blocks, SumsqGuard{bad_step, word, bad, nonfinite});
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+int vqa_sumsq_ranges_guard(const float* g, const long long* table, int R, long long n, float* out, const int* bad_step, int* word, int* bad,
+                           int* nonfinite, hipStream_t st) {
+  if (!g || !out || !table || !word || !nonfinite || !ranges_args_ok(R, n, 0, nullptr, nullptr)) return VQA_EARG;
+  const unsigned blocks = blocks_of((size_t)n / 4, 2048);
+  hipLaunchKernelGGL(sumsq_ranges_kernel, dim3(blocks), dim3(256), 0, st, g, table, R, n, out);
+  hipLaunchKernelGGL(sumsq_final_kernel<true>, dim3(1), dim3(256), 0, st, out, (int)blocks, SumsqGuard{bad_step, word, bad, nonfinite});
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+int vqa_buffers_save(const long long* table, int rows, void* scratch, hipStream_t st) {
+  if (!table || !scratch || rows < 1 || rows > 65535) return VQA_EARG;
+  hipLaunchKernelGGL(buffers_copy_kernel, dim3((unsigned)rows), dim3(256), 0, st, table, (uint32_t*)scratch, (const int*)nullptr);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+int vqa_buffers_restore(const long long* table, int rows, void* scratch, const int* word, hipStream_t st) {
+  if (!table || !scratch || !word || rows < 1 || rows > 65535) return VQA_EARG;
+  hipLaunchKernelGGL(buffers_copy_kernel, dim3((unsigned)rows), dim3(256), 0, st, table, (uint32_t*)scratch, word);
+  VQA_LAUNCH_CHECK(); return VQA_OK;
+}
+int vqa_nonfinite_scan(const float* g, const long long* table, int P, int* counts, hipStream_t st) {
+  if (!g || !table || !counts || P < 1 || P > (1 << 20)) return VQA_EARG;
+  hipLaunchKernelGGL(nonfinite_scan_kernel, dim3((unsigned)P, NONFINITE_SCAN_SLICES), dim3(256), 0, st, g, table, counts);
   VQA_LAUNCH_CHECK(); return VQA_OK;
 }
 

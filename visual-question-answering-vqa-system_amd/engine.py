@@ -102,6 +102,7 @@ class HipEngine:
         self._seed_src = None
         self.cnn_train_forwards = 0               # forwards that ran the CNN in train mode (BatchNorm running statistics moved): cached
                                                   # image features are stale after one (VQAModel._feat_stamp)
+        self._running = None                      # running_buffers(): the BatchNorm buffers' table and scratch of a guarded train step
         self.wsrc = flat
         self._wsrc_fresh = False                  # one-shot: the bf16 copy wsrc was written by the last fused AdamW launch (trainer.py)
         self._wt: Dict[str, torch.Tensor] = {}
@@ -329,6 +330,26 @@ class HipEngine:
             self.step_id += 1
         if runs_cnn and modes[0]:
             self.cnn_train_forwards += 1
+
+    def running_buffers(self):
+        """(table, rows, scratch) for vqa_buffers_save / vqa_buffers_restore: every BatchNorm running_mean / running_var (fp32) and
+        num_batches_tracked (int64) of this engine, as int64 rows {address, 32-bit words, word offset into scratch} on the device, and
+        the flat scratch a guarded train step saves them to.  Built once per engine: the buffers' addresses are as stable as the
+        BatchNorm kernels need them to be."""
+        if self._running is None:
+            rows, off = [], 0
+            for name, t in self.buf.items():
+                if name.endswith((".running_mean", ".running_var", ".num_batches_tracked")):
+                    if t.dtype not in (torch.float32, torch.int64) or not t.is_contiguous() or t.data_ptr() % 4:
+                        raise RuntimeError(f"HipEngine.running_buffers: {name} must be a contiguous fp32 or int64 buffer")
+                    words = t.numel() * t.element_size() // 4
+                    rows.append([t.data_ptr(), words, off])
+                    off += (words + 3) // 4 * 4
+            if not rows:
+                raise RuntimeError("HipEngine.running_buffers: the model has no BatchNorm buffers")
+            dev = self.flat.device
+            self._running = (torch.tensor(rows, dtype=torch.int64).to(dev), len(rows), torch.zeros(off, device=dev, dtype=torch.int32))
+        return self._running
 
     def operands_settled(self) -> bool:
         """True when the next begin_step packs the planned backward operands into the buffer it already has: a step may be captured.

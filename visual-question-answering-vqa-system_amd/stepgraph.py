@@ -82,12 +82,16 @@ STATE_BYTES = 64
 SEED_STEP_OFFSET = 8
 
 
-def table_id(generation, groups=None):
+def table_id(generation, groups=None, guard=False):
     """step_key's table_id: the generation of the optimizer's range table (None: the plain kernels), and with parameter groups their
     STRUCTURE beside it (finetune.ParamGroups.key(): the group of every parameter) -- a grouped step issues other launches, and the
     per-range group array is rebuilt with the table.  The groups' VALUES (lr_scale, weight_decay) live in a device block and never
-    enter: changing them captures nothing anew."""
-    return generation if groups is None else (generation, tuple(groups))
+    enter: changing them captures nothing anew.
+    guard: the trainer runs the non-finite guard (HipTrainer(nonfinite=...)): the step then takes its norm from other entries, hands
+    AdamW another skip word and saves / restores the BatchNorm buffers around a train-mode CNN -- the flag enters step_key here,
+    with the rest of what decides the optimizer tail's launches, as ("guard", the id without it)."""
+    tid = generation if groups is None else (generation, tuple(groups))
+    return ("guard", tid) if guard else tid
 
 
 def _sig(t):

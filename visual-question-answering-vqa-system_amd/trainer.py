@@ -9,8 +9,10 @@ or "gloo" in the CPU rehearsal tests) and divided by world size inside the optim
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes
+import struct
 from typing import List, Optional
 
 import torch
@@ -169,10 +171,18 @@ def _is_features(images) -> bool:
     return hasattr(images, "_stamp") and hasattr(images, "_handle") and hasattr(images, "tensor") and hasattr(images, "select")
 
 
+# HipTrainer.nonfinite_report(): the call number (trainer.calls) of the skipped step, its loss, (name, non-finite elements, numel) of
+# every trainable parameter whose gradient holds a NaN or inf in layout order, and the int64 indices of the batch rows whose
+# per-row loss term is not finite
+NonFiniteReport = collections.namedtuple("NonFiniteReport", "step loss parameters rows")
+
+
 class HipTrainer:
+    _guard = None                                  # the non-finite guard's device words (set by the constructor when nonfinite is given)
+
     def __init__(self, model, lr=1e-4, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
                  process_group=None, overlap=True, force_reducer=False, label_smoothing=0.0, class_weight=None, ignore_index=None,
-                 ema_decay=None, ema_warmup=False, loss="ce", param_groups=None):
+                 ema_decay=None, ema_warmup=False, loss="ce", param_groups=None, nonfinite=None):
         """loss: "ce" (default: softmax cross-entropy, exactly the step without this option) or "bce" (sigmoid + binary cross-entropy on
         SoftTargets, see step()); readable afterwards as `loss_kind` (`loss` is the device scalar).
         ema_decay (None, or a float in [0, 1]): keep an exponential moving average of the weights, self.ema (a flat fp32 buffer laid out
@@ -196,9 +206,26 @@ class HipTrainer:
         prefix that matches nothing; ValueError for a parameter in two groups, a parameter of another model, an empty group, more than
         16 groups, a value that is negative or not finite, or groups that need more than 512 ranges -- all before anything is
         allocated.  None (default): exactly the step without this feature, launch for launch.  Data parallel: the same groups on
-        every rank give the same update; nothing is communicated and the reducer's trainable set does not change."""
+        every rank give the same update; nothing is communicated and the reducer's trainable set does not change.
+        nonfinite (None, "skip" or "raise"): the non-finite guard.  A step whose global gradient sum of squares -- the sum grad_norm()
+        reports: over the trainable ranges, after the data-parallel reduction -- is NaN or +-inf is skipped ON THE DEVICE, with no host
+        sync, in step() and in step_graphed() alike, and is treated as a step that never happened: parameters, both moments, the bf16
+        operand copy, the average, the per-parameter lags and Adam's step number keep their bits, and so does every BatchNorm
+        running_mean / running_var / num_batches_tracked (saved ahead of a train-mode CNN forward, restored behind the norm; the
+        features route and an eval-mode CNN need neither).  The step still returns its NaN loss and logits; `calls` and the dropout
+        stream advance as for any call; `metrics` count its rows as they come.  The verdict rests on the gradient alone: a zero-weight
+        batch (NaN loss, zero gradient) keeps running AdamW as documented in step().  A step with an out-of-range target stays a
+        bad-target step (check() raises IndexError for it, it is not counted as non-finite), but under the guard it restores the
+        BatchNorm buffers too.  "raise": the same skipping, and check() raises FloatingPointError naming the steps skipped since the
+        last check (the model is intact).  skipped_nonfinite() reads the counters, nonfinite_report() names the parameters and batch
+        rows of the step just skipped; `t` counts both kinds of skip.  The fold block of the norm launch takes the decision
+        (vqa_sumsq_guard / vqa_sumsq_ranges_guard): a clean step has no launch more than the unguarded one, bar the two over the
+        BatchNorm buffers (40 KB).  Data parallel: every rank folds the same reduced gradient and decides the same; nothing is
+        communicated.  ValueError for any other value, before anything is allocated.  None (default): exactly the step without
+        this feature, launch for launch."""
         self.model = model
         # validated on the host before anything is allocated or launched
+        self.nonfinite = TS.check_nonfinite(nonfinite)
         if not (isinstance(loss, str) and loss in ("ce", "bce")):
             raise ValueError(f'HipTrainer: loss must be "ce" or "bce", got {loss!r}')
         if loss == "bce" and not (label_smoothing == 0.0 and class_weight is None and ignore_index is None):
@@ -239,6 +266,16 @@ class HipTrainer:
         self._bad = torch.zeros(3, device=flat.device, dtype=torch.int32)
         self.bad_targets = self._bad[:2]
         self._empty = torch.zeros(1, device=flat.device, dtype=torch.int32)   # steps whose batch had zero total weight since check()
+        # the non-finite guard: _guard = {effective skip word of the step, non-finite skips since skipped_nonfinite(), ... ever},
+        # written by the norm's fold block, which also keeps bad_targets; the AdamW launch reads the word and counts the launches
+        # that were no step -- for either reason -- in an array of its own, so that a non-finite skip never lands in bad_targets
+        if self.nonfinite is not None:
+            self._guard = torch.zeros(3, device=flat.device, dtype=torch.int32)
+            self._adam_skipped = torch.zeros(3, device=flat.device, dtype=torch.int32)
+        self._nf_checked = 0                       # non-finite skips (ever) that check() / nonfinite_report() have seen
+        self._nf_reported = 0
+        self._last_ws = None                       # the last step's per-row loss terms (kept under the guard, for nonfinite_report)
+        self._scan = None                          # nonfinite_report's table of parameter ranges and its counters
         self.calls = 0
         self._copy_sig = None                      # parameter-version signature right after the last fused AdamW launch
         self.buckets = LY.bucket_ranges(model._entries)
@@ -456,6 +493,11 @@ class HipTrainer:
         elif self._copy_sig is not None and eng.adamw_copy_target() is not None and self._copy_sig == self._param_sig():
             eng._wsrc_fresh = True                 # (one-shot, consumed by the begin_step of the forward below)
         eng._seed_src = None if state is None else state.data_ptr() + SG.SEED_STEP_OFFSET
+        # the guard: a train-mode CNN forward overwrites the BatchNorm running buffers long before the gradient is judged
+        running = None
+        if self._guard is not None and not c["features"] and (plan is None or plan.modes[0]):
+            running = eng.running_buffers()
+            call("vqa_buffers_save", ptr(running[0]), running[1], ptr(running[2]))
         try:
             if c["features"]:
                 logits, _, tape = eng.forward_features(images, token_ids, maskf, True, False, need_tape=True, lowp_logits=True, kv_index=kv_index,
@@ -498,18 +540,28 @@ class HipTrainer:
             hyper, sfx = (self.lr, b1, b2, self.eps, self.wd, self.calls), ""
             ema_args = () if self.ema is None else (ptr(self.ema), float(self.ema_decay), int(bool(self.ema_warmup)))
         tail = () if state is not None else (float(self.max_norm), gscale)
+        # the guard: the norm's fold block turns the (reduced) bad-target count and its own verdict into the effective skip word and
+        # keeps bad_targets; AdamW reads that word and counts the skipped launches of either kind in an array of the trainer's own
+        if self._guard is None:
+            gsfx, gtail, skip, skipped = "", (), self.bad_step, self._bad
+        else:
+            gsfx, gtail = "_guard", (ptr(self.bad_step), ptr(self._guard), ptr(self._bad), ptr(self._guard[1:]))
+            skip, skipped = self._guard, self._adam_skipped
+            self._last_ws = ce_ws
         if self._ranges is None:
-            call("vqa_sumsq", ptr(self.G), self.G.numel(), ptr(self.sumsq))
+            call("vqa_sumsq" + gsfx, ptr(self.G), self.G.numel(), ptr(self.sumsq), *gtail)
             call(("vqa_adamw_ema" if ema_args else "vqa_adamw") + sfx, ptr(self.model._flat), ptr(self.G), ptr(self.m), ptr(self.v), self.G.numel(),
-                 *hyper, ptr(self.sumsq), *tail, ptr(self.bad_step), ptr(self._bad), ptr(eng.adamw_copy_target()), *ema_args)
+                 *hyper, ptr(self.sumsq), *tail, ptr(skip), ptr(skipped), ptr(eng.adamw_copy_target()), *ema_args)
         else:                                      # frozen parameters: only the trainable ranges are read and written
             table, R, n, fidx, nf, garr = self._ranges
             # parameter groups: the same launch with every range's group and the block of the groups' values behind its arguments
             entry, gargs = ("vqa_adamw_ranges", ()) if garr is None else ("vqa_adamw_groups", (ptr(garr), ptr(self._group_block)))
-            call("vqa_sumsq_ranges", ptr(self.G), ptr(table), R, n, ptr(self.sumsq))
+            call("vqa_sumsq_ranges" + gsfx, ptr(self.G), ptr(table), R, n, ptr(self.sumsq), *gtail)
             call(entry + ("_ema" if ema_args else "") + sfx, ptr(self.model._flat), ptr(self.G), ptr(self.m), ptr(self.v),
-                 ptr(table), R, n, *hyper, ptr(self.sumsq), *tail, ptr(self.bad_step), ptr(self._bad), ptr(self._lag), ptr(fidx), nf,
+                 ptr(table), R, n, *hyper, ptr(self.sumsq), *tail, ptr(skip), ptr(skipped), ptr(self._lag), ptr(fidx), nf,
                  ptr(eng.adamw_copy_target()), *ema_args, *gargs)
+        if running is not None:                    # a skipped step never happened: the BatchNorm buffers go back (nothing when the word is 0)
+            call("vqa_buffers_restore", ptr(running[0]), running[1], ptr(running[2]), ptr(self._guard))
         # the kernel wrote the bf16 operand copy too: the next step() skips the cast launch if nothing touched the parameters in between
         self._copy_sig = self._param_sig() if eng.adamw_copy_target() is not None else None
         return self.loss, logits_f
@@ -519,7 +571,7 @@ class HipTrainer:
         """step() replayed from a captured HIP graph: same arguments, checks, errors and return value, bit-equal results, and the
         host enqueues three things per step instead of every launch.  The first two calls for a key (stepgraph.step_key: shapes and
         dtypes of the inputs, mask / index present, K of SoftTargets, features or images, the fine-tuning plan, the loss and its
-        options, EMA on or off, the `metrics` object, the parameter / operand-copy / packed-operand / range-table buffers) are eager steps; the third
+        options, EMA on or off, the non-finite guard on or off, the `metrics` object, the parameter / operand-copy / packed-operand / range-table buffers) are eager steps; the third
         captures the launches of _enqueue on static copies of the inputs and replays them; later calls copy the inputs in, write the
         device step-state block (vqa_step_state_set: this step's seed word and Adam step number, and lr / betas / eps / wd /
         max_norm / ema_decay / ema_warmup as they read NOW -- changing them never re-captures; the parameter groups' lr_scale and
@@ -542,7 +594,8 @@ class HipTrainer:
                           image_index=c["kv_index"], targets=c["targets"], plan=c["plan"], loss_kind=self.loss_kind,
                           loss_opts=(self.label_smoothing, self.ignore_index, None if self.class_weight is None else self.class_weight.data_ptr()),
                           ema=self.ema is not None, metrics=metrics, flat_ptr=self.model._flat.data_ptr(), wsrc_ptr=eng.wsrc.data_ptr(),
-                          table_id=SG.table_id(None if self._ranges is None else self._ranges_gen, None if self._pg is None else self._pg.key()))
+                          table_id=SG.table_id(None if self._ranges is None else self._ranges_gen, None if self._pg is None else self._pg.key(),
+                                               guard=self._guard is not None))
         g = self._graphs.pop(key, None)
         if g is not None and g[4] != eng._wt_gen:
             # the engine laid its packed backward operands out anew since the capture (another trainable set needed more of them):
@@ -578,6 +631,8 @@ class HipTrainer:
             for d_, s_ in zip(dst, self._tensors_of(src)):
                 d_.copy_(s_)
         graph.replay()
+        if self._guard is not None:
+            self._last_ws = g[3][3]
         # the captured AdamW wrote the operand copy: vouch for it as step() does
         self._copy_sig = self._param_sig() if eng.adamw_copy_target() is not None else None
         return out
@@ -623,7 +678,8 @@ class HipTrainer:
         eng._wt, eng._accbuf = {}, None                    # eager step must not pick them up (begin_step / _acc rebuild their own)
         self.graph_captures += 1
         # held: the static inputs' owners, the tracker whose counters the graph writes, the range table it reads
-        return graph, static, out, (cc, c["metrics"], self._ranges), self.engine._wt_gen
+        # (and, under the guard, the per-row loss terms nonfinite_report() reads)
+        return graph, static, out, (cc, c["metrics"], self._ranges, self._last_ws), self.engine._wt_gen
 
     def _graph_put(self, key, g):
         cap = max(1, int(self.model.graph_max_shapes))
@@ -673,13 +729,20 @@ class HipTrainer:
         torch has no place for: the parameter name of every index, calls and the counters check() reads, the frozen-time lags and
         their classes, the hyper-parameters and the groups' live values, the weight average, ema_decay / ema_warmup and the dropout
         stream (the engine's seed_base and step_id).  The model's own state (weights, BatchNorm buffers) is model.state_dict()'s.
+        Under the non-finite guard the block also holds "nonfinite": {"mode", "since", "ever", "unchecked"} -- the guard's counters;
+        "skipped_ever" stays the count of launches that were no step, for whichever reason.  Without the guard: the keys as ever.
         One host synchronisation.  RuntimeError inside ema_weights()."""
         if self._ema_swapped:
             raise RuntimeError("HipTrainer.state_dict inside ema_weights(): the model holds the averaged weights; leave the block first")
-        bad = [int(x) for x in self._bad.tolist()]
+        if self._guard is None:
+            bad, nf = [int(x) for x in self._bad.tolist()], {}
+        else:                                              # (one read: bad_targets, the launches that were no step, the guard's counters)
+            w = [int(x) for x in torch.cat([self._bad[:2], self._ever(), self._guard[1:]]).tolist()]
+            bad = w[:3]
+            nf = dict(nonfinite=self.nonfinite, nonfinite_skipped=(w[3], w[4], w[4] - self._nf_checked))
         eng = self.engine
         return TS.export(self.model._param_entries, [n for n, _ in self.model.named_parameters()], self.m, self.v, calls=self.calls,
-                         skipped_ever=bad[2], bad_targets=bad[:2], empty=int(self._empty.item()), lag=self._lag.tolist(),
+                         skipped_ever=bad[2], bad_targets=bad[:2], **nf, empty=int(self._empty.item()), lag=self._lag.tolist(),
                          lag_class=self._lag_class, ever_frozen=self._ever_frozen, lr=self.lr, betas=self.betas, eps=self.eps,
                          weight_decay=self.wd, max_grad_norm=self.max_norm, groups=self.param_groups, ema=self.ema,
                          ema_decay=self.ema_decay, ema_warmup=self.ema_warmup, seed_base=eng.seed_base, step_id=eng.step_id)
@@ -693,7 +756,8 @@ class HipTrainer:
         bit for bit.  ValueError for an unknown version, a missing or unknown parameter name, a wrong shape, groups whose membership
         differs from this trainer's, and an average in the dict when this trainer was built without ema_decay.  A trainer WITH
         ema_decay given a dict without an average restarts the average from the model's current weights, as its constructor does, and
-        keeps its own ema_decay / ema_warmup.
+        keeps its own ema_decay / ema_warmup.  The non-finite guard's counters are restored into a guarded trainer (zero when the
+        dict has none) and ignored by an unguarded one; the mode stays the constructor's.
         Without the block (torch.optim.AdamW.state_dict()): only the moments and the step numbers are read.  Index i is the i-th
         parameter of the concatenated param_groups: model.parameters() order for the one group of a trainer without groups; with
         trainer groups the dict's group sizes must equal theirs.  An index without state gets zero moments and step 0; calls becomes
@@ -713,11 +777,16 @@ class HipTrainer:
         self._lag.copy_(torch.tensor(r["lag"], dtype=torch.int32))
         self._lag_class = list(r["lag_class"])
         self._ever_frozen = r["ever_frozen"]
-        if r["bad_targets"] is None:
-            self._bad[2:3].fill_(r["skipped_ever"])
-        else:
-            self._bad.copy_(torch.tensor(r["bad_targets"] + [r["skipped_ever"]], dtype=torch.int32))
+        self._ever().fill_(r["skipped_ever"])
+        if r["bad_targets"] is not None:
+            self._bad[:2].copy_(torch.tensor(r["bad_targets"], dtype=torch.int32))
             self._empty.fill_(r["empty"])
+        if self._guard is not None:                        # (a dict written without the guard: the new counters start at zero)
+            nf = r["nonfinite"] or {"since": 0, "ever": 0, "unchecked": 0}
+            self._guard.copy_(torch.tensor([0, nf["since"], nf["ever"]], dtype=torch.int32))
+            self._nf_checked = nf["ever"] - nf["unchecked"]
+            self._nf_reported = nf["ever"]
+            self._last_ws = None
         for attr, key in (("lr", "lr"), ("betas", "betas"), ("eps", "eps"), ("wd", "weight_decay"), ("max_norm", "max_grad_norm"),
                           ("ema_decay", "ema_decay"), ("ema_warmup", "ema_warmup")):
             if r[key] is not None:
@@ -781,8 +850,59 @@ class HipTrainer:
 
     @property
     def t(self) -> int:
-        """Adam's step number = optimizer updates actually applied (one host sync; the kernels never need it from the host)."""
-        return self.calls - int(self._bad[2])
+        """Adam's step number = optimizer updates actually applied (one host sync; the kernels never need it from the host).  Under
+        the non-finite guard both kinds of skipped step are left out."""
+        return self.calls - int(self._ever())
+
+    def _ever(self):
+        """The device count of launches that were no step: AdamW's own array under the non-finite guard, else _bad[2]."""
+        return self._bad[2:3] if self._guard is None else self._adam_skipped[2:3]
+
+    # ---- the non-finite guard (nonfinite="skip" | "raise")
+    def _need_guard(self, what):
+        if self._guard is None:
+            raise RuntimeError(f'HipTrainer.{what} needs the non-finite guard: construct the trainer with nonfinite="skip" or "raise"')
+
+    def skipped_nonfinite(self):
+        """(steps skipped for a non-finite gradient since the last call, ... ever); one host sync.  Bad-target steps are not among
+        them: check() reports those."""
+        self._need_guard("skipped_nonfinite")
+        since, ever = (int(x) for x in self._guard[1:].tolist())
+        if since:
+            self._guard[1:2].zero_()
+        return since, ever
+
+    def nonfinite_report(self):
+        """What blew up in the step just skipped; one host sync.  None when the last step's gradient was finite (or the step was a
+        bad-target step: check() speaks for those), else a NonFiniteReport(step, loss, parameters, rows): the step's call number
+        (`calls`), its loss, (name, non-finite elements, numel) in layout order for every trainable parameter whose gradient holds a
+        NaN or inf (vqa_nonfinite_scan over the flat gradient, launched here and never inside a step), and the int64 indices of the
+        batch rows whose per-row loss term is not finite.  The gradient and the loss terms are the last step's: call this before
+        the next step.  RuntimeError when a non-finite step has gone by unreported and a later step has overwritten its gradient."""
+        self._need_guard("nonfinite_report")
+        if self._last_ws is None:                          # no step yet (or a state was loaded since)
+            return None
+        entries = self.model._param_entries
+        if self._scan is None or self._scan[1].device != self.G.device:
+            table = torch.tensor([[e.offset, e.offset + e.numel] for e in entries], dtype=torch.int64).to(self.G.device)
+            self._scan = (table, torch.zeros(len(entries), device=self.G.device, dtype=torch.int32))
+        table, counts = self._scan
+        counts.zero_()
+        call("vqa_nonfinite_scan", ptr(self.G), ptr(table), len(entries), ptr(counts))
+        rows = (~torch.isfinite(self._last_ws)).to(torch.int32)
+        w = torch.cat([self._scal, self._guard, counts, rows]).tolist()      # the one device-to-host read
+        loss, bad_rows, word, ever = struct.unpack("f", struct.pack("i", w[0]))[0], w[1], w[2], w[4]
+        counts, rows = w[5:5 + len(entries)], w[5 + len(entries):]
+        unreported, self._nf_reported = ever > self._nf_reported, ever
+        if word == 0 or bad_rows != 0:
+            if unreported:
+                raise RuntimeError("HipTrainer.nonfinite_report: a step was skipped for a non-finite gradient, but a later step has "
+                                   "overwritten its gradient; call nonfinite_report() right after the step, before the next one")
+            return None
+        mask = self._mask
+        params = [(e.name, n, e.numel) for j, (e, n) in enumerate(zip(entries, counts)) if n and (mask is None or mask[j])]
+        # (self.calls is that step's call number: no later step has run, or the branch above would have been taken)
+        return NonFiniteReport(self.calls, loss, params, torch.tensor([i for i, r in enumerate(rows) if r], dtype=torch.int64))
 
     def grad_norm(self) -> torch.Tensor:
         return self.sumsq[:1].sqrt() / self.world
@@ -790,12 +910,22 @@ class HipTrainer:
     def check(self):
         """Host-side error check (one sync; call it per logging interval, not per step): raises like nn.CrossEntropyLoss does
         (training/train.py:120) if any step since the last check saw a target outside [0, num_answers).  With loss options it also
-        raises ValueError if any step's batch had zero total weight (see step())"""
-        n, skipped = (int(x) for x in self.bad_targets.tolist())
+        raises ValueError if any step's batch had zero total weight (see step()).  With nonfinite="raise" it raises FloatingPointError
+        for the steps skipped for a non-finite gradient since the last check (after the IndexError, when both are due); a non-finite
+        skip never raises IndexError."""
+        if self.nonfinite == "raise":                      # (one read for both)
+            n, skipped, ever = (int(x) for x in torch.cat([self.bad_targets, self._guard[2:]]).tolist())
+        else:
+            (n, skipped), ever = (int(x) for x in self.bad_targets.tolist()), None
         if n:
             self.bad_targets.zero_()
             raise IndexError(f"{n} target(s) out of range [0, {self.model.num_answers}) since the last check: {skipped} step(s) were "
                              "skipped on every rank (parameters and optimizer state untouched; that step's loss and gradients are NaN)")
+        if ever is not None and ever > self._nf_checked:
+            k, self._nf_checked = ever - self._nf_checked, ever
+            raise FloatingPointError(f"{k} step(s) since the last check had a non-finite gradient and were skipped on every rank "
+                                     "(parameters, optimizer state and BatchNorm buffers untouched); nonfinite_report() right after "
+                                     "such a step names the parameters and batch rows")
         if self._loss_opts:
             e = int(self._empty.item())
             if e:

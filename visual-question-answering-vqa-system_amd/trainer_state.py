@@ -25,6 +25,14 @@ from . import layout as LY
 
 VERSION = 1
 BLOCK = "hip_trainer"
+NONFINITE_MODES = (None, "skip", "raise")
+
+
+def check_nonfinite(value):
+    """HipTrainer's `nonfinite` option: None (no guard), "skip" or "raise"; ValueError for anything else."""
+    if value is None or (isinstance(value, str) and value in NONFINITE_MODES):
+        return value
+    raise ValueError(f'HipTrainer: nonfinite must be None, "skip" or "raise", got {value!r}')
 
 
 # ---- flat buffer <-> named tensors
@@ -78,9 +86,15 @@ def torch_group(lr, betas, eps, weight_decay, params: List[int]) -> dict:
 
 def export(entries: Sequence[LY.Entry], order: Sequence[str], m: torch.Tensor, v: torch.Tensor, *, calls: int, skipped_ever: int,
            bad_targets: Sequence[int], empty: int, lag: Sequence[int], lag_class: Sequence[int], ever_frozen: bool, lr, betas, eps,
-           weight_decay, max_grad_norm, groups, ema: Optional[torch.Tensor], ema_decay, ema_warmup, seed_base: int, step_id: int) -> dict:
+           weight_decay, max_grad_norm, groups, ema: Optional[torch.Tensor], ema_decay, ema_warmup, seed_base: int, step_id: int,
+           nonfinite=None, nonfinite_skipped: Sequence[int] = (0, 0, 0)) -> dict:
     """The state dict.  `lag` and `lag_class` come in layout order (one per entry) and leave in index order, like everything
-    per-parameter in the dict; `groups` are the trainer's live dicts {"names", "lr_scale", "weight_decay"} or None."""
+    per-parameter in the dict; `groups` are the trainer's live dicts {"names", "lr_scale", "weight_decay"} or None.
+    nonfinite ("skip" / "raise": the trainer runs the non-finite guard): the block then also carries "nonfinite": {"mode", "since"
+    (steps skipped for a non-finite gradient since the last skipped_nonfinite()), "ever", "unchecked" (since the last check())} from
+    nonfinite_skipped = (since, ever, unchecked); `skipped_ever` stays the count of ALL launches that were no step.  None: the
+    block has exactly the keys it had before the guard existed."""
+    check_nonfinite(nonfinite)
     names = index_names(order, groups)
     by_name = {e.name: j for j, e in enumerate(entries)}
     if sorted(names) != sorted(by_name):
@@ -111,6 +125,9 @@ def export(entries: Sequence[LY.Entry], order: Sequence[str], m: torch.Tensor, v
         "ema_decay": None if ema is None else float(ema_decay), "ema_warmup": bool(ema_warmup),
         "rng": {"seed_base": int(seed_base), "step_id": int(step_id)},
     }
+    if nonfinite is not None:
+        since, ever, unchecked = (int(x) for x in nonfinite_skipped)
+        block["nonfinite"] = {"mode": nonfinite, "since": since, "ever": ever, "unchecked": unchecked}
     return {"state": state, "param_groups": pgs, BLOCK: block}
 
 
@@ -207,13 +224,14 @@ def load(entries: Sequence[LY.Entry], order: Sequence[str], sd, m: torch.Tensor,
                                                                                   trainer has no groups
         ema: "loaded" | "restart" (the trainer keeps an average, the dict has none: restart it from the weights) | None
         ema_decay, ema_warmup                                                     None unless an average was loaded
+        nonfinite: {"mode", "since", "ever", "unchecked"}                         None unless the dict was written by a guarded trainer
 
     ValueError for everything that does not fit; nothing is written then."""
     if not isinstance(sd, dict) or "state" not in sd:
         raise ValueError("trainer state: expected a dict with 'state' and 'param_groups' (HipTrainer.state_dict() or torch.optim.AdamW's)")
     by_name = {e.name: j for j, e in enumerate(entries)}
     out = dict.fromkeys(("bad_targets", "empty", "max_grad_norm", "rng", "group_values", "lr", "betas", "eps", "weight_decay", "ema",
-                         "ema_decay", "ema_warmup"))
+                         "ema_decay", "ema_warmup", "nonfinite"))
     block = sd.get(BLOCK)
     avg = None
     if block is not None:                                  # ---- an exact resume
@@ -273,6 +291,13 @@ def load(entries: Sequence[LY.Entry], order: Sequence[str], sd, m: torch.Tensor,
         if not isinstance(rng, dict):
             raise ValueError("trainer state: 'rng' must be a dict {seed_base, step_id}")
         out["rng"] = {"seed_base": _int(rng.get("seed_base"), "rng['seed_base']"), "step_id": _int(rng.get("step_id"), "rng['step_id']")}
+        nf = block.get("nonfinite")
+        if nf is not None:
+            if not isinstance(nf, dict) or nf.get("mode") not in ("skip", "raise"):
+                raise ValueError("trainer state: 'nonfinite' must be a dict {mode: 'skip' | 'raise', since, ever, unchecked}")
+            out["nonfinite"] = {"mode": nf["mode"], **{k: _int(nf.get(k), f"nonfinite['{k}']") for k in ("since", "ever", "unchecked")}}
+            if max(out["nonfinite"]["since"], out["nonfinite"]["unchecked"]) > out["nonfinite"]["ever"] or out["nonfinite"]["ever"] > skipped:
+                raise ValueError(f"trainer state: nonfinite counters {nf} do not fit skipped_ever {skipped}")
     else:                                                  # ---- a plain torch.optim.AdamW dict: the moments and the steps
         pgs, ids = _param_ids(sd)
         for gi, g in enumerate(pgs):
