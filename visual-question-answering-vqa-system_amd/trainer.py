@@ -179,6 +179,7 @@ NonFiniteReport = collections.namedtuple("NonFiniteReport", "step loss parameter
 
 class HipTrainer:
     _guard = None                                  # the non-finite guard's device words (set by the constructor when nonfinite is given)
+    pending = 0                                    # micro-batches accumulated in the open window (accumulate(); 0: no window open)
 
     def __init__(self, model, lr=1e-4, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
                  process_group=None, overlap=True, force_reducer=False, label_smoothing=0.0, class_weight=None, ignore_index=None,
@@ -277,11 +278,16 @@ class HipTrainer:
         self._last_ws = None                       # the last step's per-row loss terms (kept under the guard, for nonfinite_report)
         self._scan = None                          # nonfinite_report's table of parameter ranges and its counters
         self.calls = 0
+        # gradient accumulation (accumulate(); `pending`, the class attribute above, counts the open window's micro-batches): the
+        # window's trainable set and the BatchNorm buffers the guard saved ahead of the window's first train-mode CNN forward
+        self._win_mask = None
+        self._win_saved = None
         self._copy_sig = None                      # parameter-version signature right after the last fused AdamW launch
         self.buckets = LY.bucket_ranges(model._entries)
         self.reducer = GradBucketReducer(self.G, self.buckets, process_group, overlap, force=force_reducer,
                                          avoid_streams=[st for st in (self.engine.side, self.engine.side2) if st is not None])
         self.world = self.reducer.world
+        self._norm_div = self.world                # what grad_norm() divides by: world * n of the last update (n: its window's micro-batches)
         # fine-tuning (frozen parameters): the optimizer runs over a device table of trainable ranges (finetune.trainable_ranges),
         # rebuilt only when the trainable set changes.  _lag_class groups parameters frozen during exactly the same steps; _lag[j]
         # (device) counts the applied steps parameter j spent frozen, so each range forms torch.optim.AdamW's per-parameter step.
@@ -390,13 +396,57 @@ class HipTrainer:
         images may be an ImageFeatures (VQAModel.encode_features; with image_index: of the U images): the image encoder, which must be
         frozen and in eval mode, does not run, and everything after it is the same step -- the launches of the images step without the
         CNN forward, bit for bit.  RuntimeError before any launch when an image_encoder parameter requires grad, the image encoder is
-        in train mode, or the features are stale."""
+        in train mode, or the features are stale.
+        After k accumulate() calls the step closes their window: its own gradient is added to theirs and ONE update is applied with the
+        mean of the k + 1 per-batch mean gradients (see accumulate())."""
         return self._enqueue(self._prologue("step", images, token_ids, attention_mask, targets, metrics, image_index))
 
-    def _prologue(self, who, images, token_ids, attention_mask, targets, metrics, image_index):
+    def accumulate(self, images, token_ids, attention_mask, targets, metrics=None, image_index=None):
+        """A micro-batch of a gradient-accumulation window: step()'s arguments, checks and errors; forward, loss and backward run INTO the
+        gradient already in `G` (every weight-gradient epilogue adds), and nothing else is launched: no norm, no AdamW, no collective.
+        Returns (this micro-batch's loss, its fp32 logits); the loss is the device scalar step() returns, valid until the next call.
+        The step() that follows k accumulate() calls closes the window with one update on the MEAN of the n = k + 1 per-batch mean
+        gradients -- what (loss_i / n).backward() for each batch, clip_grad_norm_ and AdamW.step() apply; batches are not weighted by
+        their row counts.  Nothing is rescaled in the loss launches (the bf16 d logits keep their bits): the closing AdamW launch
+        takes gscale = 1 / (world * n), grad_norm() reports sqrt(sumsq) / (world * n), and `G` after the closing step holds the SUM
+        over the window.  `pending` counts the open window's micro-batches (0: no window); discard_accumulated() drops it.
+        Once per window, in the closing step: `calls`, Adam's step number, the per-parameter lags, the weight average.  Per
+        micro-batch: the dropout stream (each draws its own masks), the engine's step_id / cnn_train_forwards, the model's
+        _feat_epoch, `metrics`, and BatchNorm -- each micro-batch normalises with its OWN batch statistics and updates the running
+        buffers, as two torch forwards would, so a window of train-mode BatchNorm is not the large batch.
+        A bad target in ANY micro-batch skips the window's update: the bad-target word accumulates over the window, check() reports
+        the window's bad rows and one skipped step.  Under the non-finite guard the verdict is taken once, by the closing norm
+        launch, on the accumulated gradient, and a non-finite window never happened: the BatchNorm buffers are saved ahead of the
+        window's first train-mode CNN forward only and restored behind the closing norm, which undoes the buffer updates of all its
+        micro-batches together.  nonfinite_report() then names the parameters from the accumulated gradient and the rows of the
+        CLOSING micro-batch only.
+        The trainable set (requires_grad) must be the same for every call of a window: a change raises RuntimeError before anything
+        is launched or counted -- close or discard the window first.  Routes may be mixed: images, ImageFeatures, image_index, any B.
+        Data parallel: nothing is communicated here; the closing step reduces the accumulated `G` through the usual buckets,
+        overlapped with its own backward, and the bad-target word with them.  Every rank must use the same n (as with DDP's no_sync).
+        While a window is open step_graphed(), state_dict() and load_state_dict() raise RuntimeError: checkpoints are taken at window
+        boundaries.  explain(), eval forwards, predict*, encode_* and ema_weights() blocks between two calls leave `G` alone."""
+        return self._enqueue(self._prologue("accumulate", images, token_ids, attention_mask, targets, metrics, image_index, closing=False),
+                             closing=False)
+
+    def discard_accumulated(self):
+        """Drop an open window: the accumulated gradient, its bad-target word and the BatchNorm buffers the guard saved for it are
+        forgotten; the next step() is a plain step.  Nothing is launched: the next call, the first of a window or a plain step, zeroes
+        `G` and the scratch words as it always does, and until then `G` still holds the discarded sum.  What the micro-batches'
+        forwards did stays done, as after torch's zero_grad(): the BatchNorm running buffers moved and the dropout stream advanced.
+        Nothing when no window is open."""
+        self.pending, self._win_mask, self._win_saved = 0, None, None
+
+    def _refuse_open(self, who):
+        if self.pending:
+            raise RuntimeError(f"HipTrainer.{who}: a gradient-accumulation window is open ({self.pending} micro-batch(es) pending); close it "
+                               "with step() or drop it with discard_accumulated() first")
+
+    def _prologue(self, who, images, token_ids, attention_mask, targets, metrics, image_index, closing=True):
         """The host half of a step: validation, the fine-tuning plan, the image index's device copy, the optimizer's range table and
         -- last, once nothing can be refused any more -- the bookkeeping (calls, the engine's step_id and cnn_train_forwards, the
-        model's _feat_epoch).  Launches nothing through the C ABI.  Returns what _enqueue needs."""
+        model's _feat_epoch).  Launches nothing through the C ABI.  Returns what _enqueue needs.  closing=False (accumulate): `calls` stays,
+        it counts updates."""
         if self._ema_swapped:
             raise RuntimeError(f"HipTrainer.{who} inside ema_weights(): the model holds the averaged weights; leave the block first")
         eng = self.engine
@@ -434,6 +484,10 @@ class HipTrainer:
                                + ("" if image_index is None else " with B questions"))
         # fine-tuning: requires_grad and the parts' modes, resolved on every step (finetune.Plan; None: the plain step)
         plan = self.model._finetune_plan(self.model._param_list(), False, True)
+        win_mask = None if plan is None or all(plan.trainable) else tuple(plan.trainable)
+        if self.pending and win_mask != self._win_mask:    # (ahead of the index copy and the range table: nothing has gone out yet)
+            raise RuntimeError(f"HipTrainer.{who}: the trainable set changed inside a gradient-accumulation window ({self.pending} "
+                               "micro-batch(es) pending); close the window with step() or drop it with discard_accumulated() first")
         if feats is not None:                              # host checks, ahead of the image index's copy / range read: nothing has gone out yet
             if plan is None or plan.cnn_trains:
                 raise RuntimeError(f"HipTrainer.{who}: ImageFeatures stand in for a frozen image encoder: call "
@@ -460,8 +514,9 @@ class HipTrainer:
         if feats is None and (plan is None or plan.cnn_trains):      # this step's AdamW writes the image encoder: cached features go stale
             self.model._feat_epoch += 1
         eng.count_step(plan.modes if plan is not None else (True, True, True, True), runs_cnn=feats is None)
-        self.calls += 1
-        return dict(features=feats is not None, images=images, token_ids=token_ids, maskf=maskf, targets=targets, soft=soft, bce=bce,
+        if closing:
+            self.calls += 1
+        return dict(win_mask=win_mask, features=feats is not None, images=images, token_ids=token_ids, maskf=maskf, targets=targets, soft=soft, bce=bce,
                     metrics=metrics, kv_index=kv_index, plan=plan, group_values=group_values)
 
     def _write_groups(self, values):
@@ -474,11 +529,13 @@ class HipTrainer:
         call("vqa_group_hyper_set", ptr(self._group_block), len(scales), F(*scales), F(*wds))
         self._group_written = values
 
-    def _enqueue(self, c, state=None):
+    def _enqueue(self, c, state=None, closing=True):
         """The device half of a step: every launch, in the order the step has always issued them; returns (loss, logits fp32).
         state (step_graphed, while the step is being captured): the device step-state block.  The dropout seeds are then the flagged
         words that point into it, AdamW is the _dev entry that reads its hyper-parameters from it, and the bf16 operand copy the
-        previous AdamW launch wrote is trusted (step_graphed re-casts it eagerly before a replay when the host check fails)."""
+        previous AdamW launch wrote is trusted (step_graphed re-casts it eagerly before a replay when the host check fails).
+        closing=False (accumulate): the launches up to and including the backward, into the window's gradient; the step that closes
+        a window adds its own gradient and runs the tail on the sum.  With no window open this is the step as it has always been."""
         eng = self.engine
         images, token_ids, maskf, targets, metrics, kv_index, plan = (c[k] for k in ("images", "token_ids", "maskf", "targets", "metrics",
                                                                                       "kv_index", "plan"))
@@ -486,16 +543,20 @@ class HipTrainer:
         dev = self.G.device
         if state is None:                          # (a captured step: step_graphed wrote the block eagerly, beside the step state)
             self._write_groups(c["group_values"])
-        self.G.zero_()
-        self._scal.zero_()
+        if self.pending == 0:                      # the first call of a window, or a plain step
+            self.G.zero_()
+            self._scal.zero_()
+        else:                                      # inside a window: this call's loss alone; the bad-target word accumulates
+            self.loss.zero_()
         if state is not None:
             eng._wsrc_fresh = eng.adamw_copy_target() is not None
         elif self._copy_sig is not None and eng.adamw_copy_target() is not None and self._copy_sig == self._param_sig():
             eng._wsrc_fresh = True                 # (one-shot, consumed by the begin_step of the forward below)
         eng._seed_src = None if state is None else state.data_ptr() + SG.SEED_STEP_OFFSET
         # the guard: a train-mode CNN forward overwrites the BatchNorm running buffers long before the gradient is judged
-        running = None
-        if self._guard is not None and not c["features"] and (plan is None or plan.modes[0]):
+        # (a window: saved ahead of its FIRST such forward only, so the restore undoes every micro-batch's updates together)
+        running = self._win_saved
+        if running is None and self._guard is not None and not c["features"] and (plan is None or plan.modes[0]):
             running = eng.running_buffers()
             call("vqa_buffers_save", ptr(running[0]), running[1], ptr(running[2]))
         try:
@@ -528,11 +589,20 @@ class HipTrainer:
             fused = False
             call("vqa_cross_entropy", dt(logits), ptr(logits), ptr(targets), ptr(self.loss), ptr(dlogits), ptr(logits_f) if lowp else None, B, N, 1.0,
                  ptr(self.bad_step), ptr(ce_ws))           # per-row loss terms, folded in row order (bit-reproducible)
-        self.reducer.reduce_aux(self.bad_step)             # every rank must skip the update of a step ANY rank rejects
+        if closing:
+            self.reducer.reduce_aux(self.bad_step)         # every rank must skip the update of a step ANY rank rejects
         if metrics is not None and not soft and not fused:
             metrics.update(logits_f, targets)
-        eng.backward(tape, dlogits, self.G, on_segment=self.reducer.on_segment if self.reducer.active else None)
+        eng.backward(tape, dlogits, self.G, on_segment=self.reducer.on_segment if (closing and self.reducer.active) else None)
+        if not closing:                            # no collective, no norm, no AdamW: the parameters and the operand copy stay as they are
+            self.pending, self._win_mask, self._win_saved = self.pending + 1, c["win_mask"], running
+            return self.loss, logits_f
         gscale = self.reducer.finish()
+        n = self.pending + 1                       # the update takes the mean of the window's n per-batch mean gradients
+        if n > 1:
+            gscale = 1.0 / (self.world * n)
+        self._norm_div = self.world * n
+        self.pending, self._win_mask, self._win_saved = 0, None, None
         b1, b2 = self.betas
         if state is not None:                      # the captured form: hyper-parameters, step number and gscale come from the block
             hyper, ema_args, sfx = (ptr(state),), (() if self.ema is None else (ptr(self.ema),)), "_dev"
@@ -582,12 +652,14 @@ class HipTrainer:
         key.  check(), t, grad_norm(), ema_*, params_changed() and `metrics` work as with step().
         RuntimeError before any launch: more than one rank or force_reducer=True (no collectives inside a graph), a current stream
         that is capturing, a call inside ema_weights()."""
+        self._refuse_open("step_graphed")
         if self.reducer.active:
             raise RuntimeError("HipTrainer.step_graphed: a captured step holds no collectives -- it runs in a world of one rank "
                                "without force_reducer; use step()")
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("HipTrainer.step_graphed: the current stream is capturing; a graph is not captured inside another")
         c = self._prologue("step_graphed", images, token_ids, attention_mask, targets, metrics, image_index)
+        self._norm_div = self.world                        # a captured step is a window of one (gscale 1 / world): grad_norm() as with step()
         eng = self.engine
         eng.ensure_operand_copy()                          # (its address is part of the key from the first call on)
         key = SG.step_key(features=c["features"], images=c["images"], token_ids=c["token_ids"], attention_mask=c["maskf"],
@@ -734,6 +806,7 @@ class HipTrainer:
         One host synchronisation.  RuntimeError inside ema_weights()."""
         if self._ema_swapped:
             raise RuntimeError("HipTrainer.state_dict inside ema_weights(): the model holds the averaged weights; leave the block first")
+        self._refuse_open("state_dict")
         if self._guard is None:
             bad, nf = [int(x) for x in self._bad.tolist()], {}
         else:                                              # (one read: bad_targets, the launches that were no step, the guard's counters)
@@ -770,6 +843,7 @@ class HipTrainer:
         synchronisation.  RuntimeError inside ema_weights()."""
         if self._ema_swapped:
             raise RuntimeError("HipTrainer.load_state_dict inside ema_weights(): the model holds the averaged weights; leave the block first")
+        self._refuse_open("load_state_dict")
         r = TS.load(self.model._param_entries, [n for n, _ in self.model.named_parameters()], sd, self.m, self.v, self.ema,
                     self.param_groups)
         dev = self.G.device
@@ -905,7 +979,8 @@ class HipTrainer:
         return NonFiniteReport(self.calls, loss, params, torch.tensor([i for i, r in enumerate(rows) if r], dtype=torch.int64))
 
     def grad_norm(self) -> torch.Tensor:
-        return self.sumsq[:1].sqrt() / self.world
+        """The global gradient norm the last update clipped: sqrt(sumsq) / (world * n), n the micro-batches of its window (1: a plain step)."""
+        return self.sumsq[:1].sqrt() / self._norm_div
 
     def check(self):
         """Host-side error check (one sync; call it per logging interval, not per step): raises like nn.CrossEntropyLoss does
