@@ -601,6 +601,23 @@ int vqa_nonfinite_scan(const float* g, const long long* table, int P, int* count
    for n > 0 a NULL or not 16-byte-aligned src / dst, a NULL index, n_src == 0, or 2^24 or more chunks (n * ceil(row_bytes / 16384)).  n == 0 launches nothing. */
 int vqa_gather_rows(const void* src, const int* index, void* dst, int n, long long row_bytes, int n_src, hipStream_t stream);
 
+/* Batch draw from a resident uint8 image bank (csrc/bank_ops.hip; dropin/data/image_bank.py ImageBank.batch): the random suffix of the
+   training transform -- RandomCrop + RandomHorizontalFlip, data/preprocess.py:71-73 -- on images whose Resize was stored once.
+   bank uint8 [n_rows][S][S][3] and out uint8 [B][O][O][3], both 16-byte aligned; rows device int32 [B]; crop_yx device int32 [B][2]
+   as (y, x) or NULL (every origin (0, 0)); flip device uint8 [B] or NULL (no flip):
+     out[b][y][x][c] = bank[rows[b]][cy_b + y][cx_b + (flip_b ? O-1-x : x)][c]
+   Bytes are copied, never computed on.  Every per-sample argument is a device array, so one launch serves any B and the call can be
+   captured; no scratch.  Offsets into the bank are 64-bit (21 846 rows of 256 x 256 x 3 pass 2^32 bytes); no byte outside
+   [bank, bank + n_rows*S*S*3) is read -- a source row starts at cx*3, any alignment: the aligned dwords holding the wanted bytes are
+   loaded and shifted -- and none outside out is written.
+   A sample whose row is outside [0, n_rows) or whose origin is outside [0, S-O] in either axis keeps its out bytes as they were, reads
+   nothing and adds 1 to *err (device int, may be NULL; the caller zeroes it).
+   Status 1000 without a launch: n_rows < 1, B < 0, S or O below 4 or no multiple of 4 (output rows are whole dwords, as
+   vqa_image_normalize's W % 4 == 0), O > S, S > 32768 (offsets inside one image are 32-bit), and for B > 0 a NULL or not
+   16-byte-aligned bank / out or a NULL rows.  B == 0 launches nothing. */
+int vqa_bank_batch(const uint8_t* bank, long long n_rows, int S, const int* rows, const int* crop_yx, const uint8_t* flip,
+                   uint8_t* out, int B, int O, int* err, hipStream_t stream);
+
 /* ---- explaining an answer (csrc/explain_ops.hip; VQAModel.explain, Explanation.render) ----------------------------
  * All four accumulate in fp32 in a fixed order (no float atomics: the same bits on every run) and return status 1000 without a
  * launch for a NULL operand, a size < 1, a dtype other than 0 (fp32) / 1 (bf16) and the shapes named below.

@@ -66,3 +66,8 @@ def load_dropin_tokenizer():
 def load_dropin_preprocess():
     """The drop-in `data.preprocess` (ToTensor + Normalize on the GPU, gpu_collate_fn)."""
     return _load_dropin_file("vqa_hip_dropin_data_preprocess", "data", "preprocess.py")
+
+
+def load_dropin_image_bank():
+    """The drop-in `data.image_bank` (ImageBank: resident uint8 images augmented as they are drawn; BankSampler, BankLoader)."""
+    return _load_dropin_file("vqa_hip_dropin_data_image_bank", "data", "image_bank.py")

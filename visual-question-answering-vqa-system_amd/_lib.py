@@ -142,6 +142,7 @@ SIGNATURES = {
     "vqa_adamw_ranges_ema": [P, P, P, P, P, I, LL, F, F, F, F, F, LL, P, F, F, P, P, P, P, I, P, P, F, I, P],
     "vqa_ema_update": [P, P, LL, F, P],
     "vqa_gather_rows": [P, P, P, I, LL, I, P],
+    "vqa_bank_batch": [P, LL, I, P, P, P, P, I, I, P, P],
     "vqa_step_state_set": [P, LL, ULL, F, F, F, F, F, F, F, F, I, P],
     "vqa_adamw_dev": [P, P, P, P, LL, P, P, P, P, P, P],
     "vqa_adamw_ema_dev": [P, P, P, P, LL, P, P, P, P, P, P, P],
