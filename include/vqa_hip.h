@@ -618,6 +618,24 @@ int vqa_gather_rows(const void* src, const int* index, void* dst, int n, long lo
 int vqa_bank_batch(const uint8_t* bank, long long n_rows, int S, const int* rows, const int* crop_yx, const uint8_t* flip,
                    uint8_t* out, int B, int O, int* err, hipStream_t stream);
 
+/* Per-tensor statistics of a flat fp32 buffer (csrc/stats_ops.hip; kernels.tensor_stats, HipTrainer(monitor=...)): a deterministic
+   segmented reduction, one result row per table row, two launches, no float atomics, no host sync.
+   table: device int64 [P][3] rows {lo, hi, first_chunk}: [lo, hi) of the flat buffer with lo a multiple of 4 elements and hi
+   arbitrary (hi > lo); first_chunk = the sum of ceil((hi - lo) / VQA_STATS_CHUNK) over the rows before it, chunks = that sum over all
+   rows.  The table is trusted as written, as the range tables of the optimizer are.  With d[i] = x[i] (y NULL) or x[i] - y[i] (one
+   fp32 subtraction), row j of out -- P rows of four 32-bit words, 16-byte aligned -- is
+     { sumsq (f32), absmax (f32), nonfinite (u32), zeros (u32) }
+   nonfinite counts the d that are NaN or +-inf (inf - inf among them), zeros the d == 0 (-0.0 counts); sumsq and absmax run over the
+   FINITE d only and are 0 when there is none.  Elements outside the rows are never read.
+   Chunk c of a row is [lo + c * CHUNK, min(hi, lo + (c + 1) * CHUNK)); one 256-thread workgroup reduces one chunk in a fixed lane /
+   wave order into scratch (device, 16-byte aligned, at least 4 * chunks words), a second launch folds each row's chunks in ascending
+   order.  A row's four words are the same bits run to run and depend on (lo, hi) and the data alone: not on P, the grid, or the row's
+   place in the table.  The counts and absmax are exact; sumsq is within N_add * 2^-24 relative of the exact sum (N_add: stats_ops.hip).
+   Status 1000 without a launch: a NULL x, table, out or scratch; P outside 1 ... 4096; chunks < P or chunks >= 2^31. */
+#define VQA_STATS_CHUNK 8192
+int vqa_tensor_stats(const float* x, const float* y, const long long* table, int P, long long chunks, void* out, float* scratch,
+                     hipStream_t stream);
+
 /* ---- explaining an answer (csrc/explain_ops.hip; VQAModel.explain, Explanation.render) ----------------------------
  * All four accumulate in fp32 in a fixed order (no float atomics: the same bits on every run) and return status 1000 without a
  * launch for a NULL operand, a size < 1, a dtype other than 0 (fp32) / 1 (bf16) and the shapes named below.

@@ -4,7 +4,7 @@ Import with importlib (the directory name is not a Python identifier):
     pkg = importlib.import_module("visual-question-answering-vqa-system_amd")
 """
 from . import _lib, kernels  # noqa: F401
-from . import layout, engine, ema, trainer, trainer_state, flops, finetune  # noqa: F401,E402
+from . import layout, engine, ema, monitor, trainer, trainer_state, flops, finetune  # noqa: F401,E402
 
 
 def dropin_path() -> str:
@@ -43,6 +43,11 @@ def load_dropin_losses():
 def load_dropin_ema():
     """The drop-in `utils.ema` (ParameterEMA: a weight average for torch.optim loops, one launch per update)."""
     return _load_dropin_file("vqa_hip_dropin_utils_ema", "utils", "ema.py")
+
+
+def load_dropin_monitor():
+    """The drop-in `utils.monitor` (ParameterMonitor: per-parameter statistics for torch.optim loops, read back once per interval)."""
+    return _load_dropin_file("vqa_hip_dropin_utils_monitor", "utils", "monitor.py")
 
 
 def _load_dropin_file(name, *rel):

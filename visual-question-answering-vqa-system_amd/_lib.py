@@ -143,6 +143,7 @@ SIGNATURES = {
     "vqa_ema_update": [P, P, LL, F, P],
     "vqa_gather_rows": [P, P, P, I, LL, I, P],
     "vqa_bank_batch": [P, LL, I, P, P, P, P, I, I, P, P],
+    "vqa_tensor_stats": [P, P, P, I, LL, P, P, P],
     "vqa_step_state_set": [P, LL, ULL, F, F, F, F, F, F, F, F, I, P],
     "vqa_adamw_dev": [P, P, P, P, LL, P, P, P, P, P, P],
     "vqa_adamw_ema_dev": [P, P, P, P, LL, P, P, P, P, P, P, P],

@@ -14,7 +14,8 @@ the reference's own ATen model.  What does win is `sys.modules`: an import state
      must not shadow them),
   3. appends the reference's `models/` directory to the bound package's `__path__`, so `models.cnn_backbone` & co. (not
      used by any entry point, but importable in the reference) still resolve to the reference's files,
-  4. registers a LAST-resort finder for the drop-in's additions to `utils` that the reference has no file for (`utils.losses`, `utils.ema`):
+  4. registers a LAST-resort finder for the drop-in's additions to `utils` that the reference has no file for (`utils.losses`, `utils.ema`,
+     `utils.monitor`):
      `from utils.losses import CrossEntropyLoss` imports the reference's own `utils` package and then, only because that package
      holds no `losses.py`, the drop-in's file.  A project that has its own `utils/losses.py` keeps it.
 Nothing here touches the GPU (no HIP call, no `torch.cuda.is_available()`): `run()` may be followed by anything.
@@ -30,7 +31,8 @@ import sys
 from typing import List, Optional
 
 _BOUND_NAMES = ("models", "models.vqa_model")
-_DROPIN_ONLY = {"utils.losses": ("utils", "losses.py"), "utils.ema": ("utils", "ema.py")}      # drop-in modules without a counterpart in the reference
+_DROPIN_ONLY = {"utils.losses": ("utils", "losses.py"), "utils.ema": ("utils", "ema.py"),
+                "utils.monitor": ("utils", "monitor.py")}      # drop-in modules without a counterpart in the reference
 
 
 class _DropinOnlyFinder(importlib.abc.MetaPathFinder):

@@ -8,8 +8,9 @@ CSRC = os.path.join(HERE, "csrc")
 # (optim_ops.hip, loss_ops.hip and attention.hip were split off token_ops.hip; they are linked last, in the order they were split off, so that
 #  every other object keeps its place: profiles/optimizer_tail_ab.txt C, profiles/loss_ops_ab.txt C, profiles/attention_ab.txt C;
 #  explain_ops.hip is new and goes last for the same reason: profiles/explain_ab_parent.txt; batchnorm.hip was split off cnn_ops.hip and goes
-#  last in the same way: profiles/batchnorm_ab.txt C; bank_ops.hip is new and goes last: profiles/image_bank_ab_parent.txt)
-SOURCES = ["gemm_conv.hip", "cnn_ops.hip", "token_ops.hip", "stem_conv.hip", "conv_c64.hip", "input_ops.hip", "gemm8p.hip", "mxfp8.hip", "stem_dgrad.hip", "feature_ops.hip", "optim_ops.hip", "loss_ops.hip", "attention.hip", "explain_ops.hip", "batchnorm.hip", "bank_ops.hip"]
+#  last in the same way: profiles/batchnorm_ab.txt C; bank_ops.hip is new and goes last: profiles/image_bank_ab_parent.txt; stats_ops.hip
+#  is new and goes last: profiles/tensor_stats_ab_parent.txt)
+SOURCES = ["gemm_conv.hip", "cnn_ops.hip", "token_ops.hip", "stem_conv.hip", "conv_c64.hip", "input_ops.hip", "gemm8p.hip", "mxfp8.hip", "stem_dgrad.hip", "feature_ops.hip", "optim_ops.hip", "loss_ops.hip", "attention.hip", "explain_ops.hip", "batchnorm.hip", "bank_ops.hip", "stats_ops.hip"]
 LIB = os.path.join(HERE, "libvqa_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]

@@ -747,6 +747,75 @@ def layernorm_bwd(dout, x, gamma, stats, dgamma, dbeta, *, addend=None, drop_p=0
     return dx
 
 
+STATS_CHUNK = 8192           # VQA_STATS_CHUNK of include/vqa_hip.h: elements one workgroup of vqa_tensor_stats reduces
+STATS_MAX_ROWS = 4096
+_STATS_SCRATCH = {}          # device -> fp32 scratch of vqa_tensor_stats (four words per chunk), grown on demand
+
+
+class StatsTable(tuple):
+    """(device table int64 [P][3] of {lo, hi, first_chunk}, P, chunks) as stats_table() returns it; `extent` is the largest hi, so
+    that tensor_stats() can refuse a buffer the table reaches beyond."""
+    extent = 0
+
+
+def stats_rows(ranges):
+    """Host half of stats_table: ([[lo, hi, first_chunk], ...] in the given order, chunks).  ValueError for an empty range, a lo that
+    is negative or no multiple of 4, ranges that overlap, no range at all or more than 4096."""
+    ranges = [(int(lo), int(hi)) for lo, hi in ranges]
+    if not 1 <= len(ranges) <= STATS_MAX_ROWS:
+        raise ValueError(f"stats_table: between 1 and {STATS_MAX_ROWS} ranges, got {len(ranges)}")
+    for lo, hi in ranges:
+        if hi <= lo:
+            raise ValueError(f"stats_table: empty range [{lo}, {hi})")
+        if lo < 0 or lo % 4:
+            raise ValueError(f"stats_table: range [{lo}, {hi}) must start at a non-negative multiple of 4 elements")
+    ordered = sorted(ranges)
+    for (_, hi0), (lo1, hi1) in zip(ordered, ordered[1:]):
+        if lo1 < hi0:
+            raise ValueError(f"stats_table: range [{lo1}, {hi1}) overlaps the range that ends at {hi0}")
+    rows, chunks = [], 0
+    for lo, hi in ranges:
+        rows.append([lo, hi, chunks])
+        chunks += (hi - lo + STATS_CHUNK - 1) // STATS_CHUNK
+    return rows, chunks
+
+
+def stats_table(ranges, device="cuda"):
+    """The table vqa_tensor_stats reads, from (lo, hi) pairs on the host: a StatsTable (device table, P, chunks).  One row per range,
+    in the given order; ValueError as stats_rows.  The copy goes out from pinned memory without a sync when `device` is a GPU."""
+    rows, chunks = stats_rows(ranges)
+    t = torch.tensor(rows, dtype=torch.int64)
+    if torch.device(device).type == "cuda":
+        t = t.pin_memory().to(device, non_blocking=True)
+    out = StatsTable((t, len(rows), chunks))
+    out.extent = max(r[1] for r in rows)
+    return out
+
+
+def tensor_stats(x, table, y=None, out=None):
+    """Per-range {sumsq f32, absmax f32, nonfinite u32, zeros u32} of the flat fp32 buffer x -- of x - y when y is given -- as an
+    int32 [P][4] device tensor (vqa_tensor_stats: two launches on the current stream, no host sync; view columns 0 and 1 as float32).
+    table: a StatsTable of stats_table() on x's device.  out: an int32 [P][4] contiguous tensor to write into (a slot of a ring)."""
+    tab, P, chunks = table
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 1 and x.is_contiguous()):
+        raise ValueError("tensor_stats: x must be a contiguous flat fp32 buffer on the GPU (there is no CPU path)")
+    if tab.device != x.device:
+        raise ValueError(f"tensor_stats: the table lives on {tab.device}, x on {x.device}")
+    if x.numel() < table.extent:
+        raise ValueError(f"tensor_stats: the table reaches element {table.extent}, x has {x.numel()}")
+    if y is not None and not (y.dtype == torch.float32 and y.shape == x.shape and y.device == x.device and y.is_contiguous()):
+        raise ValueError("tensor_stats: y must be a contiguous fp32 buffer of x's size on x's device")
+    if out is None:
+        out = torch.empty((P, 4), device=x.device, dtype=torch.int32)
+    elif tuple(out.shape) != (P, 4) or out.dtype != torch.int32 or out.device != x.device or not out.is_contiguous():
+        raise ValueError(f"tensor_stats: out must be a contiguous int32 tensor of shape ({P}, 4) on {x.device}")
+    scratch = _STATS_SCRATCH.get(x.device)
+    if scratch is None or scratch.numel() < 4 * chunks:
+        scratch = _STATS_SCRATCH[x.device] = torch.empty((4 * chunks,), device=x.device, dtype=torch.float32)
+    call("vqa_tensor_stats", ptr(x), ptr(y), ptr(tab), P, chunks, ptr(out), ptr(scratch))
+    return out
+
+
 def gather_rows(src, index, out=None):
     """out[i] = src[index[i]] along the first dimension, one launch (vqa_gather_rows).  src: contiguous [n_src, ...] of any dtype whose
     rows are a multiple of 16 bytes; index: contiguous int32 [n] on src's device with every entry in [0, n_src) -- the CALLER checks the

@@ -22,6 +22,7 @@ from . import ema as EMA
 from . import finetune as FT
 from . import kernels as K
 from . import layout as LY
+from . import monitor as MON
 from . import stepgraph as SG
 from . import trainer_state as TS
 from ._lib import call, dt, ptr
@@ -180,10 +181,12 @@ NonFiniteReport = collections.namedtuple("NonFiniteReport", "step loss parameter
 class HipTrainer:
     _guard = None                                  # the non-finite guard's device words (set by the constructor when nonfinite is given)
     pending = 0                                    # micro-batches accumulated in the open window (accumulate(); 0: no window open)
+    monitor = None                                 # the TensorMonitor (set by the constructor when monitor is given)
+    _stats_tab = None
 
     def __init__(self, model, lr=1e-4, weight_decay=0.01, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
                  process_group=None, overlap=True, force_reducer=False, label_smoothing=0.0, class_weight=None, ignore_index=None,
-                 ema_decay=None, ema_warmup=False, loss="ce", param_groups=None, nonfinite=None):
+                 ema_decay=None, ema_warmup=False, loss="ce", param_groups=None, nonfinite=None, monitor=None):
         """loss: "ce" (default: softmax cross-entropy, exactly the step without this option) or "bce" (sigmoid + binary cross-entropy on
         SoftTargets, see step()); readable afterwards as `loss_kind` (`loss` is the device scalar).
         ema_decay (None, or a float in [0, 1]): keep an exponential moving average of the weights, self.ema (a flat fp32 buffer laid out
@@ -223,8 +226,29 @@ class HipTrainer:
         (vqa_sumsq_guard / vqa_sumsq_ranges_guard): a clean step has no launch more than the unguarded one, bar the two over the
         BatchNorm buffers (40 KB).  Data parallel: every rank folds the same reduced gradient and decides the same; nothing is
         communicated.  ValueError for any other value, before anything is allocated.  None (default): exactly the step without
-        this feature, launch for launch."""
+        this feature, launch for launch.
+        monitor (None, or a monitor.TensorMonitor(every, slots)): per-parameter statistics on the device.  A step whose `calls`, after
+        it is counted, is a multiple of `every` is DUE (the closing step() of an accumulation window counts; accumulate() never
+        records): it copies model._flat to a snapshot ahead of the AdamW launch (device to device, on the step's stream) and issues
+        three vqa_tensor_stats launches behind the step's last launch -- over `G` as the norm launch saw it (after the data-parallel
+        reduction, before the clip; AdamW does not write it), over model._flat after the update, and over model._flat minus the
+        snapshot -- into slot records % slots of the monitor's device ring.  Nothing is read back; the host notes (calls, gscale,
+        trainable mask) per slot, and monitor.read() fetches the ring in one copy (monitor.py: StatsRecord).  The launches only read
+        what the step computed: a monitored run keeps the unmonitored run's bits.  A skipped step (bad target, non-finite guard) is
+        recorded like any due step: its update rows are zero with update_unchanged == numel, and under the guard its grad_nonfinite
+        names the parameters nonfinite_report() names.  Frozen parameters keep their rows (trainable False, grad_zeros == numel,
+        update_norm 0).  Data parallel: every rank records the same reduced gradient; nothing is communicated.  step_graphed() hands
+        a due step to the eager step before any graph bookkeeping: it does not count towards a key's warm-up, is never captured and
+        never replays, and no captured graph holds a statistics launch.  The monitor is not part of state_dict(); `calls` is, so a
+        resumed run is due on the same steps.  A non-due step issues the plain step's launches; None (default): exactly the step
+        without this feature, launch for launch.  TypeError for anything that is not a TensorMonitor, before anything is allocated."""
         self.model = model
+        if monitor is not None:
+            if not isinstance(monitor, MON.TensorMonitor):
+                raise TypeError(f"HipTrainer: monitor must be a monitor.TensorMonitor or None, got {type(monitor).__name__}")
+            monitor._attach(self)
+        self.monitor = monitor
+        self._stats_tab = None                     # tensor_stats(): the table of parameter ranges on the device
         # validated on the host before anything is allocated or launched
         self.nonfinite = TS.check_nonfinite(nonfinite)
         if not (isinstance(loss, str) and loss in ("ce", "bce")):
@@ -610,6 +634,10 @@ class HipTrainer:
             hyper, sfx = (self.lr, b1, b2, self.eps, self.wd, self.calls), ""
             ema_args = () if self.ema is None else (ptr(self.ema), float(self.ema_decay), int(bool(self.ema_warmup)))
         tail = () if state is not None else (float(self.max_norm), gscale)
+        # the monitor: a due step keeps the weights of before the update (never inside a capture: step_graphed hands due steps here)
+        due = self.monitor is not None and state is None and self.monitor.due(self.calls)
+        if due:
+            self.monitor.snapshot(self.model._param_entries, self.model._flat)
         # the guard: the norm's fold block turns the (reduced) bad-target count and its own verdict into the effective skip word and
         # keeps bad_targets; AdamW reads that word and counts the skipped launches of either kind in an array of the trainer's own
         if self._guard is None:
@@ -632,6 +660,8 @@ class HipTrainer:
                  ptr(eng.adamw_copy_target()), *ema_args, *gargs)
         if running is not None:                    # a skipped step never happened: the BatchNorm buffers go back (nothing when the word is 0)
             call("vqa_buffers_restore", ptr(running[0]), running[1], ptr(running[2]), ptr(self._guard))
+        if due:                                    # behind the step's last launch: three reads of what it left
+            self.monitor.record(self.calls, gscale, self._mask, self.model._flat, grad=self.G)
         # the kernel wrote the bf16 operand copy too: the next step() skips the cast launch if nothing touched the parameters in between
         self._copy_sig = self._param_sig() if eng.adamw_copy_target() is not None else None
         return self.loss, logits_f
@@ -660,6 +690,8 @@ class HipTrainer:
             raise RuntimeError("HipTrainer.step_graphed: the current stream is capturing; a graph is not captured inside another")
         c = self._prologue("step_graphed", images, token_ids, attention_mask, targets, metrics, image_index)
         self._norm_div = self.world                        # a captured step is a window of one (gscale 1 / world): grad_norm() as with step()
+        if self.monitor is not None and self.monitor.due(self.calls):
+            return self._enqueue(c)                        # a due step runs eagerly and records; the graphs never see it
         eng = self.engine
         eng.ensure_operand_copy()                          # (its address is part of the key from the first call on)
         key = SG.step_key(features=c["features"], images=c["images"], token_ids=c["token_ids"], attention_mask=c["maskf"],
@@ -977,6 +1009,33 @@ class HipTrainer:
         params = [(e.name, n, e.numel) for j, (e, n) in enumerate(zip(entries, counts)) if n and (mask is None or mask[j])]
         # (self.calls is that step's call number: no later step has run, or the branch above would have been taken)
         return NonFiniteReport(self.calls, loss, params, torch.tensor([i for i, r in enumerate(rows) if r], dtype=torch.int64))
+
+    def tensor_stats(self, kinds=("grad", "param")):
+        """Per-parameter statistics of the trainer's flat buffers as they are NOW, between steps: one vqa_tensor_stats launch per kind
+        and one device-to-host copy; returns a monitor.StatsRecord (step = `calls`) whose other fields are None.  kinds out of "grad"
+        (`G`: the last update's gradient, or an accumulating window's sum once it is closed; norm and absmax scaled like
+        grad_norm()), "param" (model._flat), "moment1" / "moment2" (Adam's m and v) and "ema" (the weight average; RuntimeError
+        without ema_decay).  ValueError for "update" -- there is no snapshot to compare with; a monitored step records it --, an
+        unknown kind, a repeat or an empty selection.  RuntimeError inside ema_weights() and while an accumulation window is open.
+        Works with or without a monitor and does not touch its ring."""
+        kinds = MON.check_now_kinds(kinds)
+        if self._ema_swapped:
+            raise RuntimeError("HipTrainer.tensor_stats inside ema_weights(): the model holds the averaged weights; leave the block first")
+        self._refuse_open("tensor_stats")
+        src = {"grad": lambda: self.G, "param": lambda: self.model._flat.detach(), "moment1": lambda: self.m, "moment2": lambda: self.v,
+               "ema": lambda: self._need_ema('tensor_stats("ema")')}
+        bufs = [src[k]() for k in kinds]
+        entries = self.model._param_entries
+        if self._stats_tab is None or self._stats_tab[0].device != self.G.device:
+            self._stats_tab = K.stats_table(MON.layout_ranges(entries), self.G.device)
+        out = torch.empty((len(kinds), len(entries), 4), device=self.G.device, dtype=torch.int32)
+        for i, b in enumerate(bufs):
+            K.tensor_stats(b, self._stats_tab, out=out[i])
+        host = out.cpu()
+        mask = self._mask
+        trainable = torch.ones(len(entries), dtype=torch.bool) if mask is None else torch.tensor(mask, dtype=torch.bool)
+        return MON.make_record({k: host[i] for i, k in enumerate(kinds)}, self.calls, [e.name for e in entries],
+                               torch.tensor([e.numel for e in entries], dtype=torch.int64), trainable, 1.0 / self._norm_div)
 
     def grad_norm(self) -> torch.Tensor:
         """The global gradient norm the last update clipped: sqrt(sumsq) / (world * n), n the micro-batches of its window (1: a plain step)."""
