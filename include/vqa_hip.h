@@ -448,7 +448,7 @@ int vqa_cross_entropy(int dtype, const void* logits, const long long* targets, f
 int vqa_cross_entropy_opts(int dtype, const void* logits, const long long* targets, float* loss, void* dlogits, float* logits_f32,
                            int B, int N, float gscale, int* err, float* ws, const float* class_weight, long long ignore_index,
                            int has_ignore, float label_smoothing, unsigned long long* acc, int* empty, hipStream_t stream);
-int vqa_convert(int dtype_in, int dtype_out, const void* in, void* out, long long n, hipStream_t stream);
+int vqa_convert(int dtype_in, int dtype_out, const void* src, void* dst, long long n, hipStream_t stream);
 /* clip_grad_norm_(max_norm) + AdamW over flat fp32 buffers (training/train.py:204-208,127-132).
    skip (device int, may be NULL): when skip[0] != 0 the launch changes NOTHING (parameters, moments) and adds skip[0] to
    skipped[0], 1 to skipped[1] and 1 to skipped[2] (device int[3], may be NULL; [0] / [1] are the caller's to reset, [2] never) -- a

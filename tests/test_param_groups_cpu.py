@@ -213,6 +213,10 @@ def test_ctypes_view_of_the_group_block(rel):
     assert SG.GroupHyper.lr_scale.offset == 0 and SG.GroupHyper.wd.offset == 64
     assert SG.GROUPS_MAX == FT.GROUPS_MAX == 16 and FT.RANGES_MAX == 512
     txt = open(os.path.join(REPO, *rel.split("/"))).read()
+    if rel.endswith("common.h"):                 # the sources compile the header's block itself: common.h includes it and pins its layout
+        assert re.search(r'^#include "\.\./\.\./include/vqa_hip\.h"', txt, flags=re.M)
+        assert "static_assert(sizeof(vqa_group_hyper) == 128 && alignof(vqa_group_hyper) == 16 && offsetof(vqa_group_hyper, wd) == 64" in txt
+        return
     assert re.search(r"#define VQA_GROUPS_MAX 16\b", txt)
     m = re.search(r"typedef struct __attribute__\(\(aligned\(16\)\)\) vqa_group_hyper \{(.*?)\} vqa_group_hyper;", txt, flags=re.S)
     assert m and [d.strip() for d in m.group(1).split(";") if d.strip()] == ["float lr_scale[VQA_GROUPS_MAX]", "float wd[VQA_GROUPS_MAX]"]

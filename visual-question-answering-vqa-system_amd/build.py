@@ -11,18 +11,23 @@ CSRC = os.path.join(HERE, "csrc")
 #  last in the same way: profiles/batchnorm_ab.txt C; bank_ops.hip is new and goes last: profiles/image_bank_ab_parent.txt; stats_ops.hip
 #  is new and goes last: profiles/tensor_stats_ab_parent.txt)
 SOURCES = ["gemm_conv.hip", "cnn_ops.hip", "token_ops.hip", "stem_conv.hip", "conv_c64.hip", "input_ops.hip", "gemm8p.hip", "mxfp8.hip", "stem_dgrad.hip", "feature_ops.hip", "optim_ops.hip", "loss_ops.hip", "attention.hip", "explain_ops.hip", "batchnorm.hip", "bank_ops.hip", "stats_ops.hip"]
+HEADER = os.path.join(os.path.dirname(HERE), "include", "vqa_hip.h")
 LIB = os.path.join(HERE, "libvqa_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
+
+
+def _deps():
+    """Every file the library is compiled from: the sources, the headers next to them, and the public header common.h includes."""
+    import glob
+    return [os.path.join(CSRC, f) for f in SOURCES] + glob.glob(os.path.join(CSRC, "*.h")) + [HEADER]
 
 
 def _stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    import glob
-    deps = [os.path.join(CSRC, f) for f in SOURCES] + glob.glob(os.path.join(CSRC, "*.h"))     # every header any source includes
-    return any(os.path.getmtime(d) > t for d in deps)
+    return any(os.path.getmtime(d) > t for d in _deps())
 
 
 def build_lib(force=False, verbose=True):

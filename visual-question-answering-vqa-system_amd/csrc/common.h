@@ -1,6 +1,7 @@
 // Shared device helpers for the gfx950 (MI355X, CDNA4) VQA kernels.  Wave = 64 lanes.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "../../include/vqa_hip.h"
 #include <stddef.h>
 #include <stdint.h>
 
@@ -188,30 +189,12 @@ __device__ __forceinline__ void bn_acc_coef(const BnAcc& f, int C, int c, double
   }
 }
 
-// The device step-state block of include/vqa_hip.h (the sources do not include the public header: the definition is repeated here and
-// pinned by the assertions below and by tests/test_step_graph_cpu.py, which reads the header's).
-#ifndef VQA_STEP_STATE_DEFINED
-#define VQA_STEP_STATE_DEFINED
-typedef struct __attribute__((aligned(16))) vqa_step_state {
-  long long calls;
-  unsigned long long seed_step;
-  float lr, b1, b2, eps, wd, max_norm, gscale, ema_decay;
-  int ema_warmup;
-} vqa_step_state;
-#endif
+// include/vqa_hip.h (included above) is the one declaration of every entry and of the two device blocks: each source compiles against
+// it, so a definition whose arguments disagree with it does not compile ("conflicting types"), and nothing is declared a second time here
+// or in a source.  The assertions pin the layout the ctypes mirrors of stepgraph.py assume.
 static_assert(sizeof(vqa_step_state) == 64 && alignof(vqa_step_state) == 16, "vqa_step_state: 52 bytes of fields in a 16-byte aligned block");
 static_assert(offsetof(vqa_step_state, seed_step) == 8 && offsetof(vqa_step_state, lr) == 16 && offsetof(vqa_step_state, ema_warmup) == 48,
               "vqa_step_state: field order of include/vqa_hip.h");
-
-// The parameter groups' block of include/vqa_hip.h (HipTrainer(param_groups=...)), repeated here in the same way.
-#define VQA_GROUPS_MAX 16
-#ifndef VQA_GROUP_HYPER_DEFINED
-#define VQA_GROUP_HYPER_DEFINED
-typedef struct __attribute__((aligned(16))) vqa_group_hyper {
-  float lr_scale[VQA_GROUPS_MAX];
-  float wd[VQA_GROUPS_MAX];
-} vqa_group_hyper;
-#endif
 static_assert(sizeof(vqa_group_hyper) == 128 && alignof(vqa_group_hyper) == 16 && offsetof(vqa_group_hyper, wd) == 64,
               "vqa_group_hyper: two arrays of 16 floats in a 16-byte aligned block");
 
@@ -222,8 +205,6 @@ static_assert(sizeof(vqa_group_hyper) == 128 && alignof(vqa_group_hyper) == 16 &
 // The shape every kernel that gives a thread one 16-byte channel vector and a 256-thread workgroup whole rows asks for (BatchNorm, SE,
 // spatial attention): C a positive multiple of the vector (8 bf16 | 4 fp32), at most 256 vectors, a count that divides 256.
 static inline bool bn_vec_ok(int dtype, int C) { const int VEC = dtype ? 8 : 4; return C > 0 && !(C % VEC || C / VEC > 256 || 256 % (C / VEC)); }
-// chunks per sample of the pooling BatchNorm forward (batchnorm.hip); vqa_se_fwd (cnn_ops.hip) checks its pool_chunks against it
-extern "C" int vqa_bn_apply_pool_chunks(int dtype, int HW, int C);
 
 // dst0[c] (c < n0) / dst1[c - n0] += sum over rows r < nrows of part[r * stride + c], rows in index order (fold_rows_kernel).  Defined in
 // token_ops.hip, where the kernel lives: other translation units launch it through this, so its device code exists once.

@@ -889,8 +889,6 @@ __global__ __launch_bounds__(1024) void wgrad_c128p_reduce_kernel(const float* _
   }
 }
 
-extern "C" int vqa_slab_reduce(const float* ws, float* dw, int nslabs, long long n, hipStream_t st);
-
 extern "C" {
 
 // persistent grid of the 4-wave weight-gradient kernel (wgrad3x3_c64_kernel), 0 when it does not take the shape

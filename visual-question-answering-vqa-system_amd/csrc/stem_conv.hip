@@ -516,8 +516,6 @@ __global__ __launch_bounds__(256) void stem_wgrad_u8_kernel(const uint8_t* __res
   stem_wgrad_body<FUSED, ImgU8>(img, tab, dy, dw, B, H, W, Ho, Wo, dpool, idx, coef, bc, Hp, Wp, nsplit, ws);
 }
 
-extern "C" int vqa_slab_reduce(const float* ws, float* dw, int nslabs, long long n, hipStream_t st);
-
 // A row is contracted in nsplit pieces (Wo / nsplit pixels each, a multiple of 8).  The kernel is latency-bound in its staging phase
 // and lives off the co-resident workgroups: the smallest split whose LDS footprint lets THREE of them share a CU (224 x 224 images:
 // 2 pieces, 52 KB; the 384 x 384 stress shape: 6 pieces, 48 KB -- with the 2 pieces it used to get, 82 KB and ONE workgroup per CU,

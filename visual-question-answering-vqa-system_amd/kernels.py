@@ -7,6 +7,7 @@ coefficients, weight gradients and optimizer state are float32.  Functions alloc
 """
 from __future__ import annotations
 
+import collections
 import os
 
 import torch
@@ -40,75 +41,94 @@ def prof_end(e0, sym, flops, nbytes):
     return e1
 
 # HBM-bound entries (no FLOPs worth counting): algorithmic bytes of one call from its C-ABI argument list -- the tensors the op
-# must read and write once; recorded as ("hbm:<class>:<entry>", 0, e0, e1, bytes) while PROFILE is a list.
-_ES = lambda d: 2 if d else 4          # element size of the compute dtype argument (0 = f32, 1 = bf16)
+# must read and write once; recorded as ("hbm:<class>:<entry>", 0, e0, e1, bytes) while PROFILE is a list.  A formula reads
+# its arguments by the parameter names of include/vqa_hip.h (L.ARGNAMES), so an argument inserted into an entry moves none of them.
 _P = lambda p: 1 if p else 0           # optional operand present
-HBM_BYTES = {
+_ES = lambda d: 2 if d else 4          # element size of the compute dtype argument (0 = f32, 1 = bf16)
+# attention, es = element size (the _mfma entries take no dtype: 2): Q, K, V in and ctx out at row stride ldc (+ probs fp32); the backward
+# also reads dctx and writes dQ, dK, dV
+_attn_fwd = lambda a, es: (a.B * (a.Lq + 2 * a.Lk) * a.ldc + a.B * a.Lq * a.ldc) * es + a.B * a.H * a.Lq * a.Lk * 4
+_attn_bwd = lambda a, es: 2 * (a.B * (a.Lq + 2 * a.Lk) * a.ldc) * es + a.B * a.Lq * a.ldc * es + a.B * a.H * a.Lq * a.Lk * 4
+# indexed form (answer(), forward_grouped): queries, ctx and probs per question, K / V once per image; the backward reads Q, K, V, dctx and
+# probs and writes dQ per question, dK / dV once per image
+_attn_fwd_idx = lambda a, es: (2 * a.B * a.Lq * a.H * a.hd + 2 * a.n_kv * a.Lk * a.H * a.hd) * es + a.B * a.H * a.Lq * a.Lk * 4
+_attn_bwd_idx = lambda a, es: (3 * a.B * a.Lq + 4 * a.n_kv * a.Lk) * a.ldc * es + a.B * a.H * a.Lq * a.Lk * 4
+_bn_bwd_apply = lambda a: a.numel * _ES(a.dtype) * (3 + _P(a.outact) + 2 * _P(a.y2))
+_soft_loss = lambda a: a.B * a.N * (_ES(a.dtype) + 4) + a.B * a.K * (8 + 4 * _P(a.counts))
+_HBM_FORMULAS = {
     # BatchNorm passes (A3): statistics finalize reads the slab; apply reads y (+ residual) and writes out; backward reduce reads
     # dout, y (+ activation, + shortcut y); backward apply reads dout, y (+ activation) and writes dy (+ shortcut: y2 in, dy2 out)
-    "vqa_bn_stats_finalize": ("bn", lambda a: a[1] * a[2] * 2 * 4 + a[2] * 4 * 8),
-    "vqa_bn_apply": ("bn", lambda a: a[6] * _ES(a[0]) * (2 + _P(a[3]))),
-    "vqa_bn_apply_pool": ("bn", lambda a: a[6] * a[7] * a[8] * _ES(a[0]) * (2 + _P(a[3]))),
-    "vqa_bn_bwd_reduce": ("bn", lambda a: a[8] * a[9] * _ES(a[0]) * (2 + _P(a[2]) + _P(a[5]))),
-    "vqa_bn_apply_acc": ("bn", lambda a: a[18] * a[19] * a[20] * _ES(a[0]) * (2 + _P(a[9]))),
-    "vqa_bn_bwd_apply_acc": ("bn", lambda a: a[16] * _ES(a[0]) * (3 + _P(a[2]) + 2 * _P(a[10]))),
-    "vqa_bn_bwd_finalize": ("bn", lambda a: a[1] * a[2] * 3 * 4),
-    "vqa_bn_bwd_apply": ("bn", lambda a: a[9] * _ES(a[0]) * (3 + _P(a[2]) + 2 * _P(a[6]))),
-    "vqa_stem_pool_fwd": ("stem_pool", lambda a: a[5] * a[6] * a[7] * a[8] * _ES(a[0])
-                          + a[5] * ((a[6] - 1) // 2 + 1) * ((a[7] - 1) // 2 + 1) * a[8] * (_ES(a[0]) + 1)),
+    "vqa_bn_stats_finalize": ("bn", lambda a: a.tiles * a.C * 2 * 4 + a.C * 4 * 8),
+    "vqa_bn_apply": ("bn", lambda a: a.numel * _ES(a.dtype) * (2 + _P(a.res))),
+    "vqa_bn_apply_pool": ("bn", lambda a: a.B * a.HW * a.C * _ES(a.dtype) * (2 + _P(a.res))),
+    "vqa_bn_bwd_reduce": ("bn", lambda a: a.rows * a.C * _ES(a.dtype) * (2 + _P(a.outact) + _P(a.y2))),
+    "vqa_bn_apply_acc": ("bn", lambda a: a.B * a.HW * a.C * _ES(a.dtype) * (2 + _P(a.res))),
+    "vqa_bn_bwd_apply_acc": ("bn", _bn_bwd_apply),
+    "vqa_bn_bwd_finalize": ("bn", lambda a: a.nblk * a.C * 3 * 4),
+    "vqa_bn_bwd_apply": ("bn", _bn_bwd_apply),
+    "vqa_stem_pool_fwd": ("stem_pool", lambda a: a.B * a.H * a.W * a.C * _ES(a.dtype)
+                          + a.B * ((a.H - 1) // 2 + 1) * ((a.W - 1) // 2 + 1) * a.C * (_ES(a.dtype) + 1)),
     # SE / spatial attention (A4, A5): pool read + scale read + write forward; dout, x in and dx out backward
-    "vqa_se_fwd": ("se_spatial", lambda a: (2 if a[12] else 3) * a[8] * a[9] * a[10] * _ES(a[0])),      # pool sums handed over: no pool read
-    "vqa_se_bwd": ("se_spatial", lambda a: (3 + _P(a[17])) * a[12] * a[13] * a[14] * _ES(a[0])),        # + the BatchNorm operand when fused
-    "vqa_spatial_fwd": ("se_spatial", lambda a: 3 * a[7] * a[8] * a[9] * a[10] * _ES(a[0])),
-    "vqa_spatial_bwd": ("se_spatial", lambda a: 3 * a[10] * a[11] * a[12] * a[13] * _ES(a[0])),
+    "vqa_se_fwd": ("se_spatial", lambda a: (2 if a.pool_part else 3) * a.B * a.HW * a.C * _ES(a.dtype)),      # pool sums handed over: no pool read
+    "vqa_se_bwd": ("se_spatial", lambda a: (3 + _P(a.bn_y)) * a.B * a.HW * a.C * _ES(a.dtype)),               # + the BatchNorm operand when fused
+    "vqa_spatial_fwd": ("se_spatial", lambda a: 3 * a.B * a.H * a.W * a.C * _ES(a.dtype)),
+    "vqa_spatial_bwd": ("se_spatial", lambda a: 3 * a.B * a.H * a.W * a.C * _ES(a.dtype)),
     # token side: LayerNorm, bias / activation backward, pools, gate, adds, embedding, attention (its FLOPs are tiny: latency class)
-    "vqa_layernorm_fwd": ("token", lambda a: 2 * a[6] * a[7] * _ES(a[0])),
-    "vqa_layernorm_bwd": ("token", lambda a: (3 + _P(a[5])) * a[9] * a[10] * _ES(a[0])),
-    "vqa_bias_act_bwd": ("token", lambda a: a[5] * a[6] * _ES(a[0]) * (1 + _P(a[2]) + _P(a[3]))),
-    "vqa_add": ("token", lambda a: 3 * a[4] * _ES(a[0])),
-    "vqa_embed_fwd": ("token", lambda a: a[5] * a[7] * (4 + _ES(a[0]))),
-    "vqa_embed_bwd": ("token", lambda a: a[4] * a[5] * _ES(a[0]) + a[6] * a[5] * 4),
-    "vqa_masked_pool_fwd": ("token", lambda a: a[6] * a[7] * a[8] * _ES(a[0])),
-    "vqa_masked_pool_bwd": ("token", lambda a: a[7] * a[8] * a[9] * _ES(a[0])),
-    "vqa_masked_pool_pair_fwd": ("token", lambda a: 2 * a[5] * a[6] * a[7] * _ES(a[0])),
-    "vqa_masked_pool_pair_bwd": ("token", lambda a: 2 * a[5] * a[6] * a[7] * _ES(a[0])),
-    "vqa_attention_fwd_mfma": ("attention", lambda a: (a[10] * (a[12] + 2 * a[13]) * a[9] + a[10] * a[12] * a[9]) * 2 + a[10] * a[11] * a[12] * a[13] * 4),
-    "vqa_attention_bwd_mfma": ("attention", lambda a: 2 * (a[15] * (a[17] + 2 * a[18]) * a[1]) * 2 + a[15] * a[17] * a[1] * 2 + a[15] * a[16] * a[17] * a[18] * 4),
-    "vqa_attention_fwd": ("attention", lambda a: (a[11] * (a[13] + 2 * a[14]) * a[10] + a[11] * a[13] * a[10]) * _ES(a[0]) + a[11] * a[12] * a[13] * a[14] * 4),
-    "vqa_attention_bwd": ("attention", lambda a: 2 * (a[16] * (a[18] + 2 * a[19]) * a[2]) * _ES(a[0]) + a[16] * a[18] * a[2] * _ES(a[0]) + a[16] * a[17] * a[18] * a[19] * 4),
-    # indexed form (answer()): queries, ctx and probs per question, K / V once per image
-    "vqa_attention_fwd_mfma_idx": ("attention", lambda a: 2 * a[12] * a[14] * a[13] * a[16] * 2 + 2 * a[7] * a[15] * a[13] * a[16] * 2 + a[12] * a[13] * a[14] * a[15] * 4),
-    "vqa_attention_fwd_idx": ("attention", lambda a: (2 * a[13] * a[15] * a[14] * a[17] + 2 * a[8] * a[16] * a[14] * a[17]) * _ES(a[0]) + a[13] * a[14] * a[15] * a[16] * 4),
-    # indexed form in training (forward_grouped): the same traffic with dropout; the backward reads Q, K, V, dctx and probs and writes
-    # dQ per question, dK / dV once per image; the CSR of the image index is N + U + 1 ints written from N read
-    "vqa_attention_fwd_mfma_idx_train": ("attention", lambda a: 2 * a[12] * a[14] * a[13] * a[16] * 2 + 2 * a[7] * a[15] * a[13] * a[16] * 2 + a[12] * a[13] * a[14] * a[15] * 4),
-    "vqa_attention_fwd_idx_train": ("attention", lambda a: (2 * a[13] * a[15] * a[14] * a[17] + 2 * a[8] * a[16] * a[14] * a[17]) * _ES(a[0]) + a[13] * a[14] * a[15] * a[16] * 4),
-    "vqa_attention_bwd_mfma_idx": ("attention", lambda a: (3 * a[18] * a[20] + 4 * a[11] * a[21]) * a[1] * 2 + a[18] * a[19] * a[20] * a[21] * 4),
-    "vqa_attention_bwd_idx": ("attention", lambda a: (3 * a[19] * a[21] + 4 * a[12] * a[22]) * a[2] * _ES(a[0]) + a[19] * a[20] * a[21] * a[22] * 4),
-    "vqa_index_csr": ("token", lambda a: (2 * a[1] + a[2] + 1) * 4),
-    "vqa_cross_entropy": ("token", lambda a: a[6] * a[7] * (_ES(a[0]) + 4)),
+    "vqa_layernorm_fwd": ("token", lambda a: 2 * a.rows * a.D * _ES(a.dtype)),
+    "vqa_layernorm_bwd": ("token", lambda a: (3 + _P(a.addend)) * a.rows * a.D * _ES(a.dtype)),
+    "vqa_bias_act_bwd": ("token", lambda a: a.M * a.N * _ES(a.dtype) * (1 + _P(a.outact) + _P(a.dz))),
+    "vqa_add": ("token", lambda a: 3 * a.n * _ES(a.dtype)),
+    "vqa_embed_fwd": ("token", lambda a: a.rows * a.D * (4 + _ES(a.dtype))),
+    "vqa_embed_bwd": ("token", lambda a: a.rows * a.D * _ES(a.dtype) + a.V * a.D * 4),
+    "vqa_masked_pool_fwd": ("token", lambda a: a.B * a.L * a.D * _ES(a.dtype)),
+    "vqa_masked_pool_bwd": ("token", lambda a: a.B * a.L * a.D * _ES(a.dtype)),
+    "vqa_masked_pool_pair_fwd": ("token", lambda a: 2 * a.B * a.L * a.D * _ES(a.dtype)),
+    "vqa_masked_pool_pair_bwd": ("token", lambda a: 2 * a.B * a.L * a.D * _ES(a.dtype)),
+    "vqa_attention_fwd_mfma": ("attention", lambda a: _attn_fwd(a, 2)),
+    "vqa_attention_bwd_mfma": ("attention", lambda a: _attn_bwd(a, 2)),
+    "vqa_attention_fwd": ("attention", lambda a: _attn_fwd(a, _ES(a.dtype))),
+    "vqa_attention_bwd": ("attention", lambda a: _attn_bwd(a, _ES(a.dtype))),
+    "vqa_attention_fwd_mfma_idx": ("attention", lambda a: _attn_fwd_idx(a, 2)),
+    "vqa_attention_fwd_idx": ("attention", lambda a: _attn_fwd_idx(a, _ES(a.dtype))),
+    # indexed form in training: the same traffic with dropout; the CSR of the image index is N + U + 1 ints written from N read
+    "vqa_attention_fwd_mfma_idx_train": ("attention", lambda a: _attn_fwd_idx(a, 2)),
+    "vqa_attention_fwd_idx_train": ("attention", lambda a: _attn_fwd_idx(a, _ES(a.dtype))),
+    "vqa_attention_bwd_mfma_idx": ("attention", lambda a: _attn_bwd_idx(a, 2)),
+    "vqa_attention_bwd_idx": ("attention", lambda a: _attn_bwd_idx(a, _ES(a.dtype))),
+    "vqa_index_csr": ("token", lambda a: (2 * a.N + a.U + 1) * 4),
+    "vqa_cross_entropy": ("token", lambda a: a.B * a.N * (_ES(a.dtype) + 4)),
     # soft targets: the logits traffic of the hard kernel + ids, weights, counts [B][K]; the annotator ids are 8 bytes in, 12 out
-    "vqa_cross_entropy_soft": ("token", lambda a: a[8] * a[9] * (_ES(a[0]) + 4) + a[8] * a[4] * (8 + 4 * _P(a[13]))),
+    "vqa_cross_entropy_soft": ("token", _soft_loss),
     # sigmoid BCE on the same targets: the same tensors in and out
-    "vqa_bce_soft": ("token", lambda a: a[8] * a[9] * (_ES(a[0]) + 4) + a[8] * a[4] * (8 + 4 * _P(a[13]))),
+    "vqa_bce_soft": ("token", _soft_loss),
     # options: the hard kernel's logits traffic + the targets and the class weights once (every wave re-reads them from cache)
-    "vqa_cross_entropy_opts": ("token", lambda a: a[6] * a[7] * (_ES(a[0]) + 4) + a[6] * 8 + a[7] * 4 * _P(a[11])),
-    "vqa_challenge_accuracy_update": ("token", lambda a: a[5] * a[6] * 4 + a[5] * a[3] * 8),
-    "vqa_answer_scores": ("token", lambda a: a[4] * a[5] * 20),
+    "vqa_cross_entropy_opts": ("token", lambda a: a.B * a.N * (_ES(a.dtype) + 4) + a.B * 8 + a.N * 4 * _P(a.class_weight)),
+    "vqa_challenge_accuracy_update": ("token", lambda a: a.B * a.N * 4 + a.B * a.K * 8),
+    "vqa_answer_scores": ("token", lambda a: a.B * a.A * 20),
     # weight staging and the optimizer tail (H, N1): cast of the flat buffer, packed data-gradient operands, sum of squares, AdamW
-    "vqa_convert": ("optimizer", lambda a: a[4] * (_ES(a[0]) + _ES(a[1]))),
-    "vqa_sumsq": ("optimizer", lambda a: a[1] * 4),
-    "vqa_adamw": ("optimizer", lambda a: a[4] * 4 * 7),
-    "vqa_sumsq_ranges": ("optimizer", lambda a: a[3] * 4),
-    "vqa_adamw_ranges": ("optimizer", lambda a: a[6] * 4 * 7),
+    "vqa_convert": ("optimizer", lambda a: a.n * (_ES(a.dtype_in) + _ES(a.dtype_out))),
+    "vqa_sumsq": ("optimizer", lambda a: a.n * 4),
+    "vqa_adamw": ("optimizer", lambda a: a.n * 4 * 7),
+    "vqa_sumsq_ranges": ("optimizer", lambda a: a.n * 4),
+    "vqa_adamw_ranges": ("optimizer", lambda a: a.n * 4 * 7),
     # + the weight average: read and write `ema` (8 B per element); alone: read p, read and write ema
-    "vqa_adamw_ema": ("optimizer", lambda a: a[4] * 4 * 9),
-    "vqa_adamw_ranges_ema": ("optimizer", lambda a: a[6] * 4 * 9),
-    "vqa_ema_update": ("optimizer", lambda a: a[2] * 4 * 3),
+    "vqa_adamw_ema": ("optimizer", lambda a: a.n * 4 * 9),
+    "vqa_adamw_ranges_ema": ("optimizer", lambda a: a.n * 4 * 9),
+    "vqa_ema_update": ("optimizer", lambda a: a.n * 4 * 3),
     # parameter groups: the range kernels' traffic (the groups' block is 128 bytes)
-    "vqa_adamw_groups": ("optimizer", lambda a: a[6] * 4 * 7),
-    "vqa_adamw_groups_ema": ("optimizer", lambda a: a[6] * 4 * 9),
+    "vqa_adamw_groups": ("optimizer", lambda a: a.n * 4 * 7),
+    "vqa_adamw_groups_ema": ("optimizer", lambda a: a.n * 4 * 9),
 }
+
+
+def _by_name(name, fn):
+    """fn over the entry's named arguments -> a function of the positional argument list (or a prefix of it: the rest reads None)."""
+    names = L.ARGNAMES[name]
+    args = collections.namedtuple(name, names, defaults=(None,) * len(names))
+    return lambda seq: fn(args(*seq))
+
+
+HBM_BYTES = {name: (cls, _by_name(name, fn)) for name, (cls, fn) in _HBM_FORMULAS.items()}
 
 
 def _hbm_hook(name, args):
