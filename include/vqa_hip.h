@@ -7,7 +7,8 @@
  *   - dtype: 0 = float32 (fp32 MFMA, parity path), 1 = bfloat16 (bf16 MFMA, fp32 accumulate); statistics,
  *     coefficients, weight gradients and optimizer state are always float32;
  *   - CNN activations are NHWC, token tensors are [rows][D]; conv weights are [Cout][R][S][Cin];
- *   - "+=" outputs (weight / bias gradients) accumulate into caller-zeroed fp32 buffers.
+ *   - "+=" outputs (weight / bias gradients) accumulate into caller-zeroed fp32 buffers;
+ *   - entries read only the stated extent of each operand and write only their outputs and the reported scratch.
  * Each entry cites the reference interface (path relative to the reference checkout) it replaces.
  */
 #ifndef VQA_HIP_H

@@ -14,6 +14,8 @@ rounds (mean K * 4 * 1.5 instead of 0); the values stay inside the range.
 
 The case tables at the bottom are shared by tests/test_exactint_ref_cpu.py (which proves, on the reference alone, that every
 operand set is inside the exact range and that the wide cases really exercise the rounding) and tests/test_gpu_exact_integer.py."""
+import functools
+
 import torch
 import torch.nn.functional as F
 
@@ -424,3 +426,14 @@ def stem_dgrad_case(B, H, W):
     dy, w = ints((B, 64, Ho, Wo), WIDE[0], 1200), ints((64, 3, 7, 7), WIDE[1], 1201)
     # at most 4 x 4 taps of 64 channels reach one pixel
     return dict(dy=dy, w=w, dimg=dgrad_ref(dy, w, 2, 3, (H, W)), bound=reduction_bound(16 * 64, dy, w))
+
+
+# ------------------------------------------------------------------------------------------------ kept references
+@functools.lru_cache(maxsize=4)
+def cached(builder, *args):
+    """builder(*args), kept for the last four argument lists: the several launches of one test in tests/test_gpu_arena_gemm_conv.py
+    (plain buffers and arenas, one epilogue after the other) share one reference.  It wraps the builders by NAME instead of decorating
+    them because some of them extend the dict another builder returned (with_infer_epilogue, bnred8p_case, c64p_narrow_case): behind
+    a cache of their own the inner dict would be extended again on every call of the outer one.  The result is shared: do not modify
+    it.  After a large case (the kind-1 weight gradient holds about 600 MB of fp64) call cached.cache_clear()."""
+    return globals()[builder](*args)

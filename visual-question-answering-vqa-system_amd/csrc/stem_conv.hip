@@ -245,7 +245,7 @@ __device__ __forceinline__ void stem_conv_body(const PIX* __restrict__ img, cons
       pair = pair > 20 ? 20 : pair;                     // pairs 21..23 have zero weights; read any valid patch row
       const int c = pair / 7, r = pair - c * 7;
       const uint32_t* ap = reinterpret_cast<const uint32_t*>(&patch[(c * PR + 2 * orow + r) * PW + 2 * (ow0 + li)]);
-      u32x4 raw = {ap[0], ap[1], ap[2], ap[3]};
+      u32x4 raw = {ap[0], ap[1], ap[2], ap[3] & 0x0000ffffu};         // s8 = 7 is padding: its pixel is the window's neighbour, and 0 * NaN is NaN
       const bf16x8 af = __builtin_bit_cast(bf16x8, raw);
 #pragma unroll
       for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bfr[kk][nt], acc[nt], 0, 0, 0);
