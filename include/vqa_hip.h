@@ -304,13 +304,20 @@ int vqa_attention_fwd_mfma(const void* q, const void* k, const void* v, int ldq,
 /* cross-attention forward whose K / V rows (and kmask rows) for query batch b are those of image kv_index[b] (many questions per
  * image from one cached image encoding): k, v hold n_kv images of Lk rows each; probs / ctx are per query batch as in
  * vqa_attention_fwd(_mfma).  Inference only: no dropout.  A query batch whose index lies outside [0, n_kv) loads nothing and gets
- * NaN in its probs and ctx rows.  The _mfma form has the limits of vqa_attention_fwd_mfma and takes no dtype (bf16). */
+ * NaN in its probs and ctx rows.  The _mfma form has the limits of vqa_attention_fwd_mfma and takes no dtype (bf16).
+ * kmask (may be NULL) masks with -inf like every attention entry here, so an image whose keys are ALL masked gives NaN rows; the
+ * modelled cross-attention fills with -1e9 instead, which gives a uniform row there and the same zeros for a partly masked row.
+ * The engine passes no key mask to cross-attention, so the difference cannot be reached from the model. */
 int vqa_attention_fwd_idx(int dtype, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const int* kv_index,
                           int n_kv, const float* kmask, float* probs, void* ctx, int ldc, int B, int H, int Lq, int Lk, int hd,
                           hipStream_t stream);
 int vqa_attention_fwd_mfma_idx(const void* q, const void* k, const void* v, int ldq, int ldk, int ldv, const int* kv_index, int n_kv,
                                const float* kmask, float* probs, void* ctx, int ldc, int B, int H, int Lq, int Lk, int hd,
                                hipStream_t stream);
+/* Backward of vqa_attention_fwd from the saved probs (the dropout mask is regenerated from p and seed): dq [B*Lq], dk, dv [B*Lk].
+ * A probs row that is NaN (every key masked) gives NaN in that batch's dq, dk and dv.  Its tiles need about twice the forward's LDS
+ * (the 160 KiB limit is met at a smaller Lk), so there are shapes the forward accepts and this entry refuses (status 1000, nothing
+ * written): at Lq 20, hd 64 the forward takes Lk <= 264, the backward Lk <= 225. */
 int vqa_attention_bwd(int dtype, const void* dctx, int ldc, const void* q, const void* k, const void* v, int ldq, int ldk, int ldv,
                       const float* probs, void* dq, void* dk, void* dv, int lddq, int lddk, int lddv, int B, int H, int Lq, int Lk,
                       int hd, float p, unsigned long long seed, hipStream_t stream);
